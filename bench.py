@@ -18,6 +18,12 @@ timed region.  One step = forward NTT then inverse NTT of that column (2 transfo
 N > 1: one process per GPU, each transforming its own column (independent replicas: a single NTT
 does not shard without an all-to-all that no BASELINE config needs -- DESIGN.md (e)); no data-path
 collective, barrier + max-over-ranks timing only.
+
+A plain run does only what `value` needs: set-up, `--warmup` untimed steps, `--steps` timed steps, the line.
+`--full` adds everything else after the timed steps: the round-trip check of the timed path, the NTT `cpu_baseline`,
+and the other legs (MSM, Poseidon and BN128 Merkle trees, Groth16, the 2^24-row and config-3 proofs, the aggregation),
+each with its own roofline, CPU baseline and checks; `--no-*` drops single legs from a `--full` run.
+`--dump-outputs DIR` writes what the last timed step computed (rank 0's column) as .npy files, see dump_outputs().
 """
 import argparse
 import ctypes as C
@@ -698,6 +704,30 @@ def compact_line(out):
     return line
 
 
+DUMP_SAMPLE = 1 << 20                                                    # elements per dumped array: 3 arrays x 8 MiB x (2, 2, 1) = 40 MiB
+DUMP_SEED = 0xD0A7
+
+
+def dump_outputs(d, X, y, n):
+    """--dump-outputs DIR: what the caller of the timed path receives after the last step -- the forward transform X and the
+    inverse of it, y (= the input, bit exact) -- at a fixed, seeded set of DUMP_SAMPLE positions (all positions if n is not
+    larger).  Goldilocks words do not fit a float64 exactly, so each is written as two columns [low 32 bits, high 32 bits]:
+      ntt_forward.npy, ntt_inverse.npy   float64 [m][2]
+      sample_index.npy                   float64 [m], ascending positions in the column"""
+    import torch
+    if n <= DUMP_SAMPLE:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False)).astype(np.int64)
+    d = pathlib.Path(d)
+    d.mkdir(parents=True, exist_ok=True)
+    it = torch.from_numpy(idx).to(X.device)
+    for name, t in (("ntt_forward", X), ("ntt_inverse", y)):
+        w = t.index_select(0, it).cpu().numpy().view(np.uint64)
+        np.save(d / (name + ".npy"), np.stack([w & np.uint64(0xFFFFFFFF), w >> np.uint64(32)], axis=1).astype(np.float64))
+    np.save(d / "sample_index.npy", idx.astype(np.float64))
+
+
 def dry_run(args, rank, world):
     """--dry-run: everything of main() that is NOT GPU work -- the rank environment the launcher made, the process group (gloo), the
     product's RootExchange, the max-over-ranks clock, rank 0's one line -- so that `bench.py --gpus N` can be driven on a box without GPUs
@@ -741,7 +771,12 @@ def main():
     ap.add_argument("--no-groth16", action="store_true", help="skip the Groth16 leg")
     ap.add_argument("--groth16-log-rows", type=int, default=20)
     ap.add_argument("--dry-run", action="store_true", help="launcher / rank / collective control flow only, no GPU work (CPU tests of --gpus N)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also the round-trip check, the CPU baseline and the other legs "
+                                                        "(a plain run times the NTT steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/*.npy (float64, at most 2^20 seeded positions)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # --gpus N without a launcher in front (no RANK / WORLD_SIZE): this process becomes the launcher -- N fresh rank processes of
     # this very command, one per GPU (test/stark_aggregation.sh:70-73 loops over child provers the same way).  Nothing has touched
@@ -803,8 +838,6 @@ def main():
     for _ in range(args.warmup):
         step()
     barrier()
-    if not torch.equal(x, y):                                         # inverse(forward(x)) == x, bit exact
-        raise SystemExit("bench: NTT round trip is not bit-exact")
 
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     barrier()
@@ -819,9 +852,13 @@ def main():
     ex = _agg().RootExchange(dist, torch.device("cpu") if shared_gpu else dev)   # the collectives of the path live in the product
     wall, dev_ms = ex.max([wall, dev_ms])
     ranks_seen = len({r[0] for r in ex.gather([rank])})               # an all-gather over the communicator itself (RCCL unless shared_gpu), not an env read
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, X, y, n)
+    if args.full and not torch.equal(x, y):                            # inverse(forward(x)) == x, bit exact
+        raise SystemExit("bench: NTT round trip is not bit-exact")
 
     agg = None
-    if not args.no_agg and not args.no_prove:                          # every rank takes part (N = 1: all 8 tasks on this GPU)
+    if args.full and not args.no_agg and not args.no_prove:            # every rank takes part (N = 1: all 8 tasks on this GPU)
         try:
             n_workers = int(os.environ.get("ZK_BENCH_WORKERS", max(1, min(4, (8 + world - 1) // world))))   # no more provers than a rank has tasks
             sys.path.insert(0, str(ROOT / "tools"))
@@ -866,24 +903,25 @@ def main():
             except Exception as e:
                 out[name] = {"error": "%s: %s" % (type(e).__name__, e)}
                 print("bench: leg %s FAILED: %s: %s" % (name, type(e).__name__, e), file=sys.stderr, flush=True)
-        if not args.no_msm and world == 1:
+        full1 = args.full and world == 1                               # the extra legs are N = 1 legs
+        if not args.no_msm and full1:
             leg("msm_g1_bn254", msm_leg, zk, args.msm_logn, not args.no_cpu_baseline)
             leg("msm_g1_bls12_381", msm_leg, zk, args.msm_logn, not args.no_cpu_baseline, "bls12_381")
-        if not args.no_poseidon and world == 1:
+        if not args.no_poseidon and full1:
             leg("poseidon_merkle_gl", poseidon_leg, zk, 22, 19, not args.no_cpu_baseline)
             leg("poseidon_merkle_gl_ref_shape", poseidon_leg, zk, 24, 10, not args.no_cpu_baseline)   # starky/benches/merklehash.rs:26-27: 2^24 x 10, the one GL shape the reference benches
-        if not args.no_bn128 and world == 1:
+        if not args.no_bn128 and full1:
             leg("merkle_bn128", bn128_merkle_leg, zk, 20, 12, not args.no_cpu_baseline)
             leg("merkle_bn128_ref_shape", bn128_merkle_leg, zk, 24, 10, not args.no_cpu_baseline)   # starky/README.md:55: 2^24 x 10 with the BN128 hash, 11.04 s on the reference's CPU (context, other hardware)
-        if not args.no_groth16 and world == 1:
+        if not args.no_groth16 and full1:
             leg("groth16_prove_bn128", groth16_leg, zk, "BN128", args.groth16_log_rows, not args.no_cpu_baseline)
             leg("groth16_prove_bls12381", groth16_leg, zk, "BLS12381", args.groth16_log_rows, False)
-        if not args.no_prove and world == 1:
+        if not args.no_prove and full1:
             leg("stark_prove", prove_leg, zk, args.prove_nbits, True, not args.no_cpu_baseline, True, not args.no_one_shot)
             leg("stark_prove_cfg3", prove_leg, zk, 20, True, False, False)     # BASELINE config 3 itself: 2^20 rows, steps 21/15/11/7/4
         if agg is not None:
             out["aggregation"] = agg
-        if not args.no_cpu_baseline and world == 1:                   # a reported baseline of the N = 1 line only
+        if not args.no_cpu_baseline and full1:                         # a reported baseline of the N = 1 line only
             orc = oracle_lib.load()
             orc.ntt_blocked(x_host[:1 << 16], 16, False)                 # thread pool warm
             t0 = time.perf_counter()

@@ -4,15 +4,22 @@ declarations (starky/src/traits.rs:24-63).
 The crate cannot be compiled here (no Rust toolchain), so this is the mechanical stand-in for the first thing `rustc` would
 check: every method the trait declares is implemented, with the same number of arguments, the same argument and return types
 once the impl's associated types are substituted for `Self::X`, and the same receiver; and the impl declares every
-associated type the trait asks for.  Reads the trait file from /root/reference (absent on the GPU box: skipped there)."""
-import pathlib, re
+associated type the trait asks for.  What the shim is checked against -- the reference's signatures, public names and callee
+arities, in this parser's normal form -- is stored in tests/golden/rust_shim_reference.json (tools/gen_rust_shim_golden.py)."""
+import json, pathlib, re
 import pytest
 
 ROOT = pathlib.Path(__file__).resolve().parent.parent
-TRAITS = pathlib.Path("/root/reference/starky/src/traits.rs")
 SHIM = ROOT / "bindings" / "rust" / "starky-hip" / "src"
 
-pytestmark = pytest.mark.skipif(not TRAITS.exists(), reason="reference tree not present")
+
+def _ref():
+    return json.loads((ROOT / "tests" / "golden" / "rust_shim_reference.json").read_text())
+
+
+def _sig(s):
+    """a stored signature [generics, receiver, [argument types], return type] as _fns gives it"""
+    return (s[0], s[1], list(s[2]), s[3])
 
 
 def _strip(t):
@@ -84,10 +91,9 @@ def _subst(t, assoc):
 
 @pytest.mark.parametrize("trait,file,impl", [("MerkleTree", "merkle.rs", "MerkleTreeHipGL"), ("Transcript", "transcript.rs", "TranscriptHipGL")])
 def test_impl_matches_the_trait(trait, file, impl):
-    tsrc = _strip(TRAITS.read_text())
-    tblock = _block(tsrc, r"pub\s+trait\s+%s\b" % trait)
-    want = _fns(tblock)
-    want_types = set(re.findall(r"\btype\s+(\w+)\s*[:;]", tblock))
+    t = _ref()["traits"][trait]
+    want = {k: _sig(v) for k, v in t["methods"].items()}
+    want_types = set(t["assoc_types"])
     isrc = _strip((SHIM / file).read_text())
     iblock = _block(isrc, r"impl\s+%s\s+for\s+%s\b" % (trait, impl))
     got, assoc = _fns(iblock), _assoc(iblock)
@@ -119,18 +125,16 @@ def test_the_checker_sees_a_drift():
 def test_fft_seam_functions_match_fft_p():
     """`fft`, `ifft`, `interpolate` of the shim (src/fft.rs) carry the signatures of starky/src/fft_p.rs:242-261 -- they are
     swapped in by path, so generics, argument order and types must be the reference's"""
-    ref = pathlib.Path("/root/reference/starky/src/fft_p.rs")
-    want, got = _fns(_strip(ref.read_text())), _fns(_strip((SHIM / "fft.rs").read_text()))
+    want, got = _ref()["fns"]["fft_p"], _fns(_strip((SHIM / "fft.rs").read_text()))
     for name in ("fft", "ifft", "interpolate"):
         assert name in want and name in got, name
-        assert got[name] == want[name], (name, got[name], want[name])
+        assert got[name] == _sig(want[name]), (name, got[name], want[name])
 
 
 def test_stark_prove_entry_matches_prove_rs():
     """the shim's public `stark_prove` (src/prove.rs) takes what starky/src/prove.rs:30-41 takes: it is what zkit calls"""
-    ref = pathlib.Path("/root/reference/starky/src/prove.rs")
-    want, got = _fns(_strip(ref.read_text())), _fns(_strip((SHIM / "prove.rs").read_text()))
-    assert got["stark_prove"] == want["stark_prove"], (got["stark_prove"], want["stark_prove"])
+    want, got = _ref()["fns"]["prove"], _fns(_strip((SHIM / "prove.rs").read_text()))
+    assert got["stark_prove"] == _sig(want["stark_prove"]), (got["stark_prove"], want["stark_prove"])
 
 
 def _uses(text):
@@ -148,23 +152,20 @@ def _uses(text):
 def test_every_imported_name_exists_in_the_reference_crates():
     """name resolution by hand: each `use starky::a::B` / `use fields::a::B` of the shim names a public module of that crate
     (declared `pub mod a;` in its lib.rs, file present) and a public item of that module (or a `pub use` re-export)"""
-    crates = {"starky": pathlib.Path("/root/reference/starky/src"), "fields": pathlib.Path("/root/reference/fields/src")}
+    crates = _ref()["crates"]
     seen = 0
     for f in sorted(SHIM.glob("*.rs")):
         for crate, mods, item in _uses(_strip(f.read_text())):
-            src = crates[crate]
-            lib = _strip((src / "lib.rs").read_text())
+            c = crates[crate]
             if not mods:                                            # `use starky::X`: a module or a re-export of lib.rs
-                assert re.search(r"pub\s+mod\s+%s\s*;" % item, lib) or re.search(r"pub\s+use\s+[^;]*\b%s\b" % item, lib), (f.name, crate, item)
+                assert item in c["lib_pub_mods"] or item in c["lib_pub_use_words"], (f.name, crate, item)
                 seen += 1
                 continue
             assert len(mods) == 1, (f.name, mods)
-            assert re.search(r"pub\s+mod\s+%s\s*;" % mods[0], lib), (f.name, "module not public", mods[0])
-            mfile = src / (mods[0] + ".rs")
-            assert mfile.exists(), mfile
-            mtext = _strip(mfile.read_text())
-            decl = r"pub\s+(?:struct|enum|trait|fn|type|const|static|mod)\s+%s\b" % item
-            assert re.search(decl, mtext) or re.search(r"pub\s+use\s+[^;]*\b%s\b" % item, mtext), (f.name, crate, mods[0], item)
+            assert mods[0] in c["lib_pub_mods"], (f.name, "module not public", mods[0])
+            assert mods[0] in c["modules"], (f.name, crate, "no file %s.rs" % mods[0])
+            m = c["modules"][mods[0]]
+            assert item in m["pub_items"] or item in m["pub_use_words"], (f.name, crate, mods[0], item)
             seen += 1
     assert seen >= 15
 
@@ -183,16 +184,12 @@ def _call_args(text, callee_re):
 def test_calls_into_the_reference_have_the_callees_arity():
     """`prove` (src/prove.rs) calls StarkSetup::new, stark_verify and pil2circom: argument counts against the definitions
     (stark_setup.rs:27-32, stark_verify.rs:20-26, pil2circom.rs:21-28), and StarkOption is built with exactly its fields"""
-    ref = pathlib.Path("/root/reference/starky/src")
+    ref = _ref()
     shim = _strip((SHIM / "prove.rs").read_text())
-    setup_new = _fns(_block(_strip((ref / "stark_setup.rs").read_text()), r"impl<[^>]*>\s*StarkSetup<[^>]*>"))["new"]
-    assert len(_call_args(shim, r"StarkSetup::<\w+>::new")) == len(setup_new[2])
-    verify = _fns(_strip((ref / "stark_verify.rs").read_text()))["stark_verify"]
-    assert len(_call_args(shim, r"stark_verify::stark_verify::<[^(]*>")) == len(verify[2])
-    p2c_src = _strip((ref / "pil2circom.rs").read_text())
-    p2c = _fns(p2c_src)["pil2circom"]
-    assert len(_call_args(shim, r"pil2circom::pil2circom::<\w+>")) == len(p2c[2])
-    fields = set(re.findall(r"pub\s+(\w+)\s*:", _block(p2c_src, r"pub\s+struct\s+StarkOption\b")))
+    assert len(_call_args(shim, r"StarkSetup::<\w+>::new")) == ref["arity"]["StarkSetup::new"]
+    assert len(_call_args(shim, r"stark_verify::stark_verify::<[^(]*>")) == ref["arity"]["stark_verify"]
+    assert len(_call_args(shim, r"pil2circom::pil2circom::<\w+>")) == ref["arity"]["pil2circom"]
+    fields = set(ref["StarkOption_fields"])
     lit = re.search(r"pil2circom::StarkOption\s*\{([^}]*)\}", shim).group(1)
     used = {f.split(":")[0].strip() for f in lit.split(",") if f.strip()}
     assert used == fields, (used, fields)

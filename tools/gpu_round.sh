@@ -39,7 +39,7 @@ do_icache() {
 do_prof() { local n=$1; shift; local O=gpurun_out/prof_$n; rm -rf $O; timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O -o $n -- "$@" > $O.log 2>&1; tail -3 $O.log; stats $O 24; }
 do_profiles() {
   local O=gpurun_out/profiles; rm -rf $O; mkdir -p $O
-  timeout 1500 python bench.py --steps 50 --warmup 5 > $O/bench.json 2> $O/bench.err; tail -c 800 $O/bench.json; cp gpurun_out/bench_detail.json $O/bench_detail.json
+  timeout 1500 python bench.py --full --steps 50 --warmup 5 > $O/bench.json 2> $O/bench.err; tail -c 800 $O/bench.json; sed -n 's/^bench_detail: //p' $O/bench.err > $O/bench_detail.json
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ntt -o ntt -- python3 bench.py --steps 20 --warmup 2 --no-cpu-baseline --no-prove --no-msm --no-bn128 --no-groth16 --no-poseidon --no-agg > $O/ntt.log 2>&1
   timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prove -o prove -- python3 tools/prove_bench.py --nbits 24 --reps 3 > $O/prove.log 2>&1; tail -1 $O/prove.log | cut -c1-400
   timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/msm -o msm -- python3 tools/msm_bench.py bn254 g1 22 > $O/msm.log 2>&1; tail -2 $O/msm.log
