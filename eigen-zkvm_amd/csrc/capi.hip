@@ -1,203 +1,13 @@
-// C ABI of libzkgpu (include/zkgpu.h): thin extern "C" wrappers, error capture, host<->device
-// staging for the host-pointer entry points, and the Merkle tree handle.
+// C ABI of libzkgpu (include/zkgpu.h): thin extern "C" wrappers, host<->device staging for the
+// host-pointer entry points, and the Merkle tree handle.  (Device memory, streams, error capture: devmem.hip.)
 #include "zk_internal.h"
 #include "../../include/zkgpu.h"
-#include <atomic>
 #include <map>
 #include <mutex>
 #include <vector>
 #include <cstring>
 
 namespace zk {
-
-static thread_local std::string t_err;
-void set_error(const std::string& msg) { t_err = msg; }
-
-// ---- caching device allocator -------------------------------------------------------------------
-namespace {
-// An event recorded when blocks were freed; shared by all blocks freed in one burst (pool_defer_*), recycled by the last of them
-struct Ev { hipEvent_t e = nullptr; int refs = 0; };
-struct Block { size_t bytes = 0; std::vector<Ev*> pending; };
-std::mutex g_pool_mu;
-std::multimap<size_t, void*> g_pool_free;   // size -> idle block
-std::map<void*, Block> g_pool_blocks;       // every block handed out by pool_alloc
-std::vector<hipStream_t> g_streams{nullptr};  // streams the library has been asked to work on
-std::vector<hipEvent_t> g_event_cache;
-thread_local hipStream_t t_stream = nullptr;
-thread_local std::vector<hipStream_t> t_streams;   // non-null streams this host thread has issued on
-thread_local int t_depth = 0;                      // C-ABI calls in progress on this thread (the prover calls entry points itself)
-thread_local bool t_defer = false;                 // pool_defer_begin(): frees are collected ...
-thread_local std::vector<void*> t_deferred;        // ... here, and stamped with ONE set of events by pool_defer_flush()
-void ev_release(Ev* v) { if (--v->refs == 0) { g_event_cache.push_back(v->e); delete v; } }   // g_pool_mu held
-
-hipEvent_t event_get() {                     // g_pool_mu held; never throws (DevBuf destructors end up here): nullptr = no event to be had
-    if (!g_event_cache.empty()) { hipEvent_t e = g_event_cache.back(); g_event_cache.pop_back(); return e; }
-    hipEvent_t e = nullptr;
-    if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    return e;
-}
-}
-hipStream_t cur_stream() { return t_stream; }
-// The GPU of the process (zk_init).  HIP's current device is a property of the host thread and every new thread starts on device 0,
-// so a prover thread of rank k > 0 would otherwise allocate and launch on GPU 0: each thread is bound on its first call.
-static std::atomic<int> g_device{-1};          // -1: zk_init was never called, threads are left as the caller set them up
-// zk_init's device overrides whatever the caller (torch.cuda.set_device, another library) made current on this thread in the
-// meantime: pooled blocks, constant tables and code modules all belong to device d, so every outermost call re-checks the thread's
-// actual device (hipGetDevice is a thread-local read) instead of trusting a flag cached at the first call.
-void bind_device() noexcept {
-    const int d = g_device.load(std::memory_order_relaxed);
-    if (d < 0) return;
-    int cur = -1;
-    if (hipGetDevice(&cur) == hipSuccess && cur == d) return;
-    if (hipSetDevice(d) != hipSuccess) (void)hipGetLastError();   // the work that follows reports its own error
-}
-CallScope::CallScope() : saved(t_stream) { if (t_depth++ == 0) { t_stream = nullptr; bind_device(); } }   // a call from outside starts on the null stream,
-CallScope::~CallScope() { --t_depth; t_stream = saved; }                                // one made by the prover inherits the prover's
-hipStream_t on_stream(hipStream_t st) {
-    t_stream = st;
-    if (st) {
-        bool mine = false;
-        for (hipStream_t s : t_streams) mine |= s == st;
-        if (!mine) {
-            t_streams.push_back(st);
-            std::lock_guard<std::mutex> lk(g_pool_mu);
-            bool known = false;
-            for (hipStream_t s : g_streams) known |= s == st;
-            if (!known) {
-                // While the null stream was the only one in use, blocks went back to the pool without an event (pool_free):
-                // work queued there may still be running on them, and a non-blocking stream does not wait for the null stream.
-                // Drain once, at the moment a second stream appears; from here on every free records its events.
-                // (under the lock on purpose: no block may be handed out between the drain and the registration)
-                if (g_streams.size() == 1) (void)hipDeviceSynchronize();
-                g_streams.push_back(st);
-            }
-        }
-    }
-    return st;
-}
-// A helper stream that lives inside one call (the MSM's sort stream): registered so that this thread's frees are stamped on it while it
-// is in use, WITHOUT the one-off device drain of on_stream -- the caller guarantees that the side stream's first operation waits for an
-// event recorded on the current stream after every buffer it will touch was allocated (so it is ordered behind those blocks' previous
-// users), and calls forget_stream once the current stream has waited for the side stream's last event.  The thread's current stream is kept.
-void on_side_stream(hipStream_t ss) {
-    if (!ss) return;
-    bool mine = false;
-    for (hipStream_t s : t_streams) mine |= s == ss;
-    if (!mine) t_streams.push_back(ss);
-    std::lock_guard<std::mutex> lk(g_pool_mu);
-    bool known = false;
-    for (hipStream_t s : g_streams) known |= s == ss;
-    if (!known) g_streams.push_back(ss);
-}
-void* pool_alloc(size_t bytes, bool host_wait) {
-    if (bytes == 0) bytes = 8;
-    {
-        std::unique_lock<std::mutex> lk(g_pool_mu);
-        auto it = g_pool_free.find(bytes);
-        if (it != g_pool_free.end()) {
-            void* p = it->second; g_pool_free.erase(it);
-            std::vector<Ev*> pending;
-            pending.swap(g_pool_blocks[p].pending);                   // the block is out of the free list: nobody else sees it or its events' list
-            // whoever used the block last finishes first.  The library's own buffers: the stream this thread works on waits
-            // (asynchronous, under the lock).  A block that leaves the library (zk_dev_alloc: the caller may touch it from any
-            // stream): the HOST waits -- with the lock released, so that other provers' allocations and frees go on meanwhile.
-            if (host_wait) lk.unlock();
-            for (Ev* v : pending) {
-                const hipError_t rc = host_wait ? hipEventSynchronize(v->e) : hipStreamWaitEvent(t_stream, v->e, 0);
-                // an event whose stream has been destroyed since (a released setup's side stream: drained before it went) reports an
-                // error here; its work is done, and the error must not surface at some later hipGetLastError()
-                if (rc != hipSuccess) (void)hipGetLastError();
-            }
-            if (host_wait) lk.lock();
-            for (Ev* v : pending) ev_release(v);
-            return p;
-        }
-    }
-    void* p = nullptr;
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e != hipSuccess) {  // out of memory: drop the cache and retry once
-        (void)hipGetLastError();                                      // the failed attempt must not surface at a later check
-        pool_trim();
-        ZK_HIP(hipMalloc(&p, bytes));
-    }
-    std::lock_guard<std::mutex> lk(g_pool_mu);
-    g_pool_blocks[p].bytes = bytes;
-    return p;
-}
-namespace {
-// events for blocks freed now: the null stream and every stream the FREEING thread has issued on (a buffer is released by the
-// thread that owns it; work another thread did on it was ordered before this thread's by whoever handed it over).  Streams of
-// other threads are left alone: concurrent provers must not wait for each other.  g_pool_mu held.
-std::vector<Ev*> stamp_now() {
-    std::vector<Ev*> out;
-    if (g_streams.size() <= 1) return out;               // a single stream in use: reuse is stream ordered (on_stream drains at the second)
-    auto record = [&](hipStream_t st) {
-        hipEvent_t e = event_get();
-        if (!e) { (void)hipStreamSynchronize(st); (void)hipGetLastError(); return; }   // no event to be had: wait here instead
-        if (hipEventRecord(e, st) == hipSuccess) out.push_back(new Ev{e, 0});
-        else { (void)hipGetLastError(); g_event_cache.push_back(e); }   // a destroyed stream has nothing in flight
-    };
-    record(nullptr);
-    for (hipStream_t st : t_streams) record(st);
-    return out;
-}
-void release_stamped(void* p, const std::vector<Ev*>& evs) {   // g_pool_mu held
-    auto it = g_pool_blocks.find(p);
-    if (it == g_pool_blocks.end()) { (void)hipFree(p); return; }
-    for (Ev* v : evs) { ++v->refs; it->second.pending.push_back(v); }
-    g_pool_free.emplace(it->second.bytes, p);
-}
-}  // namespace
-void pool_free(void* p) {
-    if (!p) return;
-    if (t_defer) { t_deferred.push_back(p); return; }
-    std::lock_guard<std::mutex> lk(g_pool_mu);
-    const std::vector<Ev*> evs = stamp_now();
-    release_stamped(p, evs);
-    for (Ev* v : evs) if (v->refs == 0) { g_event_cache.push_back(v->e); delete v; }   // the block was not the pool's
-}
-// A burst of frees with no launch in between (the end of a proof: ~70 buffers and trees go at once) shares one set of events
-// instead of recording two per block: pool_defer_begin() after the last launch, pool_defer_flush() once the destructors have run.
-void pool_defer_begin() { t_defer = true; }
-void pool_defer_flush() {
-    t_defer = false;
-    if (t_deferred.empty()) return;
-    std::lock_guard<std::mutex> lk(g_pool_mu);
-    const std::vector<Ev*> evs = stamp_now();
-    for (void* p : t_deferred) release_stamped(p, evs);
-    for (Ev* v : evs) if (v->refs == 0) { g_event_cache.push_back(v->e); delete v; }
-    t_deferred.clear();
-}
-// Host <-> device copies of the library's own pooled buffers: on the stream this thread is working on (the one whose
-// queue was ordered behind the buffer's previous user by pool_alloc), then waited for -- a plain hipMemcpy runs on the
-// null stream, which a non-blocking stream does not synchronise with.
-void h2d_sync(void* d, const void* h, size_t n) {
-    if (!n) return;
-    ZK_HIP(hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, t_stream));
-    ZK_HIP(hipStreamSynchronize(t_stream));
-}
-void d2h_sync(void* h, const void* d, size_t n) {
-    if (!n) return;
-    ZK_HIP(hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, t_stream));
-    ZK_HIP(hipStreamSynchronize(t_stream));
-}
-void pool_trim() {
-    std::lock_guard<std::mutex> lk(g_pool_mu);
-    for (auto& kv : g_pool_free) {
-        Block& b = g_pool_blocks[kv.second];
-        for (Ev* v : b.pending) { if (hipEventSynchronize(v->e) != hipSuccess) (void)hipGetLastError(); ev_release(v); }
-        (void)hipFree(kv.second); g_pool_blocks.erase(kv.second);
-    }
-    g_pool_free.clear();
-}
-void forget_stream(hipStream_t st) {                                  // before hipStreamDestroy
-    for (size_t i = 0; i < t_streams.size(); ++i)
-        if (t_streams[i] == st) { t_streams.erase(t_streams.begin() + i); break; }
-    std::lock_guard<std::mutex> lk(g_pool_mu);
-    for (size_t i = 1; i < g_streams.size(); ++i)
-        if (g_streams[i] == st) { g_streams.erase(g_streams.begin() + i); break; }
-}
-
 namespace {
 
 std::mutex g_ws_mu;
@@ -206,16 +16,9 @@ std::mutex g_ws_mu;
 // (a process that still had a registered side stream at exit crashed there).
 DevBuf &g_ws_a = *new DevBuf, &g_ws_b = *new DevBuf, &g_ws_c = *new DevBuf;
 
-template <class F>
-int guard(F&& f) {
-    CallScope scope;
-    try { f(); return 0; }
-    catch (const std::exception& e) { set_error(e.what()); return -1; }
-    catch (...) { set_error("unknown error"); return -1; }
-}
-
-__global__ void gather_proof_kernel(const u64* __restrict__ elements, const u64* __restrict__ nodes, u32 width,
-                                    u64 height, u64 idx, u64* __restrict__ out /* width + depth*4 */) {
+// one opening by one block: the row, then thread 0 walks up the tree and copies the sibling of every level
+__device__ __forceinline__ void gather_proof(const u64* __restrict__ elements, const u64* __restrict__ nodes, u32 width,
+                                             u64 height, u64 idx, u64* __restrict__ out /* width + depth*4 */) {
     const u32 t = threadIdx.x;
     for (u32 i = t; i < width; i += blockDim.x) out[i] = elements[idx * width + i];
     if (t == 0) {  // merklehash.rs:64-76 merkle_gen_merkle_proof
@@ -227,6 +30,10 @@ __global__ void gather_proof_kernel(const u64* __restrict__ elements, const u64*
             off += next * 2; n = next; id >>= 1; ++d;
         }
     }
+}
+__global__ void gather_proof_kernel(const u64* __restrict__ elements, const u64* __restrict__ nodes, u32 width,
+                                    u64 height, u64 idx, u64* __restrict__ out) {
+    gather_proof(elements, nodes, width, height, idx, out);
 }
 
 // synthetic words for benchmarks and size tests: word i = splitmix64(seed + i) folded below p (one conditional subtraction)
@@ -241,19 +48,8 @@ __global__ void fill_splitmix_kernel(u64* __restrict__ out, u64 n, u64 seed) {
 // the same for n queries at once: block q serves idx[q], out + q * (width + 4 * depth)
 __global__ void gather_proofs_kernel(const u64* __restrict__ elements, const u64* __restrict__ nodes, u32 width, u64 height,
                                      u32 depth, const u64* __restrict__ idxs, u64* __restrict__ outs, u64 mask) {
-    const u32 t = threadIdx.x;
     const u64 idx = idxs[blockIdx.x] & mask;             // mask: the query index reduced to a later FRI step's domain (fri.rs:166-168)
-    u64* __restrict__ out = outs + (u64)blockIdx.x * (width + 4 * depth);
-    for (u32 i = t; i < width; i += blockDim.x) out[i] = elements[idx * width + i];
-    if (t == 0) {
-        u64 n = height, off = 0, id = idx; u32 d = 0;
-        while (n > 1) {
-            const u64* sib = nodes + 4 * (off + (id ^ 1));
-            for (int k = 0; k < 4; ++k) out[width + 4 * d + k] = sib[k];
-            u64 next = (n - 1) / 2 + 1;
-            off += next * 2; n = next; id >>= 1; ++d;
-        }
-    }
+    gather_proof(elements, nodes, width, height, idx, outs + (u64)blockIdx.x * (width + 4 * depth));
 }
 // every tree of a proof in ONE launch: block (q, j) serves query q of tree j (a small proof opened its seven or eight trees in as many
 // launches of ~5 us each); lane d copies the sibling of level d
@@ -324,10 +120,10 @@ int zk_init(int device) {
         ZK_HIP(hipGetDeviceCount(&n));
         ZK_REQUIRE(device >= 0 && device < n, "zk_init: no such device");
         ZK_HIP(hipSetDevice(device));
-        g_device.store(device, std::memory_order_relaxed);   // ... and of every thread that calls into the library from now on
+        set_device(device);                                  // ... and of every thread that calls into the library from now on
     });
 }
-const char* zk_last_error(void) { return t_err.c_str(); }
+const char* zk_last_error(void) { return last_error(); }
 int zk_device_count(void) { int n = 0; if (hipGetDeviceCount(&n) != hipSuccess) return 0; return n; }
 uint64_t zk_gl_modulus(void) { return GL_P; }
 uint64_t zk_gl_root_of_unity(uint32_t k) { return k <= 32 ? gl::hroot(k) : 0; }

@@ -635,7 +635,7 @@ struct zk_program {
     hipFunction_t fn = nullptr, fn_pow = nullptr;
     uint32_t n_instr = 0;
     uint32_t pow_entries = 0;      // (challenge, exponent) pairs of the power table, 6 words each
-    void* d_pow = nullptr;
+    DevBuf d_pow;                  // the table itself, written by zk_pow_kernel in front of every run
 };
 
 extern "C" {
@@ -722,6 +722,7 @@ int zk_program_run_rows_dev(zk_program_t* p, const zk_eval_ctx* ctx, uint32_t nb
         ZK_REQUIRE(nbits_domain <= 32, "zk_program_run_dev: domain too large");
         ZK_REQUIRE(row0 <= (1ull << nbits_domain) && count <= (1ull << nbits_domain) - row0, "zk_program_run_rows_dev: rows outside the domain");
         if (count == 0) return 0;
+        const hipStream_t st = on_stream((hipStream_t)stream);   // first: the power table, a pooled block, is ordered behind its previous users on this stream
         if (!p->module) {  // load lazily: compiling needs no GPU, running does
             auto load = [&]() -> hipError_t {
                 hipError_t e = hipModuleLoadData(&p->module, p->code->bytes.data());
@@ -736,26 +737,25 @@ int zk_program_run_rows_dev(zk_program_t* p, const zk_eval_ctx* ctx, uint32_t nb
                 e = load();
             }
             if (e != hipSuccess) throw Error(std::string("loading a constraint kernel's code object failed: ") + hipGetErrorString(e));
-            if (p->pow_entries) ZK_HIP(hipMalloc(&p->d_pow, (size_t)p->pow_entries * 48));
         }
         if (p->pow_entries) {   // powers of this run's challenges, on the same stream
-            struct { zk_eval_ctx c; void* pw; } pa{*ctx, p->d_pow};
+            p->d_pow.reserve((size_t)p->pow_entries * 48);
+            struct { zk_eval_ctx c; void* pw; } pa{*ctx, p->d_pow.p};
             size_t psz = sizeof(pa);
             void* pcfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &pa, HIP_LAUNCH_PARAM_BUFFER_SIZE, &psz, HIP_LAUNCH_PARAM_END};
-            ZK_HIP(hipModuleLaunchKernel(p->fn_pow, 1, 1, 1, 64, 1, 1, 0, on_stream((hipStream_t)stream), nullptr, pcfg));
+            ZK_HIP(hipModuleLaunchKernel(p->fn_pow, 1, 1, 1, 64, 1, 1, 0, st, nullptr, pcfg));
         }
-        struct { zk_eval_ctx c; uint64_t n; uint64_t next; const void* pw; uint64_t row0; uint64_t count; } args{*ctx, 1ull << nbits_domain, next, p->d_pow, row0, count};
+        struct { zk_eval_ctx c; uint64_t n; uint64_t next; const void* pw; uint64_t row0; uint64_t count; } args{*ctx, 1ull << nbits_domain, next, p->d_pow.p, row0, count};
         size_t size = sizeof(args);
         void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
         const uint64_t blocks = (count + 255) / 256;
-        ZK_HIP(hipModuleLaunchKernel(p->fn, (unsigned)blocks, 1, 1, 256, 1, 1, 0, on_stream((hipStream_t)stream), nullptr, cfg));
+        ZK_HIP(hipModuleLaunchKernel(p->fn, (unsigned)blocks, 1, 1, 256, 1, 1, 0, st, nullptr, cfg));
         return 0;
     } catch (const std::exception& e) { set_error(e.what()); return -1; }
 }
 
 int zk_program_free(zk_program_t* p) {
     bind_device();
-    if (p && p->d_pow) (void)hipFree(p->d_pow);
     if (p && p->module) (void)hipModuleUnload(p->module);
     delete p;
     return 0;

@@ -20,6 +20,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <vector>
+#include <atomic>
+#include <mutex>
 #include <string>
 
 namespace zk {

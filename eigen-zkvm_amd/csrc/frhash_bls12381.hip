@@ -4,6 +4,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <vector>
+#include <atomic>
+#include <mutex>
 #include <string>
 
 namespace zk {

@@ -711,21 +711,27 @@ __global__ __launch_bounds__(64) void bn128_level_grp_kernel(const u64* __restri
     if (i < n_ops && q == FH_OUT_IDX) store_raw(st[0], out + 4 * i);
 }
 
-struct DeviceTables { fe* all = nullptr; bool ready = false; };
-DeviceTables g_tables[64];
+// One device's tables, kept for the life of the process (DevConst, zk_internal.h; the array is never destroyed): load_constants
+// fills them under g_tables_mu and sets `ready` last.  mf: per t the sparse rounds, the fragments of M and P, the addends.
+struct DeviceTables { DevConst all, coop, mf[16][3]; std::atomic<bool> ready{false}; };
+DeviceTables* const g_tables = new DeviceTables[64];
+std::mutex g_tables_mu;
 const u32 NRP[16] = {FH_NRP};   // = fh_nrp(t) for t = 2..17
 
 // The matrix-pipe tables of one t (fr_mfma.hip.h): fragments of M and P, and per dense layer the addends carrying the image of the round
 // constants that follow the layer's S-boxes (poseidon_fr_reg's order: layers 0..2 M, 3 P, 4..7 M; none after the last S-boxes).
-void mf_upload(const unsigned char* canon, size_t off_c, size_t off_m, size_t off_p, size_t off_s, int T, u32 n_rp, Params& prm) {
+// Host arithmetic only; throws when a table does not pass its own check.
+struct MfHost { std::vector<unsigned char> sp; std::vector<signed char> frag; std::vector<u64> K; size_t sb = 0, fb = 0; };
+MfHost mf_build(const unsigned char* canon, size_t off_c, size_t off_m, size_t off_p, size_t off_s, int T, u32 n_rp) {
+    MfHost H;
     const MfInt q = mf_modulus();
-    const size_t fb = (size_t)T * T * 1024;
-    std::vector<signed char> frag(2 * fb);
+    const size_t fb = H.fb = (size_t)T * T * 1024;
+    std::vector<signed char>& frag = H.frag; frag.resize(2 * fb);
     std::vector<MfInt> corr(2 * T);
     std::string err = mf_build_matrix(canon + 32 * off_m, T, frag.data(), corr.data());
     if (err.empty()) err = mf_build_matrix(canon + 32 * off_p, T, frag.data() + fb, corr.data() + T);
     if (!err.empty()) throw Error(std::string(FH_NAME " Poseidon, matrix-pipe tables of t = ") + std::to_string(T) + ": " + err);
-    std::vector<u64> K((size_t)8 * T * 8);
+    std::vector<u64>& K = H.K; K.resize((size_t)8 * T * 8);
     std::vector<MfInt> cm(T);
     for (int layer = 0; layer < 8; ++layer) {
         const bool isp = layer == 3, has_c = layer < 7;
@@ -738,25 +744,16 @@ void mf_upload(const unsigned char* canon, size_t off_c, size_t off_m, size_t of
             mf_addends(add, corr[(isp ? T : 0) + o], &K[((size_t)layer * T + o) * 8]);
         }
     }
-    const size_t sb = mf_sparse_round_bytes(T) * n_rp;
-    std::vector<unsigned char> sp(sb + 1024);
+    const size_t sb = H.sb = mf_sparse_round_bytes(T) * n_rp;
+    std::vector<unsigned char>& sp = H.sp; sp.resize(sb + 1024);
     err = mf_build_sparse(canon + 32 * off_s, canon + 32 * (off_c + (size_t)5 * T), T, (int)n_rp, sp.data(), (signed char*)sp.data() + sb);
     if (!err.empty()) throw Error(std::string(FH_NAME " Poseidon, matrix-pipe tables of t = ") + std::to_string(T) + ": " + err);
-    void* d_sp = nullptr;
-    ZK_HIP(hipMalloc(&d_sp, sp.size()));
-    ZK_HIP(hipMemcpy(d_sp, sp.data(), sp.size(), hipMemcpyHostToDevice));
-    prm.mf_s = d_sp; prm.mf_i = (const char*)d_sp + sb;
-    void* d_frag = nullptr; u64* d_k = nullptr;
-    ZK_HIP(hipMalloc(&d_frag, 2 * fb));
-    ZK_HIP(hipMalloc((void**)&d_k, K.size() * 8));
-    ZK_HIP(hipMemcpy(d_frag, frag.data(), 2 * fb, hipMemcpyHostToDevice));
-    ZK_HIP(hipMemcpy(d_k, K.data(), K.size() * 8, hipMemcpyHostToDevice));
-    prm.mf_m = d_frag; prm.mf_p = (const char*)d_frag + fb; prm.mf_k = d_k;
+    return H;
 }
 
 void require_tables() {
     int dev; ZK_HIP(hipGetDevice(&dev));
-    ZK_REQUIRE(dev >= 0 && dev < 64 && g_tables[dev].ready, FH_NAME " Poseidon constants not loaded (zk_" FH_NAME "_load_constants)");
+    ZK_REQUIRE(dev >= 0 && dev < 64 && g_tables[dev].ready.load(std::memory_order_acquire), FH_NAME " Poseidon constants not loaded (zk_" FH_NAME "_load_constants)");
 }
 
 }  // namespace
@@ -808,33 +805,46 @@ std::string FH_FN(tables_selfcheck)(const char* path) {
 void FH_FN(load_constants)(const char* path) {
     int dev; ZK_HIP(hipGetDevice(&dev));
     ZK_REQUIRE(dev >= 0 && dev < 64, "device index out of range");
-    if (g_tables[dev].ready) return;
+    std::lock_guard<std::mutex> lk(g_tables_mu);                        // provers on several host threads: one of them loads, the others find it done
+    DeviceTables& D = g_tables[dev];
+    if (D.ready.load(std::memory_order_relaxed)) return;
     std::vector<unsigned char> canon; TabOff off[16];
     const size_t count = read_constants(path, canon, off);
+    // the host's part first, for every t: whatever is wrong with the file or a table is found before the first device block is taken
+    std::vector<MfHost> mf(16);
+    size_t n_coop = 0;
+    for (int k = 0; k < 16; ++k) {
+        ZK_REQUIRE(co_phase1(NRP[k]) <= CO_XLANES && NRP[k] - co_phase1(NRP[k]) <= CO_XLANES, "too many sparse rounds for the cooperative form");
+        if ((int)off[k].t >= ZK_FR_MFMA_FROM) mf[k] = mf_build(canon.data(), off[k].c, off[k].m, off[k].p, off[k].s, (int)off[k].t, NRP[k]);
+        n_coop += ((size_t)NRP[k] + 32) * NR * 64;
+    }
+    // the device's part: local owners, so that a failure from here on gives every block back and a later call starts again
     DevBuf d_canon; d_canon.reserve(canon.size());
     ZK_HIP(hipMemcpy(d_canon.p, canon.data(), canon.size(), hipMemcpyHostToDevice));
-    fe* d_all = nullptr;
-    ZK_HIP(hipMalloc((void**)&d_all, count * sizeof(fe)));
+    DevConst all(count * sizeof(fe)), coop(n_coop * sizeof(u32)), d_mf[16][3];
+    fe* const d_all = (fe*)all.p;
     hipLaunchKernelGGL(bn128_convert_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, nullptr, (const u32*)d_canon.p, (u64)count, d_all);
     ZK_HIP(hipGetLastError());
     Params prm[16];
-    size_t n_coop = 0;
-    for (int k = 0; k < 16; ++k) n_coop += ((size_t)NRP[k] + 32) * NR * 64;
-    u32* d_coop = nullptr;
-    ZK_HIP(hipMalloc((void**)&d_coop, n_coop * sizeof(u32)));
     size_t at = 0;
     for (int k = 0; k < 16; ++k) {
-        ZK_REQUIRE(co_phase1(NRP[k]) <= CO_XLANES && NRP[k] - co_phase1(NRP[k]) <= CO_XLANES, "too many sparse rounds for the cooperative form");
-        u32* coef = d_coop + at; u32* rebw = coef + (size_t)NRP[k] * NR * 64;
+        u32* coef = (u32*)coop.p + at; u32* rebw = coef + (size_t)NRP[k] * NR * 64;
         at += ((size_t)NRP[k] + 32) * NR * 64;
         prm[k] = {off[k].t, NRP[k], d_all + off[k].c, d_all + off[k].m, d_all + off[k].p, d_all + off[k].s, coef, rebw, co_phase1(NRP[k]), nullptr, nullptr, nullptr, nullptr, nullptr};
-        if ((int)off[k].t >= ZK_FR_MFMA_FROM) mf_upload(canon.data(), off[k].c, off[k].m, off[k].p, off[k].s, (int)off[k].t, NRP[k], prm[k]);
+        if (!mf[k].frag.empty()) {
+            const MfHost& H = mf[k];
+            d_mf[k][0] = DevConst(H.sp); d_mf[k][1] = DevConst(H.frag); d_mf[k][2] = DevConst(H.K);
+            prm[k].mf_s = d_mf[k][0].p; prm[k].mf_i = (const char*)d_mf[k][0].p + H.sb;
+            prm[k].mf_m = d_mf[k][1].p; prm[k].mf_p = (const char*)d_mf[k][1].p + H.fb; prm[k].mf_k = d_mf[k][2].u();
+        }
         hipLaunchKernelGGL(coop_tables_kernel, dim3(NRP[k] + 32), dim3(64), 0, nullptr, prm[k], coef, rebw);
         ZK_HIP(hipGetLastError());
     }
     ZK_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_prm), prm, sizeof(prm)));
     ZK_HIP(hipDeviceSynchronize());
-    g_tables[dev].all = d_all; g_tables[dev].ready = true;
+    D.all = std::move(all); D.coop = std::move(coop);
+    for (int k = 0; k < 16; ++k) for (int j = 0; j < 3; ++j) D.mf[k][j] = std::move(d_mf[k][j]);
+    D.ready.store(true, std::memory_order_release);
 }
 
 void FH_FN(poseidon_dev)(const u64* d_inp, uint64_t n, uint32_t n_in, const u64* d_init, uint32_t n_out, u64* d_out, hipStream_t st) {

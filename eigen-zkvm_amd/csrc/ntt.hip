@@ -228,19 +228,13 @@ __global__ void ntt_small_kernel(const u64* in, u64* out, u32 np, u32 n_in, u32 
 }
 
 // ---- host side: tables + plan -------------------------------------------------------------
-struct Tables { u64 *w256 = nullptr, *w256s = nullptr, *lo = nullptr, *hi = nullptr, *mid = nullptr; u32 dshift = 0; };
-struct ScaleTables { u64 *lo = nullptr, *hi = nullptr; };
+struct Tables { DevConst w256, w256s, lo, hi, mid; u32 dshift = 0; };
+struct ScaleTables { DevConst lo, hi; };
 
+// kept for the life of the process, per device; the maps are never destroyed (DevConst, zk_internal.h)
 std::mutex g_mu;
-std::map<std::pair<int, std::pair<u32, int>>, Tables> g_tables;      // (device,(nbits,inverse))
-std::map<std::pair<int, std::pair<u32, u64>>, ScaleTables> g_scales;  // (device,(nbits,g))
-
-u64* upload(const std::vector<u64>& v) {
-    u64* d = nullptr;
-    ZK_HIP(hipMalloc((void**)&d, v.size() * sizeof(u64)));
-    ZK_HIP(hipMemcpy(d, v.data(), v.size() * sizeof(u64), hipMemcpyHostToDevice));
-    return d;
-}
+auto& g_tables = *new std::map<std::pair<int, std::pair<u32, int>>, Tables>;       // (device,(nbits,inverse))
+auto& g_scales = *new std::map<std::pair<int, std::pair<u32, u64>>, ScaleTables>;  // (device,(nbits,g))
 
 void two_level(u64 base, u64 cst, u32 nbits, std::vector<u64>& lo, std::vector<u64>& hi) {
     lo.resize(TW_LO);
@@ -253,7 +247,7 @@ void two_level(u64 base, u64 cst, u32 nbits, std::vector<u64>& lo, std::vector<u
     for (size_t i = 0; i < nh; ++i) { hi[i] = c; c = gl::hmul(c, step); }
 }
 
-Tables get_tables(u32 nbits, bool inverse) {
+const Tables& get_tables(u32 nbits, bool inverse) {
     int dev; ZK_HIP(hipGetDevice(&dev));
     std::lock_guard<std::mutex> lk(g_mu);
     auto key = std::make_pair(dev, std::make_pair(nbits, (int)inverse));
@@ -265,12 +259,12 @@ Tables get_tables(u32 nbits, bool inverse) {
     u64 c = 1;
     for (int i = 0; i < 256; ++i) { t256[i] = c; c = gl::hmul(c, w8); }
     two_level(w, 1, nbits, lo, hi);
-    Tables T; T.w256 = upload(t256); T.lo = upload(lo); T.hi = upload(hi);
+    Tables T; T.w256 = DevConst(t256); T.lo = DevConst(lo); T.hi = DevConst(hi);
     if (inverse) {  // w_256^-e / N: folds the inverse transform's 1/N into sub-step A of its last pass
         const u64 ninv = gl::hinv((1ull << nbits) % GL_P);
         std::vector<u64> t256s(256);
         for (int i = 0; i < 256; ++i) t256s[i] = gl::hmul(t256[i], ninv);
-        T.w256s = upload(t256s);
+        T.w256s = DevConst(t256s);
     }
     {   // direct table for passes with L <= 2^16: w_N^(i << dshift)
         T.dshift = nbits > 16 ? nbits - 16 : 0;
@@ -279,13 +273,12 @@ Tables get_tables(u32 nbits, bool inverse) {
         const u64 step = gl::hpow(w, 1ull << T.dshift);
         c = 1;
         for (size_t i = 0; i < nm; ++i) { mid[i] = c; c = gl::hmul(c, step); }
-        T.mid = upload(mid);
+        T.mid = DevConst(mid);
     }
-    g_tables[key] = T;
-    return T;
+    return g_tables.emplace(key, std::move(T)).first->second;
 }
 
-ScaleTables get_scale(u32 nbits, u64 g, u64 cst) {  // cst * g^k, k < 2^nbits
+const ScaleTables& get_scale(u32 nbits, u64 g, u64 cst) {  // cst * g^k, k < 2^nbits
     int dev; ZK_HIP(hipGetDevice(&dev));
     std::lock_guard<std::mutex> lk(g_mu);
     auto key = std::make_pair(dev, std::make_pair(nbits, g));
@@ -293,9 +286,8 @@ ScaleTables get_scale(u32 nbits, u64 g, u64 cst) {  // cst * g^k, k < 2^nbits
     if (it != g_scales.end()) return it->second;
     std::vector<u64> lo, hi;
     two_level(g, cst, nbits, lo, hi);
-    ScaleTables S; S.lo = upload(lo); S.hi = upload(hi);
-    g_scales[key] = S;
-    return S;
+    ScaleTables S; S.lo = DevConst(lo); S.hi = DevConst(hi);
+    return g_scales.emplace(key, std::move(S)).first->second;
 }
 
 template <int LOGA, int LOGB>
@@ -356,9 +348,8 @@ void run_transform(const u64* in, u64* a, u64* b, /* ping-pong, result must land
     }
     const std::vector<int> radices = plan(nbits);
     const int np = (int)radices.size();
-    Tables T = get_tables(nbits, inverse);
-    ScaleTables S;
-    if (sc.on) S = get_scale(nbits, sc.g, sc.cst);
+    const Tables& T = get_tables(nbits, inverse);
+    const ScaleTables* S = sc.on ? &get_scale(nbits, sc.g, sc.cst) : nullptr;
     u32 log_s = 0;
     const u64* cur = in;
     for (int i = 0; i < np; ++i) {
@@ -367,16 +358,16 @@ void run_transform(const u64* in, u64* a, u64* b, /* ping-pong, result must land
         const bool last = (i == np - 1);
         PassParams P{};
         P.in = cur; P.out = dstbuf;
-        P.w256 = T.w256; P.tw_lo = T.lo; P.tw_hi = T.hi;
-        P.sc_lo = (last && sc.on) ? S.lo : nullptr;
-        P.sc_hi = (last && sc.on) ? S.hi : nullptr;
+        P.w256 = T.w256.u(); P.tw_lo = T.lo.u(); P.tw_hi = T.hi.u();
+        P.sc_lo = (last && sc.on) ? S->lo.u() : nullptr;
+        P.sc_hi = (last && sc.on) ? S->hi.u() : nullptr;
         const int loga = (logr + 1) / 2;
         P.sc_step = (last && sc.on) ? gl::hpow(sc.g, (1ull << loga) << log_s) : 1;
         P.out_scale = 1; P.pre_scale = 1;
         if (last && !sc.on && out_scale != 1) {
             // the only constant scaling in use is the inverse transform's 1/N (ntt_dev)
             ZK_REQUIRE(inverse && out_scale == gl::hinv(n % GL_P), "ntt: unsupported constant scaling");
-            P.w256 = T.w256s; P.pre_scale = out_scale;
+            P.w256 = T.w256s.u(); P.pre_scale = out_scale;
         }
         P.inner = (n >> logr) * n_pols;
         P.valid_in = (i == 0) ? valid_rows * n_pols : n * n_pols;
@@ -385,7 +376,7 @@ void run_transform(const u64* in, u64* a, u64* b, /* ping-pong, result must land
         P.log_s = log_s;
         P.has_tw = last ? 0 : 1;
         P.dshift = T.dshift;
-        P.tw_mid = (!last && log_s >= T.dshift) ? T.mid : nullptr;  // L = N >> log_s <= 2^16
+        P.tw_mid = (!last && log_s >= T.dshift) ? T.mid.u() : nullptr;  // L = N >> log_s <= 2^16
         const bool kmode = P.s_np < 16;
         launch_pass_logr(logr, P, kmode, inverse, st);
         cur = dstbuf;
@@ -397,7 +388,7 @@ void run_transform(const u64* in, u64* a, u64* b, /* ping-pong, result must land
 
 int ntt_num_passes(uint32_t nbits) { return nbits < 4 ? 1 : (int)plan(nbits).size(); }
 
-const u64* ntt_w256_table(bool inverse) { return get_tables(8, inverse).w256; }
+const u64* ntt_w256_table(bool inverse) { return get_tables(8, inverse).w256.u(); }
 
 void ntt_dev(const u64* d_src, u64* d_dst, u64* d_tmp, uint32_t n_pols, uint32_t nbits, bool inverse, hipStream_t st) {
     ZK_REQUIRE(nbits <= 32, "ntt: nbits > 32");

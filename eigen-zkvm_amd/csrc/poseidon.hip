@@ -1054,23 +1054,23 @@ void merkelize_dev(const u64* d_rows, uint32_t width, uint64_t height, u64* d_no
         while ((1ull << levels) < height) ++levels;
         // digest of an all-zero subtree of every height up to 2^32: a property of the hash, not of the proof --
         // computed once per device (33 serial permutations, 3 ms) and kept
-        static u64* g_zero_chain[64] = {};
+        static DevConst* const g_zero_chain = new DevConst[64];   // never destroyed (DevConst, zk_internal.h)
         static std::mutex g_zero_chain_mu;
         int dev; ZK_HIP(hipGetDevice(&dev));
         ZK_REQUIRE(levels <= 32, "merkelize: tree too tall");
+        const u64* d_h;
         {   // provers on several host threads, each on its own stream: the chain is built once, under the lock, and is in memory
             // before its address is published (a second prover's fill kernels run on another stream and would not wait for this one)
             std::lock_guard<std::mutex> lk(g_zero_chain_mu);
-            if (!g_zero_chain[dev]) {
-                u64* d = nullptr;
-                ZK_HIP(hipMalloc((void**)&d, 33 * 32));
-                hipLaunchKernelGGL(zero_tree_chain_kernel, dim3(1), dim3(64), 0, st, 32u, d);
+            if (!g_zero_chain[dev].p) {
+                DevConst d(33 * 32);
+                hipLaunchKernelGGL(zero_tree_chain_kernel, dim3(1), dim3(64), 0, st, 32u, d.u());
                 ZK_HIP(hipGetLastError());
                 ZK_HIP(hipStreamSynchronize(st));
-                g_zero_chain[dev] = d;
+                g_zero_chain[dev] = std::move(d);
             }
+            d_h = g_zero_chain[dev].u();
         }
-        const u64* d_h = g_zero_chain[dev];
         uint64_t n = height, off = 0;
         for (uint32_t l = 1; l <= levels; ++l) {  // level l has height >> l nodes, starting after level l-1
             off += n; n >>= 1;

@@ -614,13 +614,7 @@ zk_stark_setup* setup_new(const char* json, const char* ss_json, const uint64_t*
         size_t total = 0; for (size_t b : sizes) total += b;
         const char* pw = getenv("ZK_STARK_PREWARM");
         if (total >= (1ull << 30) && !(pw && !strcmp(pw, "0"))) {
-            int dev = 0; ZK_HIP(hipGetDevice(&dev));
-            prewarm = std::async(std::launch::async, [sizes, dev] {
-                if (hipSetDevice(dev) != hipSuccess) return;
-                std::vector<void*> held;
-                try { for (size_t b : sizes) held.push_back(pool_alloc(b)); } catch (...) {}       // out of memory: what fits is parked, the proof asks for the rest
-                for (void* q : held) pool_free(q);
-            });
+            prewarm = pool_reserve_async(std::move(sizes));
         }
     }
     S->const_n.reserve(std::max<u64>(1, nc * N) * 8); S->const_2ns.reserve(std::max<u64>(1, nc * Next) * 8);
@@ -1306,23 +1300,12 @@ std::string stark_gen(zk_stark_setup& S, const uint64_t* cm_pols, const u64* d_c
     return zkin;
 }
 
-struct DeferFlush { ~DeferFlush() { pool_defer_flush(); } };   // after stark_gen's locals are gone (also when it throws)
-
 // prove.rs:124-132: `assert!(stark_verify(...))` on the fresh proof, opt-in per setup (zk_stark_setup_set_self_check)
 void self_check(const zk_stark_setup& S, const std::string& zkin) {
     if (!S.self_check) return;
     pool_defer_flush();                                   // the proof's buffers go back before the verifier asks for its own
     std::string why;
     if (!stark_verify_impl(S.info, S.prog, S.ss, S.const_root, zkin.c_str(), why)) throw Error("stark_gen: the proof does not verify: " + why);
-}
-
-template <class F>
-int guard(F&& f) {
-    CallScope scope;
-    DeferFlush flush;
-    try { f(); return 0; }
-    catch (const std::exception& e) { set_error(e.what()); return -1; }
-    catch (...) { set_error("unknown error"); return -1; }
 }
 
 }  // namespace
@@ -1369,7 +1352,7 @@ char* zk_stark_gen_dev_on(zk_stark_setup_t* s, const uint64_t* d_cm_pols, uint64
             const auto t0 = std::chrono::steady_clock::now();
             const std::string z = stark_gen(*s, nullptr, K(d_cm_pols), n_words, (hipStream_t)stream);
             pool_defer_flush();                                        // stark_gen's locals are gone: their blocks are stamped with one set of events and released HERE,
-            const auto t1 = std::chrono::steady_clock::now();          // inside host_release_ms (the guard's DeferFlush only covers the error paths now)
+            const auto t1 = std::chrono::steady_clock::now();          // inside host_release_ms (the call scope's flush only covers the error paths now)
             self_check(*s, z);
             const auto t2 = std::chrono::steady_clock::now();
             out = (char*)malloc(z.size() + 1);

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <future>
 #include <string>
 #include <stdexcept>
 #include <vector>
@@ -14,6 +15,7 @@ namespace zk {
 
 // ---- error handling: C ABI returns int status, message kept per thread (include/zkgpu.h) ----
 void set_error(const std::string& msg);
+const char* last_error();
 struct Error : std::runtime_error { using std::runtime_error::runtime_error; };
 
 #define ZK_HIP(expr)                                                                              \
@@ -28,9 +30,9 @@ struct Error : std::runtime_error { using std::runtime_error::runtime_error; };
     do { if (!(cond)) throw zk::Error(std::string(msg)); } while (0)
 
 // ---- device buffers ----
-// Size-keyed free list in front of hipMalloc/hipFree (capi.hip): a prover allocates the same
-// multi-GB sections for every proof, and hipFree/hipMalloc of such buffers costs hundreds of ms and
-// synchronises the device.  Reuse is ordered across streams: every host thread keeps the set of streams it has
+// Size-keyed free list in front of the driver's allocator (devmem.hip): a prover allocates the same
+// multi-GB sections for every proof, and returning such buffers to the driver and asking for them again
+// costs hundreds of ms and synchronises the device.  Reuse is ordered across streams: every host thread keeps the set of streams it has
 // issued on (`on_stream`); pool_free records an event on the null stream and on each stream of the freeing thread,
 // and pool_alloc makes the calling thread's current stream wait for the events of the block it hands out, so a
 // block freed with kernels still in flight on stream A is never written early by stream B -- while provers running
@@ -42,17 +44,21 @@ void d2h_sync(void* h, const void* d, size_t n);
 void pool_free(void* p);
 void pool_defer_begin();   // frees of this thread are collected until pool_defer_flush() stamps them with one set of events
 void pool_defer_flush();
-void pool_trim();  // hipFree everything cached
+void pool_trim();  // everything cached goes back to the driver
+// takes blocks of these sizes on a helper thread and parks them in the free list; until the future is ready an allocation
+// that runs out of memory waits for the helper before it trims
+std::future<void> pool_reserve_async(std::vector<size_t> sizes);
 // registers `st` as a stream the library works on and makes it the calling thread's current stream (the one
 // pool_alloc orders reuse against); returns st.  Every entry point that takes a stream goes through it.
 hipStream_t on_stream(hipStream_t st);
 hipStream_t cur_stream();
 // Scope of one C-ABI call: a call from outside the library starts on the null stream, a call the prover makes on its own
 // entry points inherits the prover's current stream; either way the caller's current stream is back when the call returns.
+void set_device(int d);                // zk_init: the GPU of the process
 void bind_device() noexcept;           // the calling thread onto the GPU zk_init selected (HIP's current device is per thread)
 struct CallScope { hipStream_t saved; CallScope(); ~CallScope(); CallScope(const CallScope&) = delete; CallScope& operator=(const CallScope&) = delete; };
 void forget_stream(hipStream_t st);  // call before destroying a registered stream, or when a side stream's work has been waited for
-void on_side_stream(hipStream_t ss); // a helper stream inside one call (see capi.hip); pairs with forget_stream
+void on_side_stream(hipStream_t ss); // a helper stream inside one call (see devmem.hip); pairs with forget_stream
 
 struct DevBuf {
     void* p = nullptr; size_t bytes = 0;
@@ -67,6 +73,36 @@ struct DevBuf {
     u64* u() const { return (u64*)p; }
     void release() { if (p) { pool_free(p); p = nullptr; bytes = 0; } }
 };
+
+// A device block that lives as long as the process: constant tables, built once per device.  Not the pool's: never recycled, and
+// pool_trim() does not touch it.  The owner frees the block only when it is destroyed before it was published (an upload or a later
+// table's construction threw); where it is kept for good it sits in an object that is never destroyed (`*new`), because a static
+// destructor would give memory back after the HIP runtime's own teardown.
+void* const_alloc(size_t bytes);
+void const_free(void* p) noexcept;
+struct DevConst {
+    void* p = nullptr;
+    DevConst() = default;
+    explicit DevConst(size_t bytes) : p(const_alloc(bytes)) {}                           // filled by a kernel of the caller
+    DevConst(const void* h, size_t bytes) : p(const_alloc(bytes)) {                      // filled from host memory, here
+        const hipError_t e = bytes ? hipMemcpy(p, h, bytes, hipMemcpyHostToDevice) : hipSuccess;
+        if (e != hipSuccess) { (void)hipGetLastError(); const_free(p); throw Error(std::string("uploading a constant table failed: ") + hipGetErrorString(e)); }
+    }
+    template <class T> explicit DevConst(const std::vector<T>& v) : DevConst(v.data(), v.size() * sizeof(T)) {}
+    DevConst(DevConst&& o) noexcept : p(o.p) { o.p = nullptr; }
+    DevConst& operator=(DevConst&& o) noexcept { if (this != &o) { const_free(p); p = o.p; o.p = nullptr; } return *this; }
+    ~DevConst() { const_free(p); }
+    u64* u() const { return (u64*)p; }
+};
+
+// One C-ABI call that returns a status: the call's scope, and what it throws kept for zk_last_error()
+template <class F>
+int guard(F&& f) {
+    CallScope scope;
+    try { f(); return 0; }
+    catch (const std::exception& e) { set_error(e.what()); return -1; }
+    catch (...) { set_error("unknown error"); return -1; }
+}
 
 // ---- run-time compiled kernels (expr_jit.hip): what the code-object cache did so far in this process ----
 struct JitStats { uint64_t compiled = 0, disk_hits = 0, mem_hits = 0, spawned = 0; double ms = 0; };   // spawned: compilations done by a helper process (of `compiled`)

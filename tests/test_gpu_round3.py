@@ -68,7 +68,7 @@ def test_stage_timers_and_setup_timing(zk, orc):
 
 def test_threads_prove_on_the_device_of_zk_init(zk):
     """HIP's current device belongs to the host thread and a new thread starts on device 0: after zk_init(d) every thread that
-    calls into the library is bound to d (csrc/capi.hip bind_device) -- the prover threads of rank k > 0 must not land on GPU 0.
+    calls into the library is bound to d (csrc/devmem.hip bind_device) -- the prover threads of rank k > 0 must not land on GPU 0.
     One GPU here: the binding is exercised (a fresh thread allocates, transforms, hashes and frees), a device that does not
     exist is refused and leaves the binding alone."""
     import threading

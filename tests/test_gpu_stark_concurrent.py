@@ -1,7 +1,7 @@
 """Proofs of different setups running at the same time, each from its own host thread on its own non-blocking stream
 (zk_stark_gen_dev_on): every proof must be the proof the same setup gives alone on the default stream.  This is how the
 recursion tasks of BASELINE config 5 share one GPU (test/stark_aggregation.sh:70-73 runs them as parallel processes), and it
-exercises the cross-stream ordering of the caching allocator (csrc/capi.hip)."""
+exercises the cross-stream ordering of the caching allocator (csrc/devmem.hip)."""
 import json
 import pathlib
 import sys
