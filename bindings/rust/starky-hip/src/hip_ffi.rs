@@ -20,6 +20,35 @@ pub struct zk_stark_setup_t {
 pub struct zk_stark_ctx_t {
     _private: [u8; 0],
 }
+/// a step program behind either evaluator (zk_program_kind: ZK_EVAL_*)
+#[repr(C)]
+pub struct zk_program_t {
+    _private: [u8; 0],
+}
+/// zk_operand / zk_instr of include/zkgpu.h (interpreter.rs:187-225: one Section with its Nodes resolved to addresses)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct zk_operand {
+    pub kind: u8,
+    pub dim: u8,
+    pub prime: u8,
+    pub buf: u8,
+    pub id: u32,
+    pub stride: u32,
+    pub _pad: u32,
+    pub value: u64,
+}
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct zk_instr {
+    pub op: u32,
+    pub _pad: u32,
+    pub dest: zk_operand,
+    pub src: [zk_operand; 2],
+}
+/// the evaluator of a setup's step programs: run-time compiled kernels (the default) or bytecode for the interpreter kernel
+pub const ZK_EVAL_JIT: c_int = 0;
+pub const ZK_EVAL_BYTECODE: c_int = 1;
 pub const ZK_STEP_2PREV: c_int = 0;
 pub const ZK_STEP_3PREV: c_int = 1;
 pub const ZK_STEP_3: c_int = 2;
@@ -87,6 +116,10 @@ extern "C" {
     /// FRI::prove(transcript, pol, query_pol) alone: the caller's TranscriptGL, a device polynomial, the trees its queries open
     pub fn zk_fri_prove_dev(transcript: *mut zk_transcript_t, d_pol: *const u64, nbits_ext: u32, steps: *const u32, n_steps: u32, n_queries: u32,
                             query_trees: *const *const zk_merkle_t, n_query_trees: u32, stream: *mut c_void) -> *mut c_char;
+    pub fn zk_program_assemble(code: *const zk_instr, n_instr: u32) -> *mut zk_program_t;
+    pub fn zk_program_kind(p: *const zk_program_t) -> c_int;
+    /// the calling thread's mode for the setups it creates next; returns the previous one
+    pub fn zk_eval_set_mode(mode: c_int) -> c_int;
     pub fn zk_stream_new() -> *mut c_void;
     pub fn zk_stream_sync(stream: *mut c_void) -> c_int;
     pub fn zk_stream_free(stream: *mut c_void) -> c_int;

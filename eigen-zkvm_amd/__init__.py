@@ -30,7 +30,7 @@ EXPORTS = [
     "zk_transcript_free",
     "zk_fri_fold_dev", "zk_fri_transpose_dev", "zk_stark_x_table_dev", "zk_stark_zh_inv_dev",
     "zk_stark_xdivxsub_dev", "zk_stark_lev_dev", "zk_stark_evals_dev", "zk_stark_qsplit_dev",
-    "zk_stream_new", "zk_stream_sync", "zk_stream_free", "zk_program_compile", "zk_program_source", "zk_jit_cache_stats", "zk_program_run_dev", "zk_program_run_rows_dev", "zk_program_free",
+    "zk_stream_new", "zk_stream_sync", "zk_stream_free", "zk_program_compile", "zk_program_assemble", "zk_program_kind", "zk_eval_set_mode", "zk_program_source", "zk_jit_cache_stats", "zk_program_run_dev", "zk_program_run_rows_dev", "zk_program_free",
     "zk_stark_get_pol_dev", "zk_stark_set_pol_dev", "zk_stark_calculate_h1h2_dev", "zk_stark_calculate_z_dev",
     "zk_msm_g1_bn254", "zk_msm_g1_bn254_dev", "zk_g1_bn254_mul_generator_dev",
     "zk_msm_g1_bls12_381", "zk_msm_g1_bls12_381_dev", "zk_g1_bls12_381_mul_generator_dev",
@@ -55,6 +55,8 @@ EXPORTS = [
 
 # include/zkgpu.h enums
 OP_ADD, OP_SUB, OP_MUL, OP_COPY = 0, 1, 2, 3
+EVAL_JIT, EVAL_BYTECODE = 0, 1
+_EVAL_MODES = {"jit": EVAL_JIT, "bytecode": EVAL_BYTECODE}
 (OPND_TMP, OPND_MEM, OPND_NUMBER, OPND_PUBLIC, OPND_CHALLENGE, OPND_EVAL, OPND_X, OPND_ZI,
  OPND_XDIVXSUBXI, OPND_XDIVXSUBWXI) = range(10)
 
@@ -256,6 +258,9 @@ def _load():
         "zk_msm_g2_bls12_381_dev": (C.c_int, [vp, vp, C.c_uint64, vp, vp]),
         "zk_g2_bls12_381_mul_generator_dev": (C.c_int, [vp, C.c_uint64, vp, vp]),
         "zk_program_compile": (vp, [C.POINTER(Instr), C.c_uint32]),
+        "zk_program_assemble": (vp, [C.POINTER(Instr), C.c_uint32]),
+        "zk_program_kind": (C.c_int, [vp]),
+        "zk_eval_set_mode": (C.c_int, [C.c_int]),
         "zk_program_source": (C.c_char_p, [vp]),
         "zk_jit_cache_stats": (None, [vp]),
         "zk_stream_new": (vp, []), "zk_stream_sync": (C.c_int, [vp]), "zk_stream_free": (C.c_int, [vp]),
@@ -552,14 +557,33 @@ def instr(op, dest, src0, src1=None):
     return i
 
 
-class Program:
-    """compile_code + Block::eval (interpreter.rs:187-225, :91-175) as one run-time compiled kernel."""
+def set_eval_mode(mode):
+    """zk_eval_set_mode: the evaluator ("jit" | "bytecode") the calling thread's next setups build their programs for;
+    returns the previous one"""
+    if mode not in _EVAL_MODES:
+        raise ZkError(f"eval mode must be one of {sorted(_EVAL_MODES)}, not {mode!r}")
+    prev = lib().zk_eval_set_mode(_EVAL_MODES[mode])
+    if prev < 0:
+        raise ZkError(lib().zk_last_error().decode())
+    return "bytecode" if prev == EVAL_BYTECODE else "jit"
 
-    def __init__(self, instrs):
+
+class Program:
+    """compile_code + Block::eval (interpreter.rs:187-225, :91-175): mode="jit", one run-time compiled kernel
+    (zk_program_compile); mode="bytecode", bytecode for the interpreter kernel inside libzkgpu (zk_program_assemble)."""
+
+    def __init__(self, instrs, mode="jit"):
+        if mode not in _EVAL_MODES:
+            raise ZkError(f"eval mode must be one of {sorted(_EVAL_MODES)}, not {mode!r}")
         arr = (Instr * len(instrs))(*instrs)
-        self._h = lib().zk_program_compile(arr, len(instrs))
+        self._h = None
+        self._h = (lib().zk_program_assemble if mode == "bytecode" else lib().zk_program_compile)(arr, len(instrs))
         if not self._h:
             raise ZkError(lib().zk_last_error().decode())
+
+    @property
+    def kind(self):
+        return "bytecode" if lib().zk_program_kind(self._h) == EVAL_BYTECODE else "jit"
 
     @property
     def source(self):

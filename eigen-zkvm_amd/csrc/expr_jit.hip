@@ -146,22 +146,16 @@ struct Gen {
     static constexpr uint32_t CHUNK = 19;   // columns per staged chunk: 64 x 19 x 8 B per wave, four blocks of four waves per CU
     std::map<uint32_t, Val> tmp;                                   // tmp id -> current SSA value
     std::map<std::pair<uint32_t, uint32_t>, Val> fwd, fwd_prime;   // (buf, column) -> value this lane wrote at row i / i+next
-    // Rows are evaluated concurrently (one lane per row), the reference evaluates them in order inside a chunk
-    // (stark_gen.rs:752-783).  The two agree unless one row's lane reads a cell another row's lane writes: a write at row
-    // i and a read of an overlapping cell range at row i+next, in either order.  Reads served from this lane's own
+    // Rows are evaluated concurrently (one lane per row): the cross-lane hazard and its check are shared with the bytecode
+    // evaluator (zk_internal.h check_row_hazards).  Reads served from this lane's own
     // earlier store (fwd / fwd_prime) never reach memory and are not recorded.  Two writes of one cell (the code generator
     // stores an expression both at row i and, primed, at row i+next: t and t' of a plookup) carry the same field element
     // -- the same expression evaluated at the same row -- whichever lane lands last.
-    struct Access { uint32_t buf, id, dim; bool prime; };
+    using Access = EvalAccess;
     std::vector<Access> mem_reads, mem_writes;
     std::map<std::tuple<uint32_t, uint32_t, uint32_t, bool>, Val> loaded;   // cells already read in the prologue
-    static bool overlap(const Access& a, const Access& b) { return a.buf == b.buf && a.id < b.id + b.dim && b.id < a.id + a.dim; }
-    void check_row_hazards() const {
-        for (const Access& w : mem_writes) {
-            for (const Access& r : mem_reads)
-                ZK_REQUIRE(!(overlap(w, r) && w.prime != r.prime), "eval program: a column is written at one row and read at the next row in the same step");
-        }
-    }
+    static bool overlap(const Access& a, const Access& b) { return eval_overlap(a, b); }
+    void check_row_hazards() const { zk::check_row_hazards(mem_writes, mem_reads); }
     int n_val = 0;
     std::map<int, int> max_exp;                                     // challenge id -> highest power a materialised chain needs
     std::vector<ChainConst> chain_consts;
@@ -636,7 +630,17 @@ struct zk_program {
     uint32_t n_instr = 0;
     uint32_t pow_entries = 0;      // (challenge, exponent) pairs of the power table, 6 words each
     DevBuf d_pow;                  // the table itself, written by zk_pow_kernel in front of every run
+    Bytecode* bc = nullptr;        // zk_program_assemble: the program of the interpreter kernel instead (expr_bytecode.hip); none of the above is used
+    ~zk_program() { if (bc) bytecode_free(bc); }
 };
+namespace zk {
+zk_program* program_of_bytecode(Bytecode* b) {
+    zk_program* p = nullptr;
+    try { p = new zk_program(); } catch (...) { bytecode_free(b); throw; }
+    p->bc = b;
+    return p;
+}
+}
 
 extern "C" {
 
@@ -703,7 +707,8 @@ zk_program_t* zk_program_compile(const zk_instr* code, uint32_t n_instr) {
     } catch (const std::exception& e) { set_error(e.what()); delete p; return nullptr; }
 }
 
-const char* zk_program_source(const zk_program_t* p) { return p ? p->source.c_str() : ""; }
+const char* zk_program_source(const zk_program_t* p) { return !p ? "" : p->bc ? bytecode_listing(p->bc) : p->source.c_str(); }
+int zk_program_kind(const zk_program_t* p) { return p && p->bc ? ZK_EVAL_BYTECODE : ZK_EVAL_JIT; }
 
 void zk_jit_cache_stats(uint64_t out[3]) {
     const JitStats j = jit_stats();
@@ -723,6 +728,7 @@ int zk_program_run_rows_dev(zk_program_t* p, const zk_eval_ctx* ctx, uint32_t nb
         ZK_REQUIRE(row0 <= (1ull << nbits_domain) && count <= (1ull << nbits_domain) - row0, "zk_program_run_rows_dev: rows outside the domain");
         if (count == 0) return 0;
         const hipStream_t st = on_stream((hipStream_t)stream);   // first: the power table, a pooled block, is ordered behind its previous users on this stream
+        if (p->bc) { bytecode_run(p->bc, ctx, nbits_domain, next, row0, count, st); return 0; }
         if (!p->module) {  // load lazily: compiling needs no GPU, running does
             auto load = [&]() -> hipError_t {
                 hipError_t e = hipModuleLoadData(&p->module, p->code->bytes.data());

@@ -261,6 +261,7 @@ struct zk_stark_setup {
     std::atomic<int> early_ctx_live{0};    // contexts that currently use side_stream / ev_inputs / ev_stage3 (at most one)
     hipStream_t side_stream = nullptr;     // memory-bound stage-3 work beside the ALU-bound hashing of tree 1
     hipEvent_t ev_inputs = nullptr, ev_stage3 = nullptr;
+    int eval_mode = ZK_EVAL_JIT;           // which evaluator the step and public programs are built for: read once, on the thread that creates the setup
     std::string setup_timing;              // JSON: where StarkSetup::new's time went (zk_stark_setup_timing)
     std::string last_timing;               // JSON: the stages of the last proof, HIP-event milliseconds (ZK_STARK_TIMING=1)
     std::chrono::steady_clock::time_point t_json_begin, t_json_end;   // host time of the last proof's serialisation (timing runs only)
@@ -305,7 +306,7 @@ struct zk_stark_setup {
         return o;
     }
 
-    // compile_code (interpreter.rs:187-225): Segment.first -> one run-time compiled kernel
+    // compile_code (interpreter.rs:187-225): Segment.first -> one run-time compiled kernel, or bytecode for the interpreter kernel
     ProgramPtr compile_segment(const JVal& seg, bool ext, bool ret_to_scratch) const {
         const JVal& first = seg.at("first");
         std::vector<zk_instr> code;
@@ -329,8 +330,8 @@ struct zk_stark_setup {
             in.src[0] = resolve(first.arr.back().at("dest"), ext);
             code.push_back(in);
         }
-        if (code.empty()) return ProgramPtr();
-        zk_program_t* p = zk_program_compile(code.data(), (u32)code.size());
+        if (code.empty() && eval_mode != ZK_EVAL_BYTECODE) return ProgramPtr();   // (bytecode: an empty step is an empty program, a run of it does nothing: every program of the setup is the interpreter's)
+        zk_program_t* p = eval_mode == ZK_EVAL_BYTECODE ? zk_program_assemble(code.data(), (u32)code.size()) : zk_program_compile(code.data(), (u32)code.size());
         if (!p) throw Error(zk_last_error());
         return ProgramPtr(p);
     }
@@ -579,8 +580,9 @@ zk_stark_setup* setup_new(const char* json, const char* ss_json, const uint64_t*
     // Round 6: they start HERE, before the constants are uploaded, extended and merkelized -- the compilers are other processes on
     // host cores, the constants are copies and kernels: 0.6 s of a 2^24-row cold setup that used to stand in front of the 2.1 s of hipRTC.
     // (The futures block in their destructors: an exception below still waits for the threads that read S.)
+    S->eval_mode = eval_mode();                            // this thread's: the programs are built on threads of their own, which would see their own
     const zk_stark_setup* Sc = S.get();
-    const bool spawn = !getenv("ZK_JIT_INPROCESS");        // side by side really means one compiler process each (expr_jit.hip); the switch keeps hipRTC in this process
+    const bool spawn = S->eval_mode != ZK_EVAL_BYTECODE && !getenv("ZK_JIT_INPROCESS");        // side by side really means one compiler process each (expr_jit.hip); the switch keeps hipRTC in this process
     auto start = [Sc, spawn](const JVal& seg, bool ext, bool ret) {
         return std::async(std::launch::async, [Sc, &seg, ext, ret, spawn] {
             jit_prefer_spawn(spawn && seg.at("first").size() >= 32);            // (a handful of instructions compiles faster than a process starts)
@@ -657,11 +659,15 @@ zk_stark_setup* setup_new(const char* json, const char* ss_json, const uint64_t*
         // setup alive wants the split): JSON parsing, upload + extension + tree of the constants, kernel generation / compilation
         const clk::time_point t_jit = clk::now();         // (includes the wait for the pool's pre-sizing, reported on its own)
         const JitStats j1 = jit_stats();
+        u32 n_bytecode = 0;
+        for (const ProgramPtr* p : {&S->step2prev, &S->step3prev, &S->step3, &S->step42ns, &S->step52ns}) n_bytecode += *p && zk_program_kind(p->get()) == ZK_EVAL_BYTECODE;
+        for (const ProgramPtr& p : S->public_programs) n_bytecode += p && zk_program_kind(p.get()) == ZK_EVAL_BYTECODE;
         std::ostringstream o; o.setf(std::ios::fixed); o.precision(3);
         o << "{\"json_parse_ms\":" << ms(t_begin, t_parsed) << ",\"const_lde_merkle_ms\":" << ms(t_parsed, t_tree) << ",\"programs_ms\":" << ms(t_parsed, t_programs)
           << ",\"programs_wait_after_constants_ms\":" << ms(t_tree, t_programs) << ",\"pool_prewarm_wait_ms\":" << ms(t_programs, t_jit)
           << ",\"hiprtc_compiled\":" << (j1.compiled - j0.compiled) << ",\"hiprtc_processes\":" << (j1.spawned - j0.spawned) << ",\"code_cache_disk_hits\":" << (j1.disk_hits - j0.disk_hits)
-          << ",\"code_cache_mem_hits\":" << (j1.mem_hits - j0.mem_hits) << ",\"total_ms\":" << ms(t_begin, t_jit) << "}";
+          << ",\"code_cache_mem_hits\":" << (j1.mem_hits - j0.mem_hits)
+          << ",\"eval_mode\":\"" << (S->eval_mode == ZK_EVAL_BYTECODE ? "bytecode" : "jit") << "\",\"bytecode_programs\":" << n_bytecode << ",\"total_ms\":" << ms(t_begin, t_jit) << "}";
         S->setup_timing = o.str();
         if (getenv("ZK_STARK_TIMING") && strcmp(getenv("ZK_STARK_TIMING"), "0")) fprintf(stderr, "[zkgpu stark_setup] %s\n", S->setup_timing.c_str());
     }

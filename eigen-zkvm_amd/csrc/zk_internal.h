@@ -11,6 +11,7 @@
 
 struct zk_merkle;
 struct zk_transcript;
+struct zk_program;
 namespace zk {
 
 // ---- error handling: C ABI returns int status, message kept per thread (include/zkgpu.h) ----
@@ -109,6 +110,29 @@ struct JitStats { uint64_t compiled = 0, disk_hits = 0, mem_hits = 0, spawned = 
 JitStats jit_stats();
 // the next compilations of this thread go to a helper process each (a setup compiling several step programs at once: hipRTC is serial inside one process)
 void jit_prefer_spawn(bool on);
+
+// ---- what both evaluators of a step program check (expr_jit.hip, expr_bytecode.hip) ----
+// Rows are evaluated concurrently (one lane per row), the reference evaluates them in order inside a chunk
+// (stark_gen.rs:752-783).  The two agree unless one row's lane reads a cell another row's lane writes: a write at row
+// i and a read of an overlapping cell range at row i+next, in either order.  Reads a lane takes from its own earlier
+// store are not recorded by either evaluator.
+struct EvalAccess { uint32_t buf, id, dim; bool prime; };
+inline bool eval_overlap(const EvalAccess& a, const EvalAccess& b) { return a.buf == b.buf && a.id < b.id + b.dim && b.id < a.id + a.dim; }
+inline void check_row_hazards(const std::vector<EvalAccess>& mem_writes, const std::vector<EvalAccess>& mem_reads) {
+    for (const EvalAccess& w : mem_writes) {
+        for (const EvalAccess& r : mem_reads)
+            ZK_REQUIRE(!(eval_overlap(w, r) && w.prime != r.prime), "eval program: a column is written at one row and read at the next row in the same step");
+    }
+}
+
+// ---- the bytecode evaluator (expr_bytecode.hip): the same step program, assembled for one precompiled interpreter kernel ----
+struct Bytecode;
+void bytecode_free(Bytecode* b);
+const char* bytecode_listing(const Bytecode* b);
+// `ctx` is a zk_eval_ctx; the caller has checked the row range and made `st` the thread's current stream
+void bytecode_run(Bytecode* b, const void* ctx, uint32_t nbits_domain, uint64_t next, uint64_t row0, uint64_t count, hipStream_t st);
+struct ::zk_program* program_of_bytecode(Bytecode* b);   // expr_jit.hip owns zk_program: wraps b (and owns it from here on)
+int eval_mode();                                       // the calling thread's ZK_EVAL_* (zk_eval_set_mode, initially $ZK_EVAL)
 
 // ---- NTT (ntt.hip) ----
 // natural-order batched NTT over a row-major [1<<nbits][n_pols] device matrix; dst != src.

@@ -359,14 +359,22 @@ class NativeStarkSetup:
     """The C++ driver inside libzkgpu (csrc/stark_prover.hip): StarkSetup::new + stark_gen + FRI::prove
     behind zk_stark_setup_new / zk_stark_gen.  `program_json` = '{"starkinfo": ..., "program": ...}' text."""
 
-    def __init__(self, const_n, program_json, stark_struct_json, prover_addr=None, self_check=False):
-        """self_check: every gen() verifies its own proof before returning it, as stark_prove does (prove.rs:124-132)"""
+    def __init__(self, const_n, program_json, stark_struct_json, prover_addr=None, self_check=False, eval_mode=None):
+        """self_check: every gen() verifies its own proof before returning it, as stark_prove does (prove.rs:124-132)
+        eval_mode: "jit" | "bytecode" -- the evaluator of this setup's step programs (None: the thread's current one,
+        initially $ZK_EVAL, default jit); bytecode compiles nothing at run time"""
         c = _np(const_n)
         hash_type = json.loads(stark_struct_json).get("verificationHashType")
         if hash_type in ("BN128", "BLS12381"):
             from . import bn128_init
             bn128_init(field=hash_type.lower())
-        self._h = lib().zk_stark_setup_new(program_json.encode(), stark_struct_json.encode(), _ptr(c), c.size)
+        from . import set_eval_mode
+        prev = set_eval_mode(eval_mode) if eval_mode is not None else None
+        try:
+            self._h = lib().zk_stark_setup_new(program_json.encode(), stark_struct_json.encode(), _ptr(c), c.size)
+        finally:
+            if prev is not None:
+                set_eval_mode(prev)
         if not self._h:
             raise ZkError(lib().zk_last_error().decode())
         if prover_addr is not None:

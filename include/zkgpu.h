@@ -313,7 +313,10 @@ int zk_stark_setup_set_self_check(zk_stark_setup_t* s, int on);
  *   code-object cache: $ZK_JIT_CACHE, default ~/.cache/zkgpu, "off" disables; `hiprtc_processes`: how many of the compilations ran
  *   in a helper process -- a setup compiles its step programs side by side, one `zkgpu_jitc` (next to libzkgpu.so; $ZK_JITC names
  *   another, "off" disables) per program, because hipRTC compiles serially inside one process; a code object is sha256-checked when it
- *   comes back from disk, and a cache directory that is not the user's own or is writable by others is not used).
+ *   comes back from disk, and a cache directory that is not the user's own or is writable by others is not used);
+ *   "eval_mode": "jit" | "bytecode" and "bytecode_programs": how many of the setup's programs are interpreter bytecode: in bytecode
+ *   mode the five steps (a step without code is an empty program) and every public calculator, otherwise 0 (then nothing was compiled:
+ *   hiprtc_compiled and the cache counters stay 0).
  * zk_stark_last_timing: the stages of the last proof of this setup in HIP-event milliseconds, named after the reference's
  *   spans (stark_gen.rs:192,624,709,734,785; fri.rs:83): extend, merkelize, calculate_exps_parallel, calculate_H1H2,
  *   calculate_Z, fri_prove, ...  Collected only when the environment has ZK_STARK_TIMING=1 (also logged to stderr); "" otherwise. */
@@ -455,7 +458,22 @@ int zk_c12_exec_free(zk_c12_exec_t* e);
  * zk_program_run_dev evaluates it for every row i of the domain, reading rows (i + next*prime) % N.
  * Value widths (the F3G dim) are inferred from the operands: dim-1 op dim-1 -> 1, anything with a
  * dim-3 operand -> 3 (f3g.rs:323-449); a dim-3 result written to a section cell occupies 3 words,
- * a dim-1 result 1 word (interpreter.rs:149-159).                                                */
+ * a dim-1 result 1 word (interpreter.rs:149-159).
+ *
+ * Two evaluators stand behind the same zk_program_t (zk_program_kind says which):
+ *   ZK_EVAL_JIT       zk_program_compile: the program becomes HIP text, compiled by hipRTC (seconds per step program of a
+ *                     large PIL, once per text: the code-object cache).  The fastest evaluation; the default.
+ *   ZK_EVAL_BYTECODE  zk_program_assemble: the program becomes bytecode for ONE interpreter kernel that is part of
+ *                     libzkgpu.so.  Nothing is compiled at run time: no hipRTC, no helper process, no cache; the values are the
+ *                     same canonical words.  zk_program_source returns its listing: one line per instruction, then a
+ *                     summary line "; slots: <words> (lds <words>, arena <words>) ...".  Temporaries live in slots numbered by
+ *                     liveness (per-wave LDS first, a pooled arena in HBM past the LDS budget: no program is too large).
+ *                     It executes in program order, so a read that partially overlaps an earlier write of the same row,
+ *                     which zk_program_compile rejects (it hoists reads), is accepted; every other rejection is shared.
+ * zk_eval_set_mode chooses, for the calling thread, what the NEXT zk_stark_setup_new builds its step and public programs
+ * with (the setup keeps its mode for life); it returns the previous mode (-1 and no change for an unknown mode).  A thread
+ * starts with $ZK_EVAL = "jit" | "bytecode" (default jit).                                               */
+enum { ZK_EVAL_JIT = 0, ZK_EVAL_BYTECODE = 1 };
 enum { ZK_OP_ADD = 0, ZK_OP_SUB = 1, ZK_OP_MUL = 2, ZK_OP_COPY = 3 };
 enum { ZK_OPND_TMP = 0, ZK_OPND_MEM = 1, ZK_OPND_NUMBER = 2, ZK_OPND_PUBLIC = 3, ZK_OPND_CHALLENGE = 4,
        ZK_OPND_EVAL = 5, ZK_OPND_X = 6, ZK_OPND_ZI = 7, ZK_OPND_XDIVXSUBXI = 8, ZK_OPND_XDIVXSUBWXI = 9 };
@@ -483,7 +501,10 @@ typedef struct {
 } zk_eval_ctx;
 typedef struct zk_program zk_program_t;
 zk_program_t* zk_program_compile(const zk_instr* code, uint32_t n_instr);    /* needs no GPU */
-const char* zk_program_source(const zk_program_t* p);                         /* generated HIP text */
+zk_program_t* zk_program_assemble(const zk_instr* code, uint32_t n_instr);   /* needs no GPU, no hipRTC */
+int zk_program_kind(const zk_program_t* p);                                   /* ZK_EVAL_* */
+int zk_eval_set_mode(int mode);
+const char* zk_program_source(const zk_program_t* p);                         /* generated HIP text / bytecode listing */
 /* what the code-object cache of the step kernels did so far in this process: out = {compiled by hipRTC, taken from
  * $ZK_JIT_CACHE (default ~/.cache/zkgpu; "off" disables), taken from memory} */
 void zk_jit_cache_stats(uint64_t out[3]);

@@ -18,7 +18,7 @@ def poseidong_main(args):
         pj = PG.program(nbits)
         const, cm = PG.consts(nbits), PG.trace(nbits, None, PG.FIRST_ZERO, seed=nbits)
         t0 = time.perf_counter()
-        setup = stark.NativeStarkSetup(const, json.dumps(pj), json.dumps(ss))
+        setup = stark.NativeStarkSetup(const, json.dumps(pj), json.dumps(ss), eval_mode=args.eval)
         zk.lib().zk_dev_sync()
         t_setup = time.perf_counter() - t0
         d_cm = zk.DevArray.from_host(cm)
@@ -26,7 +26,7 @@ def poseidong_main(args):
         for _ in range(args.reps):
             t0 = time.perf_counter(); proof = setup.gen(d_cm); times.append(time.perf_counter() - t0)
         out = {"workload": "PoseidonG PIL, nBits=%d, %s hash, %d queries" % (nbits, args.hash, ss["nQueries"]),
-               "setup_s": round(t_setup, 3), "setup_split": setup.setup_timing(), "stark_gen_ms": [round(t * 1e3, 1) for t in times], "root1": proof["root1"]}
+               "eval": setup.setup_timing().get("eval_mode"), "setup_s": round(t_setup, 3), "setup_split": setup.setup_timing(), "stark_gen_ms": [round(t * 1e3, 1) for t in times], "root1": proof["root1"]}
         if setup.last_timing(): out["stages_ms"] = setup.last_timing()
         t0 = time.perf_counter(); out["verified_by_library"] = bool(setup.verify(proof)); out["verify_ms"] = round((time.perf_counter() - t0) * 1e3, 1)   # zk_stark_verify
         if args.verify and args.hash == "GL":
@@ -48,6 +48,7 @@ def main():
     ap.add_argument("--python-driver", action="store_true", help="eigen-zkvm_amd/stark.py step-by-step driver instead of zk_stark_gen")
     ap.add_argument("--verify", action="store_true", help="check the proof with the oracle's restated verifier")
     ap.add_argument("--pil", default="poseidong", choices=["poseidong", "widefib"], help="PoseidonG (BASELINE config 3) or the wide-Fibonacci stand-in")
+    ap.add_argument("--eval", default=None, choices=["jit", "bytecode"], help="evaluator of the step programs: run-time compiled kernels, or the bytecode interpreter (nothing compiled); default: $ZK_EVAL, else jit")
     args = ap.parse_args()
     if args.pil == "poseidong":
         return poseidong_main(args)
@@ -64,7 +65,7 @@ def main():
             setup = stark.StarkSetup(const, info, d["program"], ss)
         else:                                                              # C++ driver inside libzkgpu
             pj = json.dumps({"starkinfo": dict(info, exp2pol={str(k): v for k, v in info["exp2pol"].items()}), "program": d["program"]})
-            setup = stark.NativeStarkSetup(const, pj, json.dumps(ss))
+            setup = stark.NativeStarkSetup(const, pj, json.dumps(ss), eval_mode=args.eval)
             d_cm = zk.DevArray.from_host(cm)                               # trace resident in HBM
         zk.lib().zk_dev_sync()
         t_setup = time.perf_counter() - t0

@@ -72,7 +72,7 @@ def stark_prove(a):
         raise SystemExit("zkgpu_prove: --program FILE is required (this build has no code generator)")
     t_gen = time.perf_counter()
     setup = stark.NativeStarkSetup(const, program_json, json.dumps(ss), prover_addr=a.prover_addr if ss.get("verificationHashType") != "GL" else None,
-                                   self_check=not a.no_verify)                 # prove.rs:124-132: assert!(stark_verify(..)) before anything is written
+                                   self_check=not a.no_verify, eval_mode=a.eval)  # prove.rs:124-132: assert!(stark_verify(..)) before anything is written
     t_setup = time.perf_counter()
     zkin = setup.gen_json(cm)
     t_prove = time.perf_counter()
@@ -202,6 +202,8 @@ def main(argv=None):
     s.add_argument("--prover_addr", default="273030697313060285579891744179749754319274977764")
     s.add_argument("--program", help='{"starkinfo", "program"} JSON of the code generator (extension, see the module text)')
     s.add_argument("--no_verify", action="store_true", help="skip the self check of prove.rs:124-132 (extension)")
+    s.add_argument("--eval", default="jit", choices=["jit", "bytecode"],
+                   help="evaluator of the step programs (extension): jit = run-time compiled kernels; bytecode = the interpreter kernel, nothing is compiled")
     s.set_defaults(fn=stark_prove)
     v = sub.add_parser("stark_verify", help="stark_verify.rs:20-136 on a zkin file (extension: the reference runs it inside stark_prove only)")
     v.add_argument("-s", "--stark_stuct", dest="stark_struct", default="stark_struct.json")
