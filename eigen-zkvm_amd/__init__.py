@@ -51,6 +51,8 @@ EXPORTS = [
     "zk_fr_bn254_ntt", "zk_fr_bn254_ntt_dev", "zk_fr_bls12_381_ntt", "zk_fr_bls12_381_ntt_dev", "zk_fr_bn254_quotient_dev", "zk_fr_bls12_381_quotient_dev",
     "zk_c12_exec_new", "zk_c12_exec_dev", "zk_c12_exec_depth", "zk_c12_exec_free",
     "zk_fq_bn254_convert_dev", "zk_fq_bls12_381_convert_dev", "zk_groth16_setup_new", "zk_groth16_setup_info", "zk_groth16_prove", "zk_groth16_prove_dev", "zk_groth16_wtns_payload", "zk_groth16_setup_free",
+    "zk_g1_bn254_mul_generator_fr_dev", "zk_g2_bn254_mul_generator_fr_dev", "zk_g1_bls12_381_mul_generator_fr_dev", "zk_g2_bls12_381_mul_generator_fr_dev",
+    "zk_groth16_keygen_new", "zk_groth16_keygen_params_size", "zk_groth16_keygen_params", "zk_groth16_keygen_vk_json", "zk_groth16_keygen_timing", "zk_groth16_keygen_free",
 ]
 
 # include/zkgpu.h enums
@@ -245,6 +247,16 @@ def _load():
         "zk_groth16_prove_dev": (vp, [vp, vp, C.c_uint64, vp, vp, vp, vp]),
         "zk_groth16_wtns_payload": (C.c_int, [vp, C.c_size_t, C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "zk_groth16_setup_free": (C.c_int, [vp]),
+        "zk_g1_bn254_mul_generator_fr_dev": (C.c_int, [vp, C.c_uint64, vp, vp]),
+        "zk_g2_bn254_mul_generator_fr_dev": (C.c_int, [vp, C.c_uint64, vp, vp]),
+        "zk_g1_bls12_381_mul_generator_fr_dev": (C.c_int, [vp, C.c_uint64, vp, vp]),
+        "zk_g2_bls12_381_mul_generator_fr_dev": (C.c_int, [vp, C.c_uint64, vp, vp]),
+        "zk_groth16_keygen_new": (vp, [C.c_char_p, vp, C.c_size_t, vp]),
+        "zk_groth16_keygen_params_size": (C.c_size_t, [vp]),
+        "zk_groth16_keygen_params": (C.c_int, [vp, vp, C.c_size_t]),
+        "zk_groth16_keygen_vk_json": (vp, [vp, C.c_int]),
+        "zk_groth16_keygen_timing": (C.c_int, [vp, C.POINTER(C.c_double)]),
+        "zk_groth16_keygen_free": (C.c_int, [vp]),
         "zk_msm_g1_bn254": (C.c_int, [vp, vp, C.c_uint64, vp, C.POINTER(C.c_int)]),
         "zk_msm_g1_bn254_dev": (C.c_int, [vp, vp, C.c_uint64, vp, vp]),
         "zk_g1_bn254_mul_generator_dev": (C.c_int, [vp, C.c_uint64, vp, vp]),
@@ -756,6 +768,14 @@ def g1_mul_generator(d_k, curve="bn254", stream=0, group="g1"):
     """bases[i] = [k_i]G for the n non-zero u64 in d_k; returns a DevArray of n * pw words."""
     out = DevArray(d_k.n * _CURVES[curve] * (4 if group == "g2" else 2))
     _check(getattr(lib(), "zk_%s_%s_mul_generator_dev" % (group, curve))(d_k.ptr, d_k.n, out.ptr, stream)); return out
+
+
+def mul_generator_fr(d_k, curve="bn254", stream=0, group="g1"):
+    """bases[i] = [k_i]G for n full-width scalars (d_k: n x 4 u64 canonical, below the scalar field's modulus; zero gives the
+    all-zero encoding) through the generator's window table; returns a DevArray of n * pw words."""
+    n = d_k.n // 4
+    out = DevArray(max(1, n) * _CURVES[curve] * (4 if group == "g2" else 2))
+    _check(getattr(lib(), "zk_%s_%s_mul_generator_fr_dev" % (group, curve))(d_k.ptr, n, out.ptr, stream)); return out
 
 
 def g1_bn254_mul_generator(d_k, stream=0):

@@ -3,6 +3,7 @@
 #include "zk_internal.h"
 #include "../../include/zkgpu.h"
 #include <map>
+#include <memory>
 #include <mutex>
 #include <vector>
 #include <cstring>
@@ -1034,6 +1035,48 @@ int zk_groth16_wtns_payload(const void* wtns, size_t len, const char* curve, uin
 }
 int zk_groth16_setup_free(zk_groth16_setup_t* s) {
     return guard([&] { if (s) { delete s->impl; delete s; } });
+}
+
+// ---- Groth16 key generation (fixedbase_impl.hip.h, groth16_keygen_impl.hip.h) ------------------------------------
+#define ZK_MUL_GEN_FR(NAME)                                                                                              \
+    int zk_##NAME##_mul_generator_fr_dev(const uint64_t* d_k, uint64_t n, void* d_bases, void* stream) {                 \
+        return guard([&] { ZK_REQUIRE((d_k && d_bases) || n == 0, "mul_generator: null argument"); NAME##_mul_generator_fr_dev((const u64*)d_k, n, d_bases, on_stream((hipStream_t)stream)); }); \
+    }
+ZK_MUL_GEN_FR(g1_bn254)
+ZK_MUL_GEN_FR(g2_bn254)
+ZK_MUL_GEN_FR(g1_bls12_381)
+ZK_MUL_GEN_FR(g2_bls12_381)
+#undef ZK_MUL_GEN_FR
+struct zk_groth16_keygen { Groth16Key* impl; };
+zk_groth16_keygen_t* zk_groth16_keygen_new(const char* curve, const void* r1cs, size_t r1cs_len, const uint64_t* trapdoor) {
+    zk_groth16_keygen_t* out = nullptr;
+    if (guard([&] { std::unique_ptr<Groth16Key> k(groth16_keygen_new(curve, r1cs, r1cs_len, trapdoor)); out = new zk_groth16_keygen{k.get()}; k.release(); }) != 0) return nullptr;
+    return out;
+}
+size_t zk_groth16_keygen_params_size(const zk_groth16_keygen_t* k) { return k && k->impl ? k->impl->params.size() : 0; }
+int zk_groth16_keygen_params(const zk_groth16_keygen_t* k, void* out, size_t cap) {
+    return guard([&] {
+        ZK_REQUIRE(k && k->impl && out, "groth16 keygen: null argument");
+        ZK_REQUIRE(cap >= k->impl->params.size(), "groth16 keygen: the buffer holds " + std::to_string(cap) + " bytes, the key has " + std::to_string(k->impl->params.size()));
+        memcpy(out, k->impl->params.data(), k->impl->params.size());
+    });
+}
+char* zk_groth16_keygen_vk_json(const zk_groth16_keygen_t* k, int to_hex) {
+    char* out = nullptr;
+    if (guard([&] {
+            ZK_REQUIRE(k && k->impl, "groth16 keygen: null handle");
+            const std::string js = groth16_keygen_vk_json(*k->impl, to_hex != 0);
+            out = (char*)malloc(js.size() + 1);
+            ZK_REQUIRE(out, "out of memory");
+            memcpy(out, js.c_str(), js.size() + 1);
+        }) != 0) return nullptr;
+    return out;
+}
+int zk_groth16_keygen_timing(const zk_groth16_keygen_t* k, double ms[5]) {
+    return guard([&] { ZK_REQUIRE(k && k->impl && ms, "groth16 keygen: null argument"); for (int i = 0; i < 5; ++i) ms[i] = k->impl->ms[i]; });
+}
+int zk_groth16_keygen_free(zk_groth16_keygen_t* k) {
+    return guard([&] { if (k) { delete k->impl; delete k; } });
 }
 
 }  // extern "C"

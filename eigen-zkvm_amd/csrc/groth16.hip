@@ -9,10 +9,13 @@
 //   quotient         7 transforms over Fr + the pointwise step                  (frntt_impl.hip.h)
 //   h, l, a, b_g1, b_g2 sums and the final assembly through msm.hip
 //   proof.json       groth16/src/json_utils.rs:305-315
+// Key generation (`zkit groth16_setup`, groth16/src/api.rs:42-66) over the same circuit: groth16_keygen_impl.hip.h.
 // r and s are taken from the caller (the reference draws them from OsRng, api.rs:172); everything else is a
 // function of (key, circuit, witness).
 #include "zk_internal.h"
 #include <algorithm>
+#include <cerrno>
+#include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -20,6 +23,7 @@
 #include <mutex>
 #include <thread>
 #include <vector>
+#include <sys/random.h>
 
 namespace zk {
 namespace g16 {
@@ -133,6 +137,76 @@ static Params parse_params(const uint8_t* b, size_t len, int coord_bytes) {
     if (rd.o != len) throw std::runtime_error("proving key: trailing bytes");
     return P;
 }
+
+// The circuit algebraic/src/circom_circuit.rs:94-160 synthesises from an .r1cs, as the prover and key generation both see it: the rows
+// that are enforced, bellman's `input_i * 0 = 0` rows behind them, the domain, the three matrices in CSR form (coef: 8 x u32 canonical
+// per term) and what the density trackers record.  All three matrices stay on the host for the object's life, 36 B a term (about 150 MB at
+// 2^20 rows of circom shape); key generation adds a column-major copy of one matrix at a time on top of that.
+struct Circuit {
+    uint32_t ni = 0, n_aux = 0, n_wires = 0;
+    int logm = 0;
+    u64 m = 0, n_rows = 0;
+    struct Csr { std::vector<u64> ptr; std::vector<u32> cols, coef; } mat[3];
+    std::vector<char> a_aux, b_any;
+    explicit Circuit(const R1cs& rc) {
+        ni = 1 + rc.n_pub_out + rc.n_pub_in;
+        n_wires = rc.n_wires;
+        ZK_REQUIRE(n_wires >= ni, "groth16: r1cs header: fewer wires than public signals");
+        n_aux = n_wires - ni;
+        // circom_circuit.rs:143-157: rows with (A or B empty) and C empty are not enforced; prover.rs then appends
+        // one `input_i * 0 = 0` row per input
+        std::vector<const Row*> rows;
+        for (const auto& r : rc.rows)
+            if (!((r.lc[0].col.empty() || r.lc[1].col.empty()) && r.lc[2].col.empty())) rows.push_back(&r);
+        n_rows = rows.size() + ni;
+        logm = 0;
+        while ((1ull << logm) < n_rows) ++logm;
+        m = 1ull << logm;
+        a_aux.assign(n_wires, 0); b_any.assign(n_wires, 0);
+        for (int w = 0; w < 3; ++w) {
+            auto& ptr = mat[w].ptr; auto& cols = mat[w].cols; auto& coef = mat[w].coef;
+            ptr.push_back(0);
+            for (const Row* r : rows) {
+                const auto& lc = r->lc[w];
+                for (size_t k = 0; k < lc.col.size(); ++k) {
+                    ZK_REQUIRE(lc.col[k] < n_wires, "groth16: r1cs: wire index out of range");
+                    cols.push_back(lc.col[k]);
+                    coef.insert(coef.end(), lc.coeff.begin() + 8 * k, lc.coeff.begin() + 8 * k + 8);
+                    if (w == 0 && lc.col[k] >= ni) a_aux[lc.col[k]] = 1;
+                    if (w == 1) b_any[lc.col[k]] = 1;
+                }
+                ptr.push_back(cols.size());
+            }
+            for (uint32_t i = 0; i < ni; ++i) {
+                if (w == 0) { cols.push_back(i); const u32 one[8] = {1, 0, 0, 0, 0, 0, 0, 0}; coef.insert(coef.end(), one, one + 8); }
+                ptr.push_back(cols.size());
+            }
+        }
+    }
+};
+
+// canonical little-endian coordinates (nc x cw words per point) -> pairing_ce's uncompressed encoding: every coordinate big-endian, G2 as
+// x.c1 || x.c0 || y.c1 || y.c0; the all-zero point (no finite point has x = y = 0) is infinity: bit 6 of byte 0, zeros behind it
+__global__ __launch_bounds__(256) void points_to_be_kernel(const u32* __restrict__ pts, u64 n, int cw, int g2, u32* __restrict__ out) {
+    const u64 i = blockIdx.x * 256ull + threadIdx.x;
+    if (i >= n) return;
+    const int nc = g2 ? 4 : 2;
+    const u32* p = pts + i * nc * cw;
+    u32* o = out + i * nc * cw;
+    u32 any = 0;
+    for (int c = 0; c < nc; ++c) {
+        const u32* q = p + (g2 ? (c ^ 1) : c) * cw;
+        for (int k = 0; k < cw; ++k) { const u32 v = q[cw - 1 - k]; any |= v; o[c * cw + k] = __builtin_bswap32(v); }
+    }
+    if (!any) o[0] = 0x40u;
+}
+static void points_to_be_dev(const u32* d_pts, u64 n, int cw, bool g2, u32* d_out, hipStream_t st) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(points_to_be_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_pts, n, cw, g2 ? 1 : 0, d_out);
+    ZK_HIP(hipGetLastError());
+}
+// overwrite host memory that held a secret; the compiler may not drop the stores
+static void wipe(void* p, size_t n) { volatile uint8_t* q = (volatile uint8_t*)p; for (size_t i = 0; i < n; ++i) q[i] = 0; }
 }  // namespace g16
 
 namespace bn254fr {
@@ -156,7 +230,12 @@ namespace bn254fr {
 #define G16_FQ_TO_CANON fq_bn254_mont_to_canon_dev
 #define G16_JSON_CURVE "BN128"
 #define G16_FN(name) name
+#define G16_MULGEN_G1 g1_bn254_mul_generator_fr_dev
+#define G16_MULGEN_G2 g2_bn254_mul_generator_fr_dev
 #include "groth16_impl.hip.h"
+#include "groth16_keygen_impl.hip.h"
+#undef G16_MULGEN_G1
+#undef G16_MULGEN_G2
 #undef FRN_S
 #undef FRN_ROOT
 #undef G16_CW
@@ -192,7 +271,10 @@ namespace bls12381fr {
 #define G16_FQ_TO_MONT fq_bls12_381_canon_to_mont_dev
 #define G16_FQ_TO_CANON fq_bls12_381_mont_to_canon_dev
 #define G16_JSON_CURVE "BLS12381"
+#define G16_MULGEN_G1 g1_bls12_381_mul_generator_fr_dev
+#define G16_MULGEN_G2 g2_bls12_381_mul_generator_fr_dev
 #include "groth16_impl.hip.h"
+#include "groth16_keygen_impl.hip.h"
 }  // namespace bls12381fr
 
 void fr_bn254_ntt_dev(u64* d, int logn, bool inverse, bool coset, hipStream_t st) { bn254fr::ntt_dev(d, logn, inverse, coset, st); }
@@ -217,9 +299,91 @@ Groth16Setup* groth16_setup_new(const char* curve, const void* r1cs, size_t r1cs
     std::vector<u32> mod(bls ? R_BLS12_381 : R_BN254, (bls ? R_BLS12_381 : R_BN254) + 8);
     const g16::R1cs rc = g16::parse_r1cs((const uint8_t*)r1cs, r1cs_len, mod);
     const g16::Params pk = g16::parse_params((const uint8_t*)params, params_len, bls ? 48 : 32);
-    Groth16Setup* s = bls ? bls12381fr::setup_new(rc, pk) : bn254fr::setup_new(rc, pk);
+    const g16::Circuit cir(rc);
+    Groth16Setup* s = bls ? bls12381fr::setup_new(cir, pk) : bn254fr::setup_new(cir, pk);
     s->curve = curve; s->modulus = mod; s->proof_words = bls ? 96 : 64;
     return s;
+}
+
+// ---- key generation ---------------------------------------------------------------------------------------------------------------
+static bool fr_lt(const u32* a, const u32* mod) {
+    for (int i = 7; i >= 0; --i) { if (a[i] < mod[i]) return true; if (a[i] > mod[i]) return false; }
+    return false;
+}
+Groth16Key* groth16_keygen_new(const char* curve, const void* r1cs, size_t r1cs_len, const uint64_t* trapdoor) {
+    const bool bls = curve_is_bls(curve);
+    ZK_REQUIRE(r1cs, "groth16 keygen: null input");
+    const u32* mod = bls ? R_BLS12_381 : R_BN254;
+    const g16::R1cs rc = g16::parse_r1cs((const uint8_t*)r1cs, r1cs_len, std::vector<u32>(mod, mod + 8));
+    const g16::Circuit cir(rc);
+    u32 td[40];
+    struct TdGuard { u32* p; ~TdGuard() { g16::wipe(p, 160); } } td_guard{td};
+    static const char* const names[5] = {"tau", "alpha", "beta", "gamma", "delta"};
+    if (trapdoor) {
+        std::memcpy(td, trapdoor, 160);
+        for (int c = 0; c < 5; ++c) {
+            u32* v = td + 8 * c;
+            while (!fr_lt(v, mod)) { uint64_t br = 0; for (int i = 0; i < 8; ++i) { const uint64_t d = (uint64_t)v[i] - mod[i] - br; v[i] = (u32)d; br = (d >> 32) & 1; } }   // below r
+            u32 any = 0; for (int i = 0; i < 8; ++i) any |= v[i];
+            ZK_REQUIRE(any, std::string("groth16 keygen: trapdoor component ") + names[c] + " is zero");
+        }
+    } else {
+        // uniform in [1, r): bytes from the operating system, cut to the modulus' bit length, drawn again while out of range
+        const u32 top_mask = bls ? 0x7fffffffu : 0x3fffffffu;
+        for (int c = 0; c < 5; ++c) {
+            u32* v = td + 8 * c;
+            for (;;) {
+                size_t got = 0;
+                while (got < 32) {
+                    const ssize_t k = getrandom((uint8_t*)v + got, 32 - got, 0);
+                    if (k < 0 && errno == EINTR) continue;                  // a signal arrived before any byte: ask again
+                    ZK_REQUIRE(k > 0, "groth16 keygen: the operating system gave no random bytes");
+                    got += (size_t)k;
+                }
+                v[7] &= top_mask;
+                u32 any = 0; for (int i = 0; i < 8; ++i) any |= v[i];
+                if (any && fr_lt(v, mod)) break;
+            }
+        }
+    }
+    auto key = std::make_unique<Groth16Key>();
+    key->curve = curve;
+    if (bls) bls12381fr::keygen_run(cir, td, key->params, key->ms); else bn254fr::keygen_run(cir, td, key->params, key->ms);
+    return key.release();
+}
+
+// json_utils.rs:285-303 serialize_vk over the head of the key's bytes (VerifyingKey::write: alpha_g1 beta_g1 beta_g2 gamma_g2 delta_g1
+// delta_g2, count, ic); a coordinate is render_scalar_to_str's decimal string, or with to_hex the fixed-width 0x string of its repr
+std::string groth16_keygen_vk_json(const Groth16Key& k, bool to_hex) {
+    const bool bls = curve_is_bls(k.curve.c_str());
+    const size_t cb = bls ? 48 : 32;
+    const uint8_t* p = k.params.data();
+    size_t o = 0;
+    auto coord = [&](const uint8_t* q) {
+        if (to_hex) { std::string s = "\"0x"; char b[3]; for (size_t i = 0; i < cb; ++i) { snprintf(b, sizeof b, "%02x", q[i]); s += b; } return s + "\""; }
+        std::vector<u32> w(cb / 4);
+        for (size_t i = 0; i < cb / 4; ++i) { const uint8_t* e = q + cb - 4 * (i + 1); w[i] = ((u32)e[0] << 24) | ((u32)e[1] << 16) | ((u32)e[2] << 8) | e[3]; }
+        return "\"" + g16::words_to_dec(w.data(), (int)w.size()) + "\"";
+    };
+    auto g1 = [&] {
+        ZK_REQUIRE(o + 2 * cb <= k.params.size(), "groth16 keygen: truncated key");
+        std::vector<uint8_t> pt(p + o, p + o + 2 * cb); o += 2 * cb;
+        if (pt[0] & 0x40) { pt.assign(2 * cb, 0); pt[2 * cb - 1] = 1; }          // CurveAffine::zero() is (0, 1)
+        return "{\"x\":" + coord(pt.data()) + ",\"y\":" + coord(pt.data() + cb) + "}";
+    };
+    auto g2 = [&] {                                                              // file: x.c1 x.c0 y.c1 y.c0; json: [c0, c1]
+        ZK_REQUIRE(o + 4 * cb <= k.params.size(), "groth16 keygen: truncated key");
+        const uint8_t* q = p + o; o += 4 * cb;
+        return "{\"x\":[" + coord(q + cb) + "," + coord(q) + "],\"y\":[" + coord(q + 3 * cb) + "," + coord(q + 2 * cb) + "]}";
+    };
+    std::string js = std::string("{\"protocol\":\"groth16\",\"curve\":\"") + k.curve + "\"";
+    js += ",\"vk_alpha_1\":" + g1(); js += ",\"vk_beta_1\":" + g1(); js += ",\"vk_beta_2\":" + g2(); js += ",\"vk_gamma_2\":" + g2();
+    js += ",\"vk_delta_1\":" + g1(); js += ",\"vk_delta_2\":" + g2();
+    ZK_REQUIRE(o + 4 <= k.params.size(), "groth16 keygen: truncated key");
+    const u32 n_ic = ((u32)p[o] << 24) | ((u32)p[o + 1] << 16) | ((u32)p[o + 2] << 8) | p[o + 3]; o += 4;
+    js += ",\"IC\":[";
+    for (u32 i = 0; i < n_ic; ++i) { if (i) js += ","; js += g1(); }
+    return js + "]}";
 }
 
 // reader.rs:86-137 load_witness_from_bin_reader: header checks, then n x 32 B little-endian canonical values

@@ -31,40 +31,12 @@ struct G16_FN(SetupImpl) final : Groth16Setup {
 
     static constexpr size_t P1 = 2 * G16_CW, P2 = 4 * G16_CW;   // u32 words per affine point
 
-    G16_FN(SetupImpl)(const g16::R1cs& rc, const g16::Params& pk) {
+    G16_FN(SetupImpl)(const g16::Circuit& C, const g16::Params& pk) {
         hipStream_t st = nullptr;
-        ni = 1 + rc.n_pub_out + rc.n_pub_in;
-        n_wires = rc.n_wires;
-        ZK_REQUIRE(n_wires >= ni, "groth16: r1cs header: fewer wires than public signals");
-        n_aux = n_wires - ni;
-        // circom_circuit.rs:143-157: rows with (A or B empty) and C empty are not enforced; prover.rs then appends
-        // one `input_i * 0 = 0` row per input
-        std::vector<const g16::Row*> rows;
-        for (const auto& r : rc.rows)
-            if (!((r.lc[0].col.empty() || r.lc[1].col.empty()) && r.lc[2].col.empty())) rows.push_back(&r);
-        n_rows = rows.size() + ni;
-        logm = 0;
-        while ((1ull << logm) < n_rows) ++logm;
-        m = 1ull << logm;
-        std::vector<char> a_aux(n_wires, 0), b_any(n_wires, 0);
+        ni = C.ni; n_wires = C.n_wires; n_aux = C.n_aux; n_rows = C.n_rows; logm = C.logm; m = C.m;
+        const std::vector<char>&a_aux = C.a_aux, &b_any = C.b_any;
         for (int w = 0; w < 3; ++w) {
-            std::vector<u64> ptr; std::vector<u32> cols, coef;
-            ptr.push_back(0);
-            for (const g16::Row* r : rows) {
-                const auto& lc = r->lc[w];
-                for (size_t k = 0; k < lc.col.size(); ++k) {
-                    ZK_REQUIRE(lc.col[k] < n_wires, "groth16: r1cs: wire index out of range");
-                    cols.push_back(lc.col[k]);
-                    coef.insert(coef.end(), lc.coeff.begin() + 8 * k, lc.coeff.begin() + 8 * k + 8);
-                    if (w == 0 && lc.col[k] >= ni) a_aux[lc.col[k]] = 1;
-                    if (w == 1) b_any[lc.col[k]] = 1;
-                }
-                ptr.push_back(cols.size());
-            }
-            for (uint32_t i = 0; i < ni; ++i) {
-                if (w == 0) { cols.push_back(i); const u32 one[8] = {1, 0, 0, 0, 0, 0, 0, 0}; coef.insert(coef.end(), one, one + 8); }
-                ptr.push_back(cols.size());
-            }
+            const auto& ptr = C.mat[w].ptr; const auto& cols = C.mat[w].cols; const auto& coef = C.mat[w].coef;
             rp[w].reserve(ptr.size() * 8); cl[w].reserve(cols.size() * 4 + 4); cf[w].reserve(cols.size() * NR * 4 + 4);
             h2d_sync(rp[w].p, ptr.data(), ptr.size() * 8);
             if (!cols.empty()) {
@@ -243,4 +215,4 @@ struct G16_FN(SetupImpl) final : Groth16Setup {
     }
 };
 
-Groth16Setup* G16_FN(setup_new)(const g16::R1cs& rc, const g16::Params& pk) { return new G16_FN(SetupImpl)(rc, pk); }
+Groth16Setup* G16_FN(setup_new)(const g16::Circuit& C, const g16::Params& pk) { return new G16_FN(SetupImpl)(C, pk); }

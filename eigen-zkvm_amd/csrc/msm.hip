@@ -17,6 +17,8 @@
 // Field: 29-bit limbs with 64-bit column accumulators, lazily reduced (fe29_impl.hip.h); Fq2 on top of it for G2.
 // Integer-ALU bound (about 10 Fq products per point and window); HBM traffic is 96 B per point.
 #include "zk_internal.h"
+#include <map>
+#include <mutex>
 
 // fe29_impl.hip.h: the sums keep squaring as fe_mul(a, a).  The dedicated squaring of the scalar-field hashes was measured here
 // (tools/gpu_sqr_ab.sh, profiles/r05/sqr_ab_raw.txt): G1 +-1 %, BN254 G2 3 % slower -- the accumulation kernels sit at a register edge.
@@ -259,6 +261,12 @@ void msm_g2_bn254_dev(const void* d_bases, const void* d_scalars, uint64_t n, vo
 void g2_bn254_mul_generator_dev(const u64* d_k, uint64_t n, void* d_bases, hipStream_t st) { bn254::g2::g1_mul_generator_dev(d_k, n, d_bases, st); }
 void msm_g2_bls12_381_dev(const void* d_bases, const void* d_scalars, uint64_t n, void* d_out, hipStream_t st) { bls12_381::g2::msm_g1_dev(d_bases, d_scalars, n, d_out, st); }
 void g2_bls12_381_mul_generator_dev(const u64* d_k, uint64_t n, void* d_bases, hipStream_t st) { bls12_381::g2::g1_mul_generator_dev(d_k, n, d_bases, st); }
+
+// P_i = [k_i]G for full-width scalars (fixedbase_impl.hip.h): n x 4 u64 canonical, < r
+void g1_bn254_mul_generator_fr_dev(const u64* d_k, uint64_t n, void* d_bases, hipStream_t st) { bn254::g1::mul_generator_fr_dev(d_k, n, d_bases, st); }
+void g2_bn254_mul_generator_fr_dev(const u64* d_k, uint64_t n, void* d_bases, hipStream_t st) { bn254::g2::mul_generator_fr_dev(d_k, n, d_bases, st); }
+void g1_bls12_381_mul_generator_fr_dev(const u64* d_k, uint64_t n, void* d_bases, hipStream_t st) { bls12_381::g1::mul_generator_fr_dev(d_k, n, d_bases, st); }
+void g2_bls12_381_mul_generator_fr_dev(const u64* d_k, uint64_t n, void* d_bases, hipStream_t st) { bls12_381::g2::mul_generator_fr_dev(d_k, n, d_bases, st); }
 
 // window tables (fixed bases)
 #define ZK_MSM_FIXED(NAME, NS)                                                                                              \

@@ -993,5 +993,8 @@ void msm_fixed_dev(const void* d_table, uint64_t table_n, uint64_t base_off, con
     ZK_REQUIRE(d_table, "msm table: null table");
     msm_core(nullptr, d_table, table_n, base_off, d_scalars, n, d_out, st);
 }
+#if MSM_N_WIN == 16   /* not for the 128-bit half sums behind the endomorphism split */
+#include "fixedbase_impl.hip.h"
+#endif
 #undef MSM_N_WIN
 #undef MSM_SC_WORDS

@@ -203,6 +203,12 @@ void msm_g2_bn254_dev(const void* d_bases, const void* d_scalars, uint64_t n, vo
 void g2_bn254_mul_generator_dev(const u64* d_k, uint64_t n, void* d_bases, hipStream_t st);
 void msm_g2_bls12_381_dev(const void* d_bases, const void* d_scalars, uint64_t n, void* d_out, hipStream_t st);
 void g2_bls12_381_mul_generator_dev(const u64* d_k, uint64_t n, void* d_bases, hipStream_t st);
+// P_i = [k_i]G for n full-width scalars (4 x u64 canonical, < r; zero gives the all-zero encoding): a window table of the generator,
+// no doublings, one inversion per workgroup (fixedbase_impl.hip.h); the output layout of the *_mul_generator_dev above
+void g1_bn254_mul_generator_fr_dev(const u64* d_k, uint64_t n, void* d_bases, hipStream_t st);
+void g2_bn254_mul_generator_fr_dev(const u64* d_k, uint64_t n, void* d_bases, hipStream_t st);
+void g1_bls12_381_mul_generator_fr_dev(const u64* d_k, uint64_t n, void* d_bases, hipStream_t st);
+void g2_bls12_381_mul_generator_fr_dev(const u64* d_k, uint64_t n, void* d_bases, hipStream_t st);
 // window tables for fixed bases (msm_impl.hip.h): table[w * n + i] = 2^(16 w) P_i; a sum over points [off, off + n) of it
 #define ZK_MSM_FIXED_DECL(NAME)                                                                                             \
     size_t msm_##NAME##_fixed_table_bytes(uint64_t n);                                                                      \
@@ -276,5 +282,10 @@ struct Groth16Setup {
 };
 Groth16Setup* groth16_setup_new(const char* curve, const void* r1cs, size_t r1cs_len, const void* params, size_t params_len);
 void groth16_wtns_payload(const void* wtns, size_t len, const char* curve, uint64_t* offset, uint64_t* n);
+// Key generation (groth16_keygen_impl.hip.h; `zkit groth16_setup`, groth16/src/api.rs:42-66): the finished key as bellman's
+// Parameters::write lays it out.  trapdoor: 5 x 4 u64 (tau, alpha, beta, gamma, delta), or null to draw them from the OS.
+struct Groth16Key { std::string curve; std::vector<uint8_t> params; double ms[5] = {}; };   // ms: transform, column sums, G1 points, G2 points, serialisation
+Groth16Key* groth16_keygen_new(const char* curve, const void* r1cs, size_t r1cs_len, const uint64_t* trapdoor);
+std::string groth16_keygen_vk_json(const Groth16Key& k, bool to_hex);   // json_utils.rs:285-303 serialize_vk
 
 }  // namespace zk

@@ -1,7 +1,7 @@
 """Host-side mirror of the reference's Groth16 entry points over libzkgpu's C ABI (include/zkgpu.h, "Groth16 around
 the multi-scalar sums"): groth16/src/api.rs:144-205 groth16_prove = read the key, read the circuit, read the
-witness, create_random_proof, serialize_proof.  Everything after the witness is on the device; there is no CPU
-fallback."""
+witness, create_random_proof, serialize_proof; and api.rs:42-66 groth16_setup = the key itself (keygen).  Everything
+after the witness is on the device; there is no CPU fallback."""
 import ctypes as C
 import json
 import secrets
@@ -92,6 +92,41 @@ class Groth16Setup:
             self.free()
         except Exception:
             pass
+
+
+def keygen(curve, r1cs_bytes, trapdoor=None, to_hex=False, timing=None):
+    """`zkit groth16_setup` (groth16/src/api.rs:42-66): the circuit-specific key of an .r1cs, made on the device.
+    trapdoor: (tau, alpha, beta, gamma, delta) as integers, or None to let the library draw them from the operating system
+    (nothing of them survives the call).  -> (bellman Parameters bytes, verification_key.json text); `timing`, a list,
+    receives the milliseconds of the transform, the column sums, the G1 points, the G2 points and serialisation."""
+    if curve not in _FR:
+        raise ZkError('groth16: unknown curve "%s" (BN128 | BLS12381)' % curve)
+    td = None
+    if trapdoor is not None:
+        if len(trapdoor) != 5:
+            raise ZkError("groth16 keygen: the trapdoor is (tau, alpha, beta, gamma, delta)")
+        td = np.array([[(int(v) % _FR[curve] >> (64 * i)) & (2**64 - 1) for i in range(4)] for v in trapdoor], dtype=np.uint64).reshape(-1)
+    r = np.frombuffer(r1cs_bytes, dtype=np.uint8)
+    h = lib().zk_groth16_keygen_new(curve.encode(), r.ctypes.data, r.size, _ptr(td) if td is not None else None)
+    if not h:
+        raise ZkError(lib().zk_last_error().decode())
+    try:
+        n = lib().zk_groth16_keygen_params_size(h)
+        buf = np.empty(n, np.uint8)
+        _check(lib().zk_groth16_keygen_params(h, buf.ctypes.data, n))
+        p = lib().zk_groth16_keygen_vk_json(h, int(bool(to_hex)))
+        if not p:
+            raise ZkError(lib().zk_last_error().decode())
+        try:
+            vk = C.string_at(p).decode()
+        finally:
+            lib().zk_string_free(p)
+        if timing is not None:
+            ms = (C.c_double * 5)()
+            _check(lib().zk_groth16_keygen_timing(h, ms)); timing[:] = list(ms)
+        return buf.tobytes(), vk
+    finally:
+        lib().zk_groth16_keygen_free(h)
 
 
 def fq_convert(d_elems, curve="BN128", to_mont=True, stream=0):

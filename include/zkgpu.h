@@ -437,6 +437,34 @@ char* zk_groth16_prove_dev(zk_groth16_setup_t* s, const void* d_witness, uint64_
 int zk_groth16_wtns_payload(const void* wtns, size_t len, const char* curve, uint64_t* offset, uint64_t* n_values);
 int zk_groth16_setup_free(zk_groth16_setup_t* s);
 
+/* ---- Groth16 key generation (`zkit groth16_setup`, groth16/src/api.rs:42-66 -> Groth16::circuit_specific_setup,
+ * groth16.rs:77-86 -> bellman's generate_random_parameters) ----------------------------------------------------
+ * zk_*_mul_generator_fr_dev: d_bases[i] = [d_k[i]] G for n full-width scalars (4 x u64 canonical little-endian, below
+ * the scalar field's modulus), G the generator of G1 / G2; the output layout of zk_*_mul_generator_dev (affine,
+ * Montgomery), a zero scalar gives the all-zero encoding.  One window table of G per device, no doublings, one field
+ * inversion per workgroup.
+ * zk_groth16_keygen_new evaluates the QAP of the circuit zk_groth16_setup_new would synthesise at tau on the device and
+ * forms the key's points with the kernel above.  trapdoor = tau, alpha, beta, gamma, delta (5 x 4 u64 canonical; values
+ * of 2^256 range are reduced), or NULL to draw them from the operating system -- then nothing of them survives the call.
+ * Errors (NULL, zk_last_error): a zero component, tau^m = 1 for the domain size m, an unknown curve, and every .r1cs
+ * fault zk_groth16_setup_new reports.  _params writes bellman's Parameters::write layout (what zk_groth16_setup_new
+ * reads) when cap >= _params_size, and nothing otherwise; _vk_json renders verification_key.json as
+ * json_utils.rs:285-303 does (decimal coordinates, or fixed-width 0x strings with to_hex; malloc'ed, zk_string_free). */
+int zk_g1_bn254_mul_generator_fr_dev(const uint64_t* d_k, uint64_t n, void* d_bases, void* stream);
+int zk_g2_bn254_mul_generator_fr_dev(const uint64_t* d_k, uint64_t n, void* d_bases, void* stream);
+int zk_g1_bls12_381_mul_generator_fr_dev(const uint64_t* d_k, uint64_t n, void* d_bases, void* stream);
+int zk_g2_bls12_381_mul_generator_fr_dev(const uint64_t* d_k, uint64_t n, void* d_bases, void* stream);
+typedef struct zk_groth16_keygen zk_groth16_keygen_t;
+zk_groth16_keygen_t* zk_groth16_keygen_new(const char* curve, const void* r1cs, size_t r1cs_len, const uint64_t* trapdoor);
+size_t zk_groth16_keygen_params_size(const zk_groth16_keygen_t* k);
+int zk_groth16_keygen_params(const zk_groth16_keygen_t* k, void* out, size_t cap);
+char* zk_groth16_keygen_vk_json(const zk_groth16_keygen_t* k, int to_hex);
+/* Diagnostic, not part of what `zkit groth16_setup` offers: where zk_groth16_keygen_new spent its time, in milliseconds of the host clock --
+ * the transform, the column sums, the G1 points, the G2 points, serialisation.  The five stream synchronisations that separate the phases
+ * are made on every call; each phase is milliseconds to seconds of device work, and the call ends in a copy to the host anyway. */
+int zk_groth16_keygen_timing(const zk_groth16_keygen_t* k, double ms[5]);
+int zk_groth16_keygen_free(zk_groth16_keygen_t* k);
+
 /* ---- compressor12 exec (recursion/src/compressor12/compressor12_exec.rs:17-103) ----------------
  * The step between a recursive circuit's circom witness and the committed trace of its STARK: the PlonkAdd sums
  * appended to the witness (:60-66) and the s_map gather into the 12 columns of Compressor.a (:72-94).

@@ -1,7 +1,9 @@
-"""Groth16 prover timing on a synthetic circom-shaped circuit: python tools/groth16_bench.py [BN128|BLS12381] [log_rows ...]
+"""Groth16 prover timing on a synthetic circom-shaped circuit: python tools/groth16_bench.py [--real-key] [BN128|BLS12381] [log_rows ...]
 Rows i: (w[p] + c w[q]) * w[t] = w[new_i] over earlier wires (satisfied; the quotient's top coefficient is checked
 to be zero on the device result).  The proving key holds arbitrary valid points ([k]G with random 64-bit k, made
-on the device): timing does not depend on the key being a real setup, proofs made here do not verify."""
+on the device): timing does not depend on the key being a real setup, proofs made here do not verify.
+--real-key: the key comes from the library's own key generation (eigen_zkvm_amd.groth16.keygen, trapdoor drawn and
+forgotten by the library) -- its time and split are printed, and proofs made with it are valid."""
 import importlib, struct, sys, time, pathlib
 import numpy as np
 ROOT = pathlib.Path(__file__).resolve().parent.parent
@@ -84,6 +86,8 @@ def density(r1cs_bytes, ni, n_wires):
 
 def main():
     args = sys.argv[1:]
+    real_key = "--real-key" in args
+    args = [a for a in args if a != "--real-key"]
     curve = args.pop(0) if args and args[0] in FR else "BN128"
     zk = eigen_zkvm_amd; zk.init(0)
     dev = importlib.import_module("eigen_zkvm_amd.groth16")
@@ -91,7 +95,15 @@ def main():
         t = time.perf_counter()
         rb, wit, ni, n_wires = make_circuit(FR[curve], log_rows)
         t1 = time.perf_counter()
-        pb = make_params(zk, dev, curve, ni, n_wires, log_rows, density(rb, ni, n_wires))
+        if real_key:
+            dev.keygen(curve, make_circuit(FR[curve], 8)[0])                # the generator's window tables are built once per process: not this key's time
+            ms = []
+            t1 = time.perf_counter()
+            pb, _vk = dev.keygen(curve, rb, timing=ms)
+            print(f"  keygen {(time.perf_counter() - t1)*1e3:.0f} ms: transform {ms[0]:.1f}, column sums {ms[1]:.1f}, G1 points {ms[2]:.1f}, G2 points {ms[3]:.1f}, "
+                  f"serialisation {ms[4]:.1f} ms", flush=True)
+        else:
+            pb = make_params(zk, dev, curve, ni, n_wires, log_rows, density(rb, ni, n_wires))
         t2 = time.perf_counter()
         S = dev.Groth16Setup(curve, rb, pb)
         t3 = time.perf_counter()

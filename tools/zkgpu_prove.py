@@ -4,13 +4,14 @@
   zkgpu_prove.py stark_prove -s starkStruct.json -p circuit.pil.json --o circuit.const --m circuit.cm \\
                              -c verifier.circom --i zkin.json [--norm_stage] [--skip_main] [--agg_stage] [--prover_addr A] \\
                              [--program starkinfo_program.json]
+  zkgpu_prove.py groth16_setup -c BN128 --r1cs circuit.r1cs -p g16.key -v verification_key.json [-t]
   zkgpu_prove.py groth16_prove -c BN128 --r1cs circuit.r1cs -w witness.wtns -p g16.key --public-input public_input.json --proof proof.json
   zkgpu_prove.py stark_verify -s starkStruct.json -p circuit.pil.json --o circuit.const --i zkin.json [--program FILE]
   zkgpu_prove.py join_zkin --zkin1 a.zkin.json --zkin2 b.zkin.json --zkinout out.zkin.json
   zkgpu_prove.py stark_aggregate --gpus N --num_proof 8 --workspace DIR [--workers 4] [--keep_proofs]     (starts its own N ranks;
   [torchrun --nproc-per-node N] zkgpu_prove.py stark_aggregate ...                                         or runs under torchrun)
 
-Flags, defaults and file formats are zkit's (zkit/src/main.rs:98-123 StarkProveOpt, :199-217 Groth16ProveOpt;
+Flags, defaults and file formats are zkit's (zkit/src/main.rs:98-123 StarkProveOpt, :185-196 Groth16SetupOpt, :199-217 Groth16ProveOpt;
 starky/src/prove.rs:30-160, groth16/src/api.rs:144-205).  What differs, and why:
   * stark_prove needs the code generator's output, `{"starkinfo": StarkInfo, "program": Program}` (serde names, starkinfo.rs:27-95):
     `--program FILE`, or -- when the file is absent -- the library's own generator (zk_starkinfo_generate) if this build has one.
@@ -167,6 +168,17 @@ def stark_aggregate(a):
     ex.barrier()
 
 
+def groth16_setup(a):
+    """groth16/src/api.rs:42-66: circuit_specific_setup, then the key and verification_key.json written to their files"""
+    import importlib
+    _zk()
+    dev = importlib.import_module("eigen_zkvm_amd.groth16")
+    pk, vk = dev.keygen(a.curve_type, pathlib.Path(a.circuit_file).read_bytes(), to_hex=a.to_hex)
+    pathlib.Path(a.pk_file).write_bytes(pk)
+    pathlib.Path(a.vk_file).write_text(vk)
+    print("zkgpu_prove: %s key written to %s (%d bytes), verification key to %s" % (a.curve_type, a.pk_file, len(pk), a.vk_file))
+
+
 def groth16_prove(a):
     import importlib
     zk = _zk()
@@ -223,6 +235,13 @@ def main(argv=None):
     j = sub.add_parser("join_zkin", help="zkin_join.rs:9-57: the input of one recursive2 step from two proofs")
     j.add_argument("--zkin1", required=True); j.add_argument("--zkin2", required=True); j.add_argument("--zkinout", required=True)
     j.set_defaults(fn=join_zkin)
+    k = sub.add_parser("groth16_setup", help="Setup groth16 (zkit/src/main.rs:185-196)")
+    k.add_argument("-c", dest="curve_type", default="BN128")
+    k.add_argument("--r1cs", dest="circuit_file", required=True)
+    k.add_argument("-p", dest="pk_file", default="g16.zkey")
+    k.add_argument("-v", dest="vk_file", default="verification_key.json")
+    k.add_argument("-t", dest="to_hex", action="store_true", help="coordinates of the verification key as 0x strings")
+    k.set_defaults(fn=groth16_setup)
     g = sub.add_parser("groth16_prove", help="Prove with groth16 (zkit/src/main.rs:199-217)")
     g.add_argument("-c", dest="curve_type", default="BN128")
     g.add_argument("--r1cs", dest="circuit_file", required=True)
