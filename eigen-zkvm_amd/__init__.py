@@ -53,6 +53,8 @@ EXPORTS = [
     "zk_fq_bn254_convert_dev", "zk_fq_bls12_381_convert_dev", "zk_groth16_setup_new", "zk_groth16_setup_info", "zk_groth16_prove", "zk_groth16_prove_dev", "zk_groth16_wtns_payload", "zk_groth16_setup_free",
     "zk_g1_bn254_mul_generator_fr_dev", "zk_g2_bn254_mul_generator_fr_dev", "zk_g1_bls12_381_mul_generator_fr_dev", "zk_g2_bls12_381_mul_generator_fr_dev",
     "zk_groth16_keygen_new", "zk_groth16_keygen_params_size", "zk_groth16_keygen_params", "zk_groth16_keygen_vk_json", "zk_groth16_keygen_timing", "zk_groth16_keygen_free",
+    "zk_pairing_bn254", "zk_pairing_bn254_dev", "zk_pairing_bls12_381", "zk_pairing_bls12_381_dev", "zk_groth16_vk_new", "zk_groth16_vk_info", "zk_groth16_vk_free",
+    "zk_groth16_verify_batch", "zk_groth16_verify_batch_dev", "zk_groth16_verify_json", "zk_groth16_verdict_name",
 ]
 
 # include/zkgpu.h enums
@@ -257,6 +259,17 @@ def _load():
         "zk_groth16_keygen_vk_json": (vp, [vp, C.c_int]),
         "zk_groth16_keygen_timing": (C.c_int, [vp, C.POINTER(C.c_double)]),
         "zk_groth16_keygen_free": (C.c_int, [vp]),
+        "zk_pairing_bn254": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_int]),
+        "zk_pairing_bn254_dev": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_int, vp]),
+        "zk_pairing_bls12_381": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_int]),
+        "zk_pairing_bls12_381_dev": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_int, vp]),
+        "zk_groth16_vk_new": (vp, [C.c_char_p, C.c_char_p]),
+        "zk_groth16_vk_info": (C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "zk_groth16_vk_free": (C.c_int, [vp]),
+        "zk_groth16_verify_batch": (C.c_int, [vp, vp, vp, C.c_uint64, vp]),
+        "zk_groth16_verify_batch_dev": (C.c_int, [vp, vp, vp, C.c_uint64, vp, vp]),
+        "zk_groth16_verify_json": (C.c_int, [vp, C.c_char_p, C.c_char_p]),
+        "zk_groth16_verdict_name": (C.c_char_p, [C.c_int]),
         "zk_msm_g1_bn254": (C.c_int, [vp, vp, C.c_uint64, vp, C.POINTER(C.c_int)]),
         "zk_msm_g1_bn254_dev": (C.c_int, [vp, vp, C.c_uint64, vp, vp]),
         "zk_g1_bn254_mul_generator_dev": (C.c_int, [vp, C.c_uint64, vp, vp]),

@@ -1079,4 +1079,65 @@ int zk_groth16_keygen_free(zk_groth16_keygen_t* k) {
     return guard([&] { if (k) { delete k->impl; delete k; } });
 }
 
+// ---- pairings and Groth16 verification (pairing.hip) ----
+struct zk_groth16_vk { zk::Groth16Vk* impl; };
+#define ZK_PAIRING(NAME, CURVE, NLW)                                                                                              \
+    int zk_pairing_##NAME##_dev(const void* d_g1, const void* d_g2, uint64_t n, void* d_gt, int with_final_exp, void* stream) {   \
+        return guard([&] {                                                                                                        \
+            ZK_REQUIRE(n == 0 || (d_g1 && d_g2 && d_gt), "pairing: null argument");                                               \
+            pairing_dev(CURVE, d_g1, d_g2, n, d_gt, with_final_exp, on_stream((hipStream_t)stream));                              \
+        });                                                                                                                       \
+    }                                                                                                                             \
+    int zk_pairing_##NAME(const void* g1, const void* g2, uint64_t n, void* gt_out, int with_final_exp) {                         \
+        return guard([&] {                                                                                                        \
+            ZK_REQUIRE(n == 0 || (g1 && g2 && gt_out), "pairing: null argument");                                                 \
+            if (n == 0) return;                                                                                                   \
+            DevBuf d1, d2, dg;                                                                                                    \
+            d1.reserve(n * 8 * NLW); d2.reserve(n * 16 * NLW); dg.reserve(n * 48 * NLW);                                          \
+            h2d_sync(d1.p, g1, n * 8 * NLW); h2d_sync(d2.p, g2, n * 16 * NLW);                                                    \
+            pairing_dev(CURVE, d1.p, d2.p, n, dg.p, with_final_exp, cur_stream());                                                \
+            d2h_sync(gt_out, dg.p, n * 48 * NLW);                                                                                 \
+        });                                                                                                                       \
+    }
+ZK_PAIRING(bn254, "BN128", 8)
+ZK_PAIRING(bls12_381, "BLS12381", 12)
+#undef ZK_PAIRING
+zk_groth16_vk_t* zk_groth16_vk_new(const char* curve, const char* vk_json) {
+    zk_groth16_vk_t* h = nullptr;
+    if (guard([&] { Groth16Vk* v = groth16_vk_new(curve, vk_json); h = new zk_groth16_vk{v}; }) != 0) return nullptr;
+    return h;
+}
+int zk_groth16_vk_info(const zk_groth16_vk_t* vk, uint32_t* n_public, uint32_t* proof_bytes, uint32_t* gt_bytes) {
+    return guard([&] { ZK_REQUIRE(vk && vk->impl, "groth16 verify: null key"); groth16_vk_info(vk->impl, n_public, proof_bytes, gt_bytes); });
+}
+int zk_groth16_vk_free(zk_groth16_vk_t* vk) {
+    return guard([&] { if (vk) { groth16_vk_free(vk->impl); delete vk; } });
+}
+int zk_groth16_verify_batch(const zk_groth16_vk_t* vk, const void* proofs, const void* publics, uint64_t n, int* verdicts) {
+    return guard([&] { ZK_REQUIRE(vk && vk->impl, "groth16 verify: null key"); groth16_verify_batch(vk->impl, proofs, publics, n, verdicts); });
+}
+int zk_groth16_verify_batch_dev(const zk_groth16_vk_t* vk, const void* d_proofs, const void* d_publics, uint64_t n, int* d_verdicts, void* stream) {
+    return guard([&] {
+        ZK_REQUIRE(vk && vk->impl, "groth16 verify: null key");
+        groth16_verify_batch_dev(vk->impl, d_proofs, d_publics, n, d_verdicts, on_stream((hipStream_t)stream));
+    });
+}
+int zk_groth16_verify_json(const zk_groth16_vk_t* vk, const char* proof_json, const char* public_input_json) {
+    int verdict = ZK_VERDICT_ERROR;
+    if (guard([&] { ZK_REQUIRE(vk && vk->impl, "groth16 verify: null key"); verdict = groth16_verify_json(vk->impl, proof_json, public_input_json); }) != 0)
+        return ZK_VERDICT_ERROR;
+    return verdict;
+}
+const char* zk_groth16_verdict_name(int verdict) {
+    switch (verdict) {
+        case ZK_VERDICT_ACCEPTED: return "accepted";
+        case ZK_VERDICT_REJECTED: return "the verification equation does not hold";
+        case ZK_VERDICT_INPUT_NOT_CANONICAL: return "a public input is not below the group order";
+        case ZK_VERDICT_INPUT_COUNT: return "wrong number of public inputs";
+        case ZK_VERDICT_NOT_ON_CURVE: return "a proof point is not on its curve";
+        case ZK_VERDICT_NOT_IN_SUBGROUP: return "a proof point is outside the subgroup of order r";
+        default: return "error";
+    }
+}
+
 }  // extern "C"

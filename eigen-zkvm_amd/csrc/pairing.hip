@@ -1,0 +1,291 @@
+// Optimal ate pairing on BN254 and BLS12-381 and Groth16 verification for gfx950: what `zkit groth16_verify` computes
+// (zkit/src/main.rs:221-230, groth16/src/api.rs:302-341 -> bellman's prepare_verifying_key + verify_proof -> pairing_ce).
+//
+// Tower: Fq2 = Fq[u]/(u^2 + 1), Fq12 = Fq2[w]/(w^6 - xi); BN254: xi = 9 + u, D-type twist, loop count 6t + 2 and the two
+// Frobenius steps; BLS12-381: xi = 1 + u, M-type twist, loop count |x|, the Miller value conjugated because x < 0.
+// Pipeline (pairing_impl.hip.h), all on one stream:
+//   1. g2_lines_kernel    one lane per twist point: the line coefficients of every step (Jacobian, no inversion) -- once per
+//                         key for -gamma and -delta (the part of prepare_verifying_key), once per proof for B
+//   2. miller_kernel      eight lanes per item (six own the Fq2 coefficients of w^0..w^5): one squaring per step shared by
+//                         up to three pairs, the lines multiplied in as sparse elements
+//   3. final_exp_kernel   the same lanes: easy part with one inversion, hard part (q^4 - q^2 + 1)/r in a 4-bit window over
+//                         Granger-Scott squarings; the exact reduced pairing
+// and around them the input checks (curve, subgroup by [r]P = O, canonical public inputs), acc = IC_0 + sum x_j IC_j, and
+// the comparison with e(alpha, beta).  Stricter than the reference, which reads points unchecked (json_utils.rs:163-198).
+// Fq, Fq2 and the point formulas are the sums' (fe29_impl.hip.h, ecpt_impl.hip.h); fe_mul and the Fq2 product are real
+// functions here, and the loops over exponent bits stay loops: the code-size hazard recorded in msm.hip.
+#include "zk_internal.h"
+#include "curve_consts.hip.h"
+#include "pairing_consts.hip.h"
+#include "json_min.h"
+#include <cstring>
+#include <memory>
+
+namespace zk {
+
+struct MillerArgs {
+    const u32* g1[3]; u64 g1_stride[3];
+    const u32* lines[3]; u64 lines_stride[3];
+    const u32* inf[3]; u64 inf_stride[3];
+    int np;
+};
+// what the host code below needs of a curve
+struct PairingOps {
+    int nl; const char* q_hex;
+    void (*g1_check)(const void*, u64, u64, int*, u64, hipStream_t);
+    void (*g16_acc)(const void*, u32, const void*, u64, void*, int*, hipStream_t);
+    void (*g2_check)(const void*, u64, u64, int*, u64, hipStream_t);
+    size_t (*lines_bytes)(u64);
+    void (*g2_lines)(const void*, u64, u64, void*, void*, hipStream_t);
+    size_t (*f12_bytes)(u64);
+    size_t (*tab_bytes)(u64);
+    void (*miller)(const MillerArgs&, u64, void*, hipStream_t);
+    void (*final_exp)(const void*, u64, void*, void*, int, hipStream_t);
+    void (*verdict)(const void*, const void*, u64, const int*, int*, hipStream_t);
+    void (*to_mont)(void*, uint64_t, hipStream_t);
+};
+
+#define FQ_MUL_ATTR __noinline__
+
+namespace bn254 {
+namespace pg1 {
+namespace {
+#include "ecpt_impl.hip.h"
+#include "pairing_impl.hip.h"
+}
+}  // namespace pg1
+namespace pg2 {
+#define MSM_G2
+namespace {
+#include "ecpt_impl.hip.h"
+#include "pairing_impl.hip.h"
+}
+#undef MSM_G2
+#undef CF_MUL_ATTR
+#undef PT_COLD_ATTR
+}  // namespace pg2
+static const PairingOps OPS = {NL, "30644e72e131a029b85045b68181585d97816a916871ca8d3c208c16d87cfd47",
+                               pg1::g1_check_dev, pg1::g16_acc_dev, pg2::g2_check_dev, pg2::g2_lines_bytes, pg2::g2_lines_dev, pg2::f12_bytes,
+                               pg2::final_exp_tab_bytes, pg2::miller_dev, pg2::final_exp_dev, pg2::g16_verdict_dev, fq_bn254_canon_to_mont_dev};
+}  // namespace bn254
+namespace bls12_381 {
+namespace pg1 {
+namespace {
+#include "ecpt_impl.hip.h"
+#include "pairing_impl.hip.h"
+}
+}  // namespace pg1
+namespace pg2 {
+#define MSM_G2
+namespace {
+#include "ecpt_impl.hip.h"
+#include "pairing_impl.hip.h"
+}
+#undef MSM_G2
+#undef CF_MUL_ATTR
+#undef PT_COLD_ATTR
+}  // namespace pg2
+static const PairingOps OPS = {NL, "1a0111ea397fe69a4b1ba7b6434bacd764774b84f38512bf6730d2a0f6b0f6241eabfffeb153ffffb9feffffffffaaab",
+                               pg1::g1_check_dev, pg1::g16_acc_dev, pg2::g2_check_dev, pg2::g2_lines_bytes, pg2::g2_lines_dev, pg2::f12_bytes,
+                               pg2::final_exp_tab_bytes, pg2::miller_dev, pg2::final_exp_dev, pg2::g16_verdict_dev, fq_bls12_381_canon_to_mont_dev};
+}  // namespace bls12_381
+#undef FQ_MUL_ATTR
+
+static const PairingOps& ops_of(const char* curve) {
+    ZK_REQUIRE(curve, "pairing: null curve");
+    const std::string c(curve);
+    if (c == "BN128" || c == "bn254") return bn254::OPS;
+    if (c == "BLS12381" || c == "bls12_381") return bls12_381::OPS;
+    throw Error("pairing: unknown curve '" + c + "' (BN128 | BLS12381)");
+}
+struct PoolBuf {   // a block of the pool for the length of one call; freeing is ordered on the call's stream (devmem.hip)
+    void* p;
+    explicit PoolBuf(size_t n) : p(pool_alloc(n ? n : 4)) {}
+    ~PoolBuf() { pool_free(p); }
+    PoolBuf(const PoolBuf&) = delete; PoolBuf& operator=(const PoolBuf&) = delete;
+};
+
+// n pairs (G1 n x 2 NL words, G2 n x 4 NL words, external layout) -> n GT values of 12 canonical Fq
+static void pairing_run(const PairingOps& o, const void* d_g1, const void* d_g2, u64 n, void* d_gt, int with_final_exp, hipStream_t st) {
+    if (!n) return;
+    PoolBuf lines(o.lines_bytes(n)), inf(4 * n), f(o.f12_bytes(n)), tab(with_final_exp ? o.tab_bytes(n) : 4);
+    o.g2_lines(d_g2, 4 * (u64)o.nl, n, lines.p, inf.p, st);
+    MillerArgs a{};
+    a.np = 1;
+    a.g1[0] = (const u32*)d_g1; a.g1_stride[0] = 2 * (u64)o.nl;
+    a.lines[0] = (const u32*)lines.p; a.lines_stride[0] = o.lines_bytes(1) / 4;
+    a.inf[0] = (const u32*)inf.p; a.inf_stride[0] = 1;
+    o.miller(a, n, f.p, st);
+    o.final_exp(f.p, n, tab.p, d_gt, with_final_exp, st);
+}
+void pairing_dev(const char* curve, const void* d_g1, const void* d_g2, uint64_t n, void* d_gt, int with_final_exp, hipStream_t st) {
+    pairing_run(ops_of(curve), d_g1, d_g2, n, d_gt, with_final_exp, st);
+}
+
+// ---- Groth16 -------------------------------------------------------------------------------------------------------------------
+struct Groth16Vk {
+    const PairingOps* o = nullptr;
+    std::string curve;
+    uint32_t n_ic = 0;
+    void *d_ic = nullptr, *d_lines = nullptr, *d_inf = nullptr, *d_ab = nullptr;   // IC (Montgomery), the lines of -gamma and -delta, e(alpha, beta)
+    ~Groth16Vk() { for (void* p : {d_ic, d_lines, d_inf, d_ab}) if (p) pool_free(p); }
+};
+// a decimal or 0x string -> little-endian 32-bit words; false when it does not fit
+static bool parse_int(const std::string& s, u32* w, int nw) {
+    for (int i = 0; i < nw; ++i) w[i] = 0;
+    const bool hex = s.size() > 2 && s[0] == '0' && (s[1] == 'x' || s[1] == 'X');
+    ZK_REQUIRE(!s.empty() && (!hex || s.size() > 2), "groth16 verify: empty number");
+    for (size_t i = hex ? 2 : 0; i < s.size(); ++i) {
+        const char ch = s[i];
+        u32 d;
+        if (ch >= '0' && ch <= '9') d = (u32)(ch - '0');
+        else if (hex && ch >= 'a' && ch <= 'f') d = (u32)(ch - 'a' + 10);
+        else if (hex && ch >= 'A' && ch <= 'F') d = (u32)(ch - 'A' + 10);
+        else throw Error("groth16 verify: '" + s + "' is not a number");
+        uint64_t carry = d;
+        for (int k = 0; k < nw; ++k) { const uint64_t v = (uint64_t)w[k] * (hex ? 16 : 10) + carry; w[k] = (u32)v; carry = v >> 32; }
+        if (carry) return false;
+    }
+    return true;
+}
+static const std::string& jstr(const JVal& v) { ZK_REQUIRE(v.kind == JVal::Str || v.kind == JVal::Num, "groth16 verify: a number string expected"); return v.s; }
+static void parse_fq(const PairingOps& o, const JVal& v, u32* w) { ZK_REQUIRE(parse_int(jstr(v), w, o.nl), "groth16 verify: a coordinate does not fit the base field's width"); }
+// {"x", "y"} -> 2 NL canonical words; pairing_ce's zero (0, 1) becomes the all-zero encoding
+static void parse_g1(const PairingOps& o, const JVal& v, u32* w) {
+    parse_fq(o, v.at("x"), w); parse_fq(o, v.at("y"), w + o.nl);
+    bool zero = w[o.nl] == 1;
+    for (int i = 0; i < 2 * o.nl; ++i) if (i != o.nl && w[i]) zero = false;
+    if (zero) w[o.nl] = 0;
+}
+static void parse_g2(const PairingOps& o, const JVal& v, u32* w, bool negate) {
+    for (int c = 0; c < 2; ++c) { parse_fq(o, v.at("x").at(c), w + c * o.nl); parse_fq(o, v.at("y").at(c), w + (2 + c) * o.nl); }
+    bool zero = w[2 * o.nl] == 1;
+    for (int i = 0; i < 4 * o.nl; ++i) if (i != 2 * o.nl && w[i]) zero = false;
+    if (zero) w[2 * o.nl] = 0;
+    if (!negate || zero) return;
+    std::vector<u32> q(o.nl);
+    parse_int(std::string("0x") + o.q_hex, q.data(), o.nl);
+    for (int c = 2; c < 4; ++c) {                          // y -> q - y (a coordinate >= q stays as it is and fails the curve check)
+        u32* y = w + c * o.nl;
+        bool nz = false, lt = false;
+        for (int i = 0; i < o.nl; ++i) nz |= y[i] != 0;
+        for (int i = o.nl - 1; i >= 0; --i) if (y[i] != q[i]) { lt = y[i] < q[i]; break; }
+        if (!nz || !lt) continue;
+        uint64_t br = 0;
+        for (int i = 0; i < o.nl; ++i) { const uint64_t d = (uint64_t)q[i] - y[i] - br; y[i] = (u32)d; br = (d >> 32) & 1; }
+    }
+}
+static void* upload_mont(const PairingOps& o, const std::vector<u32>& canon, hipStream_t st) {
+    void* d = pool_alloc(canon.size() * 4);
+    try {
+        h2d_sync(d, canon.data(), canon.size() * 4);
+        o.to_mont(d, canon.size() / o.nl, st);
+    } catch (...) { pool_free(d); throw; }
+    return d;
+}
+
+Groth16Vk* groth16_vk_new(const char* curve, const char* vk_json) {
+    ZK_REQUIRE(vk_json, "groth16 verify: null verification key");
+    const PairingOps& o = ops_of(curve);
+    const JVal js = JParser::parse(vk_json);
+    if (const JVal* c = js.find("curve")) ZK_REQUIRE(&ops_of(c->str().c_str()) == &o, "groth16 verify: the key is for curve " + c->str());
+    const JVal& ic = js.at("IC");
+    ZK_REQUIRE(ic.kind == JVal::Arr && ic.size() >= 1, "groth16 verify: IC must hold at least one point");
+    const int nl = o.nl;
+    std::vector<u32> g1((ic.size() + 1) * 2 * nl), g2(3 * 4 * nl);              // alpha, IC... ; beta, -gamma, -delta
+    parse_g1(o, js.at("vk_alpha_1"), g1.data());
+    for (size_t i = 0; i < ic.size(); ++i) parse_g1(o, ic.at(i), g1.data() + (i + 1) * 2 * nl);
+    parse_g2(o, js.at("vk_beta_2"), g2.data(), false);
+    parse_g2(o, js.at("vk_gamma_2"), g2.data() + 4 * nl, true);
+    parse_g2(o, js.at("vk_delta_2"), g2.data() + 8 * nl, true);
+    hipStream_t st = cur_stream();
+    auto vk = std::make_unique<Groth16Vk>();
+    vk->o = &o; vk->curve = curve; vk->n_ic = (uint32_t)ic.size();
+    PoolBuf dg1(g1.size() * 4), dg2(g2.size() * 4), status(4 * (g1.size() / (2 * nl) + 3));
+    h2d_sync(dg1.p, g1.data(), g1.size() * 4); h2d_sync(dg2.p, g2.data(), g2.size() * 4);
+    o.to_mont(dg1.p, g1.size() / nl, st); o.to_mont(dg2.p, g2.size() / nl, st);
+    const u64 n1 = g1.size() / (2 * nl);
+    ZK_HIP(hipMemsetD32Async((hipDeviceptr_t)status.p, 1, n1 + 3, st));
+    o.g1_check(dg1.p, 2 * (u64)nl, n1, (int*)status.p, 1, st);
+    o.g2_check(dg2.p, 4 * (u64)nl, 3, (int*)status.p + n1, 1, st);
+    std::vector<int> hs(n1 + 3);
+    d2h_sync(hs.data(), status.p, hs.size() * 4);
+    for (size_t i = 0; i < hs.size(); ++i)
+        ZK_REQUIRE(hs[i] == 1, std::string("groth16 verify: a point of the verification key is ") + (hs[i] == -3 ? "not on its curve" : "outside the subgroup of order r"));
+    vk->d_ic = pool_alloc(ic.size() * 2 * nl * 4);
+    ZK_HIP(hipMemcpyAsync(vk->d_ic, (const u32*)dg1.p + 2 * nl, ic.size() * 2 * nl * 4, hipMemcpyDeviceToDevice, st));
+    vk->d_ab = pool_alloc(12 * nl * 4);
+    pairing_run(o, dg1.p, dg2.p, 1, vk->d_ab, 1, st);
+    vk->d_lines = pool_alloc(o.lines_bytes(2)); vk->d_inf = pool_alloc(8);
+    o.g2_lines((const u32*)dg2.p + 4 * nl, 4 * (u64)nl, 2, vk->d_lines, vk->d_inf, st);
+    ZK_HIP(hipStreamSynchronize(st));
+    return vk.release();
+}
+void groth16_vk_free(Groth16Vk* vk) { delete vk; }
+void groth16_vk_info(const Groth16Vk* vk, uint32_t* n_public, uint32_t* proof_bytes, uint32_t* gt_bytes) {
+    ZK_REQUIRE(vk, "groth16 verify: null key");
+    if (n_public) *n_public = vk->n_ic - 1;
+    if (proof_bytes) *proof_bytes = 8 * vk->o->nl * 4;
+    if (gt_bytes) *gt_bytes = 12 * vk->o->nl * 4;
+}
+// proofs: n x (A | B | C) in the layout zk_groth16_prove writes; publics: n x n_public x 8 words canonical; verdicts: n ints
+void groth16_verify_batch_dev(const Groth16Vk* vk, const void* d_proofs, const void* d_publics, uint64_t n, int* d_verdicts, hipStream_t st) {
+    ZK_REQUIRE(vk, "groth16 verify: null key");
+    if (!n) return;
+    ZK_REQUIRE(d_proofs && d_verdicts && (d_publics || vk->n_ic == 1), "groth16 verify: null argument");
+    const PairingOps& o = *vk->o;
+    const u64 nl = o.nl, pw = 8 * nl;
+    const u32* pr = (const u32*)d_proofs;
+    PoolBuf status(4 * n), acc(n * 2 * nl * 4), lines(o.lines_bytes(n)), inf(4 * n), f(o.f12_bytes(n)), tab(o.tab_bytes(n)), gt(n * 12 * nl * 4);
+    ZK_HIP(hipMemsetD32Async((hipDeviceptr_t)status.p, 1, n, st));
+    o.g1_check(pr, pw, n, (int*)status.p, 1, st);
+    o.g1_check(pr + 6 * nl, pw, n, (int*)status.p, 1, st);
+    o.g2_check(pr + 2 * nl, pw, n, (int*)status.p, 1, st);
+    o.g16_acc(vk->d_ic, vk->n_ic - 1, d_publics, n, acc.p, (int*)status.p, st);
+    o.g2_lines(pr + 2 * nl, pw, n, lines.p, inf.p, st);
+    const u64 lw = o.lines_bytes(1) / 4;
+    MillerArgs a{};
+    a.np = 3;
+    a.g1[0] = pr; a.g1_stride[0] = pw; a.lines[0] = (const u32*)lines.p; a.lines_stride[0] = lw; a.inf[0] = (const u32*)inf.p; a.inf_stride[0] = 1;
+    a.g1[1] = (const u32*)acc.p; a.g1_stride[1] = 2 * nl; a.lines[1] = (const u32*)vk->d_lines; a.lines_stride[1] = 0; a.inf[1] = (const u32*)vk->d_inf; a.inf_stride[1] = 0;
+    a.g1[2] = pr + 6 * nl; a.g1_stride[2] = pw; a.lines[2] = (const u32*)vk->d_lines + lw; a.lines_stride[2] = 0; a.inf[2] = (const u32*)vk->d_inf + 1; a.inf_stride[2] = 0;
+    o.miller(a, n, f.p, st);
+    o.final_exp(f.p, n, tab.p, gt.p, 1, st);
+    o.verdict(gt.p, vk->d_ab, n, (const int*)status.p, d_verdicts, st);
+}
+void groth16_verify_batch(const Groth16Vk* vk, const void* proofs, const void* publics, uint64_t n, int* verdicts) {
+    ZK_REQUIRE(vk, "groth16 verify: null key");
+    if (!n) return;
+    ZK_REQUIRE(proofs && verdicts && (publics || vk->n_ic == 1), "groth16 verify: null argument");
+    const size_t pb = 8 * (size_t)vk->o->nl * 4, ub = (size_t)(vk->n_ic - 1) * 32;
+    PoolBuf dp(n * pb), du(n * ub), dv(n * 4);
+    h2d_sync(dp.p, proofs, n * pb);
+    if (ub) h2d_sync(du.p, publics, n * ub);
+    groth16_verify_batch_dev(vk, dp.p, du.p, n, (int*)dv.p, cur_stream());
+    d2h_sync(verdicts, dv.p, n * 4);
+}
+// the file-level form (api.rs:302-341): proof.json and public_input.json -> verdict
+int groth16_verify_json(const Groth16Vk* vk, const char* proof_json, const char* public_json) {
+    ZK_REQUIRE(vk && proof_json && public_json, "groth16 verify: null argument");
+    const PairingOps& o = *vk->o;
+    const int nl = o.nl;
+    const JVal pj = JParser::parse(proof_json), uj = JParser::parse(public_json);
+    ZK_REQUIRE(uj.kind == JVal::Arr, "groth16 verify: public_input.json must be an array");
+    if (uj.size() != vk->n_ic - 1) return -2;
+    std::vector<u32> pts(8 * nl), pub(8 * uj.size() + 8);
+    parse_g1(o, pj.at("pi_a"), pts.data()); parse_g2(o, pj.at("pi_b"), pts.data() + 2 * nl, false); parse_g1(o, pj.at("pi_c"), pts.data() + 6 * nl);
+    for (size_t i = 0; i < uj.size(); ++i) if (!parse_int(jstr(uj.at(i)), pub.data() + 8 * i, 8)) return -1;
+    hipStream_t st = cur_stream();
+    void* dp = upload_mont(o, pts, st);
+    int verdict = 0;
+    try {
+        PoolBuf du(pub.size() * 4), dv(4);
+        h2d_sync(du.p, pub.data(), pub.size() * 4);
+        groth16_verify_batch_dev(vk, dp, du.p, 1, (int*)dv.p, st);
+        d2h_sync(&verdict, dv.p, 4);
+    } catch (...) { pool_free(dp); throw; }
+    pool_free(dp);
+    return verdict;
+}
+
+}  // namespace zk

@@ -288,4 +288,14 @@ struct Groth16Key { std::string curve; std::vector<uint8_t> params; double ms[5]
 Groth16Key* groth16_keygen_new(const char* curve, const void* r1cs, size_t r1cs_len, const uint64_t* trapdoor);
 std::string groth16_keygen_vk_json(const Groth16Key& k, bool to_hex);   // json_utils.rs:285-303 serialize_vk
 
+// ---- pairing.hip: the optimal ate pairing and Groth16 verification ("BN128" | "BLS12381") ----
+struct Groth16Vk;
+void pairing_dev(const char* curve, const void* d_g1, const void* d_g2, uint64_t n, void* d_gt, int with_final_exp, hipStream_t st);
+Groth16Vk* groth16_vk_new(const char* curve, const char* vk_json);
+void groth16_vk_free(Groth16Vk* vk);
+void groth16_vk_info(const Groth16Vk* vk, uint32_t* n_public, uint32_t* proof_bytes, uint32_t* gt_bytes);
+void groth16_verify_batch_dev(const Groth16Vk* vk, const void* d_proofs, const void* d_publics, uint64_t n, int* d_verdicts, hipStream_t st);
+void groth16_verify_batch(const Groth16Vk* vk, const void* proofs, const void* publics, uint64_t n, int* verdicts);
+int groth16_verify_json(const Groth16Vk* vk, const char* proof_json, const char* public_json);
+
 }  // namespace zk

@@ -133,3 +133,83 @@ def fq_convert(d_elems, curve="BN128", to_mont=True, stream=0):
     """Fq::from_repr / into_repr on a DevArray of base-field elements, in place"""
     nl = _FQ_WORDS[curve]
     _check(getattr(lib(), "zk_fq_%s_convert_dev" % _NAME[curve])(d_elems.ptr, d_elems.n // nl, int(to_mont), stream)); return d_elems
+
+
+# ---- verification (`zkit groth16_verify`, api.rs:302-341) ----
+ACCEPTED, REJECTED, INPUT_NOT_CANONICAL, INPUT_COUNT, NOT_ON_CURVE, NOT_IN_SUBGROUP, VERDICT_ERROR = 1, 0, -1, -2, -3, -4, -100
+
+
+def verdict_name(v):
+    return lib().zk_groth16_verdict_name(int(v)).decode()
+
+
+def pairing(g1, g2, curve="BN128", final_exp=True):
+    """n pairs in the layout of the multi-scalar sums (g1: n x 2 Fq, g2: n x 4 Fq as u64 Montgomery words; all zero = infinity)
+    -> n x 12 x (4 | 6) u64: the GT values as canonical Fq, c0 and c1 of the coefficients of w^0 .. w^5"""
+    if curve not in _FR:
+        raise ZkError('pairing: unknown curve "%s" (BN128 | BLS12381)' % curve)
+    nl = _FQ_WORDS[curve]
+    a, b = np.ascontiguousarray(_np(g1)).reshape(-1), np.ascontiguousarray(_np(g2)).reshape(-1)
+    n = a.size // (2 * nl)
+    if a.size != n * 2 * nl or b.size != n * 4 * nl:
+        raise ZkError("pairing: g1 must hold n x 2 and g2 n x 4 base-field elements")
+    out = np.zeros((n, 12, nl), np.uint64)
+    _check(getattr(lib(), "zk_pairing_%s" % _NAME[curve])(_ptr(a), _ptr(b), n, _ptr(out), int(bool(final_exp))))
+    return out
+
+
+class Groth16VerifyingKey:
+    """bellman's PreparedVerifyingKey on the device: e(alpha, beta), the line tables of -gamma and -delta, the IC points.
+    Stricter than the reference (which reads points unchecked): every point must be on its curve and of order r, every public
+    input below r; the verdict says which check failed (ACCEPTED = 1, REJECTED = 0, negative = malformed input)."""
+
+    def __init__(self, curve, vk_json):
+        if curve not in _FR:
+            raise ZkError('groth16: unknown curve "%s" (BN128 | BLS12381)' % curve)
+        self.curve = curve
+        text = vk_json if isinstance(vk_json, str) else json.dumps(vk_json)
+        self._h = lib().zk_groth16_vk_new(curve.encode(), text.encode())
+        if not self._h:
+            raise ZkError(lib().zk_last_error().decode())
+        a, b, c = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        _check(lib().zk_groth16_vk_info(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        self.n_public, self.proof_bytes = a.value, b.value
+
+    def verify(self, proof_json, public):
+        """proof.json (text or dict) and the public inputs (public_input.json text, or a list of integers / strings) -> verdict"""
+        p = proof_json if isinstance(proof_json, str) else json.dumps(proof_json)
+        u = public if isinstance(public, str) else json.dumps([str(x) for x in public])
+        v = lib().zk_groth16_verify_json(self._h, p.encode(), u.encode())
+        if v == VERDICT_ERROR:
+            raise ZkError(lib().zk_last_error().decode())
+        return v
+
+    def verify_batch(self, points, publics):
+        """points: n x (A || B || C) u64 Montgomery words as Groth16Setup.prove returns them; publics: n lists of n_public
+        integers -> n verdicts (numpy int32)"""
+        pts = np.ascontiguousarray(_np(points)).reshape(-1)
+        n = pts.size * 8 // self.proof_bytes
+        if pts.size * 8 != n * self.proof_bytes or len(publics) != n:
+            raise ZkError("groth16 verify: points must hold n proofs and publics n input lists")
+        out = np.zeros(n, np.int32)
+        ok = [i for i in range(n) if len(publics[i]) == self.n_public and all(0 <= int(x) < 2**256 for x in publics[i])]
+        bad = set(range(n)) - set(ok)
+        for i in bad:
+            out[i] = INPUT_COUNT if len(publics[i]) != self.n_public else INPUT_NOT_CANONICAL
+        if ok:
+            sel = np.ascontiguousarray(pts.reshape(n, -1)[ok]).reshape(-1)
+            pub = np.array([[(int(x) >> (64 * k)) & (2**64 - 1) for x in publics[i] for k in range(4)] for i in ok], dtype=np.uint64).reshape(-1)
+            v = np.zeros(len(ok), np.int32)
+            _check(lib().zk_groth16_verify_batch(self._h, _ptr(sel), _ptr(pub) if pub.size else None, len(ok), _ptr(v)))
+            out[ok] = v
+        return out
+
+    def free(self):
+        if self._h:
+            lib().zk_groth16_vk_free(self._h); self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass

@@ -465,6 +465,45 @@ char* zk_groth16_keygen_vk_json(const zk_groth16_keygen_t* k, int to_hex);
 int zk_groth16_keygen_timing(const zk_groth16_keygen_t* k, double ms[5]);
 int zk_groth16_keygen_free(zk_groth16_keygen_t* k);
 
+/* ---- pairings and Groth16 verification (`zkit groth16_verify`, zkit/src/main.rs:221-230, groth16/src/api.rs:302-341 ->
+ * bellman's prepare_verifying_key + verify_proof) --------------------------------------------------------------------
+ * zk_pairing_*: n pairs (g1[i], g2[i]) in the point layout of the multi-scalar sums (affine, Montgomery; the all-zero
+ * encoding is the point at infinity and gives 1) -> n values of GT, each 12 canonical little-endian Fq (32 B / 48 B):
+ * c0, c1 of the Fq2 coefficient of w^0, then of w^1 .. w^5, in Fq12 = Fq2[w]/(w^6 - xi), Fq2 = Fq[u]/(u^2 + 1), xi = 9 + u
+ * (BN254) / 1 + u (BLS12-381).  with_final_exp = 0 stops after the Miller loop (a value defined up to factors the final
+ * exponentiation removes).  The optimal ate pairing as pairing_ce computes it (BLS12-381: conjugated for the negative
+ * curve parameter).  Points are taken as they are: no curve or subgroup check here.
+ * zk_groth16_vk_new parses verification_key.json as zk_groth16_keygen_vk_json writes it and json_utils.rs reads it
+ * (decimal or 0x strings), checks every point of it (curve, subgroup) and keeps on the device e(alpha, beta), the line
+ * tables of -gamma and -delta and the IC points; NULL on error (zk_last_error).  The handle owns them: zk_groth16_vk_free.
+ * zk_groth16_verify_batch: n proofs, each A || B || C exactly as zk_groth16_prove writes its `proof` argument, and
+ * n x n_public x 32 B canonical public inputs (n_public = len(IC) - 1, zk_groth16_vk_info) -> n verdicts.  One verdict per
+ * proof; the checks are stricter than the reference's, which reads points unchecked (json_utils.rs:163-198): proof points
+ * must be on their curve and in the subgroup of order r ([r]P = O), inputs must be below r.
+ * zk_groth16_verify_json: the file-level form, proof.json and public_input.json -> the verdict, or ZK_VERDICT_ERROR
+ * (zk_last_error) when a file cannot be read as what it should be.                                                   */
+enum {
+    ZK_VERDICT_ACCEPTED = 1,
+    ZK_VERDICT_REJECTED = 0,              /* well-formed, the equation does not hold */
+    ZK_VERDICT_INPUT_NOT_CANONICAL = -1,  /* a public input >= r */
+    ZK_VERDICT_INPUT_COUNT = -2,          /* number of public inputs != len(IC) - 1 */
+    ZK_VERDICT_NOT_ON_CURVE = -3,         /* A, B or C not on its curve */
+    ZK_VERDICT_NOT_IN_SUBGROUP = -4,      /* on the curve, not of order r */
+    ZK_VERDICT_ERROR = -100               /* the call itself failed */
+};
+int zk_pairing_bn254(const void* g1, const void* g2, uint64_t n, void* gt_out, int with_final_exp);
+int zk_pairing_bn254_dev(const void* d_g1, const void* d_g2, uint64_t n, void* d_gt, int with_final_exp, void* stream);
+int zk_pairing_bls12_381(const void* g1, const void* g2, uint64_t n, void* gt_out, int with_final_exp);
+int zk_pairing_bls12_381_dev(const void* d_g1, const void* d_g2, uint64_t n, void* d_gt, int with_final_exp, void* stream);
+typedef struct zk_groth16_vk zk_groth16_vk_t;
+zk_groth16_vk_t* zk_groth16_vk_new(const char* curve, const char* vk_json);
+int zk_groth16_vk_info(const zk_groth16_vk_t* vk, uint32_t* n_public, uint32_t* proof_bytes, uint32_t* gt_bytes);
+int zk_groth16_vk_free(zk_groth16_vk_t* vk);
+int zk_groth16_verify_batch(const zk_groth16_vk_t* vk, const void* proofs, const void* publics, uint64_t n, int* verdicts);
+int zk_groth16_verify_batch_dev(const zk_groth16_vk_t* vk, const void* d_proofs, const void* d_publics, uint64_t n, int* d_verdicts, void* stream);
+int zk_groth16_verify_json(const zk_groth16_vk_t* vk, const char* proof_json, const char* public_input_json);
+const char* zk_groth16_verdict_name(int verdict);
+
 /* ---- compressor12 exec (recursion/src/compressor12/compressor12_exec.rs:17-103) ----------------
  * The step between a recursive circuit's circom witness and the committed trace of its STARK: the PlonkAdd sums
  * appended to the witness (:60-66) and the s_map gather into the 12 columns of Compressor.a (:72-94).

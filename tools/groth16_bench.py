@@ -3,7 +3,9 @@ Rows i: (w[p] + c w[q]) * w[t] = w[new_i] over earlier wires (satisfied; the quo
 to be zero on the device result).  The proving key holds arbitrary valid points ([k]G with random 64-bit k, made
 on the device): timing does not depend on the key being a real setup, proofs made here do not verify.
 --real-key: the key comes from the library's own key generation (eigen_zkvm_amd.groth16.keygen, trapdoor drawn and
-forgotten by the library) -- its time and split are printed, and proofs made with it are valid."""
+forgotten by the library) -- its time and split are printed, and proofs made with it are valid.
+--verify [BN128|BLS12381] [batch ...]: the verification leg instead -- a key and a proof of a 2^8-row circuit made here, then the latency
+of one verification and verifications per second at the batch sizes given (default 1 64 4096), proofs and inputs in host memory."""
 import importlib, struct, sys, time, pathlib
 import numpy as np
 ROOT = pathlib.Path(__file__).resolve().parent.parent
@@ -84,8 +86,32 @@ def density(r1cs_bytes, ni, n_wires):
     return ni + int((a >= ni).sum()), int(b.size)
 
 
+def verify_leg(args):
+    curve = args.pop(0) if args and args[0] in FR else "BN128"
+    zk = eigen_zkvm_amd; zk.init(0)
+    dev = importlib.import_module("eigen_zkvm_amd.groth16")
+    rb, wit, ni, _ = make_circuit(FR[curve], 8)
+    pb, vk_json = dev.keygen(curve, rb)
+    S = dev.Groth16Setup(curve, rb, pb)
+    js, pts = S.prove(wit); S.free()
+    pub = [sum(int(v) << (64 * k) for k, v in enumerate(wit[i])) for i in range(1, ni)]
+    t = time.perf_counter(); vk = dev.Groth16VerifyingKey(curve, vk_json); t_key = time.perf_counter() - t
+    assert vk.verify(js, pub) == dev.ACCEPTED and vk.verify(js, [(pub[0] + 1) % FR[curve]]) == dev.REJECTED
+    print(f"{curve}: key prepared in {t_key*1e3:.1f} ms", flush=True)
+    for n in [int(a) for a in args] or [1, 64, 4096]:
+        batch, pubs = np.tile(np.asarray(pts), n), [pub] * n
+        assert vk.verify_batch(batch, pubs).tolist() == [1] * n                 # warm-up and check
+        ts = []
+        for _ in range(5):
+            t = time.perf_counter(); vk.verify_batch(batch, pubs); ts.append(time.perf_counter() - t)
+        ts.sort()
+        print(f"  batch {n}: median {ts[2]*1e3:.2f} ms (min {ts[0]*1e3:.2f}, max {ts[-1]*1e3:.2f}) -> {n/ts[2]:.0f} verifications/s", flush=True)
+
+
 def main():
     args = sys.argv[1:]
+    if "--verify" in args:
+        return verify_leg([a for a in args if a != "--verify"])
     real_key = "--real-key" in args
     args = [a for a in args if a != "--real-key"]
     curve = args.pop(0) if args and args[0] in FR else "BN128"

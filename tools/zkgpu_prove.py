@@ -5,7 +5,8 @@
                              -c verifier.circom --i zkin.json [--norm_stage] [--skip_main] [--agg_stage] [--prover_addr A] \\
                              [--program starkinfo_program.json]
   zkgpu_prove.py groth16_setup -c BN128 --r1cs circuit.r1cs -p g16.key -v verification_key.json [-t]
-  zkgpu_prove.py groth16_prove -c BN128 --r1cs circuit.r1cs -w witness.wtns -p g16.key --public-input public_input.json --proof proof.json
+  zkgpu_prove.py groth16_prove -c BN128 --r1cs circuit.r1cs -w witness.wtns -p g16.key --public-input public_input.json --proof proof.json [--verify verification_key.json]
+  zkgpu_prove.py groth16_verify -c BN128 -v verification_key.json --public-input public_input.json --proof proof.json
   zkgpu_prove.py stark_verify -s starkStruct.json -p circuit.pil.json --o circuit.const --i zkin.json [--program FILE]
   zkgpu_prove.py join_zkin --zkin1 a.zkin.json --zkin2 b.zkin.json --zkinout out.zkin.json
   zkgpu_prove.py stark_aggregate --gpus N --num_proof 8 --workspace DIR [--workers 4] [--keep_proofs]     (starts its own N ranks;
@@ -191,11 +192,30 @@ def groth16_prove(a):
     proof, _ = setup.prove(w)
     if a.to_hex:
         raise SystemExit("zkgpu_prove: -t (hex output) is not implemented")
-    json.dump(proof, open(a.proof_file, "w"))
     to_int = lambda row: sum(int(v) << (64 * i) for i, v in enumerate(row))
+    if a.verify_vk:                                                        # extension: the proof is checked before anything is written
+        vk = dev.Groth16VerifyingKey(a.curve_type, pathlib.Path(a.verify_vk).read_text())
+        verdict = vk.verify(proof, [to_int(w[i]) for i in range(1, setup.n_inputs)])
+        vk.free()
+        if verdict != dev.ACCEPTED:
+            raise SystemExit("zkgpu_prove: verify failed: %s; nothing written" % dev.verdict_name(verdict))
+    json.dump(proof, open(a.proof_file, "w"))
     json.dump([str(to_int(w[i])) for i in range(1, setup.n_inputs)], open(a.public_input_file, "w"))   # api.rs:175-177
     setup.free()
     print("zkgpu_prove: %s proof written to %s" % (a.curve_type, a.proof_file))
+
+
+def groth16_verify(a):
+    """groth16/src/api.rs:302-341: verification_key.json, public_input.json, proof.json -> accepted or not (on the device)"""
+    import importlib
+    _zk()
+    dev = importlib.import_module("eigen_zkvm_amd.groth16")
+    vk = dev.Groth16VerifyingKey(a.curve_type, pathlib.Path(a.vk_file).read_text())
+    verdict = vk.verify(pathlib.Path(a.proof_file).read_text(), pathlib.Path(a.public_input_file).read_text())
+    vk.free()
+    if verdict != dev.ACCEPTED:
+        raise SystemExit("zkgpu_prove: verify failed: %s" % dev.verdict_name(verdict))
+    print("zkgpu_prove: %s proof %s accepted" % (a.curve_type, a.proof_file))
 
 
 def main(argv=None):
@@ -251,7 +271,15 @@ def main(argv=None):
     g.add_argument("--public-input", dest="public_input_file", default="public_input.json")
     g.add_argument("--proof", dest="proof_file", default="proof.json")
     g.add_argument("-t", dest="to_hex", action="store_true")
+    g.add_argument("--verify", dest="verify_vk", default=None, metavar="VK.json",
+                   help="check the proof against this verification key before writing it (extension)")
     g.set_defaults(fn=groth16_prove)
+    gv = sub.add_parser("groth16_verify", help="Verify with groth16 (zkit/src/main.rs:221-230)")
+    gv.add_argument("-c", dest="curve_type", default="BN128")
+    gv.add_argument("-v", dest="vk_file", default="verification_key.json")
+    gv.add_argument("--public-input", dest="public_input_file", default="public_input.json")
+    gv.add_argument("--proof", dest="proof_file", default="proof.json")
+    gv.set_defaults(fn=groth16_verify)
     a = ap.parse_args(argv)
     a._argv = list(sys.argv[1:] if argv is None else argv)
     try:
