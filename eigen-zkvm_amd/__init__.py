@@ -50,6 +50,8 @@ EXPORTS = [
     "zk_msm_g1_bn254_table_bytes", "zk_msm_g1_bn254_table_build_dev", "zk_msm_g1_bn254_table_dev", "zk_msm_g1_bls12_381_table_bytes", "zk_msm_g1_bls12_381_table_build_dev", "zk_msm_g1_bls12_381_table_dev", "zk_msm_g2_bn254_table_bytes", "zk_msm_g2_bn254_table_build_dev", "zk_msm_g2_bn254_table_dev", "zk_msm_g2_bls12_381_table_bytes", "zk_msm_g2_bls12_381_table_build_dev", "zk_msm_g2_bls12_381_table_dev",
     "zk_fr_bn254_ntt", "zk_fr_bn254_ntt_dev", "zk_fr_bls12_381_ntt", "zk_fr_bls12_381_ntt_dev", "zk_fr_bn254_quotient_dev", "zk_fr_bls12_381_quotient_dev",
     "zk_c12_exec_new", "zk_c12_exec_dev", "zk_c12_exec_depth", "zk_c12_exec_free",
+    "zk_c12_setup_new", "zk_c12_setup_n_bits", "zk_c12_setup_n_publics", "zk_c12_setup_n_used", "zk_c12_setup_n_const", "zk_c12_setup_n_gates", "zk_c12_setup_n_adds",
+    "zk_c12_setup_gates", "zk_c12_setup_pil", "zk_c12_setup_exec", "zk_c12_setup_consts_dev", "zk_c12_setup_consts", "zk_c12_setup_free", "zk_c12_sigma_dev",
     "zk_fq_bn254_convert_dev", "zk_fq_bls12_381_convert_dev", "zk_groth16_setup_new", "zk_groth16_setup_info", "zk_groth16_prove", "zk_groth16_prove_dev", "zk_groth16_wtns_payload", "zk_groth16_setup_free",
     "zk_g1_bn254_mul_generator_fr_dev", "zk_g2_bn254_mul_generator_fr_dev", "zk_g1_bls12_381_mul_generator_fr_dev", "zk_g2_bls12_381_mul_generator_fr_dev",
     "zk_groth16_keygen_new", "zk_groth16_keygen_params_size", "zk_groth16_keygen_params", "zk_groth16_keygen_vk_json", "zk_groth16_keygen_timing", "zk_groth16_keygen_free",
@@ -243,6 +245,20 @@ def _load():
         "zk_c12_exec_dev": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, vp, vp]),
         "zk_c12_exec_depth": (C.c_uint64, [vp]),
         "zk_c12_exec_free": (C.c_int, [vp]),
+        "zk_c12_setup_new": (vp, [C.c_char_p, C.c_size_t, C.c_uint32]),
+        "zk_c12_setup_n_bits": (C.c_uint32, [vp]),
+        "zk_c12_setup_n_publics": (C.c_uint64, [vp]),
+        "zk_c12_setup_n_used": (C.c_uint64, [vp]),
+        "zk_c12_setup_n_const": (C.c_uint64, [vp]),
+        "zk_c12_setup_n_gates": (C.c_uint64, [vp]),
+        "zk_c12_setup_n_adds": (C.c_uint64, [vp]),
+        "zk_c12_setup_gates": (C.c_int, [vp, vp]),
+        "zk_c12_setup_pil": (vp, [vp]),
+        "zk_c12_setup_exec": (vp, [vp]),
+        "zk_c12_setup_consts_dev": (C.c_int, [vp, vp, vp]),
+        "zk_c12_setup_consts": (C.c_int, [vp, vp]),
+        "zk_c12_setup_free": (C.c_int, [vp]),
+        "zk_c12_sigma_dev": (C.c_int, [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]),
         "zk_groth16_setup_new": (vp, [C.c_char_p, vp, C.c_size_t, vp, C.c_size_t]),
         "zk_groth16_setup_info": (C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
         "zk_groth16_prove": (vp, [vp, vp, C.c_uint64, vp, vp, vp]),

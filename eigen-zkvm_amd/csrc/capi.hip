@@ -959,6 +959,59 @@ int zk_c12_exec_free(zk_c12_exec_t* e) {
     return guard([&] { if (e) { c12_exec_free(e->impl); delete e; } });
 }
 
+// ---- compressor12 setup (c12_setup.hip) ------------------------------------------------------------------------
+struct zk_c12_setup { C12Setup* impl; };
+static char* c12_dup(const std::string& s) {
+    char* out = (char*)malloc(s.size() + 1);
+    ZK_REQUIRE(out, "out of memory");
+    memcpy(out, s.c_str(), s.size() + 1);
+    return out;
+}
+zk_c12_setup_t* zk_c12_setup_new(const void* r1cs, size_t len, uint32_t force_n_bits) {
+    zk_c12_setup_t* out = nullptr;
+    if (guard([&] { C12Setup* s = c12_setup_new(r1cs, len, force_n_bits); out = new zk_c12_setup{s}; }) != 0) return nullptr;
+    return out;
+}
+static uint64_t c12_info(const zk_c12_setup_t* s, int i) { uint64_t v[6] = {}; if (s && s->impl) c12_setup_info(s->impl, v); return v[i]; }
+uint32_t zk_c12_setup_n_bits(const zk_c12_setup_t* s) { return (uint32_t)c12_info(s, 0); }
+uint64_t zk_c12_setup_n_publics(const zk_c12_setup_t* s) { return c12_info(s, 1); }
+uint64_t zk_c12_setup_n_used(const zk_c12_setup_t* s) { return c12_info(s, 2); }
+uint64_t zk_c12_setup_n_const(const zk_c12_setup_t* s) { return c12_info(s, 3); }
+uint64_t zk_c12_setup_n_gates(const zk_c12_setup_t* s) { return c12_info(s, 4); }
+uint64_t zk_c12_setup_n_adds(const zk_c12_setup_t* s) { return c12_info(s, 5); }
+int zk_c12_setup_gates(const zk_c12_setup_t* s, uint64_t* out) {
+    return guard([&] { ZK_REQUIRE(s && s->impl && out, "compressor12 setup: null argument"); c12_setup_gates(s->impl, (u64*)out); });
+}
+char* zk_c12_setup_pil(const zk_c12_setup_t* s) {
+    char* out = nullptr;
+    if (guard([&] { ZK_REQUIRE(s && s->impl, "compressor12 setup: null handle"); out = c12_dup(c12_setup_pil(s->impl)); }) != 0) return nullptr;
+    return out;
+}
+char* zk_c12_setup_exec(const zk_c12_setup_t* s) {
+    char* out = nullptr;
+    if (guard([&] { ZK_REQUIRE(s && s->impl, "compressor12 setup: null handle"); out = c12_dup(c12_setup_exec(s->impl)); }) != 0) return nullptr;
+    return out;
+}
+int zk_c12_setup_consts_dev(const zk_c12_setup_t* s, uint64_t* d_out, void* stream) {
+    return guard([&] { ZK_REQUIRE(s && s->impl, "compressor12 setup: null handle"); c12_setup_consts_dev(s->impl, (u64*)d_out, on_stream((hipStream_t)stream)); });
+}
+int zk_c12_setup_consts(const zk_c12_setup_t* s, uint64_t* out) {
+    return guard([&] {
+        ZK_REQUIRE(s && s->impl && out, "compressor12 setup: null argument");
+        uint64_t v[6]; c12_setup_info(s->impl, v);
+        const size_t bytes = ((size_t)1 << v[0]) * v[3] * 8;
+        DevBuf d; d.reserve(bytes);
+        c12_setup_consts_dev(s->impl, d.u(), cur_stream());
+        d2h_sync(out, d.p, bytes);
+    });
+}
+int zk_c12_setup_free(zk_c12_setup_t* s) {
+    return guard([&] { if (s) { c12_setup_free(s->impl); delete s; } });
+}
+int zk_c12_sigma_dev(const uint32_t* d_s_map, uint64_t n_used, uint32_t n_bits, uint32_t n_const, uint32_t col0, uint64_t* d_out, void* stream) {
+    return guard([&] { c12_sigma_dev((const u32*)d_s_map, n_used, n_bits, n_const, col0, (u64*)d_out, on_stream((hipStream_t)stream)); });
+}
+
 // ---- Groth16 (groth16.hip) ------------------------------------------------------------------------------------
 #define ZK_FR_NTT(NAME)                                                                                                  \
     int zk_fr_##NAME##_ntt_dev(uint64_t* d, uint32_t log_n, int inverse, int coset, void* stream) {                      \

@@ -253,6 +253,17 @@ C12Exec* c12_exec_new(const char* exec_json, size_t len, uint64_t n_witness);
 void c12_exec_free(C12Exec* e);
 uint64_t c12_exec_levels(const C12Exec* e);
 void c12_exec_dev(const C12Exec* e, const u64* d_witness, uint64_t n_witness, uint64_t n_rows, u64* d_cm, hipStream_t st);
+// ---- compressor12 setup (c12_setup.hip): a Goldilocks R1CS -> .pil / .exec text and the [N][nConst] constant matrix
+struct C12Setup;
+C12Setup* c12_setup_new(const void* r1cs, size_t len, uint32_t force_n_bits);
+void c12_setup_free(C12Setup* s);
+void c12_setup_info(const C12Setup* s, uint64_t out[6]);   // n_bits, n_publics, n_used, n_const, gates, additions
+void c12_setup_gates(const C12Setup* s, u64* out);         // gates x (sl, sr, so, qm, ql, qr, qo, qc)
+std::string c12_setup_pil(const C12Setup* s);
+std::string c12_setup_exec(const C12Setup* s);
+void c12_setup_consts_dev(const C12Setup* s, u64* d_out, hipStream_t st);
+// the 12 S columns of any [n_used][12] map (0 = no wire) into columns [col0, col0 + 12) of a [2^n_bits][n_const] matrix
+void c12_sigma_dev(const u32* d_s_map, uint64_t n_used, uint32_t n_bits, uint32_t n_const, uint32_t col0, u64* d_out, hipStream_t st);
 // ---- Groth16 around the multi-scalar sums (groth16.hip): scalar-field transforms, the quotient, the prover ----
 // bellman's EvaluationDomain::{fft, ifft, coset_fft, icoset_fft} on 2^logn Fr elements (4 x u64 Montgomery), in place
 void fr_bn254_ntt_dev(u64* d_data, int logn, bool inverse, bool coset, hipStream_t st);

@@ -516,6 +516,34 @@ int zk_c12_exec_dev(const zk_c12_exec_t* e, const uint64_t* d_witness, uint64_t 
 uint64_t zk_c12_exec_depth(const zk_c12_exec_t* e);   /* launches of the addition phase (longest chain of dependent sums) */
 int zk_c12_exec_free(zk_c12_exec_t* e);
 
+/* ---- compressor12 setup (`zkit compressor12_setup`, zkit/src/main.rs:140-151; recursion/src/compressor12/plonk_setup.rs) ----
+ * From the R1CS of a recursive circuit over Goldilocks (8-byte field; custom gates Poseidon12, CMulAdd, FFT4, EvPol4) to what
+ * zk_c12_exec_new and the following proof consume: the compressor's .pil text, its .exec text and its constant matrix.
+ * zk_c12_setup_new reads the file and does the host part (R1CS -> PLONK gates and additions in the reference's order, the
+ * packing of gates into rows); force_n_bits = 0 takes the smallest power of two that holds the rows.  NULL on error
+ * (zk_last_error), e.g. "Invalid magic number", "Different prime", "Invalid custom gate X", "wire id does not fit 32 bits".
+ * zk_c12_setup_consts_dev writes the [2^n_bits][n_const] row-major matrix into caller HBM: the S columns, their wiring and
+ * the fill are kernels (the layout of the .const file, polsarray.rs:184-); zk_c12_setup_consts the same to host memory.
+ * zk_c12_setup_gates: n_gates x (sl, sr, so, qm, ql, qr, qo, qc).  The two texts are malloc'ed: zk_string_free.
+ * zk_c12_sigma_dev is the wiring on its own: d_s_map is any [n_used][12] map of 32-bit wire ids (0 = no wire; row i,
+ * column c at 12 i + c, the .exec order) in HBM; it writes S[c][i] = w^i k^c with the copy constraints applied into columns
+ * [col0, col0 + 12) of the [2^n_bits][n_const] matrix d_out and touches no other column.                                      */
+typedef struct zk_c12_setup zk_c12_setup_t;
+zk_c12_setup_t* zk_c12_setup_new(const void* r1cs, size_t len, uint32_t force_n_bits);
+uint32_t zk_c12_setup_n_bits(const zk_c12_setup_t* s);
+uint64_t zk_c12_setup_n_publics(const zk_c12_setup_t* s);
+uint64_t zk_c12_setup_n_used(const zk_c12_setup_t* s);
+uint64_t zk_c12_setup_n_const(const zk_c12_setup_t* s);
+uint64_t zk_c12_setup_n_gates(const zk_c12_setup_t* s);
+uint64_t zk_c12_setup_n_adds(const zk_c12_setup_t* s);
+int zk_c12_setup_gates(const zk_c12_setup_t* s, uint64_t* out);
+char* zk_c12_setup_pil(const zk_c12_setup_t* s);
+char* zk_c12_setup_exec(const zk_c12_setup_t* s);
+int zk_c12_setup_consts_dev(const zk_c12_setup_t* s, uint64_t* d_out, void* stream);
+int zk_c12_setup_consts(const zk_c12_setup_t* s, uint64_t* out);
+int zk_c12_setup_free(zk_c12_setup_t* s);
+int zk_c12_sigma_dev(const uint32_t* d_s_map, uint64_t n_used, uint32_t n_bits, uint32_t n_const, uint32_t col0, uint64_t* d_out, void* stream);
+
 /* ---- constraint evaluation (starky/src/interpreter.rs:91-225, stark_gen.rs:752-963) ------------
  * A step's program is the reference's Segment.first (Vec<Section{op,dest,src}>,
  * starkinfo_codegen.rs:76-89) with every Node resolved to an address exactly as

@@ -8,6 +8,8 @@
   zkgpu_prove.py groth16_prove -c BN128 --r1cs circuit.r1cs -w witness.wtns -p g16.key --public-input public_input.json --proof proof.json [--verify verification_key.json]
   zkgpu_prove.py groth16_verify -c BN128 -v verification_key.json --public-input public_input.json --proof proof.json
   zkgpu_prove.py stark_verify -s starkStruct.json -p circuit.pil.json --o circuit.const --i zkin.json [--program FILE]
+  zkgpu_prove.py compressor12_setup --r circuit.r1cs --c c12.const --p c12.pil --e c12.exec [--force_n_bits K] [--pil-json c12.pil.json]
+  zkgpu_prove.py compressor12_exec --wtns witness.wtns --p c12.pil --e c12.exec --m c12.cm
   zkgpu_prove.py join_zkin --zkin1 a.zkin.json --zkin2 b.zkin.json --zkinout out.zkin.json
   zkgpu_prove.py stark_aggregate --gpus N --num_proof 8 --workspace DIR [--workers 4] [--keep_proofs]     (starts its own N ranks;
   [torchrun --nproc-per-node N] zkgpu_prove.py stark_aggregate ...                                         or runs under torchrun)
@@ -23,6 +25,10 @@ starky/src/prove.rs:30-160, groth16/src/api.rs:144-205).  What differs, and why:
     calculator in process, api.rs:150-160: WASM execution is out of scope); `-i` is accepted and ignored.
   * stark_prove verifies its own proof before it writes anything, as the reference does (prove.rs:124-132; `--no_verify` skips it).
   * stark_verify: the check alone, on a zkin file (the reference exposes it only inside stark_prove).
+  * compressor12_setup: `--pil-json OUT` also writes the compiled PIL (tools/pilc.py; the reference leaves that step to pilcom), so
+    that the next command can be stark_prove.  compressor12_exec: the witness comes as a `.wtns` with 8-byte field elements
+    (`--wtns`; zkit runs the circuit's .wasm on `--i`, and WASM execution is out of scope); the number of rows is read from the
+    `let N: int = 2**k` line of the .pil.
   * stark_aggregate: test/stark_aggregation.sh:70-73 + :83-156 through eigen-zkvm_amd/aggregation.py -- NUM_PROOF recursion tasks
     sharded over the ranks (one process per GPU), their recursive1 nodes (root1 + digest of the whole proof) all-gathered, joined as
     a tree; the circuits are the synthetic ones of tools/aggregation_workload.py (the real ones are circom-compiled verifiers), so
@@ -169,6 +175,56 @@ def stark_aggregate(a):
     ex.barrier()
 
 
+def compressor12_setup(a):
+    """recursion/src/compressor12/compressor12_setup.rs:18-48: .r1cs -> .pil, .const (row-major u64, polsarray.rs:184-), .exec"""
+    import importlib
+    _zk()
+    dev = importlib.import_module("eigen_zkvm_amd.compressor12")
+    S = dev.Compressor12Setup.from_r1cs(pathlib.Path(a.r1cs_file).read_bytes(), a.force_n_bits)
+    pil = S.pil
+    pathlib.Path(a.pil_file).write_text(pil)
+    S.consts_host().astype("<u8").tofile(a.const_file)
+    pathlib.Path(a.exec_file).write_text(S.exec_text)
+    if a.pil_json:
+        sys.path.insert(0, str(ROOT / "tools"))
+        import pilc
+        pathlib.Path(a.pil_json).write_text(pilc.dumps(pilc.compile_pil(a.pil_file, pil)))
+    print("zkgpu_prove: compressor of 2^%d rows (%d used), %d constant columns, %d gates, %d additions -> %s %s %s"
+          % (S.n_bits, S.n_used, S.n_const, S.n_gates, S.n_adds, a.pil_file, a.const_file, a.exec_file))
+    S.free()
+
+
+def compressor12_exec(a):
+    """recursion/src/compressor12/compressor12_exec.rs:17-103 after the witness calculator: .wtns + .exec -> .cm"""
+    import importlib
+    import re
+    import struct
+    import numpy as np
+    _zk()
+    dev = importlib.import_module("eigen_zkvm_amd.compressor12")
+    if not a.wtns:
+        raise SystemExit("zkgpu_prove: compressor12_exec needs --wtns FILE (running the .wasm on --i is out of scope)")
+    b = pathlib.Path(a.wtns).read_bytes()
+    if b[:4] != b"wtns" or len(b) < 12:
+        raise SystemExit("zkgpu_prove: %s is not a .wtns file" % a.wtns)
+    secs, o = {}, 12
+    for _ in range(struct.unpack_from("<I", b, 8)[0]):
+        t, sz = struct.unpack_from("<IQ", b, o); o += 12
+        secs[t] = b[o:o + sz]; o += sz
+    fs = struct.unpack_from("<I", secs[1])[0]
+    if fs != 8 or int.from_bytes(secs[1][4:12], "little") != 0xFFFFFFFF00000001:
+        raise SystemExit("zkgpu_prove: %s is not a witness over Goldilocks (8-byte field elements)" % a.wtns)
+    n = struct.unpack_from("<I", secs[1], 12)[0]
+    w = np.frombuffer(secs[2], dtype="<u8", count=n)
+    m = re.search(r"let\s+N\s*:\s*int\s*=\s*2\*\*(\d+)", pathlib.Path(a.pil_file).read_text())
+    if not m:
+        raise SystemExit("zkgpu_prove: no `let N: int = 2**k` in %s" % a.pil_file)
+    E = dev.Compressor12Exec(pathlib.Path(a.exec_file).read_text(), n)
+    E.run(w, 1 << int(m.group(1))).to_host().astype("<u8").tofile(a.commit_file)
+    E.free()
+    print("zkgpu_prove: %d wires -> 2^%s rows of 12 columns in %s" % (n, m.group(1), a.commit_file))
+
+
 def groth16_setup(a):
     """groth16/src/api.rs:42-66: circuit_specific_setup, then the key and verification_key.json written to their files"""
     import importlib
@@ -255,6 +311,22 @@ def main(argv=None):
     j = sub.add_parser("join_zkin", help="zkin_join.rs:9-57: the input of one recursive2 step from two proofs")
     j.add_argument("--zkin1", required=True); j.add_argument("--zkin2", required=True); j.add_argument("--zkinout", required=True)
     j.set_defaults(fn=join_zkin)
+    cs = sub.add_parser("compressor12_setup", help="Setup compressor12 for converting R1CS to PIL (zkit/src/main.rs:140-151)")
+    cs.add_argument("--r", dest="r1cs_file", default="mycircuit.verifier.r1cs")
+    cs.add_argument("--c", dest="const_file", default="mycircuit.c12.const")
+    cs.add_argument("--p", dest="pil_file", default="mycircuit.c12.pil")
+    cs.add_argument("--e", dest="exec_file", default="mycircuit.c12.exec")
+    cs.add_argument("--force_n_bits", type=int, default=0)
+    cs.add_argument("--pil-json", dest="pil_json", default=None, metavar="OUT", help="also write the compiled PIL (extension)")
+    cs.set_defaults(fn=compressor12_setup)
+    ce = sub.add_parser("compressor12_exec", help="Exec compressor12 (zkit/src/main.rs:155-168) from a .wtns")
+    ce.add_argument("--i", dest="input_file", default="mycircuit.proof.zkin.json", help="accepted for zkit compatibility, not read")
+    ce.add_argument("--w", dest="wasm_file", default="mycircuit.verifier.wasm", help="accepted for zkit compatibility, not run")
+    ce.add_argument("--wtns", default=None, help="the witness the calculator wrote, 8-byte field elements (extension)")
+    ce.add_argument("--p", dest="pil_file", default="mycircuit.c12.pil")
+    ce.add_argument("--e", dest="exec_file", default="mycircuit.c12.exec")
+    ce.add_argument("--m", dest="commit_file", default="mycircuit.c12.cm")
+    ce.set_defaults(fn=compressor12_exec)
     k = sub.add_parser("groth16_setup", help="Setup groth16 (zkit/src/main.rs:185-196)")
     k.add_argument("-c", dest="curve_type", default="BN128")
     k.add_argument("--r1cs", dest="circuit_file", required=True)
