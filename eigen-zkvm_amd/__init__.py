@@ -57,6 +57,7 @@ EXPORTS = [
     "zk_groth16_keygen_new", "zk_groth16_keygen_params_size", "zk_groth16_keygen_params", "zk_groth16_keygen_vk_json", "zk_groth16_keygen_timing", "zk_groth16_keygen_free",
     "zk_pairing_bn254", "zk_pairing_bn254_dev", "zk_pairing_bls12_381", "zk_pairing_bls12_381_dev", "zk_groth16_vk_new", "zk_groth16_vk_info", "zk_groth16_vk_free",
     "zk_groth16_verify_batch", "zk_groth16_verify_batch_dev", "zk_groth16_verify_json", "zk_groth16_verdict_name",
+    "zk_pil_check_new", "zk_pil_check_listing", "zk_pil_check_run", "zk_pil_check_run_dev", "zk_pil_check_free",
 ]
 
 # include/zkgpu.h enums
@@ -312,6 +313,11 @@ def _load():
         "zk_stark_set_pol_dev": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, vp, vp]),
         "zk_stark_calculate_h1h2_dev": (C.c_int, [vp, vp, C.c_uint64, vp, vp, vp]),
         "zk_stark_calculate_z_dev": (C.c_int, [vp, vp, C.c_uint64, vp, vp]),
+        "zk_pil_check_new": (vp, [C.c_char_p]),
+        "zk_pil_check_listing": (C.c_char_p, [vp]),
+        "zk_pil_check_run": (vp, [vp, vp, vp, C.c_uint64]),
+        "zk_pil_check_run_dev": (vp, [vp, vp, vp, C.c_uint64, vp]),
+        "zk_pil_check_free": (C.c_int, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -327,6 +333,14 @@ def lib():
     if _lib is None:
         _lib = _load()
     return _lib
+
+
+def __getattr__(name):
+    """`PilCheck` (stark.py) is part of the package's surface; stark.py imports from here, so it is fetched on first use"""
+    if name == "PilCheck":
+        import importlib
+        return importlib.import_module(__name__ + ".stark").PilCheck
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
 def _check(rc):

@@ -1,7 +1,9 @@
 // C ABI of libzkgpu (include/zkgpu.h): thin extern "C" wrappers, host<->device staging for the
 // host-pointer entry points, and the Merkle tree handle.  (Device memory, streams, error capture: devmem.hip.)
 #include "zk_internal.h"
+#include "pil_check.h"
 #include "../../include/zkgpu.h"
+#include <algorithm>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -1191,6 +1193,41 @@ const char* zk_groth16_verdict_name(int verdict) {
         case ZK_VERDICT_NOT_IN_SUBGROUP: return "a proof point is outside the subgroup of order r";
         default: return "error";
     }
+}
+
+// ---- pil_verify (pil_check.hip) ----------------------------------------------------------------------------------
+struct zk_pil_check { PilCheck* impl; };
+zk_pil_check_t* zk_pil_check_new(const char* pil_json) {
+    zk_pil_check_t* h = nullptr;
+    if (guard([&] { ZK_REQUIRE(pil_json, "zk_pil_check_new: null argument"); PilCheck* c = pil_check_new(pil_json); h = new zk_pil_check{c}; }) != 0) return nullptr;
+    return h;
+}
+const char* zk_pil_check_listing(const zk_pil_check_t* c) { return c && c->impl ? pil_check_listing(c->impl) : nullptr; }
+char* zk_pil_check_run_dev(zk_pil_check_t* c, const uint64_t* d_const_pols, const uint64_t* d_cm_pols, uint64_t n_rows, void* stream) {
+    char* out = nullptr;
+    if (guard([&] {
+            ZK_REQUIRE(c && c->impl, "pil_verify: null handle");
+            out = c12_dup(pil_check_run_dev(c->impl, (const u64*)d_const_pols, (const u64*)d_cm_pols, n_rows, on_stream((hipStream_t)stream)));
+        }) != 0) return nullptr;
+    return out;
+}
+char* zk_pil_check_run(zk_pil_check_t* c, const uint64_t* const_pols, const uint64_t* cm_pols, uint64_t n_rows) {
+    char* out = nullptr;
+    if (guard([&] {
+            ZK_REQUIRE(c && c->impl, "pil_verify: null handle");
+            ZK_REQUIRE(n_rows == pil_check_rows(c->impl), "pil_verify: the trace has " + std::to_string(n_rows) + " rows, the PIL's polDeg is " + std::to_string(pil_check_rows(c->impl)));
+            uint32_t n_const = 0, n_cm = 0;
+            pil_check_widths(c->impl, &n_const, &n_cm);
+            ZK_REQUIRE((const_pols || !n_const) && (cm_pols || !n_cm), "pil_verify: null trace");
+            DevBuf d_const, d_cm;
+            d_const.reserve(std::max<size_t>(8, (size_t)n_rows * n_const * 8)); d_cm.reserve(std::max<size_t>(8, (size_t)n_rows * n_cm * 8));
+            h2d_sync(d_const.p, const_pols, (size_t)n_rows * n_const * 8); h2d_sync(d_cm.p, cm_pols, (size_t)n_rows * n_cm * 8);
+            out = c12_dup(pil_check_run_dev(c->impl, d_const.u(), d_cm.u(), n_rows, cur_stream()));
+        }) != 0) return nullptr;
+    return out;
+}
+int zk_pil_check_free(zk_pil_check_t* c) {
+    return guard([&] { if (c) { pil_check_free(c->impl); delete c; } });
 }
 
 }  // extern "C"

@@ -26,11 +26,13 @@
 // at offset + ((i + next * prime) & (n - 1)) * stride.  The grid is capped (BC_MAX_WAVES) and a wave walks its 64-row chunks,
 // so the arena's size follows the grid, not the domain.
 #include "zk_internal.h"
+#include "pil_check.h"
 #include "../../include/zkgpu.h"
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <queue>
 #include <set>
 #include <sstream>
@@ -50,6 +52,8 @@ constexpr uint32_t BC_STRIDE_BITS = 27;        // a section cell's second word: 
 enum : uint32_t { K_NONE = 0, K_LDS = 1, K_ARENA = 2, K_UNI = 3, K_MEM = 4, K_X = 5, K_ZI = 6, K_XDIV = 7, K_XDIVW = 8 };
 // opcode = 4 * {add, sub, mul} + 2 * (first source is dim 3) + (second source is dim 3); then the two copies
 enum : uint32_t { BC_COPY1 = 12, BC_COPY3 = 13 };
+// the checker's instruction (pil_check.h): a live lane whose dim-1 source is not 0 counts in count[id] and lowers first[id] to its row
+enum : uint32_t { BC_CHECK1 = 14 };
 // the table a run reads its pointers and uniform values from, in words
 enum : uint32_t { T_BUFS = 0, T_X = 16, T_ZI = 17, T_ZI_MASK = 18, T_XDIV = 19, T_XDIVW = 20, T_UNI = 21 };
 
@@ -124,8 +128,15 @@ __device__ __forceinline__ void bc_store(const BcLane& L, uint32_t kind, uint32_
 
 // One lane, one row; the grid and the row0 / count contract of the compiled kernels (expr_jit.hip zk_eval_kernel), except that
 // a wave goes on to the chunk gridDim.x * 64 rows further until the range ends.
+//
+// CHK: the checker's build of the kernel, the only one that knows check1.  The results live in bufs[PC_BUF_RESULT] as [3][n_ids] words:
+// count, first, value.  A wave takes the ballot of its failing lanes and, only when there is one, issues one atomicAdd of the population
+// count and one atomicMin of its smallest failing row (a checker's range starts at row 0 and does not wrap, so that is the row of the
+// lowest failing lane): a satisfied trace issues no atomic.  With `at_first` the launch is the second, tiny one: block b evaluates the one
+// row first[b] ends with (lane 0 alone is live) and check1 of identity b leaves its value there; identities nothing failed are skipped.
+template <bool CHK>
 __global__ __launch_bounds__(64) void zk_bc_eval_kernel(const BcInstr* __restrict__ code, uint32_t n_instr, const u64* __restrict__ tab, u64* __restrict__ arena,
-                                                         u64 n, u64 next, u64 row0, u64 count) {
+                                                         u64 n, u64 next, u64 row0, u64 count, uint32_t at_first) {
     __shared__ u64 slots[BC_LDS_WORDS * 64];
     const unsigned lane = threadIdx.x;
     BcLane L;
@@ -133,7 +144,13 @@ __global__ __launch_bounds__(64) void zk_bc_eval_kernel(const BcInstr* __restric
     L.arena_stride = (u64)gridDim.x * 64;
     L.arena = arena + (u64)blockIdx.x * 64 + lane;
     L.tab = tab;
-    for (u64 k0 = (u64)blockIdx.x * 64; k0 < count; k0 += L.arena_stride) {
+    u64 k0 = (u64)blockIdx.x * 64;
+    if (CHK && at_first) {
+        const u64* res = (const u64*)tab[T_BUFS + PC_BUF_RESULT];
+        if (res[blockIdx.x] == 0) return;
+        row0 = res[gridDim.x + blockIdx.x]; k0 = 0; count = 1;
+    }
+    for (; k0 < count; k0 += L.arena_stride) {
         const unsigned i0 = (unsigned)(row0 + k0);                // first row of this chunk (the domain has at most 2^32 rows)
         const bool live = k0 + lane < count;
         L.i = (u64)((i0 + lane) & (unsigned)(n - 1));
@@ -143,6 +160,19 @@ __global__ __launch_bounds__(64) void zk_bc_eval_kernel(const BcInstr* __restric
             const uint32_t op = in.w[0] & 255u, ka = (in.w[0] >> 8) & 15u, kb = (in.w[0] >> 12) & 15u, kd = (in.w[0] >> 16) & 15u;
             f3 r;
             if (op >= BC_COPY1) {
+                if (CHK && op == BC_CHECK1) {
+                    r = bc_load<false>(L, ka, in.w[1], in.w[2]);
+                    u64* res = (u64*)tab[T_BUFS + PC_BUF_RESULT];
+                    const uint32_t id = in.w[5], n_ids = in.w[6];
+                    if (at_first) { if (lane == 0 && id == blockIdx.x) res[2 * n_ids + id] = r.v[0]; continue; }
+                    const bool bad = live && r.v[0] != 0;
+                    const unsigned long long m = __ballot(bad);
+                    if (m != 0 && lane == (unsigned)__ffsll(m) - 1) {
+                        atomicAdd((unsigned long long*)res + id, (unsigned long long)__popcll(m));
+                        atomicMin((unsigned long long*)res + n_ids + id, (unsigned long long)L.i);
+                    }
+                    continue;
+                }
                 if (op == BC_COPY1) { r = bc_load<false>(L, ka, in.w[1], in.w[2]); bc_store<false>(L, kd, in.w[5], in.w[6], r, live); }
                 else                { r = bc_load<true>(L, ka, in.w[1], in.w[2]);  bc_store<true>(L, kd, in.w[5], in.w[6], r, live); }
                 continue;
@@ -169,7 +199,7 @@ __global__ __launch_bounds__(64) void zk_bc_eval_kernel(const BcInstr* __restric
     }
 }
 
-const char* const OP_NAME[14] = {"add11", "add13", "add31", "add33", "sub11", "sub13", "sub31", "sub33", "mul11", "mul13", "mul31", "mul33", "copy1", "copy3"};
+const char* const OP_NAME[15] = {"add11", "add13", "add31", "add33", "sub11", "sub13", "sub31", "sub33", "mul11", "mul13", "mul31", "mul33", "copy1", "copy3", "check1"};
 
 struct Ref { uint32_t kind = K_NONE, a0 = 0, a1 = 0, dim = 0; int value = -1; };   // value: the temporary it names, until slots are given out
 struct Value { uint32_t dim, def, last; uint32_t kind = K_NONE, slot = 0; };
@@ -185,6 +215,7 @@ struct Bytecode {
     std::string listing;
     DevBuf d_code, d_uni, d_tab, d_arena;      // on the device from the first run on
     bool uploaded = false;
+    bool checker = false;                      // assembled for pil_check.hip: runs the kernel that knows check1
 };
 
 namespace {
@@ -263,9 +294,15 @@ struct Assembler {
         for (uint32_t j = 0; j < dim; ++j) own_words.insert(std::make_tuple((uint32_t)d.buf, d.id + j, d.prime != 0));
         return cell(d, dim);
     }
+    bool checker = false;                                         // bytecode_assemble for pil_check.hip: check1 is an instruction
     void instr(const zk_instr& in, uint32_t at) {
         Enc e;
-        if (in.op == ZK_OP_COPY) {
+        if (checker && in.op == ZK_OP_CHECK1) {
+            e.a = load(in.src[0], at);
+            ZK_REQUIRE(e.a.dim == 1, "check program: check1 takes a dim-1 value");
+            ZK_REQUIRE(in.dest.id < in.dest.stride, "check program: identity index out of range");
+            e.op = BC_CHECK1; e.d.a0 = in.dest.id; e.d.a1 = in.dest.stride;
+        } else if (in.op == ZK_OP_COPY) {
             e.a = load(in.src[0], at);
             e.op = e.a.dim == 3 ? BC_COPY3 : BC_COPY1;
             e.d = store(in.dest, e.a.dim, at);
@@ -381,9 +418,57 @@ void bytecode_run(Bytecode* b, const void* ctx, uint32_t nbits_domain, uint64_t 
     const uint32_t n_uni = (uint32_t)b->uni.size();
     zk_bc_refresh_kernel<<<1 + (n_uni + 63) / 64, 64, 0, st>>>(*(const zk_eval_ctx*)ctx, (const BcUni*)b->d_uni.p, n_uni, b->d_tab.u());
     ZK_HIP(hipGetLastError());
-    zk_bc_eval_kernel<<<(unsigned)waves, 64, 0, st>>>((const BcInstr*)b->d_code.p, (uint32_t)b->code.size(), b->d_tab.u(), b->d_arena.u(),
-                                                    1ull << nbits_domain, next, row0, count);
+    if (b->checker)
+        zk_bc_eval_kernel<true><<<(unsigned)waves, 64, 0, st>>>((const BcInstr*)b->d_code.p, (uint32_t)b->code.size(), b->d_tab.u(), b->d_arena.u(),
+                                                              1ull << nbits_domain, next, row0, count, 0u);
+    else
+        zk_bc_eval_kernel<false><<<(unsigned)waves, 64, 0, st>>>((const BcInstr*)b->d_code.p, (uint32_t)b->code.size(), b->d_tab.u(), b->d_arena.u(),
+                                                               1ull << nbits_domain, next, row0, count, 0u);
     ZK_HIP(hipGetLastError());
+}
+
+void bytecode_run_first(Bytecode* b, const void* ctx, uint32_t nbits_domain, uint64_t next, uint32_t n_ids, hipStream_t st) {
+    ZK_REQUIRE(b->checker && b->uploaded, "bytecode_run_first: a check program that has run");
+    if (b->code.empty() || n_ids == 0) return;
+    b->d_arena.reserve(std::max<size_t>(8, (size_t)b->arena_words * n_ids * 64 * 8));
+    const uint32_t n_uni = (uint32_t)b->uni.size();
+    zk_bc_refresh_kernel<<<1 + (n_uni + 63) / 64, 64, 0, st>>>(*(const zk_eval_ctx*)ctx, (const BcUni*)b->d_uni.p, n_uni, b->d_tab.u());
+    ZK_HIP(hipGetLastError());
+    zk_bc_eval_kernel<true><<<n_ids, 64, 0, st>>>((const BcInstr*)b->d_code.p, (uint32_t)b->code.size(), b->d_tab.u(), b->d_arena.u(),
+                                                  1ull << nbits_domain, next, 0, 1, 1u);
+    ZK_HIP(hipGetLastError());
+}
+
+// the assembler behind zk_program_assemble; `checker`: a program of pil_check.hip, which may hold check1
+Bytecode* bytecode_assemble(const zk_instr* code, uint32_t n_instr, bool checker) {
+    Assembler as;
+    as.checker = checker;
+    for (uint32_t k = 0; k < n_instr; ++k) as.instr(code[k], k);
+    check_row_hazards(as.mem_writes, as.mem_reads);
+    as.allocate();
+    std::unique_ptr<Bytecode> b(new Bytecode());
+    Bytecode* B = b.get();
+    B->checker = checker;
+    std::ostringstream o;
+    for (uint32_t k = 0; k < n_instr; ++k) {
+        Assembler::Enc& e = as.enc[k];
+        as.place(e.a); as.place(e.b); as.place(e.d);
+        BcInstr in; memset(&in, 0, sizeof in);
+        in.w[0] = e.op | e.a.kind << 8 | e.b.kind << 12 | e.d.kind << 16;
+        in.w[1] = e.a.a0; in.w[2] = e.a.a1; in.w[3] = e.b.a0; in.w[4] = e.b.a1; in.w[5] = e.d.a0; in.w[6] = e.d.a1;
+        B->code.push_back(in);
+        o << k << "  " << OP_NAME[e.op] << "  ";
+        if (e.op == BC_CHECK1) o << "id" << e.d.a0; else Assembler::print(o, e.d);
+        o << " <- "; Assembler::print(o, e.a);
+        if (e.b.kind != K_NONE) { o << ", "; Assembler::print(o, e.b); }
+        o << "\n";
+    }
+    B->uni = std::move(as.uni);
+    B->tab_words = as.tab_words; B->lds_words = as.lds_used; B->arena_words = as.arena_used;
+    o << "; slots: " << as.lds_used + as.arena_used << " words (lds " << as.lds_used << ", arena " << as.arena_used << "), values " << as.values.size()
+      << ", uniforms " << as.tab_words - T_UNI << " words, instructions " << n_instr << "\n";
+    B->listing = o.str();
+    return b.release();
 }
 
 }  // namespace zk
@@ -393,36 +478,11 @@ using namespace zk;
 extern "C" {
 
 zk_program_t* zk_program_assemble(const zk_instr* code, uint32_t n_instr) {
-    Bytecode* b = nullptr;
     try {
         ZK_REQUIRE(code || n_instr == 0, "zk_program_assemble: null code");
-        Assembler as;
-        for (uint32_t k = 0; k < n_instr; ++k) as.instr(code[k], k);
-        check_row_hazards(as.mem_writes, as.mem_reads);
-        as.allocate();
-        b = new Bytecode();
-        std::ostringstream o;
-        for (uint32_t k = 0; k < n_instr; ++k) {
-            Assembler::Enc& e = as.enc[k];
-            as.place(e.a); as.place(e.b); as.place(e.d);
-            BcInstr in; memset(&in, 0, sizeof in);
-            in.w[0] = e.op | e.a.kind << 8 | e.b.kind << 12 | e.d.kind << 16;
-            in.w[1] = e.a.a0; in.w[2] = e.a.a1; in.w[3] = e.b.a0; in.w[4] = e.b.a1; in.w[5] = e.d.a0; in.w[6] = e.d.a1;
-            b->code.push_back(in);
-            o << k << "  " << OP_NAME[e.op] << "  "; Assembler::print(o, e.d); o << " <- "; Assembler::print(o, e.a);
-            if (e.b.kind != K_NONE) { o << ", "; Assembler::print(o, e.b); }
-            o << "\n";
-        }
-        b->uni = std::move(as.uni);
-        b->tab_words = as.tab_words; b->lds_words = as.lds_used; b->arena_words = as.arena_used;
-        o << "; slots: " << as.lds_used + as.arena_used << " words (lds " << as.lds_used << ", arena " << as.arena_used << "), values " << as.values.size()
-          << ", uniforms " << as.tab_words - T_UNI << " words, instructions " << n_instr << "\n";
-        b->listing = o.str();
-        Bytecode* done = b; b = nullptr;
-        return program_of_bytecode(done);
-    } catch (const std::exception& e) { set_error(e.what()); delete b; return nullptr; }
+        return program_of_bytecode(bytecode_assemble(code, n_instr, false));
+    } catch (const std::exception& e) { set_error(e.what()); return nullptr; }
 }
-
 int zk_eval_set_mode(int mode) {
     const int prev = eval_mode();
     if (mode != ZK_EVAL_JIT && mode != ZK_EVAL_BYTECODE) { set_error("zk_eval_set_mode: mode must be ZK_EVAL_JIT or ZK_EVAL_BYTECODE"); return -1; }

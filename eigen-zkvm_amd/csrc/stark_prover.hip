@@ -8,7 +8,7 @@
 // keeps the sections resident in HBM and formats the proof.  Inputs are the reference's own
 // serialised StarkInfo + Program (serde field names, starkinfo.rs:27-95) and StarkStruct
 // (types.rs): the reference's PIL front end and code generator stay in charge of them.
-// One host step remains, as in the reference: calculate_H1H2 (stark_gen.rs:624-651).
+// calculate_H1H2 (stark_gen.rs:624-651), a host step in the reference, runs on the device as well (calculate_h1h2_dev, stark.hip).
 #include "zk_internal.h"
 #include "../../include/zkgpu.h"
 #include "json_min.h"

@@ -19,6 +19,7 @@
 // transcript order and in the circom verifier (SURVEY hard part 3).  tests/test_starkinfo_native.py compares the output
 // with the test suite's independent restatement on every fixture.
 #include "zk_internal.h"
+#include "pil_check.h"
 #include "json_min.h"
 #include "../../include/zkgpu.h"
 #include <algorithm>
@@ -328,7 +329,7 @@ struct Gen {
     }
     i64 push_identity(Expr e) { e.deg = 2; const i64 i = push_expr(e); pil.pol_identities.push_back(i); return i; }
 
-    void load(const JVal& P, const JVal& S) {
+    void load_pil(const JVal& P) {                                           // the PIL as written: all pil_verify reads (check_program below)
         pil.nCommitments = P.at("nCommitments").i64(); pil.nQ = P.at("nQ").i64(); pil.nConstants = P.at("nConstants").i64();
         for (auto& p : P.at("publics").arr) {
             Public q; q.polType = p.at("polType").str(); q.polId = p.at("polId").i64(); q.idx = p.at("idx").i64(); q.id = p.at("id").i64();
@@ -354,6 +355,9 @@ struct Gen {
         idents("plookupIdentities", pil.plookups); idents("permutationIdentities", pil.permutations);
         if (const JVal* L = P.find("connectionIdentities")) if (!L->is_null())
             for (auto& d : L->arr) pil.connections.push_back({ids(d.at("pols")), ids(d.at("connections"))});
+    }
+    void load(const JVal& P, const JVal& S) {
+        load_pil(P);
         nbits = S.at("nBits").i64(); nbits_ext = S.at("nBitsExt").i64();
         ZK_REQUIRE(!pil.references.empty(), "pil: no references");
         if (((i64)1 << nbits) != pil.first_pol_deg) throw Error("stark_deg != pil_deg");
@@ -787,7 +791,189 @@ struct Gen {
     }
 };
 
+// ---- pil_verify: the PIL's own constraints as check programs (pil_check.h) --------------------------------------------------------
+// What pilcom's verifyPil evaluates (the reference's pil_verifier.js:46), before any of the prover's rewriting: the PIL stays as
+// load_pil read it, none of generate_step2 / step3 / constraint_polynomial runs.  Code comes from pil_code_gen / build_code on domain n
+// (Segment.first: the whole code, in order), `exp` results become temporaries as in the public calculators above; a `next` reads
+// row (i + 1) mod N through the primed cells.  calculate_deps generates a shared sub-expression once per program.
+struct CheckGen {
+    Pil& pil;
+    std::map<std::pair<int, i64>, i64> exp_tmp;
+    i64 tmp_used = 0;
+
+    static zk_operand zero() { zk_operand o; memset(&o, 0, sizeof o); o.dim = 1; return o; }
+    static u64 number(const std::string& s) {                                // types.rs:221-233: decimal or 0x hex, possibly negative, mod p
+        const bool neg = !s.empty() && s[0] == '-';
+        size_t i = neg ? 1 : 0;
+        const bool hex = s.size() > i + 1 && s[i] == '0' && (s[i + 1] == 'x' || s[i + 1] == 'X');
+        if (hex) i += 2;
+        ZK_REQUIRE(i < s.size(), "bad PIL number " + s);
+        unsigned __int128 v = 0;
+        for (; i < s.size(); ++i) {
+            const char c = s[i];
+            const int d = c >= '0' && c <= '9' ? c - '0' : hex && c >= 'a' && c <= 'f' ? c - 'a' + 10 : hex && c >= 'A' && c <= 'F' ? c - 'A' + 10 : -1;
+            ZK_REQUIRE(d >= 0, "bad PIL number " + s);
+            v = (v * (hex ? 16 : 10) + d) % GL_P;
+        }
+        const u64 r = (u64)v;
+        return neg && r ? GL_P - r : r;
+    }
+    zk_operand exp_operand(i64 id, bool prime) {
+        auto k = std::make_pair(prime ? 1 : 0, id);
+        if (!exp_tmp.count(k)) exp_tmp[k] = tmp_used++;
+        zk_operand o = zero(); o.kind = ZK_OPND_TMP; o.id = (uint32_t)exp_tmp[k];
+        return o;
+    }
+    zk_operand resolve(const Node& r) {
+        zk_operand o = zero();
+        const std::string& t = r.type_;
+        if (t == "tmp") { o.kind = ZK_OPND_TMP; o.id = (uint32_t)r.id; }
+        else if (t == "exp") return exp_operand(r.id, r.prime);
+        else if (t == "cm") {
+            ZK_REQUIRE(r.id >= 0 && r.id < pil.nCommitments, "cm id out of range");
+            o.kind = ZK_OPND_MEM; o.buf = PC_BUF_CM; o.id = (uint32_t)r.id; o.stride = (uint32_t)pil.nCommitments; o.prime = r.prime;
+        } else if (t == "const") {
+            ZK_REQUIRE(r.id >= 0 && r.id < pil.nConstants, "const id out of range");
+            o.kind = ZK_OPND_MEM; o.buf = PC_BUF_CONST; o.id = (uint32_t)r.id; o.stride = (uint32_t)pil.nConstants; o.prime = r.prime;
+        } else if (t == "number") { o.kind = ZK_OPND_NUMBER; o.value = number(r.value); }
+        else if (t == "public") {
+            ZK_REQUIRE(r.id >= 0 && (size_t)r.id < pil.publics.size(), "public id out of range");
+            o.kind = ZK_OPND_PUBLIC; o.id = (uint32_t)r.id;
+        } else throw Error("pil_verify: a PIL expression cannot hold '" + t + "'");
+        return o;
+    }
+    // Segment.first -> zk_instr; marks[k] = the number of sections in front of which `extra[k]` goes (ascending)
+    std::vector<zk_instr> translate(const Segment& seg, const std::vector<size_t>& marks, const std::vector<zk_instr>& extra) {
+        std::vector<zk_instr> out;
+        size_t m = 0;
+        for (size_t k = 0; k <= seg.first.size(); ++k) {
+            for (; m < marks.size() && marks[m] == k; ++m) out.push_back(extra[m]);
+            if (k == seg.first.size()) break;
+            const Section& c = seg.first[k];
+            zk_instr in; memset(&in, 0, sizeof in);
+            if (c.op == "add") in.op = ZK_OP_ADD; else if (c.op == "sub") in.op = ZK_OP_SUB;
+            else if (c.op == "mul") in.op = ZK_OP_MUL; else if (c.op == "copy") in.op = ZK_OP_COPY;
+            else throw Error("Invalid op " + c.op);
+            ZK_REQUIRE(c.src.size() >= 1 && c.src.size() <= 2, "instruction needs 1 or 2 sources");
+            in.src[0] = resolve(c.src[0]);
+            if (c.src.size() > 1) in.src[1] = resolve(c.src[1]);
+            in.dest = resolve(c.dest);
+            out.push_back(in);
+        }
+        return out;
+    }
+    // one program: the expressions `ids` in order; after the code of ids[k] comes extra(k, operand holding its value)
+    template <class F>
+    std::vector<zk_instr> program(const std::vector<i64>& ids, F&& extra_of) {
+        Ctx ctx;
+        std::vector<size_t> marks;
+        for (i64 id : ids) {
+            pil_code_gen(ctx, pil, id, false, "", 0, false);
+            size_t n = 0;
+            for (auto& c : ctx.code) n += c.code.size();
+            marks.push_back(n);
+        }
+        Segment seg = build_code(ctx, pil);
+        exp_tmp.clear(); tmp_used = seg.tmp_used;
+        std::vector<zk_instr> extra;
+        for (size_t k = 0; k < ids.size(); ++k) extra.push_back(extra_of(k, exp_operand(ids[k], false)));
+        return translate(seg, marks, extra);
+    }
+};
+
+static PilCheckSrc check_src(const JVal& d) {
+    PilCheckSrc s;
+    if (const JVal* v = d.find("fileName")) if (!v->is_null()) s.file = v->str();
+    if (const JVal* v = d.find("line")) if (!v->is_null()) s.line = v->i64();
+    return s;
+}
+
+static PilCheckProgram check_program(const JVal& P) {
+    Gen g;
+    g.load_pil(P);
+    Pil& pil = g.pil;
+    ZK_REQUIRE(!pil.references.empty(), "pil: no references");
+    PilCheckProgram out;
+    const i64 deg = pil.first_pol_deg;
+    for (auto& kv : pil.references) ZK_REQUIRE(kv.second.second == deg, "pil_verify: the references of the PIL differ in polDeg");
+    ZK_REQUIRE(deg >= 1 && (deg & (deg - 1)) == 0 && deg <= ((i64)1 << 30), "pil_verify: polDeg " + std::to_string(deg) + " is not a power of two (up to 2^30)");
+    out.n = (uint64_t)deg;
+    while (((uint64_t)1 << out.nbits) < out.n) ++out.nbits;
+    ZK_REQUIRE(pil.nCommitments >= 0 && pil.nConstants >= 0 && pil.nCommitments < (1 << 27) && pil.nConstants < (1 << 27), "pil_verify: too many columns");
+    out.n_cm = (uint32_t)pil.nCommitments; out.n_const = (uint32_t)pil.nConstants;
+    CheckGen cg{pil};
+    auto copy_to = [](uint32_t buf, uint32_t col, uint32_t stride, const zk_operand& v) {
+        zk_instr in; memset(&in, 0, sizeof in);
+        in.op = ZK_OP_COPY; in.src[0] = v;
+        in.dest = CheckGen::zero(); in.dest.kind = ZK_OPND_MEM; in.dest.buf = (uint8_t)buf; in.dest.id = col; in.dest.stride = stride;
+        return in;
+    };
+    auto one = [] { zk_operand o = CheckGen::zero(); o.kind = ZK_OPND_NUMBER; o.value = 1; return o; };
+
+    for (size_t k = 0; k < pil.publics.size(); ++k) {                      // stark_gen.rs:256-277
+        const Public& p = pil.publics[k];
+        PilCheckPublic q;
+        ZK_REQUIRE(p.idx >= 0 && p.idx < deg, "pil_verify: a public's row is outside the trace");
+        q.idx = (uint64_t)p.idx; q.pol_id = (uint32_t)p.polId;
+        if (p.polType == "imP") {
+            q.im = true;                                                     // the publics section has one row: stride 0
+            q.code = cg.program({p.polId}, [&](size_t, const zk_operand& v) { return copy_to(PC_BUF_PUBLICS, (uint32_t)k, 0, v); });
+        } else {
+            ZK_REQUIRE(p.polType == "cmP", "pil_verify: public of type " + p.polType);
+            ZK_REQUIRE(p.polId >= 0 && p.polId < pil.nCommitments, "cm id out of range");
+        }
+        out.publics.push_back(q);
+    }
+
+    const uint32_t n_ids = (uint32_t)pil.pol_identities.size();
+    out.identities = cg.program(pil.pol_identities, [&](size_t k, const zk_operand& v) {
+        zk_instr in; memset(&in, 0, sizeof in);
+        in.op = ZK_OP_CHECK1; in.src[0] = v; in.dest = CheckGen::zero(); in.dest.id = (uint32_t)k; in.dest.stride = n_ids;
+        return in;
+    });
+    for (auto& d : P.at("polIdentities").arr) out.identity_src.push_back(check_src(d));
+
+    auto sets = [&](const char* key, const std::vector<Identity>& list, int kind) {
+        for (size_t i = 0; i < list.size(); ++i) {
+            const Identity& x = list[i];
+            ZK_REQUIRE(x.f.size() == x.t.size(), std::string("pil_verify: ") + key + "[" + std::to_string(i) + "]: f and t differ in length");
+            ZK_REQUIRE(!x.f.empty() && x.f.size() < 1024, std::string("pil_verify: ") + key + "[" + std::to_string(i) + "]: between 1 and 1023 columns a side");
+            PilCheckSet s; s.kind = kind; s.index = (uint32_t)i; s.k = (uint32_t)x.f.size(); s.width = 2 * s.k + 2;
+            s.has_self = x.has_self; s.has_selt = x.has_selt; s.src = check_src(P.at(key).at(i));
+            std::vector<i64> ids; std::vector<uint32_t> cols;
+            for (uint32_t c = 0; c < s.k; ++c) { ids.push_back(x.f[c]); cols.push_back(c); }
+            if (x.has_self) { ids.push_back(x.self_); cols.push_back(s.k); }
+            for (uint32_t c = 0; c < s.k; ++c) { ids.push_back(x.t[c]); cols.push_back(s.k + 1 + c); }
+            if (x.has_selt) { ids.push_back(x.selt); cols.push_back(2 * s.k + 1); }
+            s.code = cg.program(ids, [&](size_t k, const zk_operand& v) { return copy_to(PC_BUF_SCRATCH, cols[k], s.width, v); });
+            if (!x.has_self) s.code.push_back(copy_to(PC_BUF_SCRATCH, s.k, s.width, one()));
+            if (!x.has_selt) s.code.push_back(copy_to(PC_BUF_SCRATCH, 2 * s.k + 1, s.width, one()));
+            out.sets.push_back(std::move(s));
+        }
+    };
+    sets("plookupIdentities", pil.plookups, PC_PLOOKUP);
+    sets("permutationIdentities", pil.permutations, PC_PERMUTATION);
+    for (size_t i = 0; i < pil.connections.size(); ++i) {
+        const Connection& x = pil.connections[i];
+        const std::string name = "pil_verify: connectionIdentities[" + std::to_string(i) + "]";
+        ZK_REQUIRE(x.pols.size() == x.connections.size(), name + ": pols and connections differ in length");
+        ZK_REQUIRE(!x.pols.empty() && x.pols.size() < 1024 && x.pols.size() * out.n < 0xFFFFFFFFull, name + ": too many cells");
+        PilCheckSet s; s.kind = PC_CONNECTION; s.index = (uint32_t)i; s.k = (uint32_t)x.pols.size(); s.width = 2 * s.k;
+        s.src = check_src(P.at("connectionIdentities").at(i));
+        std::vector<i64> ids = x.pols;
+        ids.insert(ids.end(), x.connections.begin(), x.connections.end());
+        s.code = cg.program(ids, [&](size_t k, const zk_operand& v) { return copy_to(PC_BUF_SCRATCH, (uint32_t)k, s.width, v); });
+        out.sets.push_back(std::move(s));
+    }
+    return out;
+}
+
 }  // namespace sgen
+
+PilCheckProgram pil_check_generate(const std::string& pil_json) {
+    const JVal P = JParser::parse(pil_json.c_str());
+    return sgen::check_program(P);
+}
 
 std::string starkinfo_generate(const std::string& pil_json, const std::string& stark_struct_json) {
     const JVal P = JParser::parse(pil_json.c_str()), S = JParser::parse(stark_struct_json.c_str());

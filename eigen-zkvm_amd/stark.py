@@ -355,6 +355,57 @@ def generate_program(pil_json, stark_struct_json):
         lib().zk_string_free(p)
 
 
+class PilCheck:
+    """pil_verify: a trace against its PIL on the device, row by row (csrc/pil_check.hip behind zk_pil_check_*) -- the check the
+    reference runs between building a trace and proving it (starkjs/src/pil_verifier.js:46).  `pil_json`: the compiled PIL, text or
+    dict.  Constructing needs no GPU; `run` does.  The report's shape is documented in include/zkgpu.h."""
+
+    def __init__(self, pil_json):
+        text = pil_json if isinstance(pil_json, (str, bytes)) else json.dumps(pil_json)
+        pil = pil_json if isinstance(pil_json, dict) else json.loads(text)
+        refs = pil.get("references") or {}
+        self.n_const, self.n_cm = pil.get("nConstants", 0), pil.get("nCommitments", 0)
+        self.n = next(iter(refs.values()))["polDeg"] if refs else 0          # N: the common polDeg (the library checks that it is common)
+        self._h = lib().zk_pil_check_new(text if isinstance(text, bytes) else text.encode())
+        if not self._h:
+            raise ZkError(lib().zk_last_error().decode())
+
+    def listing(self):
+        """the assembled check programs, one line per instruction"""
+        return lib().zk_pil_check_listing(self._h).decode()
+
+    def run(self, const_n, cm_n, n_rows=None, stream=None):
+        """-> the report (dict).  const_n / cm_n: host arrays, or DevArrays (both; borrowed, `n_rows` defaults to the PIL's polDeg)"""
+        import ctypes
+        if n_rows is None:
+            n_rows = self.n
+        if isinstance(const_n, DevArray) or isinstance(cm_n, DevArray):
+            if not (isinstance(const_n, DevArray) and isinstance(cm_n, DevArray)):
+                raise ZkError("PilCheck.run: the constants and the trace are either both on the host or both on the device")
+            p = lib().zk_pil_check_run_dev(self._h, const_n.ptr, cm_n.ptr, n_rows, stream)
+        else:
+            c, m = _np(const_n), _np(cm_n)
+            if c.size != n_rows * self.n_const or m.size != n_rows * self.n_cm:
+                raise ZkError("PilCheck.run: the arrays do not hold %d rows of %d / %d columns" % (n_rows, self.n_const, self.n_cm))
+            p = lib().zk_pil_check_run(self._h, _ptr(c), _ptr(m), n_rows)
+        if not p:
+            raise ZkError(lib().zk_last_error().decode())
+        try:
+            return json.loads(ctypes.string_at(p).decode())
+        finally:
+            lib().zk_string_free(p)
+
+    def free(self):
+        if self._h:
+            lib().zk_pil_check_free(self._h); self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class NativeStarkSetup:
     """The C++ driver inside libzkgpu (csrc/stark_prover.hip): StarkSetup::new + stark_gen + FRI::prove
     behind zk_stark_setup_new / zk_stark_gen.  `program_json` = '{"starkinfo": ..., "program": ...}' text."""

@@ -610,6 +610,40 @@ int zk_program_run_rows_dev(zk_program_t* p, const zk_eval_ctx* ctx, uint32_t nb
                             void* stream);
 int zk_program_free(zk_program_t* p);
 
+/* ---- pil_verify: a trace against its PIL, row by row (csrc/pil_check.hip) ------------------------------------------
+ * The check the reference runs between building a trace and proving it (starkjs/src/pil_verifier.js:46, pilcom's
+ * verifyPil): the PIL's own constraints -- expressions, polIdentities, plookupIdentities, permutationIdentities,
+ * connectionIdentities, publics -- on domain n, before any of the prover's rewriting; no starkStruct, no setup, no
+ * challenges.  N is the common polDeg of the PIL's references, `next` reads row (i + 1) mod N.
+ * zk_pil_check_new parses the compiled PIL (.pil.json text), generates the check programs and assembles them for the
+ * bytecode interpreter (always: $ZK_EVAL does not matter, nothing is compiled at run time); it needs no GPU.
+ * zk_pil_check_listing: the assembled programs, one line per instruction ("check1 idK <- value" closes polynomial
+ * identity K), owned by the handle.
+ * zk_pil_check_run / _run_dev: the report, JSON text (malloc'ed: zk_string_free):
+ *   {"n": N, "publics": ["..."], "checked": {"polIdentities": a, "plookupIdentities": b, "permutationIdentities": c,
+ *    "connectionIdentities": d}, "findings": [...]}
+ * Rows, counts and field words are decimal strings.  Every finding has "kind", "index" (of the identity in its list),
+ * "fileName" and "line"; polynomial identities come first, then plookups, permutations, connections, each in PIL order:
+ *   identity          n_rows, first_row, value            rows where the expression is not 0, the smallest, the value there
+ *   selector          identity ("plookup" | "permutation"), side ("f" | "t"), n_rows, first_row, value: a selector outside
+ *                     {0, 1}; listed in front of its identity's own finding (for the set checks a row is selected when the
+ *                     selector is not 0)
+ *   plookup           n_rows, first_row, values           selected f rows whose tuple no selected t row holds
+ *   permutation       n_f_unmatched, n_t_unmatched, first_f_row, first_t_row, f_values, t_values (null on a side nothing
+ *                     is unmatched on): with c = #t rows - #f rows per distinct tuple, the sum of |c| over c < 0 and of c
+ *                     over c > 0, the smallest selected row of each side whose tuple has such a c
+ *   connection_value  n_cells, col, row, value            S words that name no cell k_j w^i; first by col * N + row
+ *   connection        n_cells, col, row, partner_col, partner_row, value, partner_value: wired cells that differ
+ * The run borrows device-resident inputs ([N][nConstants] and [N][nCommitments], row-major).  NULL + zk_last_error on
+ * error: n_rows != polDeg, an expression id out of range, a set identity whose sides differ in length, a polDeg that
+ * is not a power of two. */
+typedef struct zk_pil_check zk_pil_check_t;
+zk_pil_check_t* zk_pil_check_new(const char* pil_json);                      /* needs no GPU */
+const char* zk_pil_check_listing(const zk_pil_check_t* c);
+char* zk_pil_check_run(zk_pil_check_t* c, const uint64_t* const_pols, const uint64_t* cm_pols, uint64_t n_rows);
+char* zk_pil_check_run_dev(zk_pil_check_t* c, const uint64_t* d_const_pols, const uint64_t* d_cm_pols, uint64_t n_rows, void* stream);
+int zk_pil_check_free(zk_pil_check_t* c);
+
 #ifdef __cplusplus
 }
 #endif

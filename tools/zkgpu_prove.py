@@ -7,6 +7,7 @@
   zkgpu_prove.py groth16_setup -c BN128 --r1cs circuit.r1cs -p g16.key -v verification_key.json [-t]
   zkgpu_prove.py groth16_prove -c BN128 --r1cs circuit.r1cs -w witness.wtns -p g16.key --public-input public_input.json --proof proof.json [--verify verification_key.json]
   zkgpu_prove.py groth16_verify -c BN128 -v verification_key.json --public-input public_input.json --proof proof.json
+  zkgpu_prove.py pil_verify -p circuit.pil.json --o circuit.const --m circuit.cm [--report out.json]
   zkgpu_prove.py stark_verify -s starkStruct.json -p circuit.pil.json --o circuit.const --i zkin.json [--program FILE]
   zkgpu_prove.py compressor12_setup --r circuit.r1cs --c c12.const --p c12.pil --e c12.exec [--force_n_bits K] [--pil-json c12.pil.json]
   zkgpu_prove.py compressor12_exec --wtns witness.wtns --p c12.pil --e c12.exec --m c12.cm
@@ -24,6 +25,10 @@ starky/src/prove.rs:30-160, groth16/src/api.rs:144-205).  What differs, and why:
   * groth16_prove: `-w` takes the `.wtns` the witness calculator wrote (zkit passes the .wasm and an input.json and runs the
     calculator in process, api.rs:150-160: WASM execution is out of scope); `-i` is accepted and ignored.
   * stark_prove verifies its own proof before it writes anything, as the reference does (prove.rs:124-132; `--no_verify` skips it).
+  * pil_verify: the trace check the reference runs between building a trace and proving it (starkjs/src/pil_verifier.js:46, pilcom's
+    verifyPil), on the device: one line `fileName:line: <kind> ...` per violated constraint, exit 0 when there is none and 1 otherwise;
+    `--report` also writes the whole report as JSON.  `stark_prove --check-trace` runs it first and stops with the findings (exit 1)
+    before any setup.
   * stark_verify: the check alone, on a zkin file (the reference exposes it only inside stark_prove).
   * compressor12_setup: `--pil-json OUT` also writes the compiled PIL (tools/pilc.py; the reference leaves that step to pilcom), so
     that the next command can be stark_prove.  compressor12_exec: the witness comes as a `.wtns` with 8-byte field elements
@@ -54,6 +59,55 @@ def _zk():
     return zk
 
 
+def finding_line(f):
+    """one finding of a pil_verify report as `fileName:line: <kind> ...`"""
+    head = "%s:%s: %s" % (f["fileName"], f["line"], f["kind"])
+    k = f["kind"]
+    if k == "identity":
+        return "%s %d: %s row(s) are not 0, first row %s (value %s)" % (head, f["index"], f["n_rows"], f["first_row"], f["value"])
+    if k == "selector":
+        return "%s of %s %d, side %s: %s row(s) outside {0, 1}, first row %s (value %s)" % (head, f["identity"], f["index"], f["side"], f["n_rows"], f["first_row"], f["value"])
+    if k == "plookup":
+        return "%s %d: %s selected row(s) look up a tuple the table lacks, first row %s (%s)" % (head, f["index"], f["n_rows"], f["first_row"], ", ".join(f["values"]))
+    if k == "permutation":
+        side = lambda r, v: "none" if r is None else "row %s (%s)" % (r, ", ".join(v))
+        return "%s %d: %s f row(s) and %s t row(s) unmatched; first f %s, first t %s" % (
+            head, f["index"], f["n_f_unmatched"], f["n_t_unmatched"], side(f["first_f_row"], f["f_values"]), side(f["first_t_row"], f["t_values"]))
+    if k == "connection_value":
+        return "%s %d: %s S value(s) name no cell, first at column %d row %s (%s)" % (head, f["index"], f["n_cells"], f["col"], f["row"], f["value"])
+    return "%s %d: %s wired cell(s) differ, first column %d row %s (%s) against column %d row %s (%s)" % (
+        head, f["index"], f["n_cells"], f["col"], f["row"], f["value"], f["partner_col"], f["partner_row"], f["partner_value"])
+
+
+def _check_trace(a, stark):
+    """-> the pil_verify report of the files the arguments name"""
+    import numpy as np
+    pil = json.load(open(a.piljson))
+    const = np.memmap(a.const_pols, dtype="<u8", mode="r")
+    cm = np.memmap(a.cm_pols, dtype="<u8", mode="r")
+    chk = stark.PilCheck(pil)
+    if const.size != chk.n * pil["nConstants"] or cm.size != chk.n * pil["nCommitments"]:
+        raise SystemExit("zkgpu_prove: %s / %s do not hold %d rows of %d / %d columns" % (a.const_pols, a.cm_pols, chk.n, pil["nConstants"], pil["nCommitments"]))
+    try:
+        return chk.run(const, cm)
+    finally:
+        chk.free()
+
+
+def pil_verify(a):
+    import importlib
+    _zk()
+    report = _check_trace(a, importlib.import_module("eigen_zkvm_amd.stark"))
+    if a.report:
+        with open(a.report, "w") as f:
+            json.dump(report, f, indent=1)
+    for f in report["findings"]:
+        print(finding_line(f))
+    if report["findings"]:
+        raise SystemExit(1)
+    print("zkgpu_prove: %s satisfies %s (%d rows; %s)" % (a.cm_pols, a.piljson, report["n"], ", ".join("%d %s" % (v, k) for k, v in report["checked"].items())))
+
+
 def stark_prove(a):
     import importlib
     import time
@@ -61,6 +115,12 @@ def stark_prove(a):
     import numpy as np
     zk = _zk()
     stark = importlib.import_module("eigen_zkvm_amd.stark")
+    if a.check_trace:                                                      # pil_verifier.js:46 in front of the proof: nothing is set up for a bad trace
+        findings = _check_trace(a, stark)["findings"]
+        for f in findings:
+            print(finding_line(f), file=sys.stderr)
+        if findings:
+            raise SystemExit(1)
     t_init = time.perf_counter()
     ss = json.load(open(a.stark_struct))
     pil = json.load(open(a.piljson))
@@ -274,7 +334,7 @@ def groth16_verify(a):
     print("zkgpu_prove: %s proof %s accepted" % (a.curve_type, a.proof_file))
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(prog="zkgpu_prove", description=__doc__.split("\n")[0])
     sub = ap.add_subparsers(dest="cmd", required=True)
     s = sub.add_parser("stark_prove", help="Stark proving (zkit/src/main.rs:98-123)")
@@ -292,7 +352,15 @@ def main(argv=None):
     s.add_argument("--no_verify", action="store_true", help="skip the self check of prove.rs:124-132 (extension)")
     s.add_argument("--eval", default="jit", choices=["jit", "bytecode"],
                    help="evaluator of the step programs (extension): jit = run-time compiled kernels; bytecode = the interpreter kernel, nothing is compiled")
+    s.add_argument("--check-trace", dest="check_trace", action="store_true",
+                   help="run pil_verify on the trace first and stop with its findings (exit 1) before any setup (extension)")
     s.set_defaults(fn=stark_prove)
+    pv = sub.add_parser("pil_verify", help="check a trace against its PIL, row by row (starkjs/src/pil_verifier.js:46)")
+    pv.add_argument("-p", "--piljson", default="pil.json")
+    pv.add_argument("--o", dest="const_pols", default="pols.const")
+    pv.add_argument("--m", dest="cm_pols", default="pols.cm")
+    pv.add_argument("--report", default=None, metavar="OUT.json", help="also write the whole report")
+    pv.set_defaults(fn=pil_verify)
     v = sub.add_parser("stark_verify", help="stark_verify.rs:20-136 on a zkin file (extension: the reference runs it inside stark_prove only)")
     v.add_argument("-s", "--stark_stuct", dest="stark_struct", default="stark_struct.json")
     v.add_argument("-p", "--piljson", default="pil.json")
@@ -352,7 +420,11 @@ def main(argv=None):
     gv.add_argument("--public-input", dest="public_input_file", default="public_input.json")
     gv.add_argument("--proof", dest="proof_file", default="proof.json")
     gv.set_defaults(fn=groth16_verify)
-    a = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
     a._argv = list(sys.argv[1:] if argv is None else argv)
     try:
         a.fn(a)
