@@ -1,6 +1,7 @@
-// C ABI of libzkgpu (include/zkgpu.h): thin extern "C" wrappers, host<->device staging for the
-// host-pointer entry points, and the Merkle tree handle.  (Device memory, streams, error capture: devmem.hip.)
+// C ABI of libzkgpu (include/zkgpu.h): thin extern "C" wrappers and host<->device staging for the host-pointer entry points.
+// (Device memory, streams, error capture: devmem.hip.  Merkle trees and transcripts: commit.hip.)
 #include "zk_internal.h"
+#include "commit.h"
 #include "pil_check.h"
 #include "../../include/zkgpu.h"
 #include <algorithm>
@@ -19,26 +20,6 @@ std::mutex g_ws_mu;
 // (a process that still had a registered side stream at exit crashed there).
 DevBuf &g_ws_a = *new DevBuf, &g_ws_b = *new DevBuf, &g_ws_c = *new DevBuf;
 
-// one opening by one block: the row, then thread 0 walks up the tree and copies the sibling of every level
-__device__ __forceinline__ void gather_proof(const u64* __restrict__ elements, const u64* __restrict__ nodes, u32 width,
-                                             u64 height, u64 idx, u64* __restrict__ out /* width + depth*4 */) {
-    const u32 t = threadIdx.x;
-    for (u32 i = t; i < width; i += blockDim.x) out[i] = elements[idx * width + i];
-    if (t == 0) {  // merklehash.rs:64-76 merkle_gen_merkle_proof
-        u64 n = height, off = 0, id = idx; u32 d = 0;
-        while (n > 1) {
-            const u64* sib = nodes + 4 * (off + (id ^ 1));
-            for (int k = 0; k < 4; ++k) out[width + 4 * d + k] = sib[k];
-            u64 next = (n - 1) / 2 + 1;
-            off += next * 2; n = next; id >>= 1; ++d;
-        }
-    }
-}
-__global__ void gather_proof_kernel(const u64* __restrict__ elements, const u64* __restrict__ nodes, u32 width,
-                                    u64 height, u64 idx, u64* __restrict__ out) {
-    gather_proof(elements, nodes, width, height, idx, out);
-}
-
 // synthetic words for benchmarks and size tests: word i = splitmix64(seed + i) folded below p (one conditional subtraction)
 __global__ void fill_splitmix_kernel(u64* __restrict__ out, u64 n, u64 seed) {
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
@@ -48,72 +29,10 @@ __global__ void fill_splitmix_kernel(u64* __restrict__ out, u64 n, u64 seed) {
     out[i] = z >= GL_P ? z - GL_P : z;
 }
 
-// the same for n queries at once: block q serves idx[q], out + q * (width + 4 * depth)
-__global__ void gather_proofs_kernel(const u64* __restrict__ elements, const u64* __restrict__ nodes, u32 width, u64 height,
-                                     u32 depth, const u64* __restrict__ idxs, u64* __restrict__ outs, u64 mask) {
-    const u64 idx = idxs[blockIdx.x] & mask;             // mask: the query index reduced to a later FRI step's domain (fri.rs:166-168)
-    gather_proof(elements, nodes, width, height, idx, outs + (u64)blockIdx.x * (width + 4 * depth));
-}
-// every tree of a proof in ONE launch: block (q, j) serves query q of tree j (a small proof opened its seven or eight trees in as many
-// launches of ~5 us each); lane d copies the sibling of level d
-struct GatherMulti { const u64* elements[16]; const u64* nodes[16]; u64* out[16]; u64 height[16], mask[16]; u32 width[16], depth[16]; };
-__global__ void gather_proofs_multi_kernel(const GatherMulti G, const u64* __restrict__ idxs) {
-    const u32 t = threadIdx.x, j = blockIdx.y;
-    const u32 width = G.width[j], depth = G.depth[j];
-    const u64 idx = idxs[blockIdx.x] & G.mask[j];
-    const u64* __restrict__ elements = G.elements[j];
-    const u64* __restrict__ nodes = G.nodes[j];
-    u64* __restrict__ out = G.out[j] + (u64)blockIdx.x * (width + 4 * depth);
-    for (u32 i = t; i < width; i += blockDim.x) out[i] = elements[idx * width + i];
-    for (u32 d = t; d < depth; d += blockDim.x) {
-        u64 n = G.height[j], off = 0;
-        for (u32 k = 0; k < d; ++k) { const u64 next = (n - 1) / 2 + 1; off += next * 2; n = next; }
-        const u64* sib = nodes + 4 * (off + ((idx >> d) ^ 1));
-        for (int k = 0; k < 4; ++k) out[width + 4 * d + k] = sib[k];
-    }
-}
-// arity-16 trees of the scalar-field hashes (merklehash_bn128.rs:86-106): block q -> row + depth groups of 16 digests
-__global__ void fr_gather_proofs_kernel(const u64* __restrict__ elements, const u64* __restrict__ nodes, u32 width, u64 height,
-                                        u32 depth, const u64* __restrict__ idxs, u64* __restrict__ outs) {
-    const u32 t = threadIdx.x;
-    const u64 idx = idxs[blockIdx.x];
-    u64* __restrict__ out = outs + (u64)blockIdx.x * (width + 64 * depth);
-    for (u32 i = t; i < width; i += blockDim.x) out[i] = elements[idx * width + i];
-    u64 n = height, off = 0, id = idx; u32 d = 0;
-    while (n > 1) {
-        const u64 si = id & ~(u64)15;
-        if (t < 64) out[width + 64 * d + t] = nodes[4 * (off + si) + t];
-        const u64 next = (n - 1) / 16 + 1;
-        off += next * 16; n = next; id >>= 4; ++d;
-    }
-}
-
 }  // namespace
 }  // namespace zk
 
 using namespace zk;
-
-struct zk_merkle {
-    const u64* d_elements = nullptr;  // [height][width]
-    DevBuf owned_elements;            // set when the tree owns its rows
-    DevBuf nodes;                     // merkle_n_nodes(height) * 4 words
-    DevBuf proof;                     // staging for group proofs
-    uint32_t width = 0, depth = 0;
-    uint64_t height = 0, n_nodes = 0;
-    hipStream_t stream = nullptr;
-};
-
-struct zk_transcript {
-    DevBuf state;  // TranscriptState (poseidon.hip)
-    DevBuf io;     // staging for host-word put / get
-    hipStream_t stream = nullptr;  // where the state was last worked on: the host-word calls continue (and wait) there
-};
-
-static uint32_t tree_depth(uint64_t height) {
-    uint32_t d = 0; uint64_t n = height;
-    while (n > 1) { n = (n - 1) / 2 + 1; ++d; }
-    return d;
-}
 
 extern "C" {
 
@@ -257,208 +176,63 @@ int zk_gl_linearhash(const uint64_t* v, size_t n, uint64_t out[4]) {
     });
 }
 
+// ---- MerkleTreeGL / TranscriptGL (commit.hip) --------------------------------------------------------
 uint64_t zk_merkle_n_nodes(uint64_t height) { return height ? merkle_n_nodes(height) : 0; }
 
-static zk_merkle_t* make_tree(const u64* d_rows, zk_merkle_t* t, uint32_t width, uint64_t height, hipStream_t st) {
-    t->d_elements = d_rows; t->width = width; t->height = height;
-    t->n_nodes = merkle_n_nodes(height); t->depth = tree_depth(height); t->stream = st;
-    t->nodes.reserve(t->n_nodes * 32);
-    t->proof.reserve(((size_t)width + 4 * (size_t)t->depth + 4) * sizeof(u64));
-    merkelize_dev(d_rows, width, height, t->nodes.u(), st);
-    return t;
-}
-
 zk_merkle_t* zk_gl_merkelize(const uint64_t* buff, uint32_t width, uint64_t height) {
-    zk_merkle_t* t = nullptr;
-    int rc = guard([&] {
-        ZK_REQUIRE((buff || width == 0) && height >= 1, "zk_gl_merkelize: empty matrix");
-        t = new zk_merkle();
-        const size_t bytes = (size_t)width * height * sizeof(u64);
-        t->owned_elements.reserve(bytes ? bytes : 8);
-        if (bytes) ZK_HIP(hipMemcpy(t->owned_elements.p, buff, bytes, hipMemcpyHostToDevice));
-        make_tree(t->owned_elements.u(), t, width, height, nullptr);
-        ZK_HIP(hipStreamSynchronize(nullptr));
-    });
-    if (rc != 0) { delete t; return nullptr; }
-    return t;
+    std::unique_ptr<zk_merkle> t;
+    if (guard([&] {
+            ZK_REQUIRE((buff || width == 0) && height >= 1, "zk_gl_merkelize: empty matrix");
+            t.reset(new zk_merkle); t->build_host((const u64*)buff, width, height);
+        }) != 0) return nullptr;
+    return t.release();
 }
-
 zk_merkle_t* zk_gl_merkelize_dev(const uint64_t* d_buff, uint32_t width, uint64_t height, void* stream) {
-    zk_merkle_t* t = nullptr;
-    int rc = guard([&] {
-        ZK_REQUIRE((d_buff || width == 0) && height >= 1, "zk_gl_merkelize_dev: empty matrix");
-        t = new zk_merkle();
-        make_tree((const u64*)d_buff, t, width, height, on_stream((hipStream_t)stream));
-    });
-    if (rc != 0) { delete t; return nullptr; }
-    return t;
+    std::unique_ptr<zk_merkle> t;
+    if (guard([&] {
+            ZK_REQUIRE((d_buff || width == 0) && height >= 1, "zk_gl_merkelize_dev: empty matrix");
+            t.reset(new zk_merkle); t->build_dev((const u64*)d_buff, width, height, (hipStream_t)stream);
+        }) != 0) return nullptr;
+    return t.release();
 }
-
-int zk_merkle_root(const zk_merkle_t* t, uint64_t out[4]) {
-    return guard([&] {
-        ZK_REQUIRE(t && out, "zk_merkle_root: null");
-        ZK_HIP(hipStreamSynchronize(t->stream));
-        ZK_HIP(hipMemcpy(out, t->nodes.u() + 4 * (t->n_nodes - 1), 32, hipMemcpyDeviceToHost));
-    });
-}
-
-int zk_merkle_nodes(const zk_merkle_t* t, uint64_t* out) {
-    return guard([&] {
-        ZK_REQUIRE(t && out, "zk_merkle_nodes: null");
-        ZK_HIP(hipStreamSynchronize(t->stream));
-        ZK_HIP(hipMemcpy(out, t->nodes.p, t->n_nodes * 32, hipMemcpyDeviceToHost));
-    });
-}
-
-int zk_merkle_elements(const zk_merkle_t* t, uint64_t* out) {
-    return guard([&] {
-        ZK_REQUIRE(t && out, "zk_merkle_elements: null");
-        ZK_HIP(hipStreamSynchronize(t->stream));
-        ZK_HIP(hipMemcpy(out, t->d_elements, (size_t)t->height * t->width * 8, hipMemcpyDeviceToHost));
-    });
-}
-
+int zk_merkle_root(const zk_merkle_t* t, uint64_t out[4]) { return guard([&] { ZK_REQUIRE(t && out, "zk_merkle_root: null"); t->root((u64*)out); }); }
+int zk_merkle_nodes(const zk_merkle_t* t, uint64_t* out) { return guard([&] { ZK_REQUIRE(t && out, "zk_merkle_nodes: null"); t->nodes_host((u64*)out); }); }
+int zk_merkle_elements(const zk_merkle_t* t, uint64_t* out) { return guard([&] { ZK_REQUIRE(t && out, "zk_merkle_elements: null"); t->elements_host((u64*)out); }); }
 uint32_t zk_merkle_depth(const zk_merkle_t* t) { return t ? t->depth : 0; }
-}  // extern "C"
-namespace zk {
-uint32_t merkle_width(const zk_merkle* t) { return t->width; }
-uint64_t merkle_height(const zk_merkle* t) { return t->height; }
-}
-extern "C" {
-
 int zk_merkle_group_proof(const zk_merkle_t* t, uint64_t idx, uint64_t* row_out, uint64_t* path_out) {
     return guard([&] {
         ZK_REQUIRE(t && row_out && (path_out || t->depth == 0), "zk_merkle_group_proof: null");
-        ZK_REQUIRE(idx < t->height, "MerkleTreeError: access invalid node");  // merklehash.rs:431-433
-        hipLaunchKernelGGL(gather_proof_kernel, dim3(1), dim3(64), 0, t->stream, t->d_elements, t->nodes.u(),
-                           t->width, t->height, idx, t->proof.u());
-        ZK_HIP(hipGetLastError());
-        ZK_HIP(hipStreamSynchronize(t->stream));
-        ZK_HIP(hipMemcpy(row_out, t->proof.p, t->width * sizeof(u64), hipMemcpyDeviceToHost));
-        if (t->depth)
-            ZK_HIP(hipMemcpy(path_out, t->proof.u() + t->width, (size_t)t->depth * 32, hipMemcpyDeviceToHost));
+        t->group_proof(idx, (u64*)row_out, (u64*)path_out);
     });
 }
-
 int zk_merkle_group_proofs(const zk_merkle_t* t, const uint64_t* idx, uint32_t n, uint64_t* rows_out, uint64_t* paths_out) {
     return guard([&] {
         ZK_REQUIRE(t && (n == 0 || (idx && rows_out && (paths_out || t->depth == 0))), "zk_merkle_group_proofs: null");
-        if (n == 0) return;
-        for (uint32_t q = 0; q < n; ++q) ZK_REQUIRE(idx[q] < t->height, "MerkleTreeError: access invalid node");
-        const size_t per = (size_t)t->width + 4 * (size_t)t->depth;
-        on_stream(t->stream);
-        DevBuf d_idx, d_out; d_idx.reserve(n * 8); d_out.reserve(std::max<size_t>(1, per * n) * 8);
-        ZK_HIP(hipMemcpyAsync(d_idx.p, idx, n * 8, hipMemcpyHostToDevice, t->stream));
-        hipLaunchKernelGGL(gather_proofs_kernel, dim3(n), dim3(64), 0, t->stream, t->d_elements, t->nodes.u(), t->width, t->height,
-                           t->depth, d_idx.u(), d_out.u(), ~0ull);
-        ZK_HIP(hipGetLastError());
-        std::vector<u64> h(std::max<size_t>(1, per * n));
-        ZK_HIP(hipMemcpyAsync(h.data(), d_out.p, per * n * 8, hipMemcpyDeviceToHost, t->stream));
-        ZK_HIP(hipStreamSynchronize(t->stream));
-        for (uint32_t q = 0; q < n; ++q) {
-            memcpy(rows_out + (size_t)q * t->width, h.data() + q * per, (size_t)t->width * 8);
-            if (t->depth) memcpy(paths_out + (size_t)q * 4 * t->depth, h.data() + q * per + t->width, (size_t)t->depth * 32);
-        }
+        t->group_proofs((const u64*)idx, n, (u64*)rows_out, (u64*)paths_out);
     });
 }
+const uint64_t* zk_merkle_elements_dev(const zk_merkle_t* t) { return t ? (const uint64_t*)t->d_elements : nullptr; }
+const uint64_t* zk_merkle_nodes_dev(const zk_merkle_t* t) { return t ? (const uint64_t*)t->nodes.p : nullptr; }
+int zk_merkle_free(zk_merkle_t* t) { delete t; return 0; }
 
-}  // extern "C"
-namespace zk {
-void merkle_group_proofs_async(const zk_merkle* t, const u64* d_idx, uint32_t n, u64* d_out, hipStream_t st) {
-    if (n == 0) return;
-    hipLaunchKernelGGL(gather_proofs_kernel, dim3(n), dim3(64), 0, st, t->d_elements, t->nodes.u(), t->width, t->height, t->depth, d_idx, d_out, ~0ull);
-    ZK_HIP(hipGetLastError());
-}
-// the same at the indices d_idx[q] & mask (mask + 1 = the tree's height, a power of two): the query indices stay on the device
-void merkle_group_proofs_masked_async(const zk_merkle* t, const u64* d_idx, u64 mask, uint32_t n, u64* d_out, hipStream_t st) {
-    if (n == 0) return;
-    ZK_REQUIRE(mask < t->height, "MerkleTreeError: access invalid node");
-    hipLaunchKernelGGL(gather_proofs_kernel, dim3(n), dim3(64), 0, st, t->d_elements, t->nodes.u(), t->width, t->height, t->depth, d_idx, d_out, mask);
-    ZK_HIP(hipGetLastError());
-}
-// up to 16 trees at once: tree j at d_idx[q] & mask[j] into d_out[j] (rows of width_j + 4 depth_j words per query)
-void merkle_group_proofs_multi_async(const zk_merkle* const* trees, const u64* masks, u64* const* d_outs, uint32_t n_trees, const u64* d_idx, uint32_t n, hipStream_t st) {
-    if (n == 0 || n_trees == 0) return;
-    for (uint32_t j0 = 0; j0 < n_trees; j0 += 16) {
-        GatherMulti G; memset(&G, 0, sizeof G);
-        const uint32_t m = std::min<uint32_t>(16, n_trees - j0);
-        for (uint32_t j = 0; j < m; ++j) {
-            const zk_merkle* t = trees[j0 + j];
-            ZK_REQUIRE(masks[j0 + j] < t->height, "MerkleTreeError: access invalid node");
-            G.elements[j] = t->d_elements; G.nodes[j] = t->nodes.u(); G.out[j] = d_outs[j0 + j];
-            G.height[j] = t->height; G.mask[j] = masks[j0 + j]; G.width[j] = t->width; G.depth[j] = t->depth;
-        }
-        hipLaunchKernelGGL(gather_proofs_multi_kernel, dim3(n, m), dim3(64), 0, st, G, d_idx);
-        ZK_HIP(hipGetLastError());
-    }
-}
-// get_permutations (transcript.rs:73-102) into device memory, on `st`: the indices feed the gather kernels without visiting the host
-void transcript_permutations_async(zk_transcript* t, uint32_t n, uint32_t nbits, u64* d_dst, hipStream_t st) {
-    t->stream = st;
-    transcript_permutations_dev(t->state.p, n, nbits, d_dst, st);
-}
-void transcript_put_get_async(zk_transcript* t, const u64* d_src, uint64_t n_put, u64* d_dst, uint32_t n_get, uint32_t bits, hipStream_t st) {
-    if (t->stream != st) { ZK_HIP(hipStreamSynchronize(t->stream)); t->stream = st; }
-    transcript_put_get_dev(t->state.p, d_src, n_put, d_dst, n_get, bits, st);
-}
-}  // namespace zk
-extern "C" {
-
-// ---- transcript ------------------------------------------------------------------------------
-// the sponge state lives on one stream at a time: work moves to `st` after whatever was issued on the previous stream
-static hipStream_t transcript_stream(zk_transcript_t* t, hipStream_t st) {
-    if (t->stream != st) { ZK_HIP(hipStreamSynchronize(t->stream)); t->stream = st; }
-    return on_stream(st);
-}
 zk_transcript_t* zk_transcript_new(void) {
     zk_transcript_t* t = nullptr;
-    int rc = guard([&] {
-        t = new zk_transcript();
-        t->stream = cur_stream();                                       // the caller's (a prover's own stream, or the null stream)
-        t->state.reserve(transcript_state_bytes());
-        t->io.reserve(4096 * sizeof(u64));
-        transcript_init_dev(t->state.p, t->stream);
-    });
-    if (rc != 0) { delete t; return nullptr; }
+    if (guard([&] { t = new zk_transcript; }) != 0) return nullptr;
     return t;
 }
 int zk_transcript_put_dev(zk_transcript_t* t, const uint64_t* d_src, size_t n, void* stream) {
-    return guard([&] { ZK_REQUIRE(t, "transcript: null"); transcript_put_dev(t->state.p, (const u64*)d_src, n, transcript_stream(t, (hipStream_t)stream)); });
+    return guard([&] { ZK_REQUIRE(t, "transcript: null"); t->put_dev((const u64*)d_src, n, (hipStream_t)stream); });
 }
 int zk_transcript_put(zk_transcript_t* t, const uint64_t* src, size_t n) {
-    return guard([&] {
-        ZK_REQUIRE(t && (src || n == 0), "transcript: null");
-        if (n == 0) return;
-        on_stream(t->stream);
-        t->io.reserve(n * sizeof(u64));
-        ZK_HIP(hipStreamSynchronize(t->stream));                         // io may still be read by an earlier put
-        ZK_HIP(hipMemcpy(t->io.p, src, n * sizeof(u64), hipMemcpyHostToDevice));
-        transcript_put_dev(t->state.p, t->io.u(), n, on_stream(t->stream));
-        ZK_HIP(hipStreamSynchronize(t->stream));
-    });
+    return guard([&] { ZK_REQUIRE(t && (src || n == 0), "transcript: null"); t->put_words((const u64*)src, n); });
 }
 int zk_transcript_get_field_dev(zk_transcript_t* t, uint64_t* d_out3, void* stream) {
-    return guard([&] { ZK_REQUIRE(t && d_out3, "transcript: null"); transcript_get_dev(t->state.p, (u64*)d_out3, 3, transcript_stream(t, (hipStream_t)stream)); });
+    return guard([&] { ZK_REQUIRE(t && d_out3, "transcript: null"); t->get_dev((u64*)d_out3, 3, (hipStream_t)stream); });
 }
-static int transcript_get_host(zk_transcript_t* t, uint64_t* out, uint32_t n_words) {
-    return guard([&] {
-        ZK_REQUIRE(t && out, "transcript: null");
-        transcript_get_dev(t->state.p, t->io.u(), n_words, on_stream(t->stream));
-        ZK_HIP(hipStreamSynchronize(t->stream));
-        ZK_HIP(hipMemcpy(out, t->io.p, n_words * sizeof(u64), hipMemcpyDeviceToHost));
-    });
-}
-int zk_transcript_get_field(zk_transcript_t* t, uint64_t out[3]) { return transcript_get_host(t, out, 3); }
-int zk_transcript_get_fields1(zk_transcript_t* t, uint64_t* out) { return transcript_get_host(t, out, 1); }
+int zk_transcript_get_field(zk_transcript_t* t, uint64_t out[3]) { return guard([&] { ZK_REQUIRE(t && out, "transcript: null"); t->get((u64*)out, 3); }); }
+int zk_transcript_get_fields1(zk_transcript_t* t, uint64_t* out) { return guard([&] { ZK_REQUIRE(t && out, "transcript: null"); t->get((u64*)out, 1); }); }
 int zk_transcript_get_permutations(zk_transcript_t* t, uint32_t n, uint32_t nbits, uint64_t* out) {
-    return guard([&] {
-        ZK_REQUIRE(t && out, "transcript: null");
-        on_stream(t->stream);
-        t->io.reserve((size_t)n * sizeof(u64) + 64);
-        transcript_permutations_dev(t->state.p, n, nbits, t->io.u(), t->stream);
-        ZK_HIP(hipStreamSynchronize(t->stream));
-        ZK_HIP(hipMemcpy(out, t->io.p, (size_t)n * sizeof(u64), hipMemcpyDeviceToHost));
-    });
+    return guard([&] { ZK_REQUIRE(t && out, "transcript: null"); t->get_permutations(n, nbits, (u64*)out); });
 }
 int zk_transcript_free(zk_transcript_t* t) { delete t; return 0; }
 
@@ -570,327 +344,93 @@ int zk_msm_g1_bls12_381(const void* bases, const void* scalars, uint64_t n, void
     });
 }
 
-// ---- scalar-field hashing (verificationHashType "BN128" / "BLS12381") -----------------------------------
-}  // extern "C" (reopened below): the two fields share one implementation, instantiated per field
-
-namespace {
-struct FrOps {   // one scalar field: device entry points (frhash.hip) + the host-side modulus for the sponge bookkeeping
-    const char* name;
-    uint64_t R[4], R2[4], INV;     // modulus, 2^512 mod r, -r^-1 mod 2^64
-    void (*load)(const char*);
-    std::string (*selfcheck)(const char*);
-    void (*poseidon_dev)(const u64*, uint64_t, uint32_t, const u64*, uint32_t, u64*, hipStream_t);
-    uint64_t (*n_nodes)(uint64_t);
-    void (*linearhash_rows_dev)(const u64*, uint32_t, uint64_t, u64*, hipStream_t);
-    void (*merkelize_dev)(const u64*, uint32_t, uint64_t, u64*, hipStream_t);
-};
-const FrOps FR_BN128 = {"bn128",
-    {0x43e1f593f0000001ULL, 0x2833e84879b97091ULL, 0xb85045b68181585dULL, 0x30644e72e131a029ULL},
-    {1997599621687373223ULL, 6052339484930628067ULL, 10108755138030829701ULL, 150537098327114917ULL}, 0xc2e1f593efffffffULL,
-    bn128_load_constants, bn128_tables_selfcheck, bn128_poseidon_dev, bn128_merkle_n_nodes, bn128_linearhash_rows_dev, bn128_merkelize_dev};
-const FrOps FR_BLS12381 = {"bls12381",
-    {0xffffffff00000001ULL, 0x53bda402fffe5bfeULL, 0x3339d80809a1d805ULL, 0x73eda753299d7d48ULL},
-    {14526898881837571181ULL, 3129137299524312099ULL, 419701826671360399ULL, 524908885293268753ULL}, 0xfffffffeffffffffULL,
-    bls12381_load_constants, bls12381_tables_selfcheck, bls12381_poseidon_dev, bls12381_merkle_n_nodes, bls12381_linearhash_rows_dev, bls12381_merkelize_dev};
-
-struct FrMerkle {
-    const FrOps* F = nullptr;
-    const u64* d_elements = nullptr;
-    DevBuf owned_elements, nodes;
-    uint32_t width = 0, depth = 0;
-    uint64_t height = 0, n_nodes = 0;
-};
-struct FrTranscript {   // transcript_bn128.rs:14-20: sponge bookkeeping on the host, permutations on the device
-    const FrOps* F = nullptr;
-    uint64_t state[4] = {0, 0, 0, 0};
-    std::vector<uint64_t> pending;          // raw limbs, 4 per element
-    std::vector<uint64_t> out;              // 17 x 4 raw limbs
-    size_t out_pos = 0, n_out = 0;
-    uint64_t out3[3] = {0, 0, 0}; size_t out3_pos = 0, n_out3 = 0;
+// ---- scalar-field hashing (verificationHashType "BN128" / "BLS12381"): two name families over one implementation (commit.hip) ----
+// one permutation / one row from host buffers, on the null stream
+static void fr_poseidon(const FrField& F, const uint64_t* inp, uint32_t n_in, const uint64_t* init_state, uint32_t n_out, uint64_t* out) {
+    ZK_REQUIRE(inp && init_state && out, "poseidon: null buffer");
+    ZK_REQUIRE(n_in >= 1 && n_in <= 16, "Wrong inputs length");
+    on_stream(nullptr);
     DevBuf d_in, d_init, d_out;
-};
-uint32_t fr_depth(uint64_t height) { uint32_t d = 0; uint64_t n = height; while (n > 1) { n = (n - 1) / 16 + 1; ++d; } return d; }
-void fr_mont_mul_host(const FrOps& F, const uint64_t a[4], const uint64_t b[4], uint64_t r[4]) {   // a*b/2^256 mod r (CIOS)
-    typedef unsigned __int128 u128;
-    uint64_t t[6] = {0, 0, 0, 0, 0, 0};
-    for (int i = 0; i < 4; ++i) {
-        u128 c = 0;
-        for (int j = 0; j < 4; ++j) { c += (u128)a[j] * b[i] + t[j]; t[j] = (uint64_t)c; c >>= 64; }
-        c += t[4]; t[4] = (uint64_t)c; t[5] = (uint64_t)(c >> 64);
-        const uint64_t m = t[0] * F.INV;
-        c = ((u128)m * F.R[0] + t[0]) >> 64;
-        for (int j = 1; j < 4; ++j) { c += (u128)m * F.R[j] + t[j]; t[j - 1] = (uint64_t)c; c >>= 64; }
-        c += t[4]; t[3] = (uint64_t)c; t[4] = t[5] + (uint64_t)(c >> 64);
-    }
-    for (;;) {
-        bool ge = t[4] != 0;
-        if (!ge) { ge = true; for (int i = 3; i >= 0; --i) { if (t[i] > F.R[i]) break; if (t[i] < F.R[i]) { ge = false; break; } } }
-        if (!ge) break;
-        u128 br = 0;
-        for (int i = 0; i < 4; ++i) { u128 d = (u128)t[i] - F.R[i] - br; t[i] = (uint64_t)d; br = (d >> 64) & 1; }
-        t[4] -= (uint64_t)br;
-    }
-    memcpy(r, t, 32);
-}
-}  // namespace
-namespace zk {
-// decimal text of a scalar-field element (how a digest travels in zkin JSON, digest.rs:91-94) -> the raw Montgomery limbs of
-// ElementDigest<4, Fr>; false when the text is not a canonical value below the modulus
-bool fr_digest_from_dec(bool bls12381, const std::string& dec, u64 out[4]) {
-    const FrOps& F = bls12381 ? FR_BLS12381 : FR_BN128;
-    if (dec.empty() || dec.size() > 78) return false;
-    uint64_t v[4] = {0, 0, 0, 0};
-    for (char c : dec) {
-        if (c < '0' || c > '9') return false;
-        unsigned __int128 carry = (unsigned)(c - '0');
-        for (int i = 0; i < 4; ++i) { carry += (unsigned __int128)v[i] * 10; v[i] = (uint64_t)carry; carry >>= 64; }
-        if (carry) return false;
-    }
-    for (int i = 3; i >= 0; --i) { if (v[i] < F.R[i]) break; if (v[i] > F.R[i] || i == 0) return false; }
-    uint64_t m[4];
-    fr_mont_mul_host(F, v, F.R2, m);
-    for (int i = 0; i < 4; ++i) out[i] = m[i];
-    return true;
-}
-// n hashes of 16 nodes each (hash of a group of a 16-ary tree with a zero initial state, merklehash_bn128.rs:108-128), device buffers
-// d_out [n][2][4]: the permutation's first two words -- Poseidon::hash is word 0 over BN128 (poseidon_bn128_opt.rs) and word 1 over
-// BLS12-381 (poseidon_bls12381_opt.rs:94-103)
-void fr_hash16_dev(bool bls12381, const u64* d_in /* [n][16][4] */, uint64_t n, const u64* d_zero4, u64* d_out, hipStream_t st) {
-    (bls12381 ? FR_BLS12381 : FR_BN128).poseidon_dev(d_in, n, 16, d_zero4, 2, d_out, st);
-}
-void fr_linearhash_rows_dev(bool bls12381, const u64* d_rows, uint32_t width, uint64_t height, u64* d_digests, hipStream_t st) {
-    (bls12381 ? FR_BLS12381 : FR_BN128).linearhash_rows_dev(d_rows, width, height, d_digests, st);
-}
-}  // namespace zk
-namespace {
-void fr_tr_update(FrTranscript* t) {   // transcript_bn128.rs:22-31
-    t->pending.resize(64, 0);
-    on_stream(nullptr);                         // the scalar-field sponges work on the null stream, whoever calls
-    t->d_in.reserve(64 * 8); t->d_init.reserve(32); t->d_out.reserve(17 * 32);
-    ZK_HIP(hipMemcpy(t->d_in.p, t->pending.data(), 64 * 8, hipMemcpyHostToDevice));
-    ZK_HIP(hipMemcpy(t->d_init.p, t->state, 32, hipMemcpyHostToDevice));
-    t->F->poseidon_dev(t->d_in.u(), 1, 16, t->d_init.u(), 17, t->d_out.u(), nullptr);
-    t->out.resize(68);
+    d_in.reserve(n_in * 32); d_init.reserve(32); d_out.reserve(17 * 32);
+    ZK_HIP(hipMemcpy(d_in.p, inp, n_in * 32, hipMemcpyHostToDevice));
+    ZK_HIP(hipMemcpy(d_init.p, init_state, 32, hipMemcpyHostToDevice));
+    F.poseidon_dev(d_in.u(), 1, n_in, d_init.u(), n_out, d_out.u(), nullptr);
     ZK_HIP(hipStreamSynchronize(nullptr));
-    ZK_HIP(hipMemcpy(t->out.data(), t->d_out.p, 17 * 32, hipMemcpyDeviceToHost));
-    t->out_pos = 0; t->n_out = 17; t->n_out3 = 0; t->out3_pos = 0; t->pending.clear();
-    memcpy(t->state, t->out.data(), 32);
+    ZK_HIP(hipMemcpy(out, d_out.p, n_out * 32, hipMemcpyDeviceToHost));
 }
-void fr_tr_add1(FrTranscript* t, const uint64_t raw[4]) {   // :32-40
-    t->n_out = 0; t->out_pos = 0;
-    t->pending.insert(t->pending.end(), raw, raw + 4);
-    if (t->pending.size() == 64) fr_tr_update(t);
+static void fr_linearhash(const FrField& F, const uint64_t* v, size_t n, uint64_t* out) {
+    ZK_REQUIRE(out && (v || n == 0), "linearhash: null buffer");
+    on_stream(nullptr);
+    DevBuf d_v, d_o; d_v.reserve(n * 8 + 8); d_o.reserve(32);
+    if (n) ZK_HIP(hipMemcpy(d_v.p, v, n * 8, hipMemcpyHostToDevice));
+    ZK_HIP(hipMemset(d_o.p, 0, 32));
+    F.linearhash_rows_dev(d_v.u(), (uint32_t)n, 1, d_o.u(), nullptr);
+    ZK_HIP(hipStreamSynchronize(nullptr));
+    ZK_HIP(hipMemcpy(out, d_o.p, 32, hipMemcpyDeviceToHost));
 }
-void fr_tr_get253(FrTranscript* t, uint64_t canon[4]) {   // :42-48, canonical value of the popped element
-    if (t->out_pos >= t->n_out) fr_tr_update(t);
-    const uint64_t one[4] = {1, 0, 0, 0};
-    fr_mont_mul_host(*t->F, t->out.data() + 4 * t->out_pos, one, canon);
-    ++t->out_pos;
-}
-
-int fr_poseidon(const FrOps& F, const uint64_t* inp, uint32_t n_in, const uint64_t* init_state, uint32_t n_out, uint64_t* out) {
-    return guard([&] {
-        ZK_REQUIRE(inp && init_state && out, "poseidon: null buffer");
-        ZK_REQUIRE(n_in >= 1 && n_in <= 16, "Wrong inputs length");
-        on_stream(nullptr);
-        DevBuf d_in, d_init, d_out;
-        d_in.reserve(n_in * 32); d_init.reserve(32); d_out.reserve(17 * 32);
-        ZK_HIP(hipMemcpy(d_in.p, inp, n_in * 32, hipMemcpyHostToDevice));
-        ZK_HIP(hipMemcpy(d_init.p, init_state, 32, hipMemcpyHostToDevice));
-        F.poseidon_dev(d_in.u(), 1, n_in, d_init.u(), n_out, d_out.u(), nullptr);
-        ZK_HIP(hipStreamSynchronize(nullptr));
-        ZK_HIP(hipMemcpy(out, d_out.p, n_out * 32, hipMemcpyDeviceToHost));
-    });
-}
-int fr_linearhash(const FrOps& F, const uint64_t* v, size_t n, uint64_t* out) {
-    return guard([&] {
-        ZK_REQUIRE(out && (v || n == 0), "linearhash: null buffer");
-        on_stream(nullptr);
-        DevBuf d_v, d_o; d_v.reserve(n * 8 + 8); d_o.reserve(32);
-        if (n) ZK_HIP(hipMemcpy(d_v.p, v, n * 8, hipMemcpyHostToDevice));
-        ZK_HIP(hipMemset(d_o.p, 0, 32));
-        F.linearhash_rows_dev(d_v.u(), (uint32_t)n, 1, d_o.u(), nullptr);
-        ZK_HIP(hipStreamSynchronize(nullptr));
-        ZK_HIP(hipMemcpy(out, d_o.p, 32, hipMemcpyDeviceToHost));
-    });
-}
-template <class T>
-T* fr_merkelize(const FrOps& F, const uint64_t* buff, bool on_device, uint32_t width, uint64_t height, void* stream) {
-    T* t = nullptr;
-    if (guard([&] {
-            ZK_REQUIRE(height >= 1, "merkelize: height must be >= 1");
-            ZK_REQUIRE(buff || width == 0, "merkelize: null buffer");
-            t = new T;
-            t->F = &F;
-            if (on_device) t->d_elements = (const u64*)buff;
-            else {
-                on_stream(nullptr);
-                t->owned_elements.reserve((size_t)width * height * 8 + 8);
-                if (width) ZK_HIP(hipMemcpy(t->owned_elements.p, buff, (size_t)width * height * 8, hipMemcpyHostToDevice));
-                t->d_elements = t->owned_elements.u();
-            }
-            t->width = width; t->height = height;
-            t->n_nodes = F.n_nodes(height); t->depth = fr_depth(height);
-            t->nodes.reserve(t->n_nodes * 32);
-            F.merkelize_dev(t->d_elements, width, height, t->nodes.u(), on_device ? on_stream((hipStream_t)stream) : nullptr);
-            if (!on_device) ZK_HIP(hipStreamSynchronize(nullptr));
-        }) != 0) { delete t; return nullptr; }
-    return t;
-}
-int fr_merkle_root(const FrMerkle* t, uint64_t* out) {
-    return guard([&] {
-        ZK_REQUIRE(t && out, "null argument");
-        ZK_HIP(hipDeviceSynchronize());
-        ZK_HIP(hipMemcpy(out, t->nodes.u() + 4 * (t->n_nodes - 1), 32, hipMemcpyDeviceToHost));
-    });
-}
-int fr_merkle_nodes(const FrMerkle* t, uint64_t* out) {
-    return guard([&] { ZK_REQUIRE(t && out, "null argument"); ZK_HIP(hipDeviceSynchronize()); ZK_HIP(hipMemcpy(out, t->nodes.p, t->n_nodes * 32, hipMemcpyDeviceToHost)); });
-}
-// get_group_proof (merklehash_bn128.rs:246-254): row_out[width], path_out[depth][16][4]
-int fr_merkle_group_proof(const FrMerkle* t, uint64_t idx, uint64_t* row_out, uint64_t* path_out) {
-    return guard([&] {
-        ZK_REQUIRE(t && row_out && path_out, "null argument");
-        ZK_REQUIRE(idx < t->height, "MerkleTreeError: access invalid node");
-        ZK_HIP(hipDeviceSynchronize());
-        if (t->width) ZK_HIP(hipMemcpy(row_out, t->d_elements + idx * t->width, t->width * 8, hipMemcpyDeviceToHost));
-        uint64_t n = t->height, off = 0, id = idx; uint32_t d = 0;
-        while (n > 1) {   // merklehash_bn128.rs:86-106
-            const uint64_t si = id & ~(uint64_t)15;
-            ZK_HIP(hipMemcpy(path_out + (size_t)d * 64, t->nodes.u() + 4 * (off + si), 16 * 32, hipMemcpyDeviceToHost));
-            const uint64_t next = (n - 1) / 16 + 1;
-            off += next * 16; n = next; id >>= 4; ++d;
-        }
-    });
-}
-int fr_merkle_group_proofs(const FrMerkle* t, const uint64_t* idx, uint32_t n, uint64_t* rows_out, uint64_t* paths_out) {
-    return guard([&] {
-        ZK_REQUIRE(t && (n == 0 || (idx && rows_out && paths_out)), "null argument");
-        if (n == 0) return;
-        for (uint32_t q = 0; q < n; ++q) ZK_REQUIRE(idx[q] < t->height, "MerkleTreeError: access invalid node");
-        ZK_HIP(hipDeviceSynchronize());                                   // (the tree does not remember the stream it was built on)
-        on_stream(nullptr);
-        const size_t per = (size_t)t->width + 64 * (size_t)t->depth;
-        DevBuf d_idx, d_out; d_idx.reserve(n * 8); d_out.reserve(std::max<size_t>(1, per * n) * 8);
-        ZK_HIP(hipMemcpy(d_idx.p, idx, n * 8, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(fr_gather_proofs_kernel, dim3(n), dim3(64), 0, nullptr, t->d_elements, t->nodes.u(), t->width, t->height,
-                           t->depth, d_idx.u(), d_out.u());
-        ZK_HIP(hipGetLastError());
-        std::vector<u64> h(std::max<size_t>(1, per * n));
-        ZK_HIP(hipMemcpy(h.data(), d_out.p, per * n * 8, hipMemcpyDeviceToHost));
-        for (uint32_t q = 0; q < n; ++q) {
-            memcpy(rows_out + (size_t)q * t->width, h.data() + q * per, (size_t)t->width * 8);
-            if (t->depth) memcpy(paths_out + (size_t)q * 64 * t->depth, h.data() + q * per + t->width, (size_t)t->depth * 512);
-        }
-    });
-}
-// put (transcript_bn128.rs:90-101): n == 1 -> a Goldilocks value, n == 4 -> a digest (raw limbs); anything else is an error
-int fr_transcript_put(FrTranscript* t, const uint64_t* e, size_t n) {
-    return guard([&] {
-        ZK_REQUIRE(t && e, "null argument");
-        if (n == 1) {
-            const uint64_t x[4] = {e[0], 0, 0, 0}; uint64_t m[4];
-            fr_mont_mul_host(*t->F, x, t->F->R2, m);
-            fr_tr_add1(t, m);
-        } else if (n == 4) fr_tr_add1(t, e);
-        else throw Error("Invalid elements as inputs to transcript");
-    });
-}
-int fr_transcript_get_fields1(FrTranscript* t, uint64_t* out) {   // :71-88
-    return guard([&] {
-        ZK_REQUIRE(t && out, "null argument");
-        for (;;) {
-            if (t->out3_pos < t->n_out3) { *out = t->out3[t->out3_pos++]; return; }
-            if (t->out_pos < t->n_out) {
-                uint64_t c[4];
-                fr_tr_get253(t, c);
-                for (int i = 0; i < 3; ++i) t->out3[i] = c[i] % GL_P;   // biguint_to_be (helper.rs:61-65)
-                t->out3_pos = 0; t->n_out3 = 3;
-                continue;
-            }
-            fr_tr_update(t);
-        }
-    });
-}
-int fr_transcript_get_permutations(FrTranscript* t, uint32_t n, uint32_t nbits, uint64_t* out) {   // :103-131
-    return guard([&] {
-        ZK_REQUIRE(t && out && n >= 1 && nbits >= 1 && nbits <= 63, "bad argument");
-        const uint32_t total = n * nbits, nf = (total - 1) / 253 + 1;
-        std::vector<uint64_t> f(4 * (size_t)nf);
-        for (uint32_t i = 0; i < nf; ++i) fr_tr_get253(t, f.data() + 4 * i);
-        uint32_t cf = 0, cb = 0;
-        for (uint32_t i = 0; i < n; ++i) {
-            uint64_t a = 0;
-            for (uint32_t j = 0; j < nbits; ++j) {
-                if ((f[4 * cf + cb / 64] >> (cb % 64)) & 1) a += (uint64_t)1 << j;
-                if (++cb == 253) { cb = 0; ++cf; }
-            }
-            out[i] = a;
-        }
-    });
-}
-}  // namespace
-
-struct zk_bn128_merkle : FrMerkle {};
-struct zk_bn128_transcript : FrTranscript {};
-struct zk_bls12381_merkle : FrMerkle {};
-struct zk_bls12381_transcript : FrTranscript {};
-
-extern "C" {
-#define ZK_FRHASH_CAPI(P, OPS)                                                                                          \
-    int zk_##P##_load_constants(const char* path) { return guard([&] { ZK_REQUIRE(path, "null path"); OPS.load(path); }); } \
+#define ZK_FRHASH_CAPI(P, F)                                                                                            \
+    int zk_##P##_load_constants(const char* path) { return guard([&] { ZK_REQUIRE(path, "null path"); F.load(path); }); } \
     int zk_##P##_poseidon_selfcheck(const char* path) {                  /* host arithmetic only: no CallScope, no device */ \
         try {                                                                                                           \
             if (!path) { set_error("null path"); return -1; }                                                           \
-            const std::string why = OPS.selfcheck(path);                                                                \
+            const std::string why = F.selfcheck(path);                                                                  \
             if (why.empty()) return 0;                                                                                  \
             set_error(why);                                                                                             \
         } catch (const std::exception& e) { set_error(e.what()); }                                                      \
         return -1;                                                                                                      \
     }                                                                                                                   \
     int zk_##P##_poseidon(const uint64_t* inp, uint32_t n_in, const uint64_t init_state[4], uint32_t n_out, uint64_t* out) { \
-        return fr_poseidon(OPS, inp, n_in, init_state, n_out, out);                                                     \
+        return guard([&] { fr_poseidon(F, inp, n_in, init_state, n_out, out); });                                       \
     }                                                                                                                   \
     int zk_##P##_poseidon_dev(const uint64_t* d_inp, uint64_t n, uint32_t n_in, const uint64_t* d_init_state, uint32_t n_out, \
                               uint64_t* d_out, void* stream) {                                                          \
-        return guard([&] { OPS.poseidon_dev((const u64*)d_inp, n, n_in, (const u64*)d_init_state, n_out, (u64*)d_out, on_stream((hipStream_t)stream)); }); \
+        return guard([&] { F.poseidon_dev((const u64*)d_inp, n, n_in, (const u64*)d_init_state, n_out, (u64*)d_out, on_stream((hipStream_t)stream)); }); \
     }                                                                                                                   \
-    int zk_##P##_linearhash(const uint64_t* v, size_t n, uint64_t out[4]) { return fr_linearhash(OPS, v, n, out); }       \
-    uint64_t zk_##P##_merkle_n_nodes(uint64_t height) { return height ? OPS.n_nodes(height) : 0; }                        \
-    zk_##P##_merkle_t* zk_##P##_merkelize(const uint64_t* buff, uint32_t width, uint64_t height) {                        \
-        return fr_merkelize<zk_##P##_merkle>(OPS, buff, false, width, height, nullptr);                                  \
+    int zk_##P##_linearhash(const uint64_t* v, size_t n, uint64_t out[4]) { return guard([&] { fr_linearhash(F, v, n, out); }); } \
+    uint64_t zk_##P##_merkle_n_nodes(uint64_t height) { return height ? F.n_nodes(height) : 0; }                          \
+    static zk_##P##_merkle_t* P##_merkelize(const uint64_t* buff, bool on_device, uint32_t width, uint64_t height, void* stream) { \
+        std::unique_ptr<zk_##P##_merkle> t;                                                                             \
+        if (guard([&] {                                                                                                 \
+                ZK_REQUIRE(height >= 1, "merkelize: height must be >= 1");                                              \
+                ZK_REQUIRE(buff || width == 0, "merkelize: null buffer");                                               \
+                t.reset(new zk_##P##_merkle);                                                                           \
+                if (on_device) t->build_dev((const u64*)buff, width, height, (hipStream_t)stream); else t->build_host((const u64*)buff, width, height); \
+            }) != 0) return nullptr;                                                                                    \
+        return t.release();                                                                                             \
     }                                                                                                                   \
-    zk_##P##_merkle_t* zk_##P##_merkelize_dev(const uint64_t* d_buff, uint32_t width, uint64_t height, void* stream) {    \
-        return fr_merkelize<zk_##P##_merkle>(OPS, d_buff, true, width, height, stream);                                  \
-    }                                                                                                                   \
-    int zk_##P##_merkle_root(const zk_##P##_merkle_t* t, uint64_t out[4]) { return fr_merkle_root(t, out); }              \
-    int zk_##P##_merkle_nodes(const zk_##P##_merkle_t* t, uint64_t* out) { return fr_merkle_nodes(t, out); }              \
+    zk_##P##_merkle_t* zk_##P##_merkelize(const uint64_t* buff, uint32_t width, uint64_t height) { return P##_merkelize(buff, false, width, height, nullptr); } \
+    zk_##P##_merkle_t* zk_##P##_merkelize_dev(const uint64_t* d_buff, uint32_t width, uint64_t height, void* stream) { return P##_merkelize(d_buff, true, width, height, stream); } \
+    int zk_##P##_merkle_root(const zk_##P##_merkle_t* t, uint64_t out[4]) { return guard([&] { ZK_REQUIRE(t && out, "null argument"); t->root((u64*)out); }); } \
+    int zk_##P##_merkle_nodes(const zk_##P##_merkle_t* t, uint64_t* out) { return guard([&] { ZK_REQUIRE(t && out, "null argument"); t->nodes_host((u64*)out); }); } \
     uint32_t zk_##P##_merkle_depth(const zk_##P##_merkle_t* t) { return t ? t->depth : 0; }                               \
     int zk_##P##_merkle_group_proof(const zk_##P##_merkle_t* t, uint64_t idx, uint64_t* row_out, uint64_t* path_out) {    \
-        return fr_merkle_group_proof(t, idx, row_out, path_out);                                                         \
-    }                                                                                                                    \
+        return guard([&] { ZK_REQUIRE(t && row_out && path_out, "null argument"); t->group_proof(idx, (u64*)row_out, (u64*)path_out); }); \
+    }                                                                                                                   \
     int zk_##P##_merkle_group_proofs(const zk_##P##_merkle_t* t, const uint64_t* idx, uint32_t n, uint64_t* rows_out,     \
                                      uint64_t* paths_out) {                                                              \
-        return fr_merkle_group_proofs(t, idx, n, rows_out, paths_out);                                                   \
+        return guard([&] { ZK_REQUIRE(t && (n == 0 || (idx && rows_out && paths_out)), "null argument"); t->group_proofs((const u64*)idx, n, (u64*)rows_out, (u64*)paths_out); }); \
     }                                                                                                                   \
     int zk_##P##_merkle_free(zk_##P##_merkle_t* t) { return guard([&] { delete t; }); }                                   \
     zk_##P##_transcript_t* zk_##P##_transcript_new(void) {                                                               \
         zk_##P##_transcript* t = nullptr;                                                                               \
-        if (guard([&] { t = new zk_##P##_transcript; t->F = &OPS; }) != 0) return nullptr;                               \
+        if (guard([&] { t = new zk_##P##_transcript; }) != 0) return nullptr;                                            \
         return t;                                                                                                       \
     }                                                                                                                   \
-    int zk_##P##_transcript_put(zk_##P##_transcript_t* t, const uint64_t* e, size_t n) { return fr_transcript_put(t, e, n); } \
-    int zk_##P##_transcript_get_fields1(zk_##P##_transcript_t* t, uint64_t* out) { return fr_transcript_get_fields1(t, out); } \
-    int zk_##P##_transcript_get_field(zk_##P##_transcript_t* t, uint64_t out[3]) {                                        \
-        for (int i = 0; i < 3; ++i) { const int rc = fr_transcript_get_fields1(t, out + i); if (rc) return rc; }         \
-        return 0;                                                                                                       \
+    int zk_##P##_transcript_put(zk_##P##_transcript_t* t, const uint64_t* e, size_t n) {   /* transcript_bn128.rs:90-101: a Goldilocks value or a digest */ \
+        return guard([&] {                                                                                              \
+            ZK_REQUIRE(t && e, "null argument");                                                                        \
+            if (n == 1) t->put_words((const u64*)e, 1); else if (n == 4) t->put_digest((const u64*)e);                  \
+            else throw Error("Invalid elements as inputs to transcript");                                               \
+        });                                                                                                             \
     }                                                                                                                   \
+    int zk_##P##_transcript_get_fields1(zk_##P##_transcript_t* t, uint64_t* out) { return guard([&] { ZK_REQUIRE(t && out, "null argument"); t->get((u64*)out, 1); }); } \
+    int zk_##P##_transcript_get_field(zk_##P##_transcript_t* t, uint64_t out[3]) { return guard([&] { ZK_REQUIRE(t && out, "null argument"); t->get((u64*)out, 3); }); } \
     int zk_##P##_transcript_get_permutations(zk_##P##_transcript_t* t, uint32_t n, uint32_t nbits, uint64_t* out) {       \
-        return fr_transcript_get_permutations(t, n, nbits, out);                                                         \
+        return guard([&] { ZK_REQUIRE(t && out, "bad argument"); t->get_permutations(n, nbits, (u64*)out); });          \
     }                                                                                                                   \
     int zk_##P##_transcript_free(zk_##P##_transcript_t* t) { return guard([&] { delete t; }); }
-ZK_FRHASH_CAPI(bn128, FR_BN128)
-ZK_FRHASH_CAPI(bls12381, FR_BLS12381)
+ZK_FRHASH_CAPI(bn128, (*fr_field(HASH_BN128)))
+ZK_FRHASH_CAPI(bls12381, (*fr_field(HASH_BLS12381)))
 #undef ZK_FRHASH_CAPI
 
 int zk_stark_get_pol_dev(const uint64_t* d_buf, uint64_t width, uint64_t offset, uint32_t dim, uint64_t n, uint64_t* d_out3, void* stream) {
@@ -929,9 +469,6 @@ int zk_stark_calculate_z_dev(const uint64_t* d_num3, const uint64_t* d_den3, uin
     });
 }
 
-const uint64_t* zk_merkle_elements_dev(const zk_merkle_t* t) { return t ? (const uint64_t*)t->d_elements : nullptr; }
-const uint64_t* zk_merkle_nodes_dev(const zk_merkle_t* t) { return t ? (const uint64_t*)t->nodes.p : nullptr; }
-int zk_merkle_free(zk_merkle_t* t) { delete t; return 0; }
 
 #define ZK_MSM_TABLE_API(NAME)                                                                                              \
     size_t zk_msm_##NAME##_table_bytes(uint64_t table_n) { return msm_##NAME##_fixed_table_bytes(table_n); }                \

@@ -10,6 +10,7 @@
 // (types.rs): the reference's PIL front end and code generator stay in charge of them.
 // calculate_H1H2 (stark_gen.rs:624-651), a host step in the reference, runs on the device as well (calculate_h1h2_dev, stark.hip).
 #include "zk_internal.h"
+#include "commit.h"
 #include "../../include/zkgpu.h"
 #include "json_min.h"
 #include <algorithm>
@@ -38,110 +39,34 @@ int slot_of(const std::string& s) {
     return -1;  // e.g. cm4_n: listed by the map, never materialised by the prover (an error only if used)
 }
 
-void ck(int rc) { if (rc != 0) throw Error(zk_last_error()); }
+void ck(int rc) { if (rc != 0) throw Error(zk_last_error()); }   // (the evaluator's and calculate_H1H2's entry points)
 // the C ABI speaks uint64_t (unsigned long), the kernels u64 (unsigned long long): same 8 bytes
 inline uint64_t* M(u64* p) { return reinterpret_cast<uint64_t*>(p); }
 inline const uint64_t* C(const u64* p) { return reinterpret_cast<const uint64_t*>(p); }
 inline const u64* K(const uint64_t* p) { return reinterpret_cast<const u64*>(p); }
-
-u64 parse_pil_number(const std::string& s) {  // types.rs:221-233: decimal or 0x hex, possibly negative, mod p
-    bool neg = !s.empty() && s[0] == '-';
-    size_t i = neg ? 1 : 0;
-    unsigned __int128 v = 0;
-    if (s.size() > i + 1 && s[i] == '0' && (s[i + 1] == 'x' || s[i + 1] == 'X')) {
-        for (i += 2; i < s.size(); ++i) {
-            const char c = s[i];
-            const int d = c >= '0' && c <= '9' ? c - '0' : c >= 'a' && c <= 'f' ? c - 'a' + 10 : c >= 'A' && c <= 'F' ? c - 'A' + 10 : -1;
-            if (d < 0) throw Error("bad PIL number " + s);
-            v = (v * 16 + d) % GL_P;
-        }
-    } else {
-        for (; i < s.size(); ++i) {
-            if (s[i] < '0' || s[i] > '9') throw Error("bad PIL number " + s);
-            v = (v * 10 + (s[i] - '0')) % GL_P;
-        }
-    }
-    u64 r = (u64)v;
-    return neg && r ? GL_P - r : r;
-}
 
 struct PolRef { int slot; u64 width; u64 pos; u32 dim; };
 
 struct ProgramDeleter { void operator()(zk_program_t* p) const { if (p) zk_program_free(p); } };
 using ProgramPtr = std::unique_ptr<zk_program_t, ProgramDeleter>;
 // The two instantiations of the reference's generics: StarkProof<MerkleTreeGL>::stark_gen::<TranscriptGL> and
-// StarkProof<MerkleTreeBN128>::stark_gen::<TranscriptBN128> (prove.rs:47-91), chosen by verificationHashType.
-// the scalar-field variants through their (twin) C entry points
-struct FrApi {
-    const char* name;
-    u64 R[4], INV;                                   // modulus and -r^-1 mod 2^64: digests print as canonical decimals
-    void* (*merkelize_dev)(const uint64_t*, uint32_t, uint64_t, void*);
-    int (*root)(const void*, uint64_t*);
-    uint32_t (*depth)(const void*);
-    int (*group_proof)(const void*, uint64_t, uint64_t*, uint64_t*);
-    int (*group_proofs)(const void*, const uint64_t*, uint32_t, uint64_t*, uint64_t*);
-    int (*tree_free)(void*);
-    void* (*tr_new)(void);
-    int (*tr_put)(void*, const uint64_t*, size_t);
-    int (*tr_get_field)(void*, uint64_t*);
-    int (*tr_get_permutations)(void*, uint32_t, uint32_t, uint64_t*);
-    int (*tr_free)(void*);
-};
-#define ZK_FR_API(P, R0, R1, R2, R3, INV)                                                                                     \
-    {#P, {R0, R1, R2, R3}, INV,                                                                                               \
-     [](const uint64_t* d, uint32_t w, uint64_t h, void* st) -> void* { return zk_##P##_merkelize_dev(d, w, h, st); },          \
-     [](const void* t, uint64_t* o) { return zk_##P##_merkle_root((const zk_##P##_merkle_t*)t, o); },                           \
-     [](const void* t) { return zk_##P##_merkle_depth((const zk_##P##_merkle_t*)t); },                                          \
-     [](const void* t, uint64_t i, uint64_t* r, uint64_t* p) { return zk_##P##_merkle_group_proof((const zk_##P##_merkle_t*)t, i, r, p); }, \
-     [](const void* t, const uint64_t* i, uint32_t n, uint64_t* r, uint64_t* p) { return zk_##P##_merkle_group_proofs((const zk_##P##_merkle_t*)t, i, n, r, p); }, \
-     [](void* t) { return zk_##P##_merkle_free((zk_##P##_merkle_t*)t); },                                                       \
-     []() -> void* { return zk_##P##_transcript_new(); },                                                                       \
-     [](void* t, const uint64_t* e, size_t n) { return zk_##P##_transcript_put((zk_##P##_transcript_t*)t, e, n); },             \
-     [](void* t, uint64_t* o) { return zk_##P##_transcript_get_field((zk_##P##_transcript_t*)t, o); },                          \
-     [](void* t, uint32_t n, uint32_t b, uint64_t* o) { return zk_##P##_transcript_get_permutations((zk_##P##_transcript_t*)t, n, b, o); }, \
-     [](void* t) { return zk_##P##_transcript_free((zk_##P##_transcript_t*)t); }}
-const FrApi FR_BN128 = ZK_FR_API(bn128, 0x43e1f593f0000001ULL, 0x2833e84879b97091ULL, 0xb85045b68181585dULL, 0x30644e72e131a029ULL, 0xc2e1f593efffffffULL);
-const FrApi FR_BLS12381 = ZK_FR_API(bls12381, 0xffffffff00000001ULL, 0x53bda402fffe5bfeULL, 0x3339d80809a1d805ULL, 0x73eda753299d7d48ULL, 0xfffffffeffffffffULL);
-#undef ZK_FR_API
-
-struct AnyTree {
-    zk_merkle_t* gl = nullptr; const FrApi* F = nullptr; void* fr = nullptr;
-    u32 width = 0; u64 height = 0;
-    AnyTree(const FrApi* f, const u64* d_rows, u32 w, u64 h, hipStream_t st) : F(f), width(w), height(h) {
-        if (F) fr = F->merkelize_dev(C(d_rows), w, h, st); else gl = zk_gl_merkelize_dev(C(d_rows), w, h, st);
-        if (!gl && !fr) throw Error(zk_last_error());
-    }
-    bool owned = true;
-    AnyTree(const zk_merkle_t* callers, u32 w, u64 h) : gl(const_cast<zk_merkle_t*>(callers)), width(w), height(h), owned(false) {}   // a caller's MerkleTreeGL, borrowed
-    AnyTree(const AnyTree&) = delete; AnyTree& operator=(const AnyTree&) = delete;
-    ~AnyTree() { if (!owned) return; if (gl) zk_merkle_free(gl); if (fr) F->tree_free(fr); }
-    void root(u64* out) const { ck(gl ? zk_merkle_root(gl, M(out)) : F->root(fr, M(out))); }
-    const u64* root_dev() const { return gl ? K(zk_merkle_nodes_dev(gl)) + 4 * (zk_merkle_n_nodes(height) - 1) : nullptr; }   // last node (merklehash.rs:455-457)
-    u32 depth() const { return gl ? zk_merkle_depth(gl) : F->depth(fr); }
-    u32 level_words() const { return gl ? 4 : 64; }   // one sibling digest, or the 16 digests of the group
-};
-using TreePtr = std::shared_ptr<AnyTree>;       // shared: a setup lends its all-zero tree to every proof
+// StarkProof<MerkleTreeBN128>::stark_gen::<TranscriptBN128> (prove.rs:47-91), chosen by verificationHashType: the trees and
+// transcripts of commit.h.
+using TreePtr = std::shared_ptr<const Tree>;       // shared: a setup lends its all-zero tree to every proof
 struct AnyTranscript {
-    zk_transcript_t* gl = nullptr; const FrApi* F = nullptr; void* fr = nullptr;
-    bool owned = true;
-    explicit AnyTranscript(const FrApi* f) : F(f) {
-        if (F) fr = F->tr_new(); else gl = zk_transcript_new();
-        if (!gl && !fr) throw Error(zk_last_error());
-    }
-    explicit AnyTranscript(zk_transcript_t* callers) : gl(callers), owned(false) { ZK_REQUIRE(gl != nullptr, "null transcript"); }   // a caller's TranscriptGL, borrowed
+    std::unique_ptr<Transcript> own;                   // empty: a caller's TranscriptGL, borrowed
+    Transcript* t; GlTranscript* gl;                   // gl: the sponge in device memory (deferred puts, squeezes into HBM), or nullptr
+    explicit AnyTranscript(HashType h) : own(new_transcript(h)), t(own.get()), gl(t->gl()) {}
+    explicit AnyTranscript(zk_transcript_t* callers) : t(callers), gl(callers) { ZK_REQUIRE(callers != nullptr, "null transcript"); }
     AnyTranscript(const AnyTranscript&) = delete; AnyTranscript& operator=(const AnyTranscript&) = delete;
-    ~AnyTranscript() {
-        if (!owned) { if (gl && pend_n) (void)zk_transcript_put_dev(gl, C(pend_src), pend_n, pend_st); return; }   // (a borrowed sponge must not lose an absorbed word)
-        if (gl) zk_transcript_free(gl);
-        if (fr) F->tr_free(fr);
-    }
+    ~AnyTranscript() { if (!own) try { flush(); } catch (...) {} }   // (a borrowed sponge must not lose an absorbed word)
     // Goldilocks sponge: a put is DEFERRED until the next squeeze and rides in its launch (tr_put_get_kernel) -- "absorb a root, draw two
     // challenges" is one launch instead of three.  The absorbed words must stay in HBM until then: they are roots inside live trees, the
     // context's evaluations / publics, the last FRI polynomial.  Two puts in a row, or the end of the object, flush as a plain put.
     const u64* pend_src = nullptr; size_t pend_n = 0; hipStream_t pend_st = nullptr;
     void flush() {
         if (!pend_n) return;
-        ck(zk_transcript_put_dev(gl, C(pend_src), pend_n, pend_st));
+        gl->put_dev(pend_src, pend_n, pend_st);
         pend_n = 0;
     }
     void defer(const u64* d, size_t n, hipStream_t st) { flush(); pend_src = d; pend_n = n; pend_st = st; }
@@ -152,24 +77,24 @@ struct AnyTranscript {
         std::vector<u64> h(n);
         ZK_HIP(hipStreamSynchronize(st));
         ZK_HIP(hipMemcpy(h.data(), d, 8 * n, hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < n; ++i) ck(F->tr_put(fr, M(&h[i]), 1));
+        t->put_words(h.data(), n);
     }
-    void put_root(const AnyTree& t, hipStream_t st) {   // a digest is ONE element of the scalar-field transcripts
-        if (gl) { defer(K(zk_merkle_nodes_dev(t.gl)) + 4 * (zk_merkle_n_nodes(t.height) - 1), 4, st); return; }
-        u64 r[4]; t.root(r);
-        ck(F->tr_put(fr, M(r), 4));
+    void put_root(const Tree& tree, hipStream_t st) {   // a digest is ONE element of the scalar-field transcripts
+        if (gl) { defer(tree.gl()->root_dev(), 4, st); return; }
+        u64 r[4]; tree.root(r);
+        t->put_digest(r);
     }
     // n_fields consecutive get_field()s into d_out (3 words each)
     void get_fields_dev(u64* d_out, u32 n_fields, hipStream_t st) {
         if (gl) {
             if (pend_n) ZK_REQUIRE(pend_st == st, "transcript: a deferred put moved streams");
-            transcript_put_get_async(gl, pend_src, pend_n, d_out, 3 * n_fields, 0, st);
+            gl->put_get_async(pend_src, pend_n, d_out, 3 * n_fields, 0, st);
             pend_n = 0;
             return;
         }
         for (u32 k = 0; k < n_fields; ++k) {
             u64 f[3];
-            ck(F->tr_get_field(fr, M(f)));
+            t->get(f, 3);
             ZK_HIP(hipMemcpy(d_out + 3 * k, f, 24, hipMemcpyHostToDevice));
         }
     }
@@ -177,13 +102,10 @@ struct AnyTranscript {
     void get_permutations_dev(u32 n, u32 nbits, u64* d_out, hipStream_t st) {   // Goldilocks transcript only: the indices stay in HBM
         ZK_REQUIRE(gl != nullptr, "get_permutations_dev: scalar-field transcripts keep their sponge on the host");
         ZK_REQUIRE(nbits >= 1 && nbits <= 63, "get_permutations: nbits out of range");
-        transcript_put_get_async(gl, pend_src, pend_n, d_out, n, nbits, st);
+        gl->put_get_async(pend_src, pend_n, d_out, n, nbits, st);
         pend_n = 0;
     }
-    void get_permutations(u32 n, u32 nbits, u64* out) {
-        if (gl) flush();
-        ck(gl ? zk_transcript_get_permutations(gl, n, nbits, M(out)) : F->tr_get_permutations(fr, n, nbits, M(out)));
-    }
+    void get_permutations(u32 n, u32 nbits, u64* out) { flush(); t->get_permutations(n, nbits, out); }
 };
 
 struct GroupProof { std::vector<u64> row; std::vector<u64> path; u32 depth; };
@@ -244,7 +166,8 @@ struct zk_stark_setup {
     std::vector<u64> cm_n, cm_2ns, tmpexp_n;
     std::map<u64, u64> exp2pol;
     DevBuf const_n, const_2ns;
-    const FrApi* fr = nullptr;             // verificationHashType "BN128" / "BLS12381"; nullptr = "GL"
+    HashType hash = HASH_GL;               // verificationHashType
+    const FrField* fr = nullptr;           // its scalar field ("BN128" / "BLS12381"); nullptr = "GL"
     std::string prover_addr;               // StarkProof.prover_addr (serializer.rs:255-262), non-GL proofs only
     bool self_check = false;               // verify every proof before handing it out, as stark_prove does (prove.rs:124-132)
     TreePtr const_tree;
@@ -367,43 +290,9 @@ struct JOut {
     JOut& operator<<(size_t v) { return *this << Dec{(u64)v}; }
     std::string str() { return std::move(s); }
 };
-// a BN128 digest holds the raw Montgomery limbs of an Fr; JSON carries its canonical value in decimal
-// (digest.rs:91-94 -> helper::fr_to_biguint)
-std::string fr_raw_to_dec(const FrApi& F, const u64* raw) {
-    typedef unsigned __int128 u128;
-    const u64* RM = F.R;
-    const u64 INV = F.INV;
-    u64 t[5] = {raw[0], raw[1], raw[2], raw[3], 0};     // Montgomery reduction: raw / 2^256 mod r (into_repr)
-    for (int i = 0; i < 4; ++i) {
-        const u64 m = t[0] * INV;
-        u128 c = ((u128)m * RM[0] + t[0]) >> 64;
-        for (int j = 1; j < 4; ++j) { c += (u128)m * RM[j] + t[j]; t[j - 1] = (u64)c; c >>= 64; }
-        c += t[4]; t[3] = (u64)c; t[4] = (u64)(c >> 64);
-    }
-    for (;;) {                                           // canonical: < r
-        bool ge = t[4] != 0;
-        if (!ge) { ge = true; for (int i = 3; i >= 0; --i) { if (t[i] > RM[i]) break; if (t[i] < RM[i]) { ge = false; break; } } }
-        if (!ge) break;
-        u128 br = 0;
-        for (int i = 0; i < 4; ++i) { u128 d = (u128)t[i] - RM[i] - br; t[i] = (u64)d; br = (d >> 64) & 1; }
-        t[4] -= (u64)br;
-    }
-    u64 v[4] = {t[0], t[1], t[2], t[3]};
-    std::string out;
-    for (;;) {                                           // repeated division by 10^18
-        bool zero = !(v[0] | v[1] | v[2] | v[3]);
-        if (zero) break;
-        u128 rem = 0;
-        for (int i = 3; i >= 0; --i) { u128 cur = (rem << 64) | v[i]; v[i] = (u64)(cur / 1000000000000000000ULL); rem = cur % 1000000000000000000ULL; }
-        std::string chunk = std::to_string((u64)rem);
-        const bool last = !(v[0] | v[1] | v[2] | v[3]);
-        if (!last) chunk = std::string(18 - chunk.size(), '0') + chunk;
-        out = chunk + out;
-    }
-    return out.empty() ? "0" : out;
-}
-void put_digest(JOut& o, const u64* d, const FrApi* fr) {  // digest.rs:84-112
-    if (fr) { o << '"' << fr_raw_to_dec(*fr, d) << '"'; return; }
+// a scalar-field digest travels as the decimal of its canonical value, a GL digest as its words (digest.rs:84-112)
+void put_digest(JOut& o, const u64* d, const FrField* fr) {
+    if (fr) { o << '"' << fr->to_dec(d) << '"'; return; }
     if (d[1] == 0 && d[2] == 0 && d[3] == 0) { o << '"' << dec(d[0]) << '"'; return; }
     o << "[\"" << dec(d[0]) << "\",\"" << dec(d[1]) << "\",\"" << dec(d[2]) << "\",\"" << dec(d[3]) << "\"]";
 }
@@ -412,29 +301,28 @@ void put_list(JOut& o, const u64* v, size_t n) {
     for (size_t i = 0; i < n; ++i) { if (i) o << ','; o << '"' << dec(v[i]) << '"'; }
     o << ']';
 }
-void put_path(JOut& o, const GroupProof& g, const FrApi* fr) {
+void put_path(JOut& o, const GroupProof& g, const FrField* fr) {
     o << '[';
     for (u32 l = 0; l < g.depth; ++l) {
         if (l) o << ',';
         if (!fr) { put_list(o, g.path.data() + 4 * l, 4); continue; }
         o << '[';                                        // the 16 nodes of the group, each an Fr (merklehash_bn128.rs:86-106)
-        for (int k = 0; k < 16; ++k) { if (k) o << ','; o << '"' << fr_raw_to_dec(*fr, g.path.data() + 64 * l + 4 * k) << '"'; }
+        for (int k = 0; k < 16; ++k) { if (k) o << ','; o << '"' << fr->to_dec(g.path.data() + 64 * l + 4 * k) << '"'; }
         o << ']';
     }
     o << ']';
 }
 
 // the openings of one tree at every query index, one round trip (fri.rs:160-181)
-std::vector<GroupProof> group_proofs(const AnyTree& t, const std::vector<u64>& idx) {
-    const u32 n = (u32)idx.size(), depth = t.depth(), lw = t.level_words();
-    std::vector<u64> rows(std::max<size_t>(1, (size_t)n * t.width)), paths(std::max<size_t>(1, (size_t)n * lw * depth));
-    ck(t.gl ? zk_merkle_group_proofs(t.gl, C(idx.data()), n, M(rows.data()), M(paths.data()))
-            : t.F->group_proofs(t.fr, C(idx.data()), n, M(rows.data()), M(paths.data())));
+std::vector<GroupProof> group_proofs(const Tree& t, const std::vector<u64>& idx) {
+    const u32 n = (u32)idx.size(), lw = t.level_words();
+    std::vector<u64> rows(std::max<size_t>(1, (size_t)n * t.width)), paths(std::max<size_t>(1, (size_t)n * lw * t.depth));
+    t.group_proofs(idx.data(), n, rows.data(), paths.data());
     std::vector<GroupProof> out(n);
     for (u32 q = 0; q < n; ++q) {
-        out[q].depth = depth;
+        out[q].depth = t.depth;
         out[q].row.assign(rows.begin() + (size_t)q * t.width, rows.begin() + (size_t)(q + 1) * t.width);
-        out[q].path.assign(paths.begin() + (size_t)q * lw * depth, paths.begin() + (size_t)(q + 1) * lw * depth);
+        out[q].path.assign(paths.begin() + (size_t)q * lw * t.depth, paths.begin() + (size_t)(q + 1) * lw * t.depth);
     }
     return out;
 }
@@ -497,46 +385,6 @@ struct ReadBack {
     const u64* at(size_t off) const { return host.data() + off; }
 };
 
-// the openings of several trees, tree j at the indices idx[j]: for GL trees one upload of the indices, one gather launch per
-// tree and one copy back for all of them (fri.rs:160-181, stark_gen.rs:525-557)
-std::vector<std::vector<GroupProof>> group_proofs_all(const std::vector<const AnyTree*>& trees, const std::vector<const std::vector<u64>*>& idx, hipStream_t st) {
-    std::vector<std::vector<GroupProof>> out(trees.size());
-    size_t n_idx = 0, n_out = 0;
-    for (size_t j = 0; j < trees.size(); ++j) {
-        if (!trees[j]->gl) { out[j] = group_proofs(*trees[j], *idx[j]); continue; }     // scalar-field trees: one round trip each
-        for (u64 y : *idx[j]) ZK_REQUIRE(y < trees[j]->height, "MerkleTreeError: access invalid node");
-        n_idx += idx[j]->size(); n_out += idx[j]->size() * ((size_t)trees[j]->width + 4 * (size_t)trees[j]->depth());
-    }
-    if (n_idx == 0) return out;
-    std::vector<u64> h_idx; h_idx.reserve(n_idx);
-    for (size_t j = 0; j < trees.size(); ++j) if (trees[j]->gl) h_idx.insert(h_idx.end(), idx[j]->begin(), idx[j]->end());
-    DevBuf d_idx; d_idx.reserve(n_idx * 8);
-    ZK_HIP(hipMemcpyAsync(d_idx.p, h_idx.data(), n_idx * 8, hipMemcpyHostToDevice, st));
-    ReadBack rb(n_out, st);
-    std::vector<size_t> offs(trees.size(), 0);
-    size_t i0 = 0;
-    for (size_t j = 0; j < trees.size(); ++j) {
-        if (!trees[j]->gl) continue;
-        const u32 n = (u32)idx[j]->size();
-        const size_t per = (size_t)trees[j]->width + 4 * (size_t)trees[j]->depth();
-        offs[j] = rb.words;
-        merkle_group_proofs_async(trees[j]->gl, d_idx.u() + i0, n, rb.reserve(per * n), st);
-        i0 += n;
-    }
-    rb.fetch();                                          // also orders the upload of h_idx before it goes out of scope
-    for (size_t j = 0; j < trees.size(); ++j) {
-        if (!trees[j]->gl) continue;
-        const u32 n = (u32)idx[j]->size(), depth = trees[j]->depth(), w = trees[j]->width;
-        const size_t per = (size_t)w + 4 * (size_t)depth;
-        out[j].resize(n);
-        for (u32 q = 0; q < n; ++q) {
-            const u64* p = rb.at(offs[j] + q * per);
-            out[j][q].depth = depth; out[j][q].row.assign(p, p + w); out[j][q].path.assign(p + w, p + per);
-        }
-    }
-    return out;
-}
-
 zk_stark_setup* setup_new(const char* json, const char* ss_json, const uint64_t* const_pols, uint64_t n_words) {
     std::unique_ptr<zk_stark_setup> S(new zk_stark_setup);
     using clk = std::chrono::steady_clock;
@@ -548,9 +396,8 @@ zk_stark_setup* setup_new(const char* json, const char* ss_json, const uint64_t*
     const JVal& I = S->info;
     S->nbits = (u32)S->ss.at("nBits").u64(); S->nbits_ext = (u32)S->ss.at("nBitsExt").u64();
     S->n_queries = (u32)S->ss.at("nQueries").u64();
-    const std::string& hash_type = S->ss.at("verificationHashType").str();
-    ZK_REQUIRE(hash_type == "GL" || hash_type == "BN128" || hash_type == "BLS12381", "verificationHashType must be GL, BN128 or BLS12381");
-    S->fr = hash_type == "BN128" ? &FR_BN128 : hash_type == "BLS12381" ? &FR_BLS12381 : nullptr;
+    S->hash = hash_type_of(S->ss.at("verificationHashType").str());
+    S->fr = fr_field(S->hash);
     ZK_REQUIRE(S->nbits >= 1 && S->nbits <= S->nbits_ext && S->nbits_ext <= 32, "bad nBits / nBitsExt");
     for (const JVal& st : S->ss.at("steps").arr) S->steps.push_back((u32)st.at("nBits").u64());
     ZK_REQUIRE(!S->steps.empty(), "starkStruct without FRI steps");
@@ -626,7 +473,7 @@ zk_stark_setup* setup_new(const char* json, const char* ss_json, const uint64_t*
         lde_dev(S->const_n.u(), S->const_2ns.u(), tmp.u(), (u32)nc, S->nbits, S->nbits_ext, nullptr);
         ZK_HIP(hipStreamSynchronize(nullptr));
     }
-    S->const_tree.reset(new AnyTree(S->fr, S->const_2ns.u(), (u32)nc, Next, nullptr));
+    S->const_tree = build_tree(S->hash, S->const_2ns.u(), (u32)nc, Next, nullptr);
     S->const_tree->root(S->const_root);                    // (copies the root back: the tree is built when this returns)
     {   // what every proof of this setup would otherwise rebuild: the two x tables, 1 / Z_H, and the tree of an empty section
         const u32 ext = S->nbits_ext - S->nbits;
@@ -634,7 +481,7 @@ zk_stark_setup* setup_new(const char* json, const char* ss_json, const uint64_t*
         x_table_dev(S->nbits, 1, S->x_n.u(), nullptr); x_table_dev(S->nbits_ext, 49, S->x_2ns.u(), nullptr); zh_inv_dev(S->nbits, ext, S->zi.u(), nullptr);
         bool any_empty = false;
         for (int sec : {S_CM1_N, S_CM2_N, S_CM3_N}) any_empty |= S->sN[sec] == 0;
-        if (any_empty) S->zero_tree.reset(new AnyTree(S->fr, nullptr, 0, Next, nullptr));
+        if (any_empty) S->zero_tree = build_tree(S->hash, nullptr, 0, Next, nullptr);
         ZK_HIP(hipStreamSynchronize(nullptr));
     }
     {
@@ -703,7 +550,7 @@ struct FriState {
     std::vector<u64> ys;
     DevBuf d_ys, d_sx;
     std::vector<std::unique_ptr<DevBuf>> keep;
-    void commit(AnyTranscript& tr, const FrApi* bn128, const u64* d_f, u32 nbits_ext, const std::vector<u32>& steps, u32 n_queries, hipStream_t st, StageTimer* T) {
+    void commit(AnyTranscript& tr, HashType hash, const u64* d_f, u32 nbits_ext, const std::vector<u32>& steps, u32 n_queries, hipStream_t st, StageTimer* T) {
         const size_t n_steps = steps.size();
         u32 pol_bits = nbits_ext;
         u64 shift_inv = gl::hinv(49);
@@ -724,7 +571,7 @@ struct FriState {
                 keep.emplace_back(new DevBuf); DevBuf& tb = *keep.back(); tb.reserve((3ull << step_bits) * 8);
                 fri_transpose_dev(d_pol, 1ull << step_bits, nxt, tb.u(), st);
                 width[si] = (u32)(3 * group_size);
-                trees[si].reset(new AnyTree(bn128, tb.u(), width[si], n_groups, st));
+                trees[si] = build_tree(hash, tb.u(), width[si], n_groups, st);
                 tr.put_root(*trees[si], st);                                           // (its words are read for the JSON below)
             } else {
                 tr.put_words_dev(d_pol, 3ull << step_bits, st);                         // fri.rs:136-141
@@ -738,7 +585,7 @@ struct FriState {
         // brings back roots, evaluations, the last polynomial, the publics, the indices and all openings -- one host round trip where
         // the indices, the proof's words and the openings used to be three.  Scalar-field hashing keeps its host-side sponge and trees.
         ys.assign(n_queries, 0);
-        if (!bn128) { d_ys.reserve(std::max<u32>(1, n_queries) * 8); tr.get_permutations_dev(n_queries, steps[0], d_ys.u(), st); }
+        if (tr.gl) { d_ys.reserve(std::max<u32>(1, n_queries) * 8); tr.get_permutations_dev(n_queries, steps[0], d_ys.u(), st); }
         else tr.get_permutations(n_queries, steps[0], ys.data());
         if (T) T->mark("fri_query_indices");
     }
@@ -766,7 +613,7 @@ struct zk_stark_ctx {
     u32 n_ev = 0, n_pub = 0;
     std::vector<u64> publics;
     bool pub_on_device = false;
-    const FrApi* bn128;
+    const FrField* const fr;                              // the scalar field of the proof's hashes; nullptr: Goldilocks (openings and sponge stay in device memory)
     std::unique_ptr<AnyTranscript> tr;
     std::vector<std::unique_ptr<DevBuf>> keep;            // workspaces alive until the end
     TreePtr tree[4];
@@ -791,7 +638,7 @@ struct zk_stark_ctx {
 
     zk_stark_ctx(zk_stark_setup& s, const uint64_t* cm_pols, const u64* d_cm, uint64_t n_words, hipStream_t stream)
         : S(s), st(stream), T((on_stream(stream), stream)), I(s.info), nbits(s.nbits), nbits_ext(s.nbits_ext), ext(s.nbits_ext - s.nbits),
-          N(1ull << s.nbits), Next(1ull << s.nbits_ext), sN(s.sN), bn128(s.fr) {
+          N(1ull << s.nbits), Next(1ull << s.nbits_ext), sN(s.sN), fr(s.fr) {
         ZK_REQUIRE(n_words == N * sN[S_CM1_N], "cm trace size mismatch");
         ClearList clear_list(st); clr = &clear_list;
         // sections (stark_gen.rs:204-229); const_n / const_2ns belong to the setup
@@ -871,7 +718,7 @@ struct zk_stark_ctx {
             ZK_HIP(hipStreamSynchronize(st));
             if (!publics.empty()) ZK_HIP(hipMemcpy(d_pub.p, publics.data(), 8 * publics.size(), hipMemcpyHostToDevice));
         }
-        tr.reset(new AnyTranscript(bn128));
+        tr.reset(new AnyTranscript(S.hash));
         tr->put_words_dev(d_pub.u(), n_pub, st);
         T.mark("inputs_publics");
         // the early stage 3 runs on the SETUP's side stream and is ordered by the setup's two events: one live context at a time may use them
@@ -928,7 +775,7 @@ struct zk_stark_ctx {
         }
         T.mark("extend");                                                          // the two halves of extend_and_merkelize (:709, :734)
         if (!width && S.zero_tree) return S.zero_tree;                            // an empty section: every node is the all-zero digest of its level
-        TreePtr t(new AnyTree(bn128, ptr[sec_2ns], (u32)width, Next, st));
+        TreePtr t = build_tree(S.hash, ptr[sec_2ns], (u32)width, Next, st);
         T.mark("merkelize");
         return t;
     }
@@ -991,7 +838,7 @@ struct zk_stark_ctx {
             if (stage3_early) {
                 ZK_HIP(hipStreamWaitEvent(st, S.ev_stage3, 0));                    // cm3_n and its extension are ready
                 T.mark("wait_side_stream");
-                tree[2].reset(new AnyTree(bn128, ptr[S_CM3_2NS], (u32)sN[S_CM3_N], Next, st));
+                tree[2] = build_tree(S.hash, ptr[S_CM3_2NS], (u32)sN[S_CM3_N], Next, st);
                 T.mark("merkelize");
             } else tree[2] = extend_and_merkelize(S_CM3_N, S_CM3_2NS);
         } else {
@@ -1009,7 +856,7 @@ struct zk_stark_ctx {
                 ntt_dev(qq2.u(), ptr[S_CM4_2NS], tmp4.u(), q_dim * q_deg, nbits_ext, false, st);
             }
             T.mark("q_split_ntt");
-            tree[3].reset(new AnyTree(bn128, ptr[S_CM4_2NS], (u32)sN[S_CM4_2NS], Next, st));  // stark_gen.rs:399-405
+            tree[3] = build_tree(S.hash, ptr[S_CM4_2NS], (u32)sN[S_CM4_2NS], Next, st);  // stark_gen.rs:399-405
             T.mark("merkelize");
         }
         tr->put_root(*tree[stage - 1], st);
@@ -1144,7 +991,7 @@ struct zk_stark_ctx {
     void fri_prove() {
         ZK_REQUIRE(ran[STEP_52NS] && !fri_done, "FRI::prove follows step52ns, once");
         on_stream(st);
-        F.commit(*tr, bn128, ptr[S_F_2NS], nbits_ext, S.steps, S.n_queries, st, &T);
+        F.commit(*tr, S.hash, ptr[S_F_2NS], nbits_ext, S.steps, S.n_queries, st, &T);
         fri_done = true;
     }
 
@@ -1158,36 +1005,36 @@ struct zk_stark_ctx {
         const u64 n_last = 1ull << steps.back();
         std::vector<u64> ev_host(3 * (size_t)std::max<u32>(1, n_ev)), last(3 * n_last);
         // the trees a proof opens: the folded polynomials' trees at the reduced indices, then the five trees at ys
-        std::vector<const AnyTree*> all_trees; std::vector<u64> all_mask;
+        std::vector<const Tree*> all_trees; std::vector<u64> all_mask;
         for (size_t si = 1; si < n_steps; ++si) { all_trees.push_back(F.trees[si - 1].get()); all_mask.push_back((1ull << steps[si]) - 1); }
-        for (const AnyTree* t : {tree[0].get(), tree[1].get(), tree[2].get(), tree[3].get(), S.const_tree.get()}) { all_trees.push_back(t); all_mask.push_back((1ull << steps[0]) - 1); }
+        for (const Tree* t : {tree[0].get(), tree[1].get(), tree[2].get(), tree[3].get(), S.const_tree.get()}) { all_trees.push_back(t); all_mask.push_back((1ull << steps[0]) - 1); }
         std::vector<std::vector<GroupProof>> all_gp;
         {
             size_t open_words = 0;
-            if (!bn128) for (const AnyTree* t : all_trees) open_words += (size_t)S.n_queries * ((size_t)t->width + 4 * (size_t)t->depth());
+            if (!fr) for (const Tree* t : all_trees) open_words += (size_t)S.n_queries * ((size_t)t->width + 4 * (size_t)t->depth);
             ReadBack rb(4 * (4 + n_steps) + 3 * (size_t)n_ev + 3 * n_last + 3 * (size_t)n_pub + S.n_queries + open_words + 3 * n_z, st);
-            const AnyTree* t4[4] = {tree[0].get(), tree[1].get(), tree[2].get(), tree[3].get()};
+            const Tree* t4[4] = {tree[0].get(), tree[1].get(), tree[2].get(), tree[3].get()};
             u64* r4p[4] = {r1, r2, r3, r4};
             size_t off_r[4] = {}, off_ev = 0, off_last = 0, off_ys = 0;
             std::vector<size_t> off_fri(n_steps, 0), off_open(all_trees.size(), 0);
-            if (!bn128) {
-                for (int j = 0; j < 4; ++j) off_r[j] = rb.add(t4[j]->root_dev(), 4);
-                for (size_t si = 0; si + 1 < n_steps; ++si) off_fri[si] = rb.add(F.trees[si]->root_dev(), 4);
+            if (!fr) {
+                for (int j = 0; j < 4; ++j) off_r[j] = rb.add(t4[j]->gl()->root_dev(), 4);
+                for (size_t si = 0; si + 1 < n_steps; ++si) off_fri[si] = rb.add(F.trees[si]->gl()->root_dev(), 4);
             }
             off_ev = rb.add(d_evals.u(), 3 * (size_t)n_ev);
             off_last = rb.add(F.d_pol, 3 * n_last);
             const size_t off_z = rb.add(z_checks.u(), 3 * n_z);
             const size_t off_pub = pub_on_device ? rb.add(d_pub.u(), n_pub) : 0, off_ext = pub_on_device ? rb.add(d_pub_ext.u(), 2 * (size_t)n_pub) : 0;
-            if (!bn128) {
+            if (!fr) {
                 off_ys = rb.add(F.d_ys.u(), S.n_queries);
-                std::vector<const zk_merkle_t*> mt; std::vector<u64*> mo;
+                std::vector<const GlTree*> mt; std::vector<u64*> mo;
                 for (size_t j = 0; j < all_trees.size(); ++j) {
-                    const size_t per = (size_t)all_trees[j]->width + 4 * (size_t)all_trees[j]->depth();
+                    const size_t per = (size_t)all_trees[j]->width + 4 * (size_t)all_trees[j]->depth;
                     off_open[j] = rb.words;
-                    mt.push_back(all_trees[j]->gl); mo.push_back(rb.reserve(per * S.n_queries));
+                    mt.push_back(all_trees[j]->gl()); mo.push_back(rb.reserve(per * S.n_queries));
                 }
                 rb.flush();                                   // (the pieces collected so far are copied before the openings' launch is queued: one order on `st`)
-                merkle_group_proofs_multi_async(mt.data(), all_mask.data(), mo.data(), (u32)mt.size(), F.d_ys.u(), S.n_queries, st);   // every tree, one launch
+                GlTree::open_multi_async(mt.data(), all_mask.data(), mo.data(), (u32)mt.size(), F.d_ys.u(), S.n_queries, st);   // every tree, one launch
             }
             rb.fetch();
             for (size_t i = 0; i < n_z; ++i)
@@ -1200,13 +1047,13 @@ struct zk_stark_ctx {
                     ZK_REQUIRE(rb.at(off_ext)[2 * i] == 0 && rb.at(off_ext)[2 * i + 1] == 0,
                                "public " + std::to_string(i) + ": extension-field value (only base-field publics exist in the reference)");
             }
-            if (!bn128) {
+            if (!fr) {
                 for (int j = 0; j < 4; ++j) memcpy(r4p[j], rb.at(off_r[j]), 32);
                 for (size_t si = 0; si + 1 < n_steps; ++si) memcpy(F.roots[si].data(), rb.at(off_fri[si]), 32);
                 if (S.n_queries) memcpy(F.ys.data(), rb.at(off_ys), 8 * (size_t)S.n_queries);
                 all_gp.resize(all_trees.size());
                 for (size_t j = 0; j < all_trees.size(); ++j) {
-                    const u32 depth = all_trees[j]->depth(), w = all_trees[j]->width;
+                    const u32 depth = all_trees[j]->depth, w = all_trees[j]->width;
                     const size_t per = (size_t)w + 4 * (size_t)depth;
                     all_gp[j].resize(S.n_queries);
                     for (u32 q = 0; q < S.n_queries; ++q) {
@@ -1221,30 +1068,31 @@ struct zk_stark_ctx {
             if (n_ev) memcpy(ev_host.data(), rb.at(off_ev), 24 * (size_t)n_ev);
             memcpy(last.data(), rb.at(off_last), 24 * n_last);
         }
-        if (bn128) {   // scalar-field trees: the reduced indices on the host, one round trip per tree
-            std::vector<std::vector<u64>> ysi(all_trees.size(), F.ys);
-            std::vector<const std::vector<u64>*> all_idx;
-            for (size_t j = 0; j < all_trees.size(); ++j) { for (u64& y : ysi[j]) y &= all_mask[j]; all_idx.push_back(&ysi[j]); }
-            all_gp = group_proofs_all(all_trees, all_idx, st);
+        if (fr) {   // scalar-field trees: the reduced indices on the host, one round trip per tree
+            for (size_t j = 0; j < all_trees.size(); ++j) {
+                std::vector<u64> idx = F.ys;
+                for (u64& y : idx) y &= all_mask[j];
+                all_gp.push_back(group_proofs(*all_trees[j], idx));
+            }
         }
         T.mark("openings_readback");
         S.last_timing = T.finish(nbits);
         S.t_json_begin = std::chrono::steady_clock::now();
         JOut o;
-        o << "{\"rootC\":"; put_digest(o, S.const_root, bn128);
-        o << ",\"root1\":"; put_digest(o, r1, bn128); o << ",\"root2\":"; put_digest(o, r2, bn128);
-        o << ",\"root3\":"; put_digest(o, r3, bn128); o << ",\"root4\":"; put_digest(o, r4, bn128);
+        o << "{\"rootC\":"; put_digest(o, S.const_root, fr);
+        o << ",\"root1\":"; put_digest(o, r1, fr); o << ",\"root2\":"; put_digest(o, r2, fr);
+        o << ",\"root3\":"; put_digest(o, r3, fr); o << ",\"root4\":"; put_digest(o, r4, fr);
         o << ",\"evals\":[";
         for (u32 e = 0; e < n_ev; ++e) { if (e) o << ','; put_list(o, ev_host.data() + 3 * e, 3); }
         o << ']';
         // queries of the later steps: group proofs of the folded polynomials (fri.rs:160-181)
         for (size_t si = 1; si < n_steps; ++si) {
             const std::vector<GroupProof>& gp = all_gp[si - 1];
-            o << ",\"s" << si << "_root\":"; put_digest(o, F.roots[si - 1].data(), bn128);
+            o << ",\"s" << si << "_root\":"; put_digest(o, F.roots[si - 1].data(), fr);
             o << ",\"s" << si << "_vals\":[";
             for (size_t q = 0; q < gp.size(); ++q) { if (q) o << ','; put_list(o, gp[q].row.data(), gp[q].row.size()); }
             o << "],\"s" << si << "_siblings\":[";
-            for (size_t q = 0; q < gp.size(); ++q) { if (q) o << ','; put_path(o, gp[q], bn128); }
+            for (size_t q = 0; q < gp.size(); ++q) { if (q) o << ','; put_path(o, gp[q], fr); }
             o << ']';
         }
         {   // step 0: openings of the five trees at the query indices
@@ -1257,7 +1105,7 @@ struct zk_stark_ctx {
             }
             for (int j = 0; j < 5; ++j) {
                 o << ",\"s0_siblings" << names[j] << "\":[";
-                for (size_t q = 0; q < gp[j].size(); ++q) { if (q) o << ','; put_path(o, gp[j][q], bn128); }
+                for (size_t q = 0; q < gp[j].size(); ++q) { if (q) o << ','; put_path(o, gp[j][q], fr); }
                 o << ']';
             }
         }
@@ -1267,7 +1115,7 @@ struct zk_stark_ctx {
             o << ']';
         }
         o << ",\"publics\":"; put_list(o, publics.data(), publics.size());
-        if (bn128) {                                          // serializer.rs:255-262: non-GL proofs carry the prover address
+        if (fr) {                                          // serializer.rs:255-262: non-GL proofs carry the prover address
             o << ",\"proverAddr\":\"";
             for (char c : S.prover_addr) { if (c == '"' || c == '\\') o << '\\'; o << c; }
             o << '"';
@@ -1458,8 +1306,8 @@ char* zk_stark_finish(zk_stark_ctx_t* c) {
 const uint64_t* zk_stark_fri_pol_dev(const zk_stark_ctx_t* c) { return c && c->ran[STEP_52NS] ? C(c->ptr[S_F_2NS]) : nullptr; }
 const zk_merkle_t* zk_stark_tree(const zk_stark_ctx_t* c, int j) {
     if (!c || j < 1 || j > 5) return nullptr;
-    const AnyTree* t = j == 5 ? c->S.const_tree.get() : (j <= c->committed ? c->tree[j - 1].get() : nullptr);
-    return t ? t->gl : nullptr;                           // (scalar-field trees have no zk_merkle_t: NULL)
+    const Tree* t = j == 5 ? c->S.const_tree.get() : (j <= c->committed ? c->tree[j - 1].get() : nullptr);
+    return dynamic_cast<const zk_merkle_t*>(t);           // (scalar-field trees have no zk_merkle_t: NULL)
 }
 int zk_stark_free(zk_stark_ctx_t* c) { return guard([&] { if (c) { on_stream(c->st); pool_defer_begin(); delete c; } }); }
 
@@ -1478,33 +1326,31 @@ char* zk_fri_prove_dev(zk_transcript_t* transcript, const uint64_t* d_pol, uint3
             const std::vector<u32> sv(steps, steps + n_steps);
             FriState F;                                    // declared BEFORE the borrowed transcript: on an exception the transcript goes first and
             AnyTranscript tr(transcript);                  // flushes its deferred put while the buffers it points into (F's) still exist
-            F.commit(tr, nullptr, K(d_pol), nbits_ext, sv, n_queries, st, nullptr);
-            std::vector<std::unique_ptr<AnyTree>> borrowed;
-            std::vector<const AnyTree*> all_trees; std::vector<u64> all_mask;
+            F.commit(tr, HASH_GL, K(d_pol), nbits_ext, sv, n_queries, st, nullptr);
+            std::vector<const Tree*> all_trees; std::vector<u64> all_mask;
             for (size_t si = 1; si < n_steps; ++si) { all_trees.push_back(F.trees[si - 1].get()); all_mask.push_back((1ull << sv[si]) - 1); }
             for (u32 j = 0; j < n_query_trees; ++j) {
                 ZK_REQUIRE(query_trees[j], "zk_fri_prove_dev: null query tree");
-                borrowed.emplace_back(new AnyTree(query_trees[j], merkle_width(query_trees[j]), merkle_height(query_trees[j])));
-                ZK_REQUIRE(borrowed.back()->height >= (1ull << sv[0]), "zk_fri_prove_dev: a query tree is shorter than the first FRI step");
-                all_trees.push_back(borrowed.back().get()); all_mask.push_back((1ull << sv[0]) - 1);
+                ZK_REQUIRE(query_trees[j]->height >= (1ull << sv[0]), "zk_fri_prove_dev: a query tree is shorter than the first FRI step");
+                all_trees.push_back(query_trees[j]); all_mask.push_back((1ull << sv[0]) - 1);
             }
             const u64 n_last = 1ull << sv.back();
             size_t open_words = 0;
-            for (const AnyTree* t : all_trees) open_words += (size_t)n_queries * ((size_t)t->width + 4 * (size_t)t->depth());
+            for (const Tree* t : all_trees) open_words += (size_t)n_queries * ((size_t)t->width + 4 * (size_t)t->depth);
             ReadBack rb(4 * n_steps + 3 * n_last + n_queries + open_words, st);
             std::vector<size_t> off_root(n_steps, 0), off_open(all_trees.size(), 0);
-            for (size_t si = 0; si + 1 < n_steps; ++si) off_root[si] = rb.add(F.trees[si]->root_dev(), 4);
+            for (size_t si = 0; si + 1 < n_steps; ++si) off_root[si] = rb.add(F.trees[si]->gl()->root_dev(), 4);
             const size_t off_last = rb.add(F.d_pol, 3 * n_last), off_ys = rb.add(F.d_ys.u(), n_queries);
-            std::vector<const zk_merkle_t*> mt; std::vector<u64*> mo;
+            std::vector<const GlTree*> mt; std::vector<u64*> mo;
             for (size_t j = 0; j < all_trees.size(); ++j) {
-                const size_t per = (size_t)all_trees[j]->width + 4 * (size_t)all_trees[j]->depth();
+                const size_t per = (size_t)all_trees[j]->width + 4 * (size_t)all_trees[j]->depth;
                 off_open[j] = rb.words;
-                mt.push_back(all_trees[j]->gl); mo.push_back(rb.reserve(per * n_queries));
+                mt.push_back(all_trees[j]->gl()); mo.push_back(rb.reserve(per * n_queries));
             }
-            merkle_group_proofs_multi_async(mt.data(), all_mask.data(), mo.data(), (u32)mt.size(), F.d_ys.u(), n_queries, st);
+            GlTree::open_multi_async(mt.data(), all_mask.data(), mo.data(), (u32)mt.size(), F.d_ys.u(), n_queries, st);
             rb.fetch();
             auto openings = [&](JOut& o, size_t j, bool paths) {
-                const u32 depth = all_trees[j]->depth(), w = all_trees[j]->width;
+                const u32 depth = all_trees[j]->depth, w = all_trees[j]->width;
                 const size_t per = (size_t)w + 4 * (size_t)depth;
                 o << '[';
                 for (u32 q = 0; q < n_queries; ++q) {

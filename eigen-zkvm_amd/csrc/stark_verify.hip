@@ -10,6 +10,7 @@
 // Input = the zkin JSON the prover wrote (serializer.rs:146-261) + the setup's StarkInfo / Program / StarkStruct + the root of the constants.
 // Result: 1 accepted, 0 rejected (zk_last_error() says which check), -1 malformed input or a device error.
 #include "zk_internal.h"
+#include "commit.h"
 #include "../../include/zkgpu.h"
 #include "json_min.h"
 #include <array>
@@ -24,10 +25,6 @@ using namespace zk;
 namespace {
 
 struct Reject { std::string why; };                     // a well-formed proof that does not verify
-
-inline const uint64_t* C(const u64* p) { return reinterpret_cast<const uint64_t*>(p); }
-inline uint64_t* M(u64* p) { return reinterpret_cast<uint64_t*>(p); }
-void ck(int rc) { if (rc != 0) throw Error(zk_last_error()); }
 
 // ---- Goldilocks and its cubic extension on the host (f3g.rs:207-235, 323-449); a base-field value is (a, 0, 0) ----
 inline u64 hadd(u64 a, u64 b) { const unsigned __int128 s = (unsigned __int128)a + b; return (u64)(s >= GL_P ? s - GL_P : s); }
@@ -106,48 +103,16 @@ u64 parse_word(const JVal& v) {                           // a Goldilocks word a
     if (x >> 64) throw Error("zkin: number out of range");
     return (u64)(x % GL_P);                               // FGL::from(u64) reduces
 }
-u64 parse_pil_number(const std::string& s) {              // types.rs:221-233
-    bool neg = !s.empty() && s[0] == '-';
-    size_t i = neg ? 1 : 0;
-    unsigned __int128 v = 0;
-    if (s.size() > i + 1 && s[i] == '0' && (s[i + 1] == 'x' || s[i + 1] == 'X')) {
-        for (i += 2; i < s.size(); ++i) {
-            const char c = s[i];
-            const int d = c >= '0' && c <= '9' ? c - '0' : c >= 'a' && c <= 'f' ? c - 'a' + 10 : c >= 'A' && c <= 'F' ? c - 'A' + 10 : -1;
-            if (d < 0) throw Error("bad PIL number " + s);
-            v = (v * 16 + d) % GL_P;
-        }
-    } else for (; i < s.size(); ++i) { if (s[i] < '0' || s[i] > '9') throw Error("bad PIL number " + s); v = (v * 10 + (s[i] - '0')) % GL_P; }
-    const u64 r = (u64)v;
-    return neg && r ? GL_P - r : r;
-}
-
-enum Hash { H_GL, H_BN128, H_BLS12381 };
-
-// the sponge of the proof's hash type through the library's own transcripts (device permutations)
+// the sponge of the proof's hash type: the library's own transcripts (device permutations)
 struct Sponge {
-    Hash h; zk_transcript_t* gl = nullptr; zk_bn128_transcript_t* bn = nullptr; zk_bls12381_transcript_t* bls = nullptr;
-    explicit Sponge(Hash hh) : h(hh) {
-        if (h == H_GL) gl = zk_transcript_new(); else if (h == H_BN128) bn = zk_bn128_transcript_new(); else bls = zk_bls12381_transcript_new();
-        if (!gl && !bn && !bls) throw Error(zk_last_error());
-    }
-    Sponge(const Sponge&) = delete; Sponge& operator=(const Sponge&) = delete;
-    ~Sponge() { if (gl) zk_transcript_free(gl); if (bn) zk_bn128_transcript_free(bn); if (bls) zk_bls12381_transcript_free(bls); }
-    void put_words(const u64* w, size_t n) {              // n one-word elements (publics, evaluations, the last polynomial)
-        if (!n) return;
-        if (gl) { ck(zk_transcript_put(gl, C(w), n)); return; }
-        for (size_t i = 0; i < n; ++i) ck(bn ? zk_bn128_transcript_put(bn, C(w + i), 1) : zk_bls12381_transcript_put(bls, C(w + i), 1));
-    }
-    void put_root(const u64 r[4]) { ck(gl ? zk_transcript_put(gl, C(r), 4) : bn ? zk_bn128_transcript_put(bn, C(r), 4) : zk_bls12381_transcript_put(bls, C(r), 4)); }
-    F3 get_field() {
-        u64 o[3];
-        ck(gl ? zk_transcript_get_field(gl, M(o)) : bn ? zk_bn128_transcript_get_field(bn, M(o)) : zk_bls12381_transcript_get_field(bls, M(o)));
-        return f3(o[0], o[1], o[2]);
-    }
+    std::unique_ptr<Transcript> t;
+    explicit Sponge(HashType h) : t(new_transcript(h)) {}
+    void put_words(const u64* w, size_t n) { t->put_words(w, n); }   // n one-word elements (publics, evaluations, the last polynomial)
+    void put_root(const u64 r[4]) { t->put_digest(r); }
+    F3 get_field() { u64 o[3]; t->get(o, 3); return f3(o[0], o[1], o[2]); }
     std::vector<u64> get_permutations(u32 n, u32 nbits) {
         std::vector<u64> o(std::max<u32>(1, n));
-        ck(gl ? zk_transcript_get_permutations(gl, n, nbits, M(o.data())) : bn ? zk_bn128_transcript_get_permutations(bn, n, nbits, M(o.data()))
-                                                                                : zk_bls12381_transcript_get_permutations(bls, n, nbits, M(o.data())));
+        t->get_permutations(n, nbits, o.data());
         o.resize(n);
         return o;
     }
@@ -157,7 +122,7 @@ struct Opening { std::vector<u64> row; std::vector<u64> path; u32 depth = 0; }; 
 struct TreeOpenings { u64 root[4]; std::vector<Opening> q; };
 
 struct Proof {
-    Hash h = H_GL;
+    HashType h = HASH_GL;
     u64 root[4][4];
     std::vector<F3> evals; std::vector<u64> publics;
     TreeOpenings s0[5];                                    // tree1..4, constants (root filled by the caller)
@@ -165,22 +130,22 @@ struct Proof {
     std::vector<F3> last;
 };
 
-void parse_digest(const JVal& v, Hash h, u64 out[4]) {     // digest.rs:84-112 read backwards
-    if (h == H_GL) {
+void parse_digest(const JVal& v, HashType h, u64 out[4]) {     // digest.rs:84-112 read backwards
+    if (h == HASH_GL) {
         if (v.kind == JVal::Arr) { if (v.size() != 4) throw Error("zkin: a digest has 4 words"); for (int i = 0; i < 4; ++i) out[i] = parse_word(v.at(i)); }
         else { out[0] = parse_word(v); out[1] = out[2] = out[3] = 0; }
         return;
     }
-    if (v.kind != JVal::Str || !fr_digest_from_dec(h == H_BLS12381, v.s, out)) throw Error("zkin: a digest is a canonical scalar-field element in decimal");
+    if (v.kind != JVal::Str || !fr_field(h)->from_dec(v.s, out)) throw Error("zkin: a digest is a canonical scalar-field element in decimal");
 }
-Opening parse_opening(const JVal& row, const JVal& sib, Hash h) {
+Opening parse_opening(const JVal& row, const JVal& sib, HashType h) {
     Opening o;
     if (row.kind != JVal::Arr || sib.kind != JVal::Arr) throw Error("zkin: opening: arrays expected");
     for (const JVal& w : row.arr) o.row.push_back(parse_word(w));
     o.depth = (u32)sib.size();
     if (o.depth > 64) throw Error("zkin: path too long");
     for (const JVal& lvl : sib.arr) {
-        if (h == H_GL) {
+        if (h == HASH_GL) {
             if (lvl.kind != JVal::Arr || lvl.size() != 4) throw Error("zkin: a sibling is a digest of 4 words");
             for (const JVal& w : lvl.arr) o.path.push_back(parse_word(w));
         } else {
@@ -194,12 +159,12 @@ F3 parse_f3(const JVal& v) {                               // serializer.rs:21-3
     if (v.kind == JVal::Arr) { if (v.size() != 3) throw Error("zkin: an extension value has 3 words"); return f3(parse_word(v.at(0)), parse_word(v.at(1)), parse_word(v.at(2))); }
     return f3(parse_word(v));
 }
-void parse_tree(const JVal& Z, const std::string& vals, const std::string& sibs, Hash h, u32 nq, TreeOpenings& t) {
+void parse_tree(const JVal& Z, const std::string& vals, const std::string& sibs, HashType h, u32 nq, TreeOpenings& t) {
     const JVal &V = Z.at(vals), &S = Z.at(sibs);
     if (V.size() != nq || S.size() != nq) throw Reject{vals + ": one opening per query expected"};
     for (u32 i = 0; i < nq; ++i) t.q.push_back(parse_opening(V.at(i), S.at(i), h));
 }
-Proof parse_proof(const JVal& Z, Hash h, u32 nq, size_t n_steps) {
+Proof parse_proof(const JVal& Z, HashType h, u32 nq, size_t n_steps) {
     Proof P; P.h = h;
     const char* rn[4] = {"root1", "root2", "root3", "root4"};
     for (int j = 0; j < 4; ++j) parse_digest(Z.at(rn[j]), h, P.root[j]);
@@ -282,15 +247,14 @@ F3 execute_code(const JVal& code, const ExecCtx& c) {
 // parity tests against the restated verifier.
 thread_local int g_reference_compat = 0;   // per calling thread: a parity test on one thread must not weaken verifications running on others (advisor finding, round 5)
 struct PathRef { const Opening* o; u64 idx; const u64* want; const char* what; };
-void check_paths(Hash h, const std::vector<std::vector<PathRef>>& trees /* paths of one tree share the row width */) {
+void check_paths(HashType h, const std::vector<std::vector<PathRef>>& trees /* paths of one tree share the row width */) {
     size_t n = 0; u32 max_depth = 1;
     for (auto& t : trees) { n += t.size(); for (auto& p : t) max_depth = std::max(max_depth, p.o->depth); }
     if (n == 0) return;
-    hipStream_t st = cur_stream();                       // (the scalar-field sponges move the thread to the null stream: come back)
-    on_stream(st);
+    hipStream_t st = cur_stream();
     size_t levels = 0;                                  // scalar fields: every level of every path is hashed (16 nodes of 4 words each)
     for (auto& t : trees) for (auto& p : t) levels += p.o->depth;
-    std::vector<u64> h_paths(h == H_GL ? n * max_depth * 4 : std::max<size_t>(1, levels) * 64, 0), h_idx(n);
+    std::vector<u64> h_paths(h == HASH_GL ? n * max_depth * 4 : std::max<size_t>(1, levels) * 64, 0), h_idx(n);
     std::vector<u32> h_depth(n);
     DevBuf d_leaves, d_paths, d_idx, d_depth, d_roots, d_zero;
     d_leaves.reserve(n * 32); d_roots.reserve(std::max(n, levels) * 64); d_paths.reserve(h_paths.size() * 8); d_idx.reserve(n * 8); d_depth.reserve(n * 4);
@@ -305,33 +269,33 @@ void check_paths(Hash h, const std::vector<std::vector<PathRef>>& trees /* paths
             memcpy(rows.data() + i * w, t[i].o->row.data(), w * 8);
             const Opening& o = *t[i].o;
             h_idx[k + i] = t[i].idx; h_depth[k + i] = o.depth;
-            if (h == H_GL) memcpy(h_paths.data() + (k + i) * max_depth * 4, o.path.data(), (size_t)o.depth * 32);
+            if (h == HASH_GL) memcpy(h_paths.data() + (k + i) * max_depth * 4, o.path.data(), (size_t)o.depth * 32);
             else if (o.depth) { memcpy(h_paths.data() + lv * 64, o.path.data(), (size_t)o.depth * 512); lv += o.depth; }
         }
         rows_keep.emplace_back(new DevBuf); DevBuf& d_rows = *rows_keep.back(); d_rows.reserve(rows.size() * 8);
         h2d_sync(d_rows.p, rows.data(), rows.size() * 8);
-        if (h == H_GL) linearhash_rows_dev(d_rows.u(), (u32)w, t.size(), d_leaves.u() + 4 * k, st);
-        else fr_linearhash_rows_dev(h == H_BLS12381, d_rows.u(), (u32)w, t.size(), d_leaves.u() + 4 * k, st);
+        if (h == HASH_GL) linearhash_rows_dev(d_rows.u(), (u32)w, t.size(), d_leaves.u() + 4 * k, st);
+        else fr_field(h)->linearhash_rows_dev(d_rows.u(), (u32)w, t.size(), d_leaves.u() + 4 * k, st);
         k += t.size();
     }
     h2d_sync(d_paths.p, h_paths.data(), h_paths.size() * 8);
     std::vector<u64> got(8 * std::max(n, levels)), leaves;   // scalar fields: two words of the permutation per level, the hash is word 0 (BN128) or 1 (BLS12-381)
-    const size_t stride = h == H_GL ? 4 : 8, pick = h == H_BLS12381 ? 4 : 0;
-    if (h == H_GL) {
+    const size_t stride = h == HASH_GL ? 4 : 8, pick = h == HASH_GL ? 0 : 4 * fr_field(h)->hash_word;
+    if (h == HASH_GL) {
         h2d_sync(d_idx.p, h_idx.data(), n * 8); h2d_sync(d_depth.p, h_depth.data(), n * 4);
         merkle_roots_from_paths_dev(d_leaves.u(), d_paths.u(), (const u32*)d_depth.p, d_idx.u(), (u32)n, max_depth, d_roots.u(), st);
     } else {
         d_zero.reserve(32); ZK_HIP(hipMemsetAsync(d_zero.p, 0, 32, st));
-        if (levels) fr_hash16_dev(h == H_BLS12381, d_paths.u(), levels, d_zero.u(), d_roots.u(), st);
+        if (levels) fr_field(h)->poseidon_dev(d_paths.u(), levels, 16, d_zero.u(), 2, d_roots.u(), st);   // the hash of each group of 16 nodes, zero initial state (merklehash_bn128.rs:108-128)
         leaves.resize(4 * n); d2h_sync(leaves.data(), d_leaves.p, n * 32);
     }
-    d2h_sync(got.data(), d_roots.p, (h == H_GL ? n : levels) * stride * 8);
+    d2h_sync(got.data(), d_roots.p, (h == HASH_GL ? n : levels) * stride * 8);
     const bool strict = g_reference_compat == 0;
     k = 0; lv = 0;
     for (auto& t : trees)
         for (auto& p : t) {
             const u64* r;
-            if (h == H_GL) r = got.data() + stride * k;
+            if (h == HASH_GL) r = got.data() + stride * k;
             else {                                       // walk the 16-ary path: leaf digest -> level 0 -> ... -> root
                 r = leaves.data() + 4 * k;
                 u64 idx = p.idx;
@@ -351,9 +315,7 @@ void check_paths(Hash h, const std::vector<std::vector<PathRef>>& trees /* paths
 bool verify(const JVal& info, const JVal& prog, const JVal& ss, const u64 const_root[4], const char* zkin_json) {
     const u32 nbits = (u32)ss.at("nBits").u64(), nbits_ext = (u32)ss.at("nBitsExt").u64(), nq = (u32)ss.at("nQueries").u64();
     ZK_REQUIRE(nbits >= 1 && nbits <= nbits_ext && nbits_ext <= 32, "bad nBits / nBitsExt");
-    const std::string& ht = ss.at("verificationHashType").str();
-    ZK_REQUIRE(ht == "GL" || ht == "BN128" || ht == "BLS12381", "verificationHashType must be GL, BN128 or BLS12381");
-    const Hash h = ht == "GL" ? H_GL : ht == "BN128" ? H_BN128 : H_BLS12381;
+    const HashType h = hash_type_of(ss.at("verificationHashType").str());
     std::vector<u32> steps;
     for (const JVal& s : ss.at("steps").arr) steps.push_back((u32)s.at("nBits").u64());
     ZK_REQUIRE(!steps.empty() && steps[0] <= 32, "starkStruct without FRI steps");
@@ -418,7 +380,7 @@ bool verify(const JVal& info, const JVal& prog, const JVal& ss, const u64 const_
             for (u32 i = 0; i < nq; ++i) trees[4 + si].push_back(PathRef{&P.steps[si - 1].q[i], yr[i], P.steps[si - 1].root, "a FRI step"});
         }
         // ... and every path is as deep as the tree its StarkStruct implies (binary GL trees: log2 height; 16-ary scalar-field trees: ceil(log16))
-        auto want_depth = [&](u32 height_bits) -> u32 { return h == H_GL ? height_bits : (height_bits + 3) / 4; };
+        auto want_depth = [&](u32 height_bits) -> u32 { return h == HASH_GL ? height_bits : (height_bits + 3) / 4; };
         for (size_t j = 0; j < trees.size(); ++j) {
             const u32 hb = j < 5 ? nbits_ext : steps[j - 4];
             for (const PathRef& pr : trees[j])

@@ -9,8 +9,6 @@
 #include <vector>
 #include "gl.hip.h"
 
-struct zk_merkle;
-struct zk_transcript;
 struct zk_program;
 namespace zk {
 
@@ -29,6 +27,22 @@ struct Error : std::runtime_error { using std::runtime_error::runtime_error; };
 
 #define ZK_REQUIRE(cond, msg)                                                                     \
     do { if (!(cond)) throw zk::Error(std::string(msg)); } while (0)
+
+// a number of a PIL program (types.rs:221-233): decimal or 0x hex, possibly negative, reduced mod p
+inline u64 parse_pil_number(const std::string& s) {
+    const bool neg = !s.empty() && s[0] == '-';
+    size_t i = neg ? 1 : 0;
+    const bool hex = s.size() > i + 1 && s[i] == '0' && (s[i + 1] == 'x' || s[i + 1] == 'X');
+    unsigned __int128 v = 0;
+    for (i += hex ? 2 : 0; i < s.size(); ++i) {
+        const char c = s[i];
+        const int d = c >= '0' && c <= '9' ? c - '0' : !hex ? -1 : c >= 'a' && c <= 'f' ? c - 'a' + 10 : c >= 'A' && c <= 'F' ? c - 'A' + 10 : -1;
+        if (d < 0) throw Error("bad PIL number " + s);
+        v = (v * (hex ? 16 : 10) + d) % GL_P;
+    }
+    const u64 r = (u64)v;
+    return neg && r ? GL_P - r : r;
+}
 
 // ---- device buffers ----
 // Size-keyed free list in front of the driver's allocator (devmem.hip): a prover allocates the same
@@ -179,16 +193,6 @@ void evals_k_dev(const EvalDescKHost* descs, uint32_t n_ev, uint32_t nbits, u64*
 void evals_dev(const EvalDescHost* descs, uint32_t n_ev, uint32_t nbits, uint32_t ext, const u64* d_LEv, const u64* d_LpEv, u64* d_out, hipStream_t st);
 void pol_get_dev(const u64* d_buf, uint64_t width, uint64_t offset, uint32_t dim, uint64_t n, u64* d_out, hipStream_t st);
 void pol_set_dev(u64* d_buf, uint64_t width, uint64_t offset, uint32_t dim, uint64_t n, const u64* d_in, hipStream_t st);
-// openings of a GL tree at n device-resident (already range-checked) indices, written to device memory as
-// n x (width + 4 * depth) words: no host round trip (capi.hip; the prover batches the openings of all its trees)
-void merkle_group_proofs_async(const struct ::zk_merkle* t, const u64* d_idx, uint32_t n, u64* d_out, hipStream_t st);
-void merkle_group_proofs_multi_async(const struct ::zk_merkle* const* trees, const u64* masks, u64* const* d_outs, uint32_t n_trees, const u64* d_idx, uint32_t n, hipStream_t st);
-uint32_t merkle_width(const struct ::zk_merkle* t);
-uint64_t merkle_height(const struct ::zk_merkle* t);
-void merkle_group_proofs_masked_async(const struct ::zk_merkle* t, const u64* d_idx, u64 mask, uint32_t n, u64* d_out, hipStream_t st);
-void transcript_permutations_async(struct ::zk_transcript* t, uint32_t n, uint32_t nbits, u64* d_dst, hipStream_t st);
-// put d_src[0..n_put) and squeeze n_get words (bits == 0) or n_get indices of `bits` bits, one launch on `st`
-void transcript_put_get_async(struct ::zk_transcript* t, const u64* d_src, uint64_t n_put, u64* d_dst, uint32_t n_get, uint32_t bits, hipStream_t st);
 uint64_t h1h2_work_words(uint64_t n);
 void calculate_h1h2_dev(const u64* d_f, const u64* d_t, uint64_t n, u64* d_h1, u64* d_h2, u64* d_work, u64** d_missing, hipStream_t st);
 void calculate_z_dev(const u64* d_num, const u64* d_den, uint64_t n, u64* d_z, u64* d_work, u64* d_check, hipStream_t st);
@@ -219,7 +223,7 @@ ZK_MSM_FIXED_DECL(g2_bn254)
 ZK_MSM_FIXED_DECL(g1_bls12_381)
 ZK_MSM_FIXED_DECL(g2_bls12_381)
 #undef ZK_MSM_FIXED_DECL
-// ---- BN128-field hashing (poseidon_bn128.hip); digests = 4 raw (Montgomery, R = 2^256) limbs
+// ---- BN128-field hashing (frhash.hip; reached through the field table of commit.h); digests = 4 raw (Montgomery, R = 2^256) limbs
 void bn128_load_constants(const char* path);
 std::string bn128_tables_selfcheck(const char* path);   // host only: the matrix-pipe tables (fr_mfma.hip.h) against the constants; "" or what is wrong
 void bn128_poseidon_dev(const u64* d_inp, uint64_t n, uint32_t n_in, const u64* d_init, uint32_t n_out, u64* d_out, hipStream_t st);
@@ -236,10 +240,6 @@ void bls12381_merkelize_dev(const u64* d_rows, uint32_t width, uint64_t height, 
 // stark_verify (stark_verify.hip): 1 accepted, 0 rejected (`why` names the failed check); throws Error on malformed input
 struct JVal;
 int stark_verify_impl(const JVal& info, const JVal& prog, const JVal& ss, const u64 const_root[4], const char* zkin_json, std::string& why);
-// the verifier's side of the scalar-field trees and digests (capi.hip)
-bool fr_digest_from_dec(bool bls12381, const std::string& dec, u64 out[4]);
-void fr_hash16_dev(bool bls12381, const u64* d_in, uint64_t n, const u64* d_zero4, u64* d_out, hipStream_t st);
-void fr_linearhash_rows_dev(bool bls12381, const u64* d_rows, uint32_t width, uint64_t height, u64* d_digests, hipStream_t st);
 void qsplit_dev(const u64* d_qq1, uint32_t nbits, uint32_t q_dim, uint32_t q_deg, u64* d_qq2, hipStream_t st);
 // base-field elements in place: canonical integers <-> Montgomery (msm.hip); n = number of Fq elements
 void fq_bn254_canon_to_mont_dev(void* d, uint64_t n, hipStream_t st);

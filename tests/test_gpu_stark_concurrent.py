@@ -62,6 +62,51 @@ def test_concurrent_proofs_equal_sequential_proofs(zk):
     for st in streams: st.free()
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("hash_type", ["BN128", "BLS12381"])
+def test_concurrent_scalar_field_proofs_equal_sequential_proofs(zk, hash_type):
+    """The scalar-field sponges and the host-buffer paths of their trees work on the null stream whoever calls; each such
+    step must hand the calling thread's stream back, or the rest of a streamed proof allocates against the null stream.
+    Two threads, a non-blocking stream and a setup each, two proofs each: every one is the proof its setup gives alone."""
+    import importlib
+    import aggregation_workload as AW
+    import poseidong as PG
+    stark = importlib.import_module("eigen_zkvm_amd.stark")
+    assert zk.lib().zk_device_count() >= 1
+    zk.init(0)
+    W, ROUNDS = 2, 2
+    struct = dict(AW.STRUCTS["fib"], verificationHashType=hash_type)
+    prog = json.dumps(PG.native_program(AW.fib_pil(), struct))
+    workers = []
+    for w in range(W):
+        su = stark.NativeStarkSetup(AW.fib_consts(), prog, json.dumps(struct), prover_addr="1")
+        workers.append((su, [zk.DevArray.from_host(AW.fib_trace(ROUNDS * w + r)) for r in range(ROUNDS)]))
+    alone = [[su.gen_json(cm) for cm in cms] for su, cms in workers]       # default stream, one at a time
+    assert len({z for zs in alone for z in zs}) == W * ROUNDS
+    got = [[None] * ROUNDS for _ in range(W)]
+    errors = []
+    streams = [zk.Stream() for _ in range(W)]
+    barrier = threading.Barrier(W)
+
+    def work(w):
+        try:
+            su, cms = workers[w]
+            barrier.wait()
+            for r, cm in enumerate(cms):
+                got[w][r] = su.gen_json(cm, streams[w].handle)
+        except BaseException as e:                                        # noqa: BLE001 -- reported by the main thread
+            errors.append((w, repr(e)))
+
+    threads = [threading.Thread(target=work, args=(w,)) for w in range(W)]
+    for t in threads: t.start()
+    for t in threads: t.join(timeout=600)
+    assert not any(t.is_alive() for t in threads), "a prover thread hangs"
+    assert not errors, errors
+    zk.lib().zk_dev_sync()
+    assert got == alone
+    for st in streams: st.free()
+
+
 _COLD = r'''
 import json, sys, threading, importlib, pathlib
 ROOT = pathlib.Path(sys.argv[1]); mode = sys.argv[2]
