@@ -229,6 +229,51 @@ __device__ __forceinline__ u64 add_nc(u64 a, u64 b) {
     return mk64(r0, r1);
 }
 
+// ---- the NTT passes' twiddle product: a 64 x 64 product whose four multiply-adds take the 32-bit halves directly.
+// gl::mul chains its multiply-adds through the HIGH word of the one before (p1 = a0 b1 + (p0 >> 32), ...): a 64-bit
+// addend has to be a register pair, so every link costs a move beside a zero register (4 moves and a 64-bit add per product).
+// Here only the two cross products chain (64-bit result into 64-bit addend, no move); the columns are then summed with
+// 32-bit carry adds, and the last carry rides as the borrow-in of the 2^96 fold instead of being added to r3 first:
+//   a b = L + 2^32 (c:M) + 2^64 H,  L = a0 b0, c:M = a0 b1 + a1 b0 (65 bits), H = a1 b1
+//   w0 = L0, w1 = L1 + M0 -> k1, r2 = M1 + H0 + k1 -> k2, r3 = H1 + c + k2   (H1 <= 2^32 - 2: H1 + c cannot wrap)
+// Returns (w1:w0) - r3 folded as sub_word_fold does (minus 2^32 - 1 more if that borrowed) and r2 for mad_eps / mad_eps_nc:
+// 12 instructions where the plain product and sub_word_fold spend 14.  Any u64 operands.  The asm is as opaque to the
+// optimiser as GL_OPAQUE makes the operands of gl::mul.  The cross products come first: their carry c, an SGPR pair, has the
+// two other multiply-adds between its producer and its consumer.  That distance is load-bearing: on the gfx940 family (gfx950
+// included) an SGPR written by a VALU instruction may be read by a VALU instruction only 2 wait states later, the compiler cannot
+// add wait states inside asm, and the first instruction of the second block reads c.  Whoever reorders the four multiply-adds
+// keeps two instructions after the one that writes c (or puts an `s_nop 1` there).
+__device__ __forceinline__ u64 mul_fold96(u64 a, u64 b, u32& r2) {
+    const u32 a0 = (u32)a, a1 = (u32)(a >> 32), b0 = (u32)b, b1 = (u32)(b >> 32);
+    u64 l, m, h, c;
+    asm("v_mad_u64_u32 %1, vcc, %4, %7, 0\n\t"
+        "v_mad_u64_u32 %1, %3, %5, %6, %1\n\t"
+        "v_mad_u64_u32 %0, vcc, %4, %6, 0\n\t"
+        "v_mad_u64_u32 %2, vcc, %5, %7, 0"
+        : "=&v"(l), "=&v"(m), "=&v"(h), "=&s"(c) : "v"(a0), "v"(a1), "v"(b0), "v"(b1) : "vcc");
+    u32 t0, t1, mb, h1, w1;
+    asm("v_addc_co_u32 %3, vcc, 0, %10, %11\n\t"
+        "v_add_co_u32 %4, vcc, %6, %7\n\t"
+        "s_nop 1\n\t"
+        "v_addc_co_u32 %5, vcc, %8, %9, vcc\n\t"
+        "s_nop 1\n\t"
+        "v_subb_co_u32 %0, vcc, %12, %3, vcc\n\t"
+        "s_nop 1\n\t"
+        "v_subbrev_co_u32 %1, vcc, 0, %4, vcc\n\t"
+        "s_nop 1\n\t"
+        "v_cndmask_b32_e64 %2, 0, -1, vcc\n\t"
+        "v_sub_co_u32 %0, vcc, %0, %2\n\t"
+        "s_nop 1\n\t"
+        "v_subbrev_co_u32 %1, vcc, 0, %1, vcc"
+        : "=&v"(t0), "=&v"(t1), "=&v"(mb), "=&v"(h1), "=&v"(w1), "=&v"(r2)
+        : "v"((u32)(l >> 32)), "v"((u32)m), "v"((u32)(m >> 32)), "v"((u32)h), "v"((u32)(h >> 32)), "s"(c), "v"((u32)l) : "vcc");
+    return mk64(t0, t1);
+}
+// x * w mod p, any u64 in, canonical out: bit for bit what gl::mul returns (19 instructions against 21 and no zero register pair)
+__device__ __forceinline__ u64 mul_tw(u64 x, u64 w) { u32 r2; const u64 t = mul_fold96(x, w, r2); return mad_eps(r2, t); }
+// the same without the final canonicalisation (15 instructions): for a product that feeds only other products
+__device__ __forceinline__ u64 mul_tw_nc(u64 x, u64 w) { u32 r2; const u64 t = mul_fold96(x, w, r2); return mad_eps_nc(r2, t); }
+
 // x * 2^E mod p for a compile-time 0 <= E < 96, canonical x -> canonical result.  2 has order 192
 // and 2^96 = -1, so every root of unity of order <= 64 is a power of two (MG.0[6] = 2^39,
 // constant.rs:54-68): the butterflies' small twiddles are shifts, not field multiplications.
@@ -241,9 +286,20 @@ __device__ __forceinline__ u64 mul_pow2(u64 x) {
         return x;
     } else if constexpr (E <= 32) {                       // lo + top*2^64, top < 2^32
         return mad_eps((u32)(x >> (64 - E)), x << E);
-    } else if constexpr (E < 64) {                        // lo + hi*2^64, hi < 2^E
-        const u64 lo = x << E, hi = x >> (64 - E);
-        return reduce_words((u32)lo, (u32)(lo >> 32), (u32)hi, (u32)(hi >> 32));
+    } else if constexpr (E < 64) {
+        // E = 32 + r: x 2^r = t2:t1:t0 (t2 < 2^r), so x 2^E = t0 2^32 + t1 2^64 + t2 2^96 = t0 2^32 + t1 (2^32 - 1) - t2.  With the addend
+        // (t0 : ~t2) = t0 2^32 + (2^32 - 1) - t2 one multiply-add gives u + carry 2^64 = value + 2^32 - 1, i.e. value = u if it carried
+        // (2^64 = 2^32 - 1) and u - (2^32 - 1) if not.  Both are already canonical: carried, u <= (2^32 - 1) 2^33 - 2^64 < p; not carried,
+        // u - (2^32 - 1) < 2^64 - (2^32 - 1) = p.  Only t0 = t1 = 0 makes the difference negative (-t2), which the fold's second step turns
+        // into p - t2.  11 instructions; lo + hi 2^64 through reduce_words and a canonicalisation took 15.
+        constexpr int r = E - 32;
+        const u32 x0 = (u32)x, x1 = (u32)(x >> 32);
+        const u32 t1 = __builtin_amdgcn_alignbit(x1, x0, 32 - r);
+        const u64 addend = mk64(~(x1 >> (32 - r)), x0 << r);
+        u64 u; u32 m;
+        asm("v_mad_u64_u32 %0, vcc, %2, -1, %3\n\ts_nop 1\n\tv_cndmask_b32_e64 %1, -1, 0, vcc"
+                     : "=&v"(u), "=v"(m) : "v"(t1), "v"(addend) : "vcc");
+        return sub_word_fold((u32)u, (u32)(u >> 32), m);
     } else {                                              // E = 64 + r: t0*2^64 - (x*2^r >> 32), t0 = low word of x*2^r
         constexpr int r = E - 64;
         const u32 t0 = (u32)x << r;

@@ -57,8 +57,10 @@ struct PassParams {
     u32 has_tw;        // L > R (not the last pass)
 };
 
+// Two-level table look-up w^e.  The result is NOT canonical (some u64 congruent to it): every use below is a factor of a further product
+// (gl::mul_tw / gl::mul_tw_nc take any u64), so the canonicalisation would be spent for nothing.
 __device__ __forceinline__ u64 tab2(const u64* __restrict__ lo, const u64* __restrict__ hi, u64 e) {
-    return gl::mul(hi[e >> TW_LO_BITS], lo[e & (TW_LO - 1)]);
+    return gl::mul_tw_nc(hi[e >> TW_LO_BITS], lo[e & (TW_LO - 1)]);
 }
 
 template <int LOGA, int LOGB, bool KMODE, bool INV>
@@ -133,8 +135,8 @@ __global__ __launch_bounds__(NTT_TILE / 16) void ntt_pass_kernel(const PassParam
 #pragma unroll
                 for (int ka = 0; ka < RA; ++ka) {
                     u64 v = x[g][bitrev_c(ka, LOGA)];
-                    if (LOGB > 0 && ka > 0) v = gl::mul(v, P.w256[(jb * ka) << (8 - LOGR)]);
-                    else if (P.pre_scale != 1) v = gl::mul(v, P.pre_scale);
+                    if (LOGB > 0 && ka > 0) v = gl::mul_tw(v, P.w256[(jb * ka) << (8 - LOGR)]);
+                    else if (P.pre_scale != 1) v = gl::mul_tw(v, P.pre_scale);
                     lds[ka * ROW + jb * C + c] = v;
                 }
             }
@@ -186,7 +188,7 @@ __global__ __launch_bounds__(NTT_TILE / 16) void ntt_pass_kernel(const PassParam
 #pragma unroll
                 for (int kb = 0; kb < RB; ++kb) {
                     u64 v = y[g][bitrev_c(kb, LOGB)];
-                    v = gl::mul(v, tw[g][kb]);
+                    v = gl::mul_tw(v, tw[g][kb]);
                     outp[(u64)(RA * kb + ka) * kstride] = v;
                 }
             }
@@ -206,8 +208,8 @@ __global__ __launch_bounds__(NTT_TILE / 16) void ntt_pass_kernel(const PassParam
             for (int kb = 0; kb < RB; ++kb) {
                 u64 v = y[g][bitrev_c(kb, LOGB)];
                 if (scaled) {
-                    v = gl::mul(v, f);
-                    if (kb + 1 < RB) f = gl::mul(f, fstep);
+                    v = gl::mul_tw(v, f);                               // canonical: it is stored
+                    if (kb + 1 < RB) f = gl::mul_tw_nc(f, fstep);       // the running factor only ever feeds products
                 }
                 outp[(u64)(RA * kb + ka) * kstride] = v;
             }
