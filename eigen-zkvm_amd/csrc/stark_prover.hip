@@ -108,8 +108,6 @@ struct AnyTranscript {
     void get_permutations(u32 n, u32 nbits, u64* out) { flush(); t->get_permutations(n, nbits, out); }
 };
 
-struct GroupProof { std::vector<u64> row; std::vector<u64> path; u32 depth; };
-
 void zero(DevBuf& b, size_t words, hipStream_t st) { if (words) ZK_HIP(hipMemsetAsync(b.p, 0, words * 8, st)); }
 
 // Per-stage device time of one proof, opt-in (ZK_STARK_TIMING=1): the reference's `#[time_profiler]` spans
@@ -301,30 +299,16 @@ void put_list(JOut& o, const u64* v, size_t n) {
     for (size_t i = 0; i < n; ++i) { if (i) o << ','; o << '"' << dec(v[i]) << '"'; }
     o << ']';
 }
-void put_path(JOut& o, const GroupProof& g, const FrField* fr) {
+void put_path(JOut& o, const u64* path, u32 depth, const FrField* fr) {   // path[depth][4], or [depth][64] of a scalar-field tree
     o << '[';
-    for (u32 l = 0; l < g.depth; ++l) {
+    for (u32 l = 0; l < depth; ++l) {
         if (l) o << ',';
-        if (!fr) { put_list(o, g.path.data() + 4 * l, 4); continue; }
+        if (!fr) { put_list(o, path + 4 * l, 4); continue; }
         o << '[';                                        // the 16 nodes of the group, each an Fr (merklehash_bn128.rs:86-106)
-        for (int k = 0; k < 16; ++k) { if (k) o << ','; o << '"' << fr->to_dec(g.path.data() + 64 * l + 4 * k) << '"'; }
+        for (int k = 0; k < 16; ++k) { if (k) o << ','; o << '"' << fr->to_dec(path + 64 * l + 4 * k) << '"'; }
         o << ']';
     }
     o << ']';
-}
-
-// the openings of one tree at every query index, one round trip (fri.rs:160-181)
-std::vector<GroupProof> group_proofs(const Tree& t, const std::vector<u64>& idx) {
-    const u32 n = (u32)idx.size(), lw = t.level_words();
-    std::vector<u64> rows(std::max<size_t>(1, (size_t)n * t.width)), paths(std::max<size_t>(1, (size_t)n * lw * t.depth));
-    t.group_proofs(idx.data(), n, rows.data(), paths.data());
-    std::vector<GroupProof> out(n);
-    for (u32 q = 0; q < n; ++q) {
-        out[q].depth = t.depth;
-        out[q].row.assign(rows.begin() + (size_t)q * t.width, rows.begin() + (size_t)(q + 1) * t.width);
-        out[q].path.assign(paths.begin() + (size_t)q * lw * t.depth, paths.begin() + (size_t)(q + 1) * lw * t.depth);
-    }
-    return out;
 }
 
 // Device words the host needs for the proof's JSON (roots, evaluations, the last FRI polynomial): collected in one device
@@ -540,17 +524,115 @@ zk_stark_setup* setup_new(const char* json, const char* ss_json, const uint64_t*
     return S.release();
 }
 
-// FRI::prove's commit phase (fri.rs:84-157) on a device polynomial, whoever owns the transcript: the folds, the trees over their groups, the
-// last polynomial's absorption, then the query indices (fri.rs:158-159).  Used by a proof context and by zk_fri_prove_dev.
+// What a proof opens (fri.rs:160-181): every tree added here at every query index, reduced by the tree's mask.  Goldilocks trees are opened
+// in device memory, all of them by one launch, into regions of the proof's ReadBack; a scalar-field tree takes one round trip
+// (Tree::group_proofs) into arrays held here.  resolve() leaves one view per tree -- where row q and path q lie, whoever holds them -- and
+// vals() / siblings() write the zkin lists from it.
+struct Openings {
+    struct View { const u64* rows; const u64* paths; size_t row_stride, path_stride; u32 depth, width, level_words; };
+    std::vector<const Tree*> trees; std::vector<u64> masks;
+    std::vector<size_t> off;                               // Goldilocks: tree j's region of the read-back block
+    std::vector<std::vector<u64>> held;                    // scalar field: the rows and the paths of every tree
+    std::vector<View> views;
+    u32 n = 0;                                             // queries
+    const FrField* fr = nullptr;
+    void add(const Tree* t, u64 mask) { trees.push_back(t); masks.push_back(mask); }
+    static size_t per(const Tree& t) { return (size_t)t.width + (size_t)t.level_words() * t.depth; }   // words of one opening
+    size_t readback_words() const {
+        size_t w = 0;
+        if (!fr) for (const Tree* t : trees) w += n * per(*t);
+        return w;
+    }
+    void queue(ReadBack& rb, const u64* d_ys) {            // Goldilocks only: the indices are in device memory
+        std::vector<const GlTree*> mt; std::vector<u64*> mo;
+        off.clear();
+        for (const Tree* t : trees) { off.push_back(rb.words); mt.push_back(t->gl()); mo.push_back(rb.reserve(n * per(*t))); }
+        rb.flush();                                        // (the pieces collected so far are copied before the openings' launch is queued: one order on `st`)
+        GlTree::open_multi_async(mt.data(), masks.data(), mo.data(), (u32)mt.size(), d_ys, n, rb.st);   // every tree, one launch
+    }
+    void resolve(const ReadBack& rb, const std::vector<u64>& ys) {   // after rb.fetch()
+        views.clear(); held.clear();
+        for (size_t j = 0; j < trees.size(); ++j) {
+            const Tree& t = *trees[j];
+            View v{nullptr, nullptr, per(t), per(t), t.depth, t.width, t.level_words()};
+            if (!fr) { v.rows = rb.at(off[j]); v.paths = v.rows + t.width; }
+            else {   // the reduced indices on the host, one round trip per tree
+                std::vector<u64> idx = ys;
+                for (u64& y : idx) y &= masks[j];
+                v.row_stride = t.width; v.path_stride = (size_t)v.level_words * t.depth;
+                held.emplace_back(std::max<size_t>(1, n * v.row_stride)); held.emplace_back(std::max<size_t>(1, n * v.path_stride));
+                v.rows = held[2 * j].data(); v.paths = held[2 * j + 1].data();
+                t.group_proofs(idx.data(), n, held[2 * j].data(), held[2 * j + 1].data());
+            }
+            views.push_back(v);
+        }
+    }
+    void vals(JOut& o, size_t j) const {
+        const View& v = views[j];
+        o << '[';
+        for (u32 q = 0; q < n; ++q) { if (q) o << ','; put_list(o, v.rows + q * v.row_stride, v.width); }
+        o << ']';
+    }
+    void siblings(JOut& o, size_t j) const {
+        const View& v = views[j];
+        o << '[';
+        for (u32 q = 0; q < n; ++q) { if (q) o << ','; put_path(o, v.paths + q * v.path_stride, v.depth, fr); }
+        o << ']';
+    }
+};
+
+// FRI::prove (fri.rs:84-184) on a device polynomial, whoever owns the transcript.  commit() is its commit phase (:84-157) -- the folds, the
+// trees over their groups, the last polynomial's absorption -- and the draw of the query indices (:158-159).  The queries (:160-181) follow
+// in three steps around the caller's one ReadBack: queue() adds the fold roots, the last polynomial, the indices and the openings of every
+// tree (its own, then the caller's: add_query_tree), resolve() reads them after the fetch, put_zkin() writes the FRI part of a zkin
+// (serializer.rs:189-252).  Used by a proof context and by zk_fri_prove_dev.
 struct FriState {
     std::vector<TreePtr> trees;                            // tree of step i+1's groups at [i]
-    std::vector<u32> width;
+    std::vector<u32> width, steps;
     std::vector<std::array<u64, 4>> roots;
     const u64* d_pol = nullptr;                            // the last polynomial, 3 << steps.back() words
     std::vector<u64> ys;
     DevBuf d_ys, d_sx;
     std::vector<std::unique_ptr<DevBuf>> keep;
-    void commit(AnyTranscript& tr, HashType hash, const u64* d_f, u32 nbits_ext, const std::vector<u32>& steps, u32 n_queries, hipStream_t st, StageTimer* T) {
+    Openings open;                                         // the folded polynomials' trees, then the caller's query trees
+    const FrField* fr = nullptr;
+    std::vector<size_t> off_root; size_t off_last = 0, off_ys = 0;   // in the ReadBack
+    void add_query_tree(const Tree* t) {                   // opened at the query indices themselves: step 0
+        ZK_REQUIRE(t, "zk_fri_prove_dev: null query tree");
+        ZK_REQUIRE(t->height >= (1ull << steps[0]), "zk_fri_prove_dev: a query tree is shorter than the first FRI step");
+        open.add(t, (1ull << steps[0]) - 1);
+    }
+    size_t readback_words() const { return 4 * steps.size() + (3ull << steps.back()) + open.n + open.readback_words(); }
+    void queue(ReadBack& rb) {
+        off_root.assign(steps.size(), 0);
+        if (!fr) for (size_t si = 0; si + 1 < steps.size(); ++si) off_root[si] = rb.add(trees[si]->gl()->root_dev(), 4);
+        off_last = rb.add(d_pol, 3ull << steps.back());
+        if (!fr) { off_ys = rb.add(d_ys.u(), open.n); open.queue(rb, d_ys.u()); }
+    }
+    void resolve(const ReadBack& rb) {
+        for (size_t si = 0; si + 1 < steps.size(); ++si) {
+            if (!fr) memcpy(roots[si].data(), rb.at(off_root[si]), 32); else trees[si]->root(roots[si].data());
+        }
+        if (!fr && open.n) memcpy(ys.data(), rb.at(off_ys), 8 * (size_t)open.n);
+        open.resolve(rb, ys);
+    }
+    // s<k>_root / s<k>_vals / s<k>_siblings of the folded polynomials, s0_vals<name> / s0_siblings<name> of the query trees, finalPol
+    void put_zkin(JOut& o, const ReadBack& rb, const std::vector<std::string>& names) const {
+        const size_t n_steps = steps.size();
+        for (size_t si = 1; si < n_steps; ++si) {
+            o << ",\"s" << si << "_root\":"; put_digest(o, roots[si - 1].data(), fr);
+            o << ",\"s" << si << "_vals\":"; open.vals(o, si - 1);
+            o << ",\"s" << si << "_siblings\":"; open.siblings(o, si - 1);
+        }
+        for (size_t j = 0; j < names.size(); ++j) { o << ",\"s0_vals" << names[j] << "\":"; open.vals(o, n_steps - 1 + j); }
+        for (size_t j = 0; j < names.size(); ++j) { o << ",\"s0_siblings" << names[j] << "\":"; open.siblings(o, n_steps - 1 + j); }
+        const u64 n_last = 1ull << steps.back();
+        o << ",\"finalPol\":[";
+        for (u64 i = 0; i < n_last; ++i) { if (i) o << ','; put_list(o, rb.at(off_last) + 3 * i, 3); }
+        o << ']';
+    }
+    void commit(AnyTranscript& tr, HashType hash, const u64* d_f, u32 nbits_ext, const std::vector<u32>& steps_, u32 n_queries, hipStream_t st, StageTimer* T) {
+        steps = steps_; fr = fr_field(hash);
         const size_t n_steps = steps.size();
         u32 pol_bits = nbits_ext;
         u64 shift_inv = gl::hinv(49);
@@ -588,6 +670,8 @@ struct FriState {
         if (tr.gl) { d_ys.reserve(std::max<u32>(1, n_queries) * 8); tr.get_permutations_dev(n_queries, steps[0], d_ys.u(), st); }
         else tr.get_permutations(n_queries, steps[0], ys.data());
         if (T) T->mark("fri_query_indices");
+        open.n = n_queries; open.fr = fr;
+        for (size_t si = 1; si < n_steps; ++si) open.add(trees[si - 1].get(), (1ull << steps[si]) - 1);
     }
 };
 
@@ -987,11 +1071,13 @@ struct zk_stark_ctx {
         T.mark("evals");
     }
 
-    // ---- FRI::prove (fri.rs:84-184) over the polynomial step52ns left in f_2ns: folds, their trees, the last polynomial, the query indices
+    // ---- FRI::prove (fri.rs:84-184) over the polynomial step52ns left in f_2ns: folds, their trees, the last polynomial, the query indices;
+    // its queries open the proof's five trees
     void fri_prove() {
         ZK_REQUIRE(ran[STEP_52NS] && !fri_done, "FRI::prove follows step52ns, once");
         on_stream(st);
         F.commit(*tr, S.hash, ptr[S_F_2NS], nbits_ext, S.steps, S.n_queries, st, &T);
+        for (const Tree* t : {tree[0].get(), tree[1].get(), tree[2].get(), tree[3].get(), S.const_tree.get()}) F.add_query_tree(t);
         fri_done = true;
     }
 
@@ -999,121 +1085,39 @@ struct zk_stark_ctx {
     std::string finish() {
         ZK_REQUIRE(fri_done, "finish follows FRI::prove");
         on_stream(st);
-        const std::vector<u32>& steps = S.steps;
-        const size_t n_steps = steps.size();
-        u64 r1[4], r2[4], r3[4], r4[4];
-        const u64 n_last = 1ull << steps.back();
-        std::vector<u64> ev_host(3 * (size_t)std::max<u32>(1, n_ev)), last(3 * n_last);
-        // the trees a proof opens: the folded polynomials' trees at the reduced indices, then the five trees at ys
-        std::vector<const Tree*> all_trees; std::vector<u64> all_mask;
-        for (size_t si = 1; si < n_steps; ++si) { all_trees.push_back(F.trees[si - 1].get()); all_mask.push_back((1ull << steps[si]) - 1); }
-        for (const Tree* t : {tree[0].get(), tree[1].get(), tree[2].get(), tree[3].get(), S.const_tree.get()}) { all_trees.push_back(t); all_mask.push_back((1ull << steps[0]) - 1); }
-        std::vector<std::vector<GroupProof>> all_gp;
-        {
-            size_t open_words = 0;
-            if (!fr) for (const Tree* t : all_trees) open_words += (size_t)S.n_queries * ((size_t)t->width + 4 * (size_t)t->depth);
-            ReadBack rb(4 * (4 + n_steps) + 3 * (size_t)n_ev + 3 * n_last + 3 * (size_t)n_pub + S.n_queries + open_words + 3 * n_z, st);
-            const Tree* t4[4] = {tree[0].get(), tree[1].get(), tree[2].get(), tree[3].get()};
-            u64* r4p[4] = {r1, r2, r3, r4};
-            size_t off_r[4] = {}, off_ev = 0, off_last = 0, off_ys = 0;
-            std::vector<size_t> off_fri(n_steps, 0), off_open(all_trees.size(), 0);
-            if (!fr) {
-                for (int j = 0; j < 4; ++j) off_r[j] = rb.add(t4[j]->gl()->root_dev(), 4);
-                for (size_t si = 0; si + 1 < n_steps; ++si) off_fri[si] = rb.add(F.trees[si]->gl()->root_dev(), 4);
-            }
-            off_ev = rb.add(d_evals.u(), 3 * (size_t)n_ev);
-            off_last = rb.add(F.d_pol, 3 * n_last);
-            const size_t off_z = rb.add(z_checks.u(), 3 * n_z);
-            const size_t off_pub = pub_on_device ? rb.add(d_pub.u(), n_pub) : 0, off_ext = pub_on_device ? rb.add(d_pub_ext.u(), 2 * (size_t)n_pub) : 0;
-            if (!fr) {
-                off_ys = rb.add(F.d_ys.u(), S.n_queries);
-                std::vector<const GlTree*> mt; std::vector<u64*> mo;
-                for (size_t j = 0; j < all_trees.size(); ++j) {
-                    const size_t per = (size_t)all_trees[j]->width + 4 * (size_t)all_trees[j]->depth;
-                    off_open[j] = rb.words;
-                    mt.push_back(all_trees[j]->gl()); mo.push_back(rb.reserve(per * S.n_queries));
-                }
-                rb.flush();                                   // (the pieces collected so far are copied before the openings' launch is queued: one order on `st`)
-                GlTree::open_multi_async(mt.data(), all_mask.data(), mo.data(), (u32)mt.size(), F.d_ys.u(), S.n_queries, st);   // every tree, one launch
-            }
-            rb.fetch();
-            for (size_t i = 0; i < n_z; ++i)
-                ZK_REQUIRE(rb.at(off_z)[3 * i] == 1 && rb.at(off_z)[3 * i + 1] == 0 && rb.at(off_z)[3 * i + 2] == 0, "calculate_Z: z does not close (grand product != 1)");
-            if (pub_on_device) {
-                publics.assign(rb.at(off_pub), rb.at(off_pub) + n_pub);
-                // The reference absorbs ctx.publics[i].as_elements() (stark_gen.rs:272-277): one word for a base-field value; a
-                // computed public with extension words means a malformed program (see the host-trace path above)
-                for (u32 i = 0; i < n_pub; ++i)
-                    ZK_REQUIRE(rb.at(off_ext)[2 * i] == 0 && rb.at(off_ext)[2 * i + 1] == 0,
-                               "public " + std::to_string(i) + ": extension-field value (only base-field publics exist in the reference)");
-            }
-            if (!fr) {
-                for (int j = 0; j < 4; ++j) memcpy(r4p[j], rb.at(off_r[j]), 32);
-                for (size_t si = 0; si + 1 < n_steps; ++si) memcpy(F.roots[si].data(), rb.at(off_fri[si]), 32);
-                if (S.n_queries) memcpy(F.ys.data(), rb.at(off_ys), 8 * (size_t)S.n_queries);
-                all_gp.resize(all_trees.size());
-                for (size_t j = 0; j < all_trees.size(); ++j) {
-                    const u32 depth = all_trees[j]->depth, w = all_trees[j]->width;
-                    const size_t per = (size_t)w + 4 * (size_t)depth;
-                    all_gp[j].resize(S.n_queries);
-                    for (u32 q = 0; q < S.n_queries; ++q) {
-                        const u64* p = rb.at(off_open[j] + q * per);
-                        all_gp[j][q].depth = depth; all_gp[j][q].row.assign(p, p + w); all_gp[j][q].path.assign(p + w, p + per);
-                    }
-                }
-            } else {
-                for (int j = 0; j < 4; ++j) t4[j]->root(r4p[j]);
-                for (size_t si = 0; si + 1 < n_steps; ++si) F.trees[si]->root(F.roots[si].data());
-            }
-            if (n_ev) memcpy(ev_host.data(), rb.at(off_ev), 24 * (size_t)n_ev);
-            memcpy(last.data(), rb.at(off_last), 24 * n_last);
+        ReadBack rb(4 * 4 + 3 * (size_t)n_ev + 3 * (size_t)n_pub + 3 * n_z + F.readback_words(), st);   // lives until the text is written: its words are read in place
+        u64 r_host[4][4]; const u64* r[4];                // root1..4: in the read-back block, or fetched from a scalar-field tree
+        size_t off_r[4] = {};
+        if (!fr) for (int j = 0; j < 4; ++j) off_r[j] = rb.add(tree[j]->gl()->root_dev(), 4);
+        const size_t off_ev = rb.add(d_evals.u(), 3 * (size_t)n_ev), off_z = rb.add(z_checks.u(), 3 * n_z);
+        const size_t off_pub = pub_on_device ? rb.add(d_pub.u(), n_pub) : 0, off_ext = pub_on_device ? rb.add(d_pub_ext.u(), 2 * (size_t)n_pub) : 0;
+        F.queue(rb);
+        rb.fetch();
+        for (size_t i = 0; i < n_z; ++i)
+            ZK_REQUIRE(rb.at(off_z)[3 * i] == 1 && rb.at(off_z)[3 * i + 1] == 0 && rb.at(off_z)[3 * i + 2] == 0, "calculate_Z: z does not close (grand product != 1)");
+        if (pub_on_device) {
+            publics.assign(rb.at(off_pub), rb.at(off_pub) + n_pub);
+            // The reference absorbs ctx.publics[i].as_elements() (stark_gen.rs:272-277): one word for a base-field value; a
+            // computed public with extension words means a malformed program (see the host-trace path above)
+            for (u32 i = 0; i < n_pub; ++i)
+                ZK_REQUIRE(rb.at(off_ext)[2 * i] == 0 && rb.at(off_ext)[2 * i + 1] == 0,
+                           "public " + std::to_string(i) + ": extension-field value (only base-field publics exist in the reference)");
         }
-        if (fr) {   // scalar-field trees: the reduced indices on the host, one round trip per tree
-            for (size_t j = 0; j < all_trees.size(); ++j) {
-                std::vector<u64> idx = F.ys;
-                for (u64& y : idx) y &= all_mask[j];
-                all_gp.push_back(group_proofs(*all_trees[j], idx));
-            }
+        for (int j = 0; j < 4; ++j) {
+            if (!fr) r[j] = rb.at(off_r[j]); else { tree[j]->root(r_host[j]); r[j] = r_host[j]; }
         }
+        F.resolve(rb);
         T.mark("openings_readback");
         S.last_timing = T.finish(nbits);
         S.t_json_begin = std::chrono::steady_clock::now();
         JOut o;
         o << "{\"rootC\":"; put_digest(o, S.const_root, fr);
-        o << ",\"root1\":"; put_digest(o, r1, fr); o << ",\"root2\":"; put_digest(o, r2, fr);
-        o << ",\"root3\":"; put_digest(o, r3, fr); o << ",\"root4\":"; put_digest(o, r4, fr);
+        o << ",\"root1\":"; put_digest(o, r[0], fr); o << ",\"root2\":"; put_digest(o, r[1], fr);
+        o << ",\"root3\":"; put_digest(o, r[2], fr); o << ",\"root4\":"; put_digest(o, r[3], fr);
         o << ",\"evals\":[";
-        for (u32 e = 0; e < n_ev; ++e) { if (e) o << ','; put_list(o, ev_host.data() + 3 * e, 3); }
+        for (u32 e = 0; e < n_ev; ++e) { if (e) o << ','; put_list(o, rb.at(off_ev) + 3 * e, 3); }
         o << ']';
-        // queries of the later steps: group proofs of the folded polynomials (fri.rs:160-181)
-        for (size_t si = 1; si < n_steps; ++si) {
-            const std::vector<GroupProof>& gp = all_gp[si - 1];
-            o << ",\"s" << si << "_root\":"; put_digest(o, F.roots[si - 1].data(), fr);
-            o << ",\"s" << si << "_vals\":[";
-            for (size_t q = 0; q < gp.size(); ++q) { if (q) o << ','; put_list(o, gp[q].row.data(), gp[q].row.size()); }
-            o << "],\"s" << si << "_siblings\":[";
-            for (size_t q = 0; q < gp.size(); ++q) { if (q) o << ','; put_path(o, gp[q], fr); }
-            o << ']';
-        }
-        {   // step 0: openings of the five trees at the query indices
-            const char* names[5] = {"1", "2", "3", "4", "C"};
-            const std::vector<GroupProof>* gp = all_gp.data() + (n_steps - 1);
-            for (int j = 0; j < 5; ++j) {
-                o << ",\"s0_vals" << names[j] << "\":[";
-                for (size_t q = 0; q < gp[j].size(); ++q) { if (q) o << ','; put_list(o, gp[j][q].row.data(), gp[j][q].row.size()); }
-                o << ']';
-            }
-            for (int j = 0; j < 5; ++j) {
-                o << ",\"s0_siblings" << names[j] << "\":[";
-                for (size_t q = 0; q < gp[j].size(); ++q) { if (q) o << ','; put_path(o, gp[j][q], fr); }
-                o << ']';
-            }
-        }
-        {
-            o << ",\"finalPol\":[";
-            for (u64 i = 0; i < n_last; ++i) { if (i) o << ','; put_list(o, last.data() + 3 * i, 3); }
-            o << ']';
-        }
+        F.put_zkin(o, rb, {"1", "2", "3", "4", "C"});
         o << ",\"publics\":"; put_list(o, publics.data(), publics.size());
         if (fr) {                                          // serializer.rs:255-262: non-GL proofs carry the prover address
             o << ",\"proverAddr\":\"";
@@ -1327,54 +1331,16 @@ char* zk_fri_prove_dev(zk_transcript_t* transcript, const uint64_t* d_pol, uint3
             FriState F;                                    // declared BEFORE the borrowed transcript: on an exception the transcript goes first and
             AnyTranscript tr(transcript);                  // flushes its deferred put while the buffers it points into (F's) still exist
             F.commit(tr, HASH_GL, K(d_pol), nbits_ext, sv, n_queries, st, nullptr);
-            std::vector<const Tree*> all_trees; std::vector<u64> all_mask;
-            for (size_t si = 1; si < n_steps; ++si) { all_trees.push_back(F.trees[si - 1].get()); all_mask.push_back((1ull << sv[si]) - 1); }
-            for (u32 j = 0; j < n_query_trees; ++j) {
-                ZK_REQUIRE(query_trees[j], "zk_fri_prove_dev: null query tree");
-                ZK_REQUIRE(query_trees[j]->height >= (1ull << sv[0]), "zk_fri_prove_dev: a query tree is shorter than the first FRI step");
-                all_trees.push_back(query_trees[j]); all_mask.push_back((1ull << sv[0]) - 1);
-            }
-            const u64 n_last = 1ull << sv.back();
-            size_t open_words = 0;
-            for (const Tree* t : all_trees) open_words += (size_t)n_queries * ((size_t)t->width + 4 * (size_t)t->depth);
-            ReadBack rb(4 * n_steps + 3 * n_last + n_queries + open_words, st);
-            std::vector<size_t> off_root(n_steps, 0), off_open(all_trees.size(), 0);
-            for (size_t si = 0; si + 1 < n_steps; ++si) off_root[si] = rb.add(F.trees[si]->gl()->root_dev(), 4);
-            const size_t off_last = rb.add(F.d_pol, 3 * n_last), off_ys = rb.add(F.d_ys.u(), n_queries);
-            std::vector<const GlTree*> mt; std::vector<u64*> mo;
-            for (size_t j = 0; j < all_trees.size(); ++j) {
-                const size_t per = (size_t)all_trees[j]->width + 4 * (size_t)all_trees[j]->depth;
-                off_open[j] = rb.words;
-                mt.push_back(all_trees[j]->gl()); mo.push_back(rb.reserve(per * n_queries));
-            }
-            GlTree::open_multi_async(mt.data(), all_mask.data(), mo.data(), (u32)mt.size(), F.d_ys.u(), n_queries, st);
+            std::vector<std::string> names;
+            for (u32 j = 0; j < n_query_trees; ++j) { F.add_query_tree(query_trees[j]); names.push_back(std::to_string(j + 1)); }
+            ReadBack rb(F.readback_words(), st);
+            F.queue(rb);
             rb.fetch();
-            auto openings = [&](JOut& o, size_t j, bool paths) {
-                const u32 depth = all_trees[j]->depth, w = all_trees[j]->width;
-                const size_t per = (size_t)w + 4 * (size_t)depth;
-                o << '[';
-                for (u32 q = 0; q < n_queries; ++q) {
-                    const u64* p = rb.at(off_open[j] + q * per);
-                    if (q) o << ',';
-                    if (!paths) { put_list(o, p, w); continue; }
-                    o << '[';
-                    for (u32 l = 0; l < depth; ++l) { if (l) o << ','; put_list(o, p + w + 4 * l, 4); }
-                    o << ']';
-                }
-                o << ']';
-            };
+            F.resolve(rb);
             JOut o;
-            o << "{\"ys\":"; put_list(o, rb.at(off_ys), n_queries);
-            for (size_t si = 1; si < n_steps; ++si) {
-                o << ",\"s" << si << "_root\":"; put_digest(o, rb.at(off_root[si - 1]), nullptr);
-                o << ",\"s" << si << "_vals\":"; openings(o, si - 1, false);
-                o << ",\"s" << si << "_siblings\":"; openings(o, si - 1, true);
-            }
-            for (u32 j = 0; j < n_query_trees; ++j) { o << ",\"s0_vals" << (size_t)(j + 1) << "\":"; openings(o, n_steps - 1 + j, false); }
-            for (u32 j = 0; j < n_query_trees; ++j) { o << ",\"s0_siblings" << (size_t)(j + 1) << "\":"; openings(o, n_steps - 1 + j, true); }
-            o << ",\"finalPol\":[";
-            for (u64 i = 0; i < n_last; ++i) { if (i) o << ','; put_list(o, rb.at(off_last) + 3 * i, 3); }
-            o << "]}";
+            o << "{\"ys\":"; put_list(o, F.ys.data(), n_queries);
+            F.put_zkin(o, rb, names);
+            o << '}';
             const std::string z = o.str();
             pool_defer_begin();
             out = (char*)malloc(z.size() + 1);

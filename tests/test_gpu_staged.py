@@ -129,12 +129,9 @@ def test_stages_are_accepted_in_the_references_order_only(zk):
     ns.free()
 
 
-def test_a_caller_with_its_own_transcript_and_fri_prove_alone(zk):
-    """What a Rust caller that keeps its own stark_gen.rs does: ITS TranscriptGL absorbs the publics and the roots commit_stage hands out and
-    squeezes the challenges it then sets; the evaluations come back from zk_stark_evals; FRI::prove runs through zk_fri_prove_dev with that
-    transcript, the context's f polynomial and the five trees.  Everything equals the one-call proof."""
-    stark, ns, cm = _setup(zk, "plookup_gl", _struct())
-    z = json.loads(ns.gen_bytes(cm))
+def _fri_prove_alone(zk, stark, ns, cm, ss, z):
+    """Drives a staged proof with a transcript of the caller's up to step52ns (checking the roots and evaluations against the one-call
+    proof z on the way) and runs FRI::prove through zk_fri_prove_dev over the context's f polynomial and its five trees -> its dict"""
     p = ns.staged(cm)
     tr = zk.TranscriptGL()
     tr.put([int(v) for v in z["publics"]])
@@ -160,11 +157,91 @@ def test_a_caller_with_its_own_transcript_and_fri_prove_alone(zk):
     tr.put([int(v) for v in out])
     chal(5); chal(6)
     p.eval(stark.STEP_52NS)
-    ss = _struct()
     fri = stark.fri_prove_dev(tr._h, p.fri_pol_dev(), ss["nBitsExt"], [s["nBits"] for s in ss["steps"]], ss["nQueries"], [p.tree(j) for j in range(1, 6)])
+    p.free()
+    return fri
+
+
+def _fri_part_equals(fri, z, ss):
+    """every key of zk_fri_prove_dev's answer against the one-call proof: the folded steps, the step-0 openings, finalPol"""
+    n_steps = len(ss["steps"])
+    assert list(fri) == (["ys"] + ["s%d_%s" % (k, w) for k in range(1, n_steps) for w in ("root", "vals", "siblings")]
+                         + ["s0_vals%d" % j for j in range(1, 6)] + ["s0_siblings%d" % j for j in range(1, 6)] + ["finalPol"])
+    for k in list(fri)[1:1 + 3 * (n_steps - 1)] + ["finalPol"]:
+        assert fri[k] == z[k], k
+    for j, nm in enumerate(["1", "2", "3", "4", "C"]):
+        assert fri["s0_vals%d" % (j + 1)] == z["s0_vals" + nm] and fri["s0_siblings%d" % (j + 1)] == z["s0_siblings" + nm]
+    assert len(fri["ys"]) == ss["nQueries"]
+
+
+def test_a_caller_with_its_own_transcript_and_fri_prove_alone(zk):
+    """What a Rust caller that keeps its own stark_gen.rs does: ITS TranscriptGL absorbs the publics and the roots commit_stage hands out and
+    squeezes the challenges it then sets; the evaluations come back from zk_stark_evals; FRI::prove runs through zk_fri_prove_dev with that
+    transcript, the context's f polynomial and the five trees.  Everything equals the one-call proof."""
+    ss = _struct()
+    stark, ns, cm = _setup(zk, "plookup_gl", ss)
+    z = json.loads(ns.gen_bytes(cm))
+    fri = _fri_prove_alone(zk, stark, ns, cm, ss, z)
     for k in ("s1_root", "s1_vals", "s1_siblings", "s2_root", "s2_vals", "s2_siblings", "finalPol"):
         assert fri[k] == z[k], k
     for j, nm in enumerate(["1", "2", "3", "4", "C"]):
         assert fri["s0_vals%d" % (j + 1)] == z["s0_vals" + nm] and fri["s0_siblings%d" % (j + 1)] == z["s0_siblings" + nm]
     assert len(fri["ys"]) == ss["nQueries"]
-    p.free(); ns.free()
+    ns.free()
+
+
+# ---- shapes of the queries that no fixture struct has: the prover's two paths share one opening and zkin writer (FriState, Openings)
+ONE_STEP = {"nBits": 10, "nBitsExt": 11, "nQueries": 8, "verificationHashType": "GL", "steps": [{"nBits": 11}]}
+# one query; the last two steps equal: the tree of step 2 has groups of ONE value (width 3), the narrowest tree a proof opens
+NARROW = {"nBits": 10, "nBitsExt": 11, "nQueries": 1, "verificationHashType": "GL", "steps": [{"nBits": 11}, {"nBits": 7}, {"nBits": 7}]}
+
+
+def _oracle_zkin(orc, ss):
+    """the oracle prover's zkin of the fib fixture under ss"""
+    sys.path.insert(0, str(ROOT / "oracle"))
+    import stark_prover as SP
+    pil_f, const_f, cm_f = CASES["fib_gl"]
+    b = orc if ss["verificationHashType"] == "GL" else SP.BN128Backend(orc)
+    su = SP.setup(json.load(open(D / pil_f)), D / const_f, ss, b)
+    proof = SP.stark_gen(D / cm_f, su, ss, b)
+    return SP.to_zkin(proof) if b is orc else SP.to_zkin_bn128(proof, b, "1")
+
+
+def _one_call_equals_oracle(zk, orc, ss):
+    stark, ns, cm = _setup(zk, "fib_gl", ss)
+    exp = _oracle_zkin(orc, ss)
+    got = json.loads(ns.gen_bytes(cm))
+    assert list(got.keys()) == list(exp.keys())                               # serializer.rs key order
+    for k in exp:
+        assert got[k] == exp[k], k
+    return stark, ns, cm, got
+
+
+def test_a_single_fri_step(zk, orc):
+    """steps = [nBitsExt]: no folded polynomial has a tree, so the zkin has no s1_* member, every opening is a step-0 opening and finalPol
+    is the whole polynomial.  One-call proof == oracle zkin; zk_fri_prove_dev == the one-call proof key by key."""
+    stark, ns, cm, z = _one_call_equals_oracle(zk, orc, ONE_STEP)
+    assert not [k for k in z if k.startswith("s") and not k.startswith("s0_")]
+    assert len(z["finalPol"]) == 1 << ONE_STEP["nBitsExt"]
+    assert all(len(z[k]) == ONE_STEP["nQueries"] for k in z if k.startswith("s0_"))
+    _fri_part_equals(_fri_prove_alone(zk, stark, ns, cm, ONE_STEP, z), z, ONE_STEP)
+    ns.free()
+
+
+def test_one_query_and_a_tree_of_width_three(zk, orc):
+    """nQueries = 1, steps 11 / 7 / 7: the tree of the second folded polynomial has groups of one extension value.  One-call proof ==
+    oracle zkin; zk_fri_prove_dev == the one-call proof key by key."""
+    stark, ns, cm, z = _one_call_equals_oracle(zk, orc, NARROW)
+    assert [len(r) for r in z["s2_vals"]] == [3] and [len(r) for r in z["s1_vals"]] == [48]
+    assert len(z["s2_siblings"][0]) == 7 and len(z["finalPol"]) == 1 << 7
+    _fri_part_equals(_fri_prove_alone(zk, stark, ns, cm, NARROW, z), z, NARROW)
+    ns.free()
+
+
+def test_one_query_and_a_tree_of_width_three_bn128(zk, orc):
+    """the same struct with scalar-field trees: the 16-ary levels (64 words each) of a path travel through the same opening writer.
+    One-call proof == oracle zkin (there is no scalar-field zk_fri_prove_dev)."""
+    stark, ns, cm, z = _one_call_equals_oracle(zk, orc, dict(NARROW, verificationHashType="BN128"))
+    assert [len(r) for r in z["s2_vals"]] == [3] and [len(lvl) for lvl in z["s2_siblings"][0]] == [16, 16]   # 2^7 leaves: two levels of arity 16
+    assert z["proverAddr"] == "1"
+    ns.free()
