@@ -9,6 +9,8 @@ using gl::add_word;
 // each) and the state words x_j given as 32-bit halves.  Six 64-bit accumulators take the 22x32-bit partial products straight
 // from v_mad_u64_u32 (n * 2^54 < 2^64 for n <= 512: no carries); ONE recombination and ONE reduction per dot product instead
 // of a multiplication with a reduction per term.
+// host: a canonical constant -> its two table words, limbs 0 and 1 in the halves of the first, limb 2 in the second
+inline void acc_split(u64 c, u64* out /* 2 words */) { out[0] = (c & 0x3FFFFF) | (((c >> 22) & 0x3FFFFF) << 32); out[1] = c >> 44; }
 struct Acc6 { u64 a00, a10, a20, a01, a11, a21; };   // a[i][h]: limb i of the constants x half h of the words
 __device__ __forceinline__ void acc_zero(Acc6& A) { A.a00 = A.a10 = A.a20 = A.a01 = A.a11 = A.a21 = 0; }
 __device__ __forceinline__ void acc_word(Acc6& A, u64 s) { A.a00 = (u32)s; A.a01 = s >> 32; A.a10 = A.a20 = A.a11 = A.a21 = 0; }   // 1 * s
@@ -37,7 +39,8 @@ __device__ __forceinline__ u64 mul32(u32 a, u32 b) {
 }
 // V = sum_{i,h} a[i][h] 2^(22 i + 32 h).  The six accumulators sit at bit offsets 0, 22, 44 = 32 + 12, 32, 54 = 32 + 22 and
 // 76 = 64 + 12: their 32-bit halves, shifted by 22 or 12 bits, are accumulated by multiply-adds into four 64-bit columns
-// Z0..Z3 spaced 32 bits apart (every column < 2^61), three more multiply-adds carry each column's high word into the next,
+// Z0..Z3 spaced 32 bits apart (every column < 2^64 for n <= 512 terms: a column is one accumulator, < 2^63, plus three words shifted
+// by at most 22 bits, < 3 * 2^54), three more multiply-adds carry each column's high word into the next,
 // and with t = 2^32, t^2 = t - 1, t^3 = -1:  V = (w0 + w1 t) + w2 (2^32 - 1) - Y3  -- 11 multiply-adds and one reduction
 // where the 128-bit shifts and additions of the first version took 56 instructions.  Any u64 in, nc out.
 __device__ __forceinline__ u64 acc_finish(const Acc6& A) {

@@ -900,7 +900,7 @@ void build_coop_image(u64* tab) {
         const u64 c = ZK_POSEIDON_C[i], c2 = gl::hmul(c, c), c3 = gl::hmul(c2, c), c7 = gl::hmul(gl::hmul(c3, c3), c), k = ZK_POSEIDON_C[12 + i];
         tab[T_K0 + i - 8] = c7 + k >= GL_P || c7 + k < c7 ? c7 + k - GL_P : c7 + k;
     }
-    auto split = [&](int at, u64 c) { tab[at] = (c & 0x3FFFFF) | (((c >> 22) & 0x3FFFFF) << 32); tab[at + 1] = c >> 44; };
+    auto split = [&](int at, u64 c) { acc_split(c, tab + at); };
     for (int i = 0; i < 12; ++i)
         for (int j = 0; j < 12; ++j) split(T_PT + 2 * (12 * i + j), ZK_POSEIDON_P[12 * j + i]);
     for (int r = 0; r < 22; ++r) {
