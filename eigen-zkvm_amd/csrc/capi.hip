@@ -2,6 +2,7 @@
 // (Device memory, streams, error capture: devmem.hip.  Merkle trees and transcripts: commit.hip.)
 #include "zk_internal.h"
 #include "commit.h"
+#include "curve.h"
 #include "pil_check.h"
 #include "../../include/zkgpu.h"
 #include <algorithm>
@@ -267,82 +268,108 @@ int zk_stark_qsplit_dev(const uint64_t* d_qq1, uint32_t nbits, uint32_t q_dim, u
     return guard([&] { qsplit_dev((const u64*)d_qq1, nbits, q_dim, q_deg, (u64*)d_qq2, on_stream((hipStream_t)stream)); });
 }
 
-int zk_msm_g1_bn254_dev(const void* d_bases, const void* d_scalars, uint64_t n, void* d_out, void* stream) {
-    return guard([&] { msm_g1_bn254_dev(d_bases, d_scalars, n, d_out, on_stream((hipStream_t)stream)); });
-}
-int zk_g1_bn254_mul_generator_dev(const uint64_t* d_k, uint64_t n, void* d_bases, void* stream) {
-    return guard([&] { g1_bn254_mul_generator_dev((const u64*)d_k, n, d_bases, on_stream((hipStream_t)stream)); });
-}
-int zk_msm_g1_bn254(const void* bases, const void* scalars, uint64_t n, void* out, int* is_infinity) {
+// ---- the curves (curve.h): one function per contract, taking the curve, the group and the sizes from the table; the exported names are
+// stamped below as one-line calls ----
+static int msm_host(CurveId id, Group g, const void* bases, const void* scalars, uint64_t n, void* out, int* is_infinity) {
     return guard([&] {
         ZK_REQUIRE(out && is_infinity, "msm: null output");
         ZK_REQUIRE(n == 0 || (bases && scalars), "msm: null input");
-        if (n == 0) { memset(out, 0, 64); *is_infinity = 1; return; }  // empty sum
+        const size_t pb = curve(id).point_bytes(g);
+        if (n == 0) { memset(out, 0, pb); *is_infinity = 1; return; }  // empty sum
         DevBuf db, ds, dout;
-        db.reserve(n * 64); ds.reserve(n * 32); dout.reserve(68);
-        ZK_HIP(hipMemcpy(db.p, bases, n * 64, hipMemcpyHostToDevice));
+        db.reserve(n * pb); ds.reserve(n * 32); dout.reserve(pb + 4);
+        ZK_HIP(hipMemcpy(db.p, bases, n * pb, hipMemcpyHostToDevice));
         ZK_HIP(hipMemcpy(ds.p, scalars, n * 32, hipMemcpyHostToDevice));
-        msm_g1_bn254_dev(db.p, ds.p, n, dout.p, nullptr);
-        uint32_t h[17];
+        curve(id).group(g).msm_dev(db.p, ds.p, n, dout.p, nullptr);
+        std::vector<uint32_t> h(pb / 4 + 1);                           // the point and the flag word
         ZK_HIP(hipStreamSynchronize(nullptr));
-        ZK_HIP(hipMemcpy(h, dout.p, 68, hipMemcpyDeviceToHost));
-        memcpy(out, h, 64);
-        *is_infinity = (int)h[16];
+        ZK_HIP(hipMemcpy(h.data(), dout.p, pb + 4, hipMemcpyDeviceToHost));
+        memcpy(out, h.data(), pb);
+        *is_infinity = (int)h[pb / 4];
     });
 }
-
-// G2 variants: same contract, points of PB bytes
-#define ZK_MSM_G2(NAME, PB)                                                                                               \
-    int zk_g2_##NAME##_mul_generator_dev(const uint64_t* d_k, uint64_t n, void* d_bases, void* stream) {                 \
-        return guard([&] { g2_##NAME##_mul_generator_dev((const u64*)d_k, n, d_bases, on_stream((hipStream_t)stream)); });          \
-    }                                                                                                                   \
-    int zk_msm_g2_##NAME##_dev(const void* d_bases, const void* d_scalars, uint64_t n, void* d_out, void* stream) {       \
-        return guard([&] { msm_g2_##NAME##_dev(d_bases, d_scalars, n, d_out, on_stream((hipStream_t)stream)); });                   \
-    }                                                                                                                   \
-    int zk_msm_g2_##NAME(const void* bases, const void* scalars, uint64_t n, void* out, int* is_infinity) {               \
-        return guard([&] {                                                                                              \
-            ZK_REQUIRE(out && is_infinity, "msm: null output");                                                        \
-            ZK_REQUIRE(n == 0 || (bases && scalars), "msm: null input");                                               \
-            if (n == 0) { memset(out, 0, PB); *is_infinity = 1; return; }                                               \
-            DevBuf db, ds, dout;                                                                                        \
-            db.reserve(n * PB); ds.reserve(n * 32); dout.reserve(PB + 4);                                               \
-            ZK_HIP(hipMemcpy(db.p, bases, n * PB, hipMemcpyHostToDevice));                                              \
-            ZK_HIP(hipMemcpy(ds.p, scalars, n * 32, hipMemcpyHostToDevice));                                            \
-            msm_g2_##NAME##_dev(db.p, ds.p, n, dout.p, nullptr);                                                        \
-            uint32_t h[PB / 4 + 1];                                                                                     \
-            ZK_HIP(hipStreamSynchronize(nullptr));                                                                      \
-            ZK_HIP(hipMemcpy(h, dout.p, PB + 4, hipMemcpyDeviceToHost));                                                \
-            memcpy(out, h, PB);                                                                                         \
-            *is_infinity = (int)h[PB / 4];                                                                              \
-        });                                                                                                             \
+static int msm_device(CurveId id, Group g, const void* d_bases, const void* d_scalars, uint64_t n, void* d_out, void* stream) {
+    return guard([&] { curve(id).group(g).msm_dev(d_bases, d_scalars, n, d_out, on_stream((hipStream_t)stream)); });
+}
+static int mul_generator(CurveId id, Group g, bool full_width, const uint64_t* d_k, uint64_t n, void* d_bases, void* stream) {
+    return guard([&] {
+        const GroupOps& o = curve(id).group(g);
+        if (full_width) ZK_REQUIRE((d_k && d_bases) || n == 0, "mul_generator: null argument");
+        (full_width ? o.mul_generator_fr_dev : o.mul_generator_dev)((const u64*)d_k, n, d_bases, on_stream((hipStream_t)stream));
+    });
+}
+static int msm_table_build(CurveId id, Group g, const void* d_bases, uint64_t table_n, void* d_table, void* stream) {
+    return guard([&] { ZK_REQUIRE(d_bases && d_table, "msm table: null argument"); curve(id).group(g).fixed_prepare_dev(d_bases, table_n, d_table, on_stream((hipStream_t)stream)); });
+}
+static int msm_table(CurveId id, Group g, const void* d_table, uint64_t table_n, uint64_t offset, const void* d_scalars, uint64_t n, void* d_out, void* stream) {
+    return guard([&] { ZK_REQUIRE(d_table && d_scalars && d_out, "msm table: null argument"); curve(id).group(g).fixed_dev(d_table, table_n, offset, d_scalars, n, d_out, on_stream((hipStream_t)stream)); });
+}
+static int fr_ntt_device(CurveId id, uint64_t* d, uint32_t log_n, int inverse, int coset, void* stream) {
+    return guard([&] { ZK_REQUIRE(d, "fr ntt: null data"); curve(id).groth16().fr_ntt_dev((u64*)d, (int)log_n, inverse != 0, coset != 0, on_stream((hipStream_t)stream)); });
+}
+static int fr_ntt_host(CurveId id, uint64_t* data, uint32_t log_n, int inverse, int coset) {
+    return guard([&] {
+        ZK_REQUIRE(data, "fr ntt: null data");
+        ZK_REQUIRE(log_n <= 32, "fr ntt: domain too large");
+        const size_t bytes = ((size_t)32) << log_n;
+        DevBuf d; d.reserve(bytes);
+        ZK_HIP(hipMemcpy(d.p, data, bytes, hipMemcpyHostToDevice));
+        curve(id).groth16().fr_ntt_dev((u64*)d.p, (int)log_n, inverse != 0, coset != 0, nullptr);
+        ZK_HIP(hipStreamSynchronize(nullptr));
+        ZK_HIP(hipMemcpy(data, d.p, bytes, hipMemcpyDeviceToHost));
+    });
+}
+static int fr_quotient(CurveId id, uint64_t* a, const uint64_t* b, const uint64_t* c, uint32_t log_n, void* stream) {
+    return guard([&] { ZK_REQUIRE(a && b && c, "fr quotient: null data"); curve(id).groth16().fr_quotient_dev((u64*)a, (const u64*)b, (const u64*)c, (int)log_n, on_stream((hipStream_t)stream)); });
+}
+static int fq_convert(CurveId id, void* d, uint64_t n, int to_mont, void* stream) {
+    return guard([&] {
+        ZK_REQUIRE(d || n == 0, "fq convert: null data");
+        const MsmOps& o = curve(id).msm();
+        (to_mont ? o.fq_canon_to_mont_dev : o.fq_mont_to_canon_dev)(d, n, on_stream((hipStream_t)stream));
+    });
+}
+static int pairing_device(CurveId id, const void* d_g1, const void* d_g2, uint64_t n, void* d_gt, int with_final_exp, void* stream) {
+    return guard([&] {
+        ZK_REQUIRE(n == 0 || (d_g1 && d_g2 && d_gt), "pairing: null argument");
+        pairing_dev(curve(id), d_g1, d_g2, n, d_gt, with_final_exp, on_stream((hipStream_t)stream));
+    });
+}
+static int pairing_host(CurveId id, const void* g1, const void* g2, uint64_t n, void* gt_out, int with_final_exp) {
+    return guard([&] {
+        ZK_REQUIRE(n == 0 || (g1 && g2 && gt_out), "pairing: null argument");
+        if (n == 0) return;
+        const Curve& cv = curve(id);
+        DevBuf d1, d2, dg;
+        d1.reserve(n * cv.point_bytes(G1)); d2.reserve(n * cv.point_bytes(G2)); dg.reserve(n * cv.gt_bytes());
+        h2d_sync(d1.p, g1, n * cv.point_bytes(G1)); h2d_sync(d2.p, g2, n * cv.point_bytes(G2));
+        pairing_dev(cv, d1.p, d2.p, n, dg.p, with_final_exp, cur_stream());
+        d2h_sync(gt_out, dg.p, n * cv.gt_bytes());
+    });
+}
+#define ZK_GROUP_API(GN, NAME, ID, G)                                                                                                         \
+    int zk_msm_##GN##_##NAME(const void* bases, const void* scalars, uint64_t n, void* out, int* is_infinity) { return msm_host(ID, G, bases, scalars, n, out, is_infinity); } \
+    int zk_msm_##GN##_##NAME##_dev(const void* d_bases, const void* d_scalars, uint64_t n, void* d_out, void* stream) { return msm_device(ID, G, d_bases, d_scalars, n, d_out, stream); } \
+    int zk_##GN##_##NAME##_mul_generator_dev(const uint64_t* d_k, uint64_t n, void* d_bases, void* stream) { return mul_generator(ID, G, false, d_k, n, d_bases, stream); } \
+    int zk_##GN##_##NAME##_mul_generator_fr_dev(const uint64_t* d_k, uint64_t n, void* d_bases, void* stream) { return mul_generator(ID, G, true, d_k, n, d_bases, stream); } \
+    size_t zk_msm_##GN##_##NAME##_table_bytes(uint64_t table_n) { return curve(ID).group(G).fixed_table_bytes(table_n); }                     \
+    int zk_msm_##GN##_##NAME##_table_build_dev(const void* d_bases, uint64_t table_n, void* d_table, void* stream) { return msm_table_build(ID, G, d_bases, table_n, d_table, stream); } \
+    int zk_msm_##GN##_##NAME##_table_dev(const void* d_table, uint64_t table_n, uint64_t offset, const void* d_scalars, uint64_t n, void* d_out, void* stream) { \
+        return msm_table(ID, G, d_table, table_n, offset, d_scalars, n, d_out, stream);                                                       \
     }
-ZK_MSM_G2(bn254, 128)
-ZK_MSM_G2(bls12_381, 192)
-#undef ZK_MSM_G2
-
-int zk_g1_bls12_381_mul_generator_dev(const uint64_t* d_k, uint64_t n, void* d_bases, void* stream) {
-    return guard([&] { g1_bls12_381_mul_generator_dev((const u64*)d_k, n, d_bases, on_stream((hipStream_t)stream)); });
-}
-int zk_msm_g1_bls12_381_dev(const void* d_bases, const void* d_scalars, uint64_t n, void* d_out, void* stream) {
-    return guard([&] { msm_g1_bls12_381_dev(d_bases, d_scalars, n, d_out, on_stream((hipStream_t)stream)); });
-}
-int zk_msm_g1_bls12_381(const void* bases, const void* scalars, uint64_t n, void* out, int* is_infinity) {
-    return guard([&] {
-        ZK_REQUIRE(out && is_infinity, "msm: null output");
-        ZK_REQUIRE(n == 0 || (bases && scalars), "msm: null input");
-        if (n == 0) { memset(out, 0, 96); *is_infinity = 1; return; }  // empty sum
-        DevBuf db, ds, dout;
-        db.reserve(n * 96); ds.reserve(n * 32); dout.reserve(100);
-        ZK_HIP(hipMemcpy(db.p, bases, n * 96, hipMemcpyHostToDevice));
-        ZK_HIP(hipMemcpy(ds.p, scalars, n * 32, hipMemcpyHostToDevice));
-        msm_g1_bls12_381_dev(db.p, ds.p, n, dout.p, nullptr);
-        uint32_t h[25];
-        ZK_HIP(hipStreamSynchronize(nullptr));
-        ZK_HIP(hipMemcpy(h, dout.p, 100, hipMemcpyDeviceToHost));
-        memcpy(out, h, 96);
-        *is_infinity = (int)h[24];
-    });
-}
+#define ZK_CURVE_API(NAME, ID)                                                                                                                \
+    ZK_GROUP_API(g1, NAME, ID, G1)                                                                                                            \
+    ZK_GROUP_API(g2, NAME, ID, G2)                                                                                                            \
+    int zk_fr_##NAME##_ntt_dev(uint64_t* d, uint32_t log_n, int inverse, int coset, void* stream) { return fr_ntt_device(ID, d, log_n, inverse, coset, stream); } \
+    int zk_fr_##NAME##_ntt(uint64_t* data, uint32_t log_n, int inverse, int coset) { return fr_ntt_host(ID, data, log_n, inverse, coset); }   \
+    int zk_fr_##NAME##_quotient_dev(uint64_t* a, const uint64_t* b, const uint64_t* c, uint32_t log_n, void* stream) { return fr_quotient(ID, a, b, c, log_n, stream); } \
+    int zk_fq_##NAME##_convert_dev(void* d, uint64_t n, int to_mont, void* stream) { return fq_convert(ID, d, n, to_mont, stream); }          \
+    int zk_pairing_##NAME##_dev(const void* d_g1, const void* d_g2, uint64_t n, void* d_gt, int with_final_exp, void* stream) { return pairing_device(ID, d_g1, d_g2, n, d_gt, with_final_exp, stream); } \
+    int zk_pairing_##NAME(const void* g1, const void* g2, uint64_t n, void* gt_out, int with_final_exp) { return pairing_host(ID, g1, g2, n, gt_out, with_final_exp); }
+ZK_CURVE_API(bn254, CURVE_BN254)
+ZK_CURVE_API(bls12_381, CURVE_BLS12_381)
+#undef ZK_CURVE_API
+#undef ZK_GROUP_API
 
 // ---- scalar-field hashing (verificationHashType "BN128" / "BLS12381"): two name families over one implementation (commit.hip) ----
 // one permutation / one row from host buffers, on the null stream
@@ -469,20 +496,6 @@ int zk_stark_calculate_z_dev(const uint64_t* d_num3, const uint64_t* d_den3, uin
     });
 }
 
-
-#define ZK_MSM_TABLE_API(NAME)                                                                                              \
-    size_t zk_msm_##NAME##_table_bytes(uint64_t table_n) { return msm_##NAME##_fixed_table_bytes(table_n); }                \
-    int zk_msm_##NAME##_table_build_dev(const void* d_bases, uint64_t table_n, void* d_table, void* stream) {               \
-        return guard([&] { ZK_REQUIRE(d_bases && d_table, "msm table: null argument"); msm_##NAME##_fixed_prepare_dev(d_bases, table_n, d_table, on_stream((hipStream_t)stream)); }); \
-    }                                                                                                                       \
-    int zk_msm_##NAME##_table_dev(const void* d_table, uint64_t table_n, uint64_t offset, const void* d_scalars, uint64_t n, void* d_out, void* stream) { \
-        return guard([&] { ZK_REQUIRE(d_table && d_scalars && d_out, "msm table: null argument"); msm_##NAME##_fixed_dev(d_table, table_n, offset, d_scalars, n, d_out, on_stream((hipStream_t)stream)); }); \
-    }
-ZK_MSM_TABLE_API(g1_bn254)
-ZK_MSM_TABLE_API(g2_bn254)
-ZK_MSM_TABLE_API(g1_bls12_381)
-ZK_MSM_TABLE_API(g2_bls12_381)
-#undef ZK_MSM_TABLE_API
 // ---- compressor12 exec (compressor12.hip) ----------------------------------------------------------------------
 struct zk_c12_exec { C12Exec* impl; };
 zk_c12_exec_t* zk_c12_exec_new(const char* exec_json, size_t len, uint64_t n_witness) {
@@ -552,57 +565,26 @@ int zk_c12_sigma_dev(const uint32_t* d_s_map, uint64_t n_used, uint32_t n_bits, 
 }
 
 // ---- Groth16 (groth16.hip) ------------------------------------------------------------------------------------
-#define ZK_FR_NTT(NAME)                                                                                                  \
-    int zk_fr_##NAME##_ntt_dev(uint64_t* d, uint32_t log_n, int inverse, int coset, void* stream) {                      \
-        return guard([&] { ZK_REQUIRE(d, "fr ntt: null data"); fr_##NAME##_ntt_dev((u64*)d, (int)log_n, inverse != 0, coset != 0, on_stream((hipStream_t)stream)); }); \
-    }                                                                                                                    \
-    int zk_fr_##NAME##_ntt(uint64_t* data, uint32_t log_n, int inverse, int coset) {                                     \
-        return guard([&] {                                                                                               \
-            ZK_REQUIRE(data, "fr ntt: null data");                                                                       \
-            ZK_REQUIRE(log_n <= 32, "fr ntt: domain too large");                                                         \
-            const size_t bytes = ((size_t)32) << log_n;                                                                  \
-            DevBuf d; d.reserve(bytes);                                                                                  \
-            ZK_HIP(hipMemcpy(d.p, data, bytes, hipMemcpyHostToDevice));                                                  \
-            fr_##NAME##_ntt_dev((u64*)d.p, (int)log_n, inverse != 0, coset != 0, nullptr);                               \
-            ZK_HIP(hipStreamSynchronize(nullptr));                                                                       \
-            ZK_HIP(hipMemcpy(data, d.p, bytes, hipMemcpyDeviceToHost));                                                  \
-        });                                                                                                              \
-    }                                                                                                                    \
-    int zk_fr_##NAME##_quotient_dev(uint64_t* a, const uint64_t* b, const uint64_t* c, uint32_t log_n, void* stream) {   \
-        return guard([&] { ZK_REQUIRE(a && b && c, "fr quotient: null data"); fr_##NAME##_quotient_dev((u64*)a, (const u64*)b, (const u64*)c, (int)log_n, on_stream((hipStream_t)stream)); }); \
-    }
-ZK_FR_NTT(bn254)
-ZK_FR_NTT(bls12_381)
-#undef ZK_FR_NTT
-
-int zk_fq_bn254_convert_dev(void* d, uint64_t n, int to_mont, void* stream) {
-    return guard([&] { ZK_REQUIRE(d || n == 0, "fq convert: null data"); if (to_mont) fq_bn254_canon_to_mont_dev(d, n, on_stream((hipStream_t)stream)); else fq_bn254_mont_to_canon_dev(d, n, on_stream((hipStream_t)stream)); });
-}
-int zk_fq_bls12_381_convert_dev(void* d, uint64_t n, int to_mont, void* stream) {
-    return guard([&] { ZK_REQUIRE(d || n == 0, "fq convert: null data"); if (to_mont) fq_bls12_381_canon_to_mont_dev(d, n, on_stream((hipStream_t)stream)); else fq_bls12_381_mont_to_canon_dev(d, n, on_stream((hipStream_t)stream)); });
-}
-struct zk_groth16_setup { Groth16Setup* impl; };
 zk_groth16_setup_t* zk_groth16_setup_new(const char* curve, const void* r1cs, size_t r1cs_len, const void* params, size_t params_len) {
     zk_groth16_setup_t* out = nullptr;
-    if (guard([&] { Groth16Setup* g = groth16_setup_new(curve, r1cs, r1cs_len, params, params_len); out = new zk_groth16_setup{g}; }) != 0) return nullptr;
+    if (guard([&] { out = groth16_setup_new(curve, r1cs, r1cs_len, params, params_len); }) != 0) return nullptr;
     return out;
 }
 int zk_groth16_setup_info(const zk_groth16_setup_t* s, uint32_t* n_wires, uint32_t* n_inputs, uint32_t* domain_log) {
     return guard([&] {
-        ZK_REQUIRE(s && s->impl, "groth16: null setup");
-        if (n_wires) *n_wires = s->impl->num_wires();
-        if (n_inputs) *n_inputs = s->impl->num_inputs();
-        if (domain_log) *domain_log = s->impl->domain_log();
+        ZK_REQUIRE(s, "groth16: null setup");
+        if (n_wires) *n_wires = s->num_wires();
+        if (n_inputs) *n_inputs = s->num_inputs();
+        if (domain_log) *domain_log = s->domain_log();
     });
 }
-static char* groth16_prove_any(zk_groth16_setup_t* s, const void* witness, bool on_device, uint64_t n_wires, const uint64_t* r, const uint64_t* s_, void* proof, uint64_t* d_h) {
+static char* groth16_prove_any(zk_groth16_setup_t* g, const void* witness, bool on_device, uint64_t n_wires, const uint64_t* r, const uint64_t* s_, void* proof, uint64_t* d_h) {
     char* out = nullptr;
     if (guard([&] {
-            ZK_REQUIRE(s && s->impl, "groth16: null setup");
+            ZK_REQUIRE(g, "groth16: null setup");
             ZK_REQUIRE(witness && r && s_, "groth16: null argument");
-            Groth16Setup* g = s->impl;
             ZK_REQUIRE(n_wires == g->num_wires(), "groth16: the witness has " + std::to_string(n_wires) + " values, the circuit has " + std::to_string(g->num_wires()) + " wires");
-            auto lt = [&](const u32* v) { for (int i = 7; i >= 0; --i) { if (v[i] < g->modulus[i]) return true; if (v[i] > g->modulus[i]) return false; } return false; };
+            auto lt = [&](const u32* v) { return g->curve->fr_canonical(v); };
             ZK_REQUIRE(lt((const u32*)r) && lt((const u32*)s_), "groth16: r and s must be canonical field elements");
             if (!on_device) {   // Fr::from_repr (reader.rs:131-134) rejects non-canonical values
                 const u32* w = (const u32*)witness;
@@ -626,38 +608,28 @@ int zk_groth16_wtns_payload(const void* wtns, size_t len, const char* curve, uin
     return guard([&] { ZK_REQUIRE(wtns && offset && n_values, "wtns: null argument"); groth16_wtns_payload(wtns, len, curve, offset, n_values); });
 }
 int zk_groth16_setup_free(zk_groth16_setup_t* s) {
-    return guard([&] { if (s) { delete s->impl; delete s; } });
+    return guard([&] { delete s; });
 }
 
 // ---- Groth16 key generation (fixedbase_impl.hip.h, groth16_keygen_impl.hip.h) ------------------------------------
-#define ZK_MUL_GEN_FR(NAME)                                                                                              \
-    int zk_##NAME##_mul_generator_fr_dev(const uint64_t* d_k, uint64_t n, void* d_bases, void* stream) {                 \
-        return guard([&] { ZK_REQUIRE((d_k && d_bases) || n == 0, "mul_generator: null argument"); NAME##_mul_generator_fr_dev((const u64*)d_k, n, d_bases, on_stream((hipStream_t)stream)); }); \
-    }
-ZK_MUL_GEN_FR(g1_bn254)
-ZK_MUL_GEN_FR(g2_bn254)
-ZK_MUL_GEN_FR(g1_bls12_381)
-ZK_MUL_GEN_FR(g2_bls12_381)
-#undef ZK_MUL_GEN_FR
-struct zk_groth16_keygen { Groth16Key* impl; };
 zk_groth16_keygen_t* zk_groth16_keygen_new(const char* curve, const void* r1cs, size_t r1cs_len, const uint64_t* trapdoor) {
     zk_groth16_keygen_t* out = nullptr;
-    if (guard([&] { std::unique_ptr<Groth16Key> k(groth16_keygen_new(curve, r1cs, r1cs_len, trapdoor)); out = new zk_groth16_keygen{k.get()}; k.release(); }) != 0) return nullptr;
+    if (guard([&] { out = groth16_keygen_new(curve, r1cs, r1cs_len, trapdoor); }) != 0) return nullptr;
     return out;
 }
-size_t zk_groth16_keygen_params_size(const zk_groth16_keygen_t* k) { return k && k->impl ? k->impl->params.size() : 0; }
+size_t zk_groth16_keygen_params_size(const zk_groth16_keygen_t* k) { return k ? k->params.size() : 0; }
 int zk_groth16_keygen_params(const zk_groth16_keygen_t* k, void* out, size_t cap) {
     return guard([&] {
-        ZK_REQUIRE(k && k->impl && out, "groth16 keygen: null argument");
-        ZK_REQUIRE(cap >= k->impl->params.size(), "groth16 keygen: the buffer holds " + std::to_string(cap) + " bytes, the key has " + std::to_string(k->impl->params.size()));
-        memcpy(out, k->impl->params.data(), k->impl->params.size());
+        ZK_REQUIRE(k && out, "groth16 keygen: null argument");
+        ZK_REQUIRE(cap >= k->params.size(), "groth16 keygen: the buffer holds " + std::to_string(cap) + " bytes, the key has " + std::to_string(k->params.size()));
+        memcpy(out, k->params.data(), k->params.size());
     });
 }
 char* zk_groth16_keygen_vk_json(const zk_groth16_keygen_t* k, int to_hex) {
     char* out = nullptr;
     if (guard([&] {
-            ZK_REQUIRE(k && k->impl, "groth16 keygen: null handle");
-            const std::string js = groth16_keygen_vk_json(*k->impl, to_hex != 0);
+            ZK_REQUIRE(k, "groth16 keygen: null handle");
+            const std::string js = groth16_keygen_vk_json(*k, to_hex != 0);
             out = (char*)malloc(js.size() + 1);
             ZK_REQUIRE(out, "out of memory");
             memcpy(out, js.c_str(), js.size() + 1);
@@ -665,58 +637,36 @@ char* zk_groth16_keygen_vk_json(const zk_groth16_keygen_t* k, int to_hex) {
     return out;
 }
 int zk_groth16_keygen_timing(const zk_groth16_keygen_t* k, double ms[5]) {
-    return guard([&] { ZK_REQUIRE(k && k->impl && ms, "groth16 keygen: null argument"); for (int i = 0; i < 5; ++i) ms[i] = k->impl->ms[i]; });
+    return guard([&] { ZK_REQUIRE(k && ms, "groth16 keygen: null argument"); for (int i = 0; i < 5; ++i) ms[i] = k->ms[i]; });
 }
 int zk_groth16_keygen_free(zk_groth16_keygen_t* k) {
-    return guard([&] { if (k) { delete k->impl; delete k; } });
+    return guard([&] { delete k; });
 }
 
 // ---- pairings and Groth16 verification (pairing.hip) ----
-struct zk_groth16_vk { zk::Groth16Vk* impl; };
-#define ZK_PAIRING(NAME, CURVE, NLW)                                                                                              \
-    int zk_pairing_##NAME##_dev(const void* d_g1, const void* d_g2, uint64_t n, void* d_gt, int with_final_exp, void* stream) {   \
-        return guard([&] {                                                                                                        \
-            ZK_REQUIRE(n == 0 || (d_g1 && d_g2 && d_gt), "pairing: null argument");                                               \
-            pairing_dev(CURVE, d_g1, d_g2, n, d_gt, with_final_exp, on_stream((hipStream_t)stream));                              \
-        });                                                                                                                       \
-    }                                                                                                                             \
-    int zk_pairing_##NAME(const void* g1, const void* g2, uint64_t n, void* gt_out, int with_final_exp) {                         \
-        return guard([&] {                                                                                                        \
-            ZK_REQUIRE(n == 0 || (g1 && g2 && gt_out), "pairing: null argument");                                                 \
-            if (n == 0) return;                                                                                                   \
-            DevBuf d1, d2, dg;                                                                                                    \
-            d1.reserve(n * 8 * NLW); d2.reserve(n * 16 * NLW); dg.reserve(n * 48 * NLW);                                          \
-            h2d_sync(d1.p, g1, n * 8 * NLW); h2d_sync(d2.p, g2, n * 16 * NLW);                                                    \
-            pairing_dev(CURVE, d1.p, d2.p, n, dg.p, with_final_exp, cur_stream());                                                \
-            d2h_sync(gt_out, dg.p, n * 48 * NLW);                                                                                 \
-        });                                                                                                                       \
-    }
-ZK_PAIRING(bn254, "BN128", 8)
-ZK_PAIRING(bls12_381, "BLS12381", 12)
-#undef ZK_PAIRING
 zk_groth16_vk_t* zk_groth16_vk_new(const char* curve, const char* vk_json) {
     zk_groth16_vk_t* h = nullptr;
-    if (guard([&] { Groth16Vk* v = groth16_vk_new(curve, vk_json); h = new zk_groth16_vk{v}; }) != 0) return nullptr;
+    if (guard([&] { h = groth16_vk_new(curve, vk_json); }) != 0) return nullptr;
     return h;
 }
 int zk_groth16_vk_info(const zk_groth16_vk_t* vk, uint32_t* n_public, uint32_t* proof_bytes, uint32_t* gt_bytes) {
-    return guard([&] { ZK_REQUIRE(vk && vk->impl, "groth16 verify: null key"); groth16_vk_info(vk->impl, n_public, proof_bytes, gt_bytes); });
+    return guard([&] { ZK_REQUIRE(vk, "groth16 verify: null key"); groth16_vk_info(vk, n_public, proof_bytes, gt_bytes); });
 }
 int zk_groth16_vk_free(zk_groth16_vk_t* vk) {
-    return guard([&] { if (vk) { groth16_vk_free(vk->impl); delete vk; } });
+    return guard([&] { delete vk; });
 }
 int zk_groth16_verify_batch(const zk_groth16_vk_t* vk, const void* proofs, const void* publics, uint64_t n, int* verdicts) {
-    return guard([&] { ZK_REQUIRE(vk && vk->impl, "groth16 verify: null key"); groth16_verify_batch(vk->impl, proofs, publics, n, verdicts); });
+    return guard([&] { ZK_REQUIRE(vk, "groth16 verify: null key"); groth16_verify_batch(vk, proofs, publics, n, verdicts); });
 }
 int zk_groth16_verify_batch_dev(const zk_groth16_vk_t* vk, const void* d_proofs, const void* d_publics, uint64_t n, int* d_verdicts, void* stream) {
     return guard([&] {
-        ZK_REQUIRE(vk && vk->impl, "groth16 verify: null key");
-        groth16_verify_batch_dev(vk->impl, d_proofs, d_publics, n, d_verdicts, on_stream((hipStream_t)stream));
+        ZK_REQUIRE(vk, "groth16 verify: null key");
+        groth16_verify_batch_dev(vk, d_proofs, d_publics, n, d_verdicts, on_stream((hipStream_t)stream));
     });
 }
 int zk_groth16_verify_json(const zk_groth16_vk_t* vk, const char* proof_json, const char* public_input_json) {
     int verdict = ZK_VERDICT_ERROR;
-    if (guard([&] { ZK_REQUIRE(vk && vk->impl, "groth16 verify: null key"); verdict = groth16_verify_json(vk->impl, proof_json, public_input_json); }) != 0)
+    if (guard([&] { ZK_REQUIRE(vk, "groth16 verify: null key"); verdict = groth16_verify_json(vk, proof_json, public_input_json); }) != 0)
         return ZK_VERDICT_ERROR;
     return verdict;
 }

@@ -1,0 +1,145 @@
+// The pairing curves (BN254, BLS12-381) as one table: what msm.hip, groth16.hip, pairing.hip and the C ABI (capi.hip) need of a curve, as
+// data plus entry points.  To the curves what commit.h is to the hash types; no other unit sees it.  Each of the three units fills the
+// slice of what it compiles (msm_ops, groth16_ops, pairing_ops below); identity, sizes and the scalar modulus live here, and curve_of()
+// is the one place where a name becomes a curve.  The Groth16 handles of include/zkgpu.h ARE the library's objects (bottom of this file).
+#pragma once
+#include "zk_internal.h"
+
+struct zk_groth16_setup;
+struct zk_groth16_keygen;
+struct zk_groth16_vk;
+
+namespace zk {
+
+using Groth16Setup = ::zk_groth16_setup;
+using Groth16Key = ::zk_groth16_keygen;
+using Groth16Vk = ::zk_groth16_vk;
+namespace g16 { struct Circuit; struct Params; }
+struct MillerArgs;
+struct Curve;
+
+enum CurveId { CURVE_BN254, CURVE_BLS12_381 };
+enum Group { G1, G2 };
+
+// ---- msm.hip: the sums of one group.  Points affine (x, y), Fq in Montgomery form, little-endian limbs (G2: x.c0 || x.c1 || y.c0 || y.c1);
+// scalars 32 B canonical; a result is one point and a flag word (1 = infinity)
+struct GroupOps {
+    void (*msm_dev)(const void* d_bases, const void* d_scalars, uint64_t n, void* d_out, hipStream_t st);
+    void (*mul_generator_dev)(const u64* d_k, uint64_t n, void* d_bases, hipStream_t st);      // P_i = [k_i]G, k_i != 0, one u64 each
+    // P_i = [k_i]G for n full-width scalars (4 x u64 canonical, < r; zero gives the all-zero encoding): a window table of the generator,
+    // no doublings, one inversion per workgroup (fixedbase_impl.hip.h)
+    void (*mul_generator_fr_dev)(const u64* d_k, uint64_t n, void* d_bases, hipStream_t st);
+    // window tables for fixed bases (msm_impl.hip.h): table[w * n + i] = 2^(16 w) P_i; a sum over points [off, off + n) of it
+    size_t (*fixed_table_bytes)(uint64_t n);
+    void (*fixed_prepare_dev)(const void* d_bases, uint64_t n, void* d_table, hipStream_t st);
+    void (*fixed_dev)(const void* d_table, uint64_t table_n, uint64_t off, const void* d_scalars, uint64_t n, void* d_out, hipStream_t st);
+};
+struct MsmOps {
+    GroupOps g[2];                                                          // by Group
+    void (*fq_canon_to_mont_dev)(void* d, uint64_t n, hipStream_t st);      // n base-field elements in place: canonical integers <-> Montgomery
+    void (*fq_mont_to_canon_dev)(void* d, uint64_t n, hipStream_t st);
+};
+// ---- groth16.hip: the scalar field's transforms and the prover / key generation built on them
+struct Groth16Ops {
+    // bellman's EvaluationDomain::{fft, ifft, coset_fft, icoset_fft} on 2^logn Fr elements (4 x u64 Montgomery), in place
+    void (*fr_ntt_dev)(u64* d_data, int logn, bool inverse, bool coset, hipStream_t st);
+    // a <- coefficients of (A B - C) / (X^n - 1) from the row evaluations a, b, c (prover.rs create_proof's h block)
+    void (*fr_quotient_dev)(u64* d_a, const u64* d_b, const u64* d_c, int logn, hipStream_t st);
+    Groth16Setup* (*setup_new)(const Curve& cv, const g16::Circuit& C, const g16::Params& pk);
+    void (*keygen_run)(const Curve& cv, const g16::Circuit& C, const u32* td, std::vector<uint8_t>& out, double* ms);
+};
+// ---- pairing.hip: the steps of the optimal ate pairing and of Groth16 verification (pairing_impl.hip.h)
+struct PairingOps {
+    const char* q_hex;                                                      // the base field's modulus
+    void (*g1_check)(const void*, u64, u64, int*, u64, hipStream_t);
+    void (*g16_acc)(const void*, u32, const void*, u64, void*, int*, hipStream_t);
+    void (*g2_check)(const void*, u64, u64, int*, u64, hipStream_t);
+    size_t (*lines_bytes)(u64);
+    void (*g2_lines)(const void*, u64, u64, void*, void*, hipStream_t);
+    size_t (*f12_bytes)(u64);
+    size_t (*tab_bytes)(u64);
+    void (*miller)(const MillerArgs&, u64, void*, hipStream_t);
+    void (*final_exp)(const void*, u64, void*, void*, int, hipStream_t);
+    void (*verdict)(const void*, const void*, u64, const int*, int*, hipStream_t);
+};
+const MsmOps& msm_ops(CurveId id);
+const Groth16Ops& groth16_ops(CurveId id);
+const PairingOps& pairing_ops(CurveId id);
+
+struct Curve {
+    CurveId id;
+    const char* name;        // the reference's curve_type (groth16/src/api.rs:148-204), also what proof.json and the key's JSON carry
+    const char* abi_name;    // as the symbols of include/zkgpu.h spell it
+    uint32_t fq_words;       // u32 words per base-field element
+    u32 r[8];                // the scalar field's modulus
+    size_t point_words(Group g) const { return (g == G1 ? 2 : 4) * (size_t)fq_words; }   // affine; a sum's result is this and a flag word
+    size_t point_bytes(Group g) const { return 4 * point_words(g); }
+    size_t proof_words() const { return 2 * point_words(G1) + point_words(G2); }         // A || B || C
+    size_t gt_bytes() const { return 48 * (size_t)fq_words; }                            // 12 canonical Fq
+    int r_bits() const { return 256 - __builtin_clz(r[7]); }
+    bool fr_canonical(const u32* v) const {                                              // 8 words, below r
+        for (int i = 7; i >= 0; --i) { if (v[i] < r[i]) return true; if (v[i] > r[i]) return false; }
+        return false;
+    }
+    const MsmOps& msm() const { return msm_ops(id); }
+    const GroupOps& group(Group g) const { return msm_ops(id).g[g]; }
+    const Groth16Ops& groth16() const { return groth16_ops(id); }
+    const PairingOps& pairing() const { return pairing_ops(id); }
+};
+inline const Curve CURVES[2] = {
+    {CURVE_BN254, "BN128", "bn254", 8, {0xf0000001u, 0x43e1f593u, 0x79b97091u, 0x2833e848u, 0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u}},
+    {CURVE_BLS12_381, "BLS12381", "bls12_381", 12, {0x00000001u, 0xffffffffu, 0xfffe5bfeu, 0x53bda402u, 0x09a1d805u, 0x3339d808u, 0x299d7d48u, 0x73eda753u}},
+};
+inline const Curve& curve(CurveId id) { return CURVES[id]; }
+// Which names an entry point takes, and how it words its refusal: the Groth16 prover and key generation know the reference's names only,
+// the pairing side also the ABI's and refuses a null name apart
+enum CurveNames { GROTH16_NAMES, PAIRING_NAMES };
+inline const Curve& curve_of(const char* name, CurveNames rule) {
+    ZK_REQUIRE(name || rule == GROTH16_NAMES, "pairing: null curve");
+    const std::string c = name ? name : "";
+    for (const Curve& cv : CURVES)
+        if (c == cv.name || (rule == PAIRING_NAMES && c == cv.abi_name)) return cv;
+    throw Error(rule == GROTH16_NAMES ? "groth16: unknown curve \"" + c + "\" (BN128 | BLS12381)" : "pairing: unknown curve '" + c + "' (BN128 | BLS12381)");
+}
+
+// ---- Groth16 around the multi-scalar sums (groth16.hip) ----
+void groth16_wtns_payload(const void* wtns, size_t len, const char* curve, uint64_t* offset, uint64_t* n);
+// Key generation (groth16_keygen_impl.hip.h; `zkit groth16_setup`, groth16/src/api.rs:42-66): the finished key as bellman's
+// Parameters::write lays it out.  trapdoor: 5 x 4 u64 (tau, alpha, beta, gamma, delta), or null to draw them from the OS.
+Groth16Setup* groth16_setup_new(const char* curve, const void* r1cs, size_t r1cs_len, const void* params, size_t params_len);
+Groth16Key* groth16_keygen_new(const char* curve, const void* r1cs, size_t r1cs_len, const uint64_t* trapdoor);
+std::string groth16_keygen_vk_json(const Groth16Key& k, bool to_hex);   // json_utils.rs:285-303 serialize_vk
+
+// ---- pairing.hip: the optimal ate pairing and Groth16 verification ----
+void pairing_dev(const Curve& cv, const void* d_g1, const void* d_g2, uint64_t n, void* d_gt, int with_final_exp, hipStream_t st);
+Groth16Vk* groth16_vk_new(const char* curve, const char* vk_json);
+void groth16_vk_info(const Groth16Vk* vk, uint32_t* n_public, uint32_t* proof_bytes, uint32_t* gt_bytes);
+void groth16_verify_batch_dev(const Groth16Vk* vk, const void* d_proofs, const void* d_publics, uint64_t n, int* d_verdicts, hipStream_t st);
+void groth16_verify_batch(const Groth16Vk* vk, const void* proofs, const void* publics, uint64_t n, int* verdicts);
+int groth16_verify_json(const Groth16Vk* vk, const char* proof_json, const char* public_json);
+
+}  // namespace zk
+
+// the opaque handles of include/zkgpu.h
+struct zk_groth16_setup {    // a proving key and its circuit, resident on the device (groth16_impl.hip.h implements it per scalar field)
+    const zk::Curve* curve = nullptr;
+    virtual ~zk_groth16_setup() {}
+    // witness: n_wires x 32 B canonical (host or device); proof_out: A || B || C affine Montgomery words; d_h_out:
+    // optional device buffer for the quotient's (2^domain_log - 1) x 32 B canonical coefficients
+    virtual void prove(const void* witness, bool on_device, const u64 r[4], const u64 s[4], u32* proof_out, std::string* json, u64* d_h_out) = 0;
+    virtual uint32_t num_wires() const = 0;
+    virtual uint32_t num_inputs() const = 0;
+    virtual uint32_t domain_log() const = 0;
+};
+struct zk_groth16_keygen {   // a finished key
+    const zk::Curve* curve = nullptr;
+    std::vector<uint8_t> params;
+    double ms[5] = {};       // transform, column sums, G1 points, G2 points, serialisation
+};
+struct zk_groth16_vk {       // a verification key, checked and prepared
+    const zk::Curve* curve = nullptr;
+    uint32_t n_ic = 0;
+    void *d_ic = nullptr, *d_lines = nullptr, *d_inf = nullptr, *d_ab = nullptr;   // IC (Montgomery), the lines of -gamma and -delta, e(alpha, beta)
+    zk_groth16_vk() = default; zk_groth16_vk(const zk_groth16_vk&) = delete; zk_groth16_vk& operator=(const zk_groth16_vk&) = delete;
+    ~zk_groth16_vk() { for (void* p : {d_ic, d_lines, d_inf, d_ab}) if (p) zk::pool_free(p); }
+};

@@ -12,7 +12,7 @@
 // Key generation (`zkit groth16_setup`, groth16/src/api.rs:42-66) over the same circuit: groth16_keygen_impl.hip.h.
 // r and s are taken from the caller (the reference draws them from OsRng, api.rs:172); everything else is a
 // function of (key, circuit, witness).
-#include "zk_internal.h"
+#include "curve.h"
 #include <algorithm>
 #include <cerrno>
 #include <chrono>
@@ -28,6 +28,12 @@
 namespace zk {
 namespace g16 {
 
+struct Lc { std::vector<u32> col, coeff; };            // coeff: 8 x u32 canonical per term
+struct Row { Lc lc[3]; };
+struct R1cs { uint32_t n_wires = 0, n_pub_out = 0, n_pub_in = 0, n_prv_in = 0; std::vector<Row> rows; };
+struct PointVec { uint64_t n = 0; std::vector<u32> w; std::vector<char> inf; };   // canonical little-endian words
+struct Params { PointVec vk[6]; PointVec ic, h, l, a, b_g1, b_g2; };               // vk: alpha_g1 beta_g1 beta_g2 gamma_g2 delta_g1 delta_g2
+
 namespace {
 struct Reader {
     const uint8_t* p; size_t n, o = 0; const char* what;
@@ -37,13 +43,9 @@ struct Reader {
     uint32_t u32be() { need(4); uint32_t v = ((uint32_t)p[o] << 24) | ((uint32_t)p[o + 1] << 16) | ((uint32_t)p[o + 2] << 8) | p[o + 3]; o += 4; return v; }
     const uint8_t* take(size_t k) { need(k); const uint8_t* q = p + o; o += k; return q; }
 };
-bool words_lt(const u32* a, const u32* b, int n) {
-    for (int i = n - 1; i >= 0; --i) { if (a[i] < b[i]) return true; if (a[i] > b[i]) return false; }
-    return false;
-}
 }  // namespace
 
-std::string words_to_dec(const u32* w, int n) {
+static std::string words_to_dec(const u32* w, int n) {
     std::vector<u32> v(w, w + n);
     std::string out;
     while (true) {
@@ -62,7 +64,7 @@ std::string words_to_dec(const u32* w, int n) {
 }
 
 // r1cs_file.rs:185-270 from_reader (sections may come in any order; custom gates are not supported there either)
-static R1cs parse_r1cs(const uint8_t* b, size_t len, const std::vector<u32>& modulus) {
+static R1cs parse_r1cs(const uint8_t* b, size_t len, const Curve& cv) {
     Reader rd{b, len, 0, "r1cs"};
     if (std::memcmp(rd.take(4), "r1cs", 4) != 0) throw std::runtime_error("r1cs: Invalid magic number");
     if (rd.u32le() != 1) throw std::runtime_error("r1cs: Unsupported version");
@@ -79,7 +81,7 @@ static R1cs parse_r1cs(const uint8_t* b, size_t len, const std::vector<u32>& mod
     if (sec[1].second != 32 + (uint64_t)fs) throw std::runtime_error("r1cs: Invalid header section size");
     if (fs != 32) throw std::runtime_error("r1cs: field size " + std::to_string(fs) + " is not 32 bytes");
     const uint8_t* prime = h.take(fs);
-    if (std::memcmp(prime, modulus.data(), 32) != 0) throw std::runtime_error("r1cs: the file's prime is not the scalar field of the selected curve");
+    if (std::memcmp(prime, cv.r, 32) != 0) throw std::runtime_error("r1cs: the file's prime is not the scalar field of the selected curve");
     R1cs rc;
     rc.n_wires = h.u32le(); rc.n_pub_out = h.u32le(); rc.n_pub_in = h.u32le(); rc.n_prv_in = h.u32le();
     (void)h.u64le();
@@ -95,7 +97,7 @@ static R1cs parse_r1cs(const uint8_t* b, size_t len, const std::vector<u32>& mod
             Lc& lc = rc.rows[i].lc[w];
             for (auto& t : terms) {
                 u32 v[8]; std::memcpy(v, t.second, 32);
-                if (!words_lt(v, modulus.data(), 8)) throw std::runtime_error("r1cs: coefficient is not a canonical field element");   // Fr::from_repr
+                if (!cv.fr_canonical(v)) throw std::runtime_error("r1cs: coefficient is not a canonical field element");   // Fr::from_repr
                 lc.col.push_back(t.first); lc.coeff.insert(lc.coeff.end(), v, v + 8);
             }
         }
@@ -217,39 +219,10 @@ namespace bn254fr {
 #define FRN_ROOT 0xb639feb8u, 0x9632c7c5u, 0x0d0ff299u, 0x985ce340u, 0x01b0ecd8u, 0xb2dd8800u, 0x6d98ce29u, 0x1d69070du   // 7^((r-1)/2^28) * 2^256
 #define FRN_FN(name) name
 #include "frntt_impl.hip.h"
-#define G16_CW 8
-#define G16_MSM_G1 msm_g1_bn254_dev
-#define G16_MSM_G2 msm_g2_bn254_dev
-#define G16_MSM_G1_TABLE_BYTES msm_g1_bn254_fixed_table_bytes
-#define G16_MSM_G2_TABLE_BYTES msm_g2_bn254_fixed_table_bytes
-#define G16_MSM_G1_PREPARE msm_g1_bn254_fixed_prepare_dev
-#define G16_MSM_G2_PREPARE msm_g2_bn254_fixed_prepare_dev
-#define G16_MSM_G1_FIXED msm_g1_bn254_fixed_dev
-#define G16_MSM_G2_FIXED msm_g2_bn254_fixed_dev
-#define G16_FQ_TO_MONT fq_bn254_canon_to_mont_dev
-#define G16_FQ_TO_CANON fq_bn254_mont_to_canon_dev
-#define G16_JSON_CURVE "BN128"
-#define G16_FN(name) name
-#define G16_MULGEN_G1 g1_bn254_mul_generator_fr_dev
-#define G16_MULGEN_G2 g2_bn254_mul_generator_fr_dev
 #include "groth16_impl.hip.h"
 #include "groth16_keygen_impl.hip.h"
-#undef G16_MULGEN_G1
-#undef G16_MULGEN_G2
 #undef FRN_S
 #undef FRN_ROOT
-#undef G16_CW
-#undef G16_MSM_G1
-#undef G16_MSM_G2
-#undef G16_MSM_G1_TABLE_BYTES
-#undef G16_MSM_G2_TABLE_BYTES
-#undef G16_MSM_G1_PREPARE
-#undef G16_MSM_G2_PREPARE
-#undef G16_MSM_G1_FIXED
-#undef G16_MSM_G2_FIXED
-#undef G16_FQ_TO_MONT
-#undef G16_FQ_TO_CANON
-#undef G16_JSON_CURVE
 }  // namespace bn254fr
 
 namespace bls12381fr {
@@ -259,62 +232,31 @@ namespace bls12381fr {
 #define FRN_S 32
 #define FRN_ROOT 0x5f0e466au, 0xb9b58d8cu, 0x1819d7ecu, 0x5b1b4c80u, 0x52a31e64u, 0x0af53ae3u, 0x19e9b27bu, 0x5bf3addau   // 7^((r-1)/2^32) * 2^256
 #include "frntt_impl.hip.h"
-#define G16_CW 12
-#define G16_MSM_G1 msm_g1_bls12_381_dev
-#define G16_MSM_G2 msm_g2_bls12_381_dev
-#define G16_MSM_G1_TABLE_BYTES msm_g1_bls12_381_fixed_table_bytes
-#define G16_MSM_G2_TABLE_BYTES msm_g2_bls12_381_fixed_table_bytes
-#define G16_MSM_G1_PREPARE msm_g1_bls12_381_fixed_prepare_dev
-#define G16_MSM_G2_PREPARE msm_g2_bls12_381_fixed_prepare_dev
-#define G16_MSM_G1_FIXED msm_g1_bls12_381_fixed_dev
-#define G16_MSM_G2_FIXED msm_g2_bls12_381_fixed_dev
-#define G16_FQ_TO_MONT fq_bls12_381_canon_to_mont_dev
-#define G16_FQ_TO_CANON fq_bls12_381_mont_to_canon_dev
-#define G16_JSON_CURVE "BLS12381"
-#define G16_MULGEN_G1 g1_bls12_381_mul_generator_fr_dev
-#define G16_MULGEN_G2 g2_bls12_381_mul_generator_fr_dev
 #include "groth16_impl.hip.h"
 #include "groth16_keygen_impl.hip.h"
 }  // namespace bls12381fr
 
-void fr_bn254_ntt_dev(u64* d, int logn, bool inverse, bool coset, hipStream_t st) { bn254fr::ntt_dev(d, logn, inverse, coset, st); }
-void fr_bls12_381_ntt_dev(u64* d, int logn, bool inverse, bool coset, hipStream_t st) { bls12381fr::ntt_dev(d, logn, inverse, coset, st); }
-void fr_bn254_quotient_dev(u64* a, const u64* b, const u64* c, int logn, hipStream_t st) { bn254fr::quotient_dev(a, b, c, logn, st); }
-void fr_bls12_381_quotient_dev(u64* a, const u64* b, const u64* c, int logn, hipStream_t st) { bls12381fr::quotient_dev(a, b, c, logn, st); }
-
-static const u32 R_BN254[8] = {0xf0000001u, 0x43e1f593u, 0x79b97091u, 0x2833e848u, 0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u};
-static const u32 R_BLS12_381[8] = {0x00000001u, 0xffffffffu, 0xfffe5bfeu, 0x53bda402u, 0x09a1d805u, 0x3339d808u, 0x299d7d48u, 0x73eda753u};
-
-static bool curve_is_bls(const char* curve) {
-    // the reference's curve_type strings (groth16/src/api.rs:148-204)
-    const std::string c = curve ? curve : "";
-    if (c == "BN128") return false;
-    if (c == "BLS12381") return true;
-    throw std::runtime_error("groth16: unknown curve \"" + c + "\" (BN128 | BLS12381)");
+const Groth16Ops& groth16_ops(CurveId id) {   // the table's slice of this unit (curve.h)
+    static const Groth16Ops OPS[2] = {{bn254fr::ntt_dev, bn254fr::quotient_dev, bn254fr::setup_new, bn254fr::keygen_run},
+                                      {bls12381fr::ntt_dev, bls12381fr::quotient_dev, bls12381fr::setup_new, bls12381fr::keygen_run}};
+    return OPS[id];
 }
 
 Groth16Setup* groth16_setup_new(const char* curve, const void* r1cs, size_t r1cs_len, const void* params, size_t params_len) {
-    const bool bls = curve_is_bls(curve);
+    const Curve& cv = curve_of(curve, GROTH16_NAMES);
     ZK_REQUIRE(r1cs && params, "groth16: null input");
-    std::vector<u32> mod(bls ? R_BLS12_381 : R_BN254, (bls ? R_BLS12_381 : R_BN254) + 8);
-    const g16::R1cs rc = g16::parse_r1cs((const uint8_t*)r1cs, r1cs_len, mod);
-    const g16::Params pk = g16::parse_params((const uint8_t*)params, params_len, bls ? 48 : 32);
+    const g16::R1cs rc = g16::parse_r1cs((const uint8_t*)r1cs, r1cs_len, cv);
+    const g16::Params pk = g16::parse_params((const uint8_t*)params, params_len, 4 * (int)cv.fq_words);
     const g16::Circuit cir(rc);
-    Groth16Setup* s = bls ? bls12381fr::setup_new(cir, pk) : bn254fr::setup_new(cir, pk);
-    s->curve = curve; s->modulus = mod; s->proof_words = bls ? 96 : 64;
-    return s;
+    return cv.groth16().setup_new(cv, cir, pk);
 }
 
 // ---- key generation ---------------------------------------------------------------------------------------------------------------
-static bool fr_lt(const u32* a, const u32* mod) {
-    for (int i = 7; i >= 0; --i) { if (a[i] < mod[i]) return true; if (a[i] > mod[i]) return false; }
-    return false;
-}
 Groth16Key* groth16_keygen_new(const char* curve, const void* r1cs, size_t r1cs_len, const uint64_t* trapdoor) {
-    const bool bls = curve_is_bls(curve);
+    const Curve& cv = curve_of(curve, GROTH16_NAMES);
     ZK_REQUIRE(r1cs, "groth16 keygen: null input");
-    const u32* mod = bls ? R_BLS12_381 : R_BN254;
-    const g16::R1cs rc = g16::parse_r1cs((const uint8_t*)r1cs, r1cs_len, std::vector<u32>(mod, mod + 8));
+    const u32* mod = cv.r;
+    const g16::R1cs rc = g16::parse_r1cs((const uint8_t*)r1cs, r1cs_len, cv);
     const g16::Circuit cir(rc);
     u32 td[40];
     struct TdGuard { u32* p; ~TdGuard() { g16::wipe(p, 160); } } td_guard{td};
@@ -323,13 +265,13 @@ Groth16Key* groth16_keygen_new(const char* curve, const void* r1cs, size_t r1cs_
         std::memcpy(td, trapdoor, 160);
         for (int c = 0; c < 5; ++c) {
             u32* v = td + 8 * c;
-            while (!fr_lt(v, mod)) { uint64_t br = 0; for (int i = 0; i < 8; ++i) { const uint64_t d = (uint64_t)v[i] - mod[i] - br; v[i] = (u32)d; br = (d >> 32) & 1; } }   // below r
+            while (!cv.fr_canonical(v)) { uint64_t br = 0; for (int i = 0; i < 8; ++i) { const uint64_t d = (uint64_t)v[i] - mod[i] - br; v[i] = (u32)d; br = (d >> 32) & 1; } }   // below r
             u32 any = 0; for (int i = 0; i < 8; ++i) any |= v[i];
             ZK_REQUIRE(any, std::string("groth16 keygen: trapdoor component ") + names[c] + " is zero");
         }
     } else {
         // uniform in [1, r): bytes from the operating system, cut to the modulus' bit length, drawn again while out of range
-        const u32 top_mask = bls ? 0x7fffffffu : 0x3fffffffu;
+        const u32 top_mask = (1u << (cv.r_bits() - 224)) - 1;
         for (int c = 0; c < 5; ++c) {
             u32* v = td + 8 * c;
             for (;;) {
@@ -342,21 +284,20 @@ Groth16Key* groth16_keygen_new(const char* curve, const void* r1cs, size_t r1cs_
                 }
                 v[7] &= top_mask;
                 u32 any = 0; for (int i = 0; i < 8; ++i) any |= v[i];
-                if (any && fr_lt(v, mod)) break;
+                if (any && cv.fr_canonical(v)) break;
             }
         }
     }
     auto key = std::make_unique<Groth16Key>();
-    key->curve = curve;
-    if (bls) bls12381fr::keygen_run(cir, td, key->params, key->ms); else bn254fr::keygen_run(cir, td, key->params, key->ms);
+    key->curve = &cv;
+    cv.groth16().keygen_run(cv, cir, td, key->params, key->ms);
     return key.release();
 }
 
 // json_utils.rs:285-303 serialize_vk over the head of the key's bytes (VerifyingKey::write: alpha_g1 beta_g1 beta_g2 gamma_g2 delta_g1
 // delta_g2, count, ic); a coordinate is render_scalar_to_str's decimal string, or with to_hex the fixed-width 0x string of its repr
 std::string groth16_keygen_vk_json(const Groth16Key& k, bool to_hex) {
-    const bool bls = curve_is_bls(k.curve.c_str());
-    const size_t cb = bls ? 48 : 32;
+    const size_t cb = 4 * k.curve->fq_words;
     const uint8_t* p = k.params.data();
     size_t o = 0;
     auto coord = [&](const uint8_t* q) {
@@ -376,7 +317,7 @@ std::string groth16_keygen_vk_json(const Groth16Key& k, bool to_hex) {
         const uint8_t* q = p + o; o += 4 * cb;
         return "{\"x\":[" + coord(q + cb) + "," + coord(q) + "],\"y\":[" + coord(q + 3 * cb) + "," + coord(q + 2 * cb) + "]}";
     };
-    std::string js = std::string("{\"protocol\":\"groth16\",\"curve\":\"") + k.curve + "\"";
+    std::string js = std::string("{\"protocol\":\"groth16\",\"curve\":\"") + k.curve->name + "\"";
     js += ",\"vk_alpha_1\":" + g1(); js += ",\"vk_beta_1\":" + g1(); js += ",\"vk_beta_2\":" + g2(); js += ",\"vk_gamma_2\":" + g2();
     js += ",\"vk_delta_1\":" + g1(); js += ",\"vk_delta_2\":" + g2();
     ZK_REQUIRE(o + 4 <= k.params.size(), "groth16 keygen: truncated key");
@@ -388,7 +329,7 @@ std::string groth16_keygen_vk_json(const Groth16Key& k, bool to_hex) {
 
 // reader.rs:86-137 load_witness_from_bin_reader: header checks, then n x 32 B little-endian canonical values
 void groth16_wtns_payload(const void* wtns, size_t len, const char* curve, uint64_t* offset, uint64_t* n) {
-    const bool bls = curve_is_bls(curve);
+    const Curve& cv = curve_of(curve, GROTH16_NAMES);
     g16::Reader rd{(const uint8_t*)wtns, len, 0, "wtns"};
     if (std::memcmp(rd.take(4), "wtns", 4) != 0) throw std::runtime_error("wtns: Invalid file header");
     if (rd.u32le() > 2) throw std::runtime_error("wtns: unsupported file version");
@@ -396,7 +337,7 @@ void groth16_wtns_payload(const void* wtns, size_t len, const char* curve, uint6
     if (rd.u32le() != 1) throw std::runtime_error("wtns: invalid section type");
     if (rd.u64le() != 4 + 32 + 4) throw std::runtime_error("wtns: invalid section len");
     if (rd.u32le() != 32) throw std::runtime_error("wtns: invalid field byte size");
-    if (std::memcmp(rd.take(32), bls ? R_BLS12_381 : R_BN254, 32) != 0) throw std::runtime_error("wtns: invalid curve prime");
+    if (std::memcmp(rd.take(32), cv.r, 32) != 0) throw std::runtime_error("wtns: invalid curve prime");
     const uint32_t cnt = rd.u32le();
     if (rd.u32le() != 2) throw std::runtime_error("wtns: invalid section type");
     if (rd.u64le() != (uint64_t)cnt * 32) throw std::runtime_error("wtns: Invalid witness section size");

@@ -1,15 +1,12 @@
 // The Groth16 prover around the multi-scalar sums, generic over the curve; included inside the scalar field's
-// namespace after frntt_impl.hip.h with
-//   G16_CW                      u32 words per base-field element (8: BN254, 12: BLS12-381)
-//   G16_MSM_G1 / G16_MSM_G2     the curve's multi-scalar sums (msm.hip)
-//   G16_FQ_TO_MONT / _TO_CANON  base-field conversions in place (msm.hip)
-//   G16_JSON_CURVE              "BN128" / "BLS12381" (json_utils.rs:305-315)
-//   G16_FN(name)                exported factory name
+// namespace after frntt_impl.hip.h.  The field's own parameters are compile-time (ZK_FR29_FIELD, FRN_S, FRN_ROOT select device
+// code); everything of the curve -- the words per base-field element, the sums, the base-field conversions, the name proof.json
+// carries -- comes from the curve table (curve.h) at run time.
 // Restates bellman_ce groth16/prover.rs create_proof with explicit r, s (the reference draws them from its rng,
 // groth16/src/groth16.rs:88-96) over the circuit algebraic/src/circom_circuit.rs:94-160 synthesises.
 // No include guard on purpose.
 
-struct G16_FN(SetupImpl) final : Groth16Setup {
+struct SetupImpl final : Groth16Setup {
     uint32_t ni = 0, n_aux = 0, n_wires = 0;
     int logm = 0;
     u64 m = 0, n_rows = 0;
@@ -29,9 +26,13 @@ struct G16_FN(SetupImpl) final : Groth16Setup {
     bool tables = false;
     u64 off_l = 0, off_b = 0, off_a = 0, n_g1 = 0;
 
-    static constexpr size_t P1 = 2 * G16_CW, P2 = 4 * G16_CW;   // u32 words per affine point
+    const MsmOps& M;
+    const GroupOps &M1, &M2;
+    const size_t CW, P1, P2;                                     // u32 words per base-field element and per affine point
 
-    G16_FN(SetupImpl)(const g16::Circuit& C, const g16::Params& pk) {
+    SetupImpl(const Curve& cv, const g16::Circuit& C, const g16::Params& pk)
+        : M(cv.msm()), M1(M.g[G1]), M2(M.g[G2]), CW(cv.fq_words), P1(cv.point_words(G1)), P2(cv.point_words(G2)) {
+        curve = &cv;
         hipStream_t st = nullptr;
         ni = C.ni; n_wires = C.n_wires; n_aux = C.n_aux; n_rows = C.n_rows; logm = C.logm; m = C.m;
         const std::vector<char>&a_aux = C.a_aux, &b_any = C.b_any;
@@ -91,13 +92,13 @@ struct G16_FN(SetupImpl) final : Groth16Setup {
         put(g2b, 0, pk.b_g2, P2, nb, false, "b_g2");
         put(g2b, nb, pk.vk[5], P2, 1, false, "delta_g2");
         put(g2b, nb + 1, pk.vk[2], P2, 1, false, "beta_g2");
-        G16_FQ_TO_MONT(g1b.p, n_g1 * P1 / G16_CW, st);
-        G16_FQ_TO_MONT(g2b.p, (nb + 2) * P2 / G16_CW, st);
+        M.fq_canon_to_mont_dev(g1b.p, n_g1 * P1 / CW, st);
+        M.fq_canon_to_mont_dev(g2b.p, (nb + 2) * P2 / CW, st);
         tables = n_g1 < (1ull << 24) && !getenv("ZK_GROTH16_NO_TABLES");   // the knob keeps the plain-array path testable at small sizes
         if (tables) {
-            g1t.reserve(G16_MSM_G1_TABLE_BYTES(n_g1)); g2t.reserve(G16_MSM_G2_TABLE_BYTES(nb + 2));
-            G16_MSM_G1_PREPARE(g1b.p, n_g1, g1t.p, st);
-            G16_MSM_G2_PREPARE(g2b.p, nb + 2, g2t.p, st);
+            g1t.reserve(M1.fixed_table_bytes(n_g1)); g2t.reserve(M2.fixed_table_bytes(nb + 2));
+            M1.fixed_prepare_dev(g1b.p, n_g1, g1t.p, st);
+            M2.fixed_prepare_dev(g2b.p, nb + 2, g2t.p, st);
             ZK_HIP(hipStreamSynchronize(st));
             g1b.release(); g2b.release();
         }
@@ -115,7 +116,7 @@ struct G16_FN(SetupImpl) final : Groth16Setup {
     hipStream_t streams[3] = {nullptr, nullptr, nullptr};
     hipEvent_t ev_ready = nullptr;
     int device = -1;
-    ~G16_FN(SetupImpl)() override {
+    ~SetupImpl() override {
         for (auto& st : streams) if (st) { forget_stream(st); (void)hipStreamDestroy(st); }
         if (ev_ready) (void)hipEventDestroy(ev_ready);
     }
@@ -161,8 +162,8 @@ struct G16_FN(SetupImpl) final : Groth16Setup {
                 ZK_HIP(hipSetDevice(device));
                 on_stream(streams[k + 1]);                                  // this thread's allocations are ordered on its own stream
                 ZK_HIP(hipStreamWaitEvent(streams[k + 1], ev_ready, 0));
-                if (k == 0) { if (tables) G16_MSM_G2_FIXED(g2t.p, nb + 2, 0, scB.p, nb + 2, o_b.p, streams[1]); else G16_MSM_G2(g2b.p, scB.p, nb + 2, o_b.p, streams[1]); }
-                else { if (tables) G16_MSM_G1_FIXED(g1t.p, n_g1, off_a, scA.p, na + 2, o_a.p, streams[2]); else G16_MSM_G1((const u32*)g1b.p + off_a * P1, scA.p, na + 2, o_a.p, streams[2]); }
+                if (k == 0) { if (tables) M2.fixed_dev(g2t.p, nb + 2, 0, scB.p, nb + 2, o_b.p, streams[1]); else M2.msm_dev(g2b.p, scB.p, nb + 2, o_b.p, streams[1]); }
+                else { if (tables) M1.fixed_dev(g1t.p, n_g1, off_a, scA.p, na + 2, o_a.p, streams[2]); else M1.msm_dev((const u32*)g1b.p + off_a * P1, scA.p, na + 2, o_a.p, streams[2]); }
             } catch (...) { err[k] = std::current_exception(); }
         };
         std::thread tb(side, 0), ta(side, 1);
@@ -182,7 +183,7 @@ struct G16_FN(SetupImpl) final : Groth16Setup {
             gather(C0 + off_b * 8, b_idx, nb, rs_fe);            // r w_b
             gather(C0 + off_a * 8, a_idx, na, rs_fe + 1);        // s w_a
             ZK_HIP(hipGetLastError());
-            if (tables) G16_MSM_G1_FIXED(g1t.p, n_g1, 0, scC.p, n_g1, o_c.p, st); else G16_MSM_G1(g1b.p, scC.p, n_g1, o_c.p, st);
+            if (tables) M1.fixed_dev(g1t.p, n_g1, 0, scC.p, n_g1, o_c.p, st); else M1.msm_dev(g1b.p, scC.p, n_g1, o_c.p, st);
             ZK_HIP(hipStreamSynchronize(st));                     // ev[] goes back to the pool
         } catch (...) { main_err = std::current_exception(); }
         tb.join(); ta.join();
@@ -204,15 +205,15 @@ struct G16_FN(SetupImpl) final : Groth16Setup {
             std::memcpy(all.data(), A.data(), P1 * 4); std::memcpy(all.data() + P1, B.data(), P2 * 4); std::memcpy(all.data() + P1 + P2, Cc.data(), P1 * 4);
             DevBuf d; d.reserve(all.size() * 4);
             h2d_sync(d.p, all.data(), all.size() * 4);
-            G16_FQ_TO_CANON(d.p, all.size() / G16_CW, st);
+            M.fq_mont_to_canon_dev(d.p, all.size() / CW, st);
             ZK_HIP(hipStreamSynchronize(st));
             ZK_HIP(hipMemcpy(all.data(), d.p, all.size() * 4, hipMemcpyDeviceToHost));
-            auto dec = [&](size_t i) { return "\"" + g16::words_to_dec(all.data() + i * G16_CW, G16_CW) + "\""; };
+            auto dec = [&](size_t i) { return "\"" + g16::words_to_dec(all.data() + i * CW, (int)CW) + "\""; };
             // json_utils.rs:305-315 serialize_proof (to_hex = false); G2 coordinates as [c0, c1] (json_utils.rs:153-161)
             *json = "{\"pi_a\":{\"x\":" + dec(0) + ",\"y\":" + dec(1) + "},\"pi_b\":{\"x\":[" + dec(2) + "," + dec(3) + "],\"y\":[" + dec(4) + "," + dec(5) +
-                    "]},\"pi_c\":{\"x\":" + dec(6) + ",\"y\":" + dec(7) + "},\"protocol\":\"groth16\",\"curve\":\"" G16_JSON_CURVE "\"}";
+                    "]},\"pi_c\":{\"x\":" + dec(6) + ",\"y\":" + dec(7) + "},\"protocol\":\"groth16\",\"curve\":\"" + curve->name + "\"}";
         }
     }
 };
 
-Groth16Setup* G16_FN(setup_new)(const g16::Circuit& C, const g16::Params& pk) { return new G16_FN(SetupImpl)(C, pk); }
+Groth16Setup* setup_new(const Curve& cv, const g16::Circuit& C, const g16::Params& pk) { return new SetupImpl(cv, C, pk); }

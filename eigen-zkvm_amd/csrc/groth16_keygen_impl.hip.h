@@ -1,6 +1,5 @@
 // Groth16 key generation on the device, generic over the curve; included after groth16_impl.hip.h inside the scalar
-// field's namespace, with that file's macros and
-//   G16_MULGEN_G1 / G16_MULGEN_G2   [k]G for full-width scalars (fixedbase_impl.hip.h through msm.hip)
+// field's namespace; [k]G for full-width scalars (fixedbase_impl.hip.h) and the base-field conversions come from the curve table.
 // Restates bellman_ce groth16/generator.rs generate_parameters with an explicit trapdoor (the reference draws it from
 // its rng: groth16/src/groth16.rs:77-86 circuit_specific_setup -> generate_random_parameters) over the circuit
 // g16::Circuit describes -- the same rows, input rows and domain the prover uses:
@@ -9,7 +8,7 @@
 //   a_j, b_j, c_j(tau) = sum over the wire's column            column-major matrices built on the host, one wave per wire,
 //                                                              summed in a fixed order: no atomics
 //   h_i = tau^i t(tau) / delta, l_j | ic_j = (beta a_j + alpha b_j + c_j) / (delta | gamma)
-//   the points of all of them                                  G16_MULGEN_*: one launch per group and scalar array
+//   the points of all of them                                  mul_generator_fr_dev: one launch per group and scalar array
 // and writes Parameters::write's layout; points at infinity are dropped from a, b_g1, b_g2 (generator.rs), in wire order.
 // No include guard on purpose.
 
@@ -89,11 +88,12 @@ __global__ __launch_bounds__(256) void kg_wire_sums_kernel(const KgCsc A, const 
 
 // td: the trapdoor, 5 x 8 canonical words, non-zero and below r.  out: the key's bytes.  ms: transform, column sums, G1 points,
 // G2 points, serialisation.  Every device buffer that held the trapdoor or a scalar derived from it is overwritten before return.
-void G16_FN(keygen_run)(const g16::Circuit& C, const u32* td, std::vector<uint8_t>& out, double* ms) {
+void keygen_run(const Curve& cv, const g16::Circuit& C, const u32* td, std::vector<uint8_t>& out, double* ms) {
     hipStream_t st = cur_stream();
     const u64 m = C.m, nh = m - 1, nw = C.n_wires;
     const FrDomain& D = frn_domain(C.logm, st);
-    constexpr size_t P1 = 2 * G16_CW, P2 = 4 * G16_CW;
+    const MsmOps& M = cv.msm();
+    const size_t P1 = cv.point_words(G1), P2 = cv.point_words(G2);
     const u64 n1 = 3 + 3 * nw + nh, n2 = 3 + nw;
     // G1 scalars: [alpha beta delta | x (ic, then l) | h | a | b];  G2: [beta gamma delta], then the b of the G1 array
     const u64 o_x = 3, o_h = o_x + nw, o_a = o_h + nh, o_b = o_a + nw;
@@ -162,24 +162,24 @@ void G16_FN(keygen_run)(const g16::Circuit& C, const u32* td, std::vector<uint8_
     ms[1] = since(t1, t2);
 
     pts1.reserve(n1 * P1 * 4); pts2.reserve(n2 * P2 * 4);
-    G16_MULGEN_G1((const u64*)sc1.p, n1, pts1.p, st);
+    M.g[G1].mul_generator_fr_dev((const u64*)sc1.p, n1, pts1.p, st);
     auto t3 = now();
     ms[2] = since(t2, t3);
-    G16_MULGEN_G2((const u64*)sc2.p, 3, pts2.p, st);
-    G16_MULGEN_G2((const u64*)(S1 + o_b * 8), nw, (u32*)pts2.p + 3 * P2, st);
+    M.g[G2].mul_generator_fr_dev((const u64*)sc2.p, 3, pts2.p, st);
+    M.g[G2].mul_generator_fr_dev((const u64*)(S1 + o_b * 8), nw, (u32*)pts2.p + 3 * P2, st);
     auto t4 = now();
     ms[3] = since(t3, t4);
 
     // canonical coordinates, then pairing_ce's uncompressed big-endian bytes
-    G16_FQ_TO_CANON(pts1.p, n1 * 2, st); G16_FQ_TO_CANON(pts2.p, n2 * 4, st);
+    M.fq_mont_to_canon_dev(pts1.p, n1 * 2, st); M.fq_mont_to_canon_dev(pts2.p, n2 * 4, st);
     be1.reserve(n1 * P1 * 4); be2.reserve(n2 * P2 * 4);
-    g16::points_to_be_dev((const u32*)pts1.p, n1, G16_CW, false, (u32*)be1.p, st);
-    g16::points_to_be_dev((const u32*)pts2.p, n2, G16_CW, true, (u32*)be2.p, st);
+    g16::points_to_be_dev((const u32*)pts1.p, n1, (int)cv.fq_words, false, (u32*)be1.p, st);
+    g16::points_to_be_dev((const u32*)pts2.p, n2, (int)cv.fq_words, true, (u32*)be2.p, st);
     ZK_HIP(hipStreamSynchronize(st));
     pts1.release(); pts2.release();
     std::vector<uint8_t> h1(n1 * P1 * 4), h2(n2 * P2 * 4);
     d2h_sync(h1.data(), be1.p, h1.size()); d2h_sync(h2.data(), be2.p, h2.size());
-    constexpr size_t B1 = P1 * 4, B2 = P2 * 4;
+    const size_t B1 = P1 * 4, B2 = P2 * 4;
     out.clear();
     out.reserve(h1.size() + h2.size() + 24);
     auto put = [&](const std::vector<uint8_t>& src, size_t pb, u64 at, u64 n) { out.insert(out.end(), src.begin() + at * pb, src.begin() + (at + n) * pb); };

@@ -16,7 +16,7 @@
 //   5. Horner over the windows + conversion to affine (one lane)
 // Field: 29-bit limbs with 64-bit column accumulators, lazily reduced (fe29_impl.hip.h); Fq2 on top of it for G2.
 // Integer-ALU bound (about 10 Fq products per point and window); HBM traffic is 96 B per point.
-#include "zk_internal.h"
+#include "curve.h"
 #include "curve_consts.hip.h"
 #include <map>
 #include <mutex>
@@ -168,44 +168,15 @@ namespace {
 }  // namespace g2
 }  // namespace bls12_381
 
-void msm_g1_bn254_dev(const void* d_bases, const void* d_scalars, uint64_t n, void* d_out, hipStream_t st) {
-    bn254::g1::msm_g1_dev(d_bases, d_scalars, n, d_out, st);
+// the table's slice of this unit (curve.h)
+#define ZK_GROUP_OPS(NS) {NS::msm_g1_dev, NS::g1_mul_generator_dev, NS::mul_generator_fr_dev, NS::msm_fixed_table_bytes, NS::msm_fixed_prepare_dev, NS::msm_fixed_dev}
+const MsmOps& msm_ops(CurveId id) {
+    static const MsmOps OPS[2] = {
+        {{ZK_GROUP_OPS(bn254::g1), ZK_GROUP_OPS(bn254::g2)}, bn254::g1::fq_canon_to_mont_dev, bn254::g1::fq_mont_to_canon_dev},
+        {{ZK_GROUP_OPS(bls12_381::g1), ZK_GROUP_OPS(bls12_381::g2)}, bls12_381::g1::fq_canon_to_mont_dev, bls12_381::g1::fq_mont_to_canon_dev},
+    };
+    return OPS[id];
 }
-void g1_bn254_mul_generator_dev(const u64* d_k, uint64_t n, void* d_bases, hipStream_t st) {
-    bn254::g1::g1_mul_generator_dev(d_k, n, d_bases, st);
-}
-void msm_g1_bls12_381_dev(const void* d_bases, const void* d_scalars, uint64_t n, void* d_out, hipStream_t st) {
-    bls12_381::g1::msm_g1_dev(d_bases, d_scalars, n, d_out, st);
-}
-void g1_bls12_381_mul_generator_dev(const u64* d_k, uint64_t n, void* d_bases, hipStream_t st) {
-    bls12_381::g1::g1_mul_generator_dev(d_k, n, d_bases, st);
-}
-
-// G2: points n x 4 coordinates-words (x.c0, x.c1, y.c0, y.c1), i.e. 128 B (BN254) / 192 B (BLS12-381) each
-void fq_bn254_canon_to_mont_dev(void* d, uint64_t n, hipStream_t st) { bn254::g1::fq_canon_to_mont_dev(d, n, st); }
-void fq_bn254_mont_to_canon_dev(void* d, uint64_t n, hipStream_t st) { bn254::g1::fq_mont_to_canon_dev(d, n, st); }
-void fq_bls12_381_canon_to_mont_dev(void* d, uint64_t n, hipStream_t st) { bls12_381::g1::fq_canon_to_mont_dev(d, n, st); }
-void fq_bls12_381_mont_to_canon_dev(void* d, uint64_t n, hipStream_t st) { bls12_381::g1::fq_mont_to_canon_dev(d, n, st); }
-void msm_g2_bn254_dev(const void* d_bases, const void* d_scalars, uint64_t n, void* d_out, hipStream_t st) { bn254::g2::msm_g1_dev(d_bases, d_scalars, n, d_out, st); }
-void g2_bn254_mul_generator_dev(const u64* d_k, uint64_t n, void* d_bases, hipStream_t st) { bn254::g2::g1_mul_generator_dev(d_k, n, d_bases, st); }
-void msm_g2_bls12_381_dev(const void* d_bases, const void* d_scalars, uint64_t n, void* d_out, hipStream_t st) { bls12_381::g2::msm_g1_dev(d_bases, d_scalars, n, d_out, st); }
-void g2_bls12_381_mul_generator_dev(const u64* d_k, uint64_t n, void* d_bases, hipStream_t st) { bls12_381::g2::g1_mul_generator_dev(d_k, n, d_bases, st); }
-
-// P_i = [k_i]G for full-width scalars (fixedbase_impl.hip.h): n x 4 u64 canonical, < r
-void g1_bn254_mul_generator_fr_dev(const u64* d_k, uint64_t n, void* d_bases, hipStream_t st) { bn254::g1::mul_generator_fr_dev(d_k, n, d_bases, st); }
-void g2_bn254_mul_generator_fr_dev(const u64* d_k, uint64_t n, void* d_bases, hipStream_t st) { bn254::g2::mul_generator_fr_dev(d_k, n, d_bases, st); }
-void g1_bls12_381_mul_generator_fr_dev(const u64* d_k, uint64_t n, void* d_bases, hipStream_t st) { bls12_381::g1::mul_generator_fr_dev(d_k, n, d_bases, st); }
-void g2_bls12_381_mul_generator_fr_dev(const u64* d_k, uint64_t n, void* d_bases, hipStream_t st) { bls12_381::g2::mul_generator_fr_dev(d_k, n, d_bases, st); }
-
-// window tables (fixed bases)
-#define ZK_MSM_FIXED(NAME, NS)                                                                                              \
-    size_t msm_##NAME##_fixed_table_bytes(uint64_t n) { return NS::msm_fixed_table_bytes(n); }                              \
-    void msm_##NAME##_fixed_prepare_dev(const void* b, uint64_t n, void* t, hipStream_t st) { NS::msm_fixed_prepare_dev(b, n, t, st); } \
-    void msm_##NAME##_fixed_dev(const void* t, uint64_t tn, uint64_t off, const void* s, uint64_t n, void* o, hipStream_t st) { NS::msm_fixed_dev(t, tn, off, s, n, o, st); }
-ZK_MSM_FIXED(g1_bn254, bn254::g1)
-ZK_MSM_FIXED(g2_bn254, bn254::g2)
-ZK_MSM_FIXED(g1_bls12_381, bls12_381::g1)
-ZK_MSM_FIXED(g2_bls12_381, bls12_381::g2)
-#undef ZK_MSM_FIXED
+#undef ZK_GROUP_OPS
 
 }  // namespace zk

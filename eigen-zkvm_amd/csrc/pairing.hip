@@ -14,7 +14,7 @@
 // the comparison with e(alpha, beta).  Stricter than the reference, which reads points unchecked (json_utils.rs:163-198).
 // Fq, Fq2 and the point formulas are the sums' (fe29_impl.hip.h, ecpt_impl.hip.h); fe_mul and the Fq2 product are real
 // functions here, and the loops over exponent bits stay loops: the code-size hazard recorded in msm.hip.
-#include "zk_internal.h"
+#include "curve.h"
 #include "curve_consts.hip.h"
 #include "pairing_consts.hip.h"
 #include "json_min.h"
@@ -29,22 +29,6 @@ struct MillerArgs {
     const u32* inf[3]; u64 inf_stride[3];
     int np;
 };
-// what the host code below needs of a curve
-struct PairingOps {
-    int nl; const char* q_hex;
-    void (*g1_check)(const void*, u64, u64, int*, u64, hipStream_t);
-    void (*g16_acc)(const void*, u32, const void*, u64, void*, int*, hipStream_t);
-    void (*g2_check)(const void*, u64, u64, int*, u64, hipStream_t);
-    size_t (*lines_bytes)(u64);
-    void (*g2_lines)(const void*, u64, u64, void*, void*, hipStream_t);
-    size_t (*f12_bytes)(u64);
-    size_t (*tab_bytes)(u64);
-    void (*miller)(const MillerArgs&, u64, void*, hipStream_t);
-    void (*final_exp)(const void*, u64, void*, void*, int, hipStream_t);
-    void (*verdict)(const void*, const void*, u64, const int*, int*, hipStream_t);
-    void (*to_mont)(void*, uint64_t, hipStream_t);
-};
-
 #define FQ_MUL_ATTR __noinline__
 
 namespace bn254 {
@@ -64,9 +48,9 @@ namespace {
 #undef CF_MUL_ATTR
 #undef PT_COLD_ATTR
 }  // namespace pg2
-static const PairingOps OPS = {NL, "30644e72e131a029b85045b68181585d97816a916871ca8d3c208c16d87cfd47",
+static const PairingOps OPS = {"30644e72e131a029b85045b68181585d97816a916871ca8d3c208c16d87cfd47",
                                pg1::g1_check_dev, pg1::g16_acc_dev, pg2::g2_check_dev, pg2::g2_lines_bytes, pg2::g2_lines_dev, pg2::f12_bytes,
-                               pg2::final_exp_tab_bytes, pg2::miller_dev, pg2::final_exp_dev, pg2::g16_verdict_dev, fq_bn254_canon_to_mont_dev};
+                               pg2::final_exp_tab_bytes, pg2::miller_dev, pg2::final_exp_dev, pg2::g16_verdict_dev};
 }  // namespace bn254
 namespace bls12_381 {
 namespace pg1 {
@@ -85,19 +69,13 @@ namespace {
 #undef CF_MUL_ATTR
 #undef PT_COLD_ATTR
 }  // namespace pg2
-static const PairingOps OPS = {NL, "1a0111ea397fe69a4b1ba7b6434bacd764774b84f38512bf6730d2a0f6b0f6241eabfffeb153ffffb9feffffffffaaab",
+static const PairingOps OPS = {"1a0111ea397fe69a4b1ba7b6434bacd764774b84f38512bf6730d2a0f6b0f6241eabfffeb153ffffb9feffffffffaaab",
                                pg1::g1_check_dev, pg1::g16_acc_dev, pg2::g2_check_dev, pg2::g2_lines_bytes, pg2::g2_lines_dev, pg2::f12_bytes,
-                               pg2::final_exp_tab_bytes, pg2::miller_dev, pg2::final_exp_dev, pg2::g16_verdict_dev, fq_bls12_381_canon_to_mont_dev};
+                               pg2::final_exp_tab_bytes, pg2::miller_dev, pg2::final_exp_dev, pg2::g16_verdict_dev};
 }  // namespace bls12_381
 #undef FQ_MUL_ATTR
 
-static const PairingOps& ops_of(const char* curve) {
-    ZK_REQUIRE(curve, "pairing: null curve");
-    const std::string c(curve);
-    if (c == "BN128" || c == "bn254") return bn254::OPS;
-    if (c == "BLS12381" || c == "bls12_381") return bls12_381::OPS;
-    throw Error("pairing: unknown curve '" + c + "' (BN128 | BLS12381)");
-}
+const PairingOps& pairing_ops(CurveId id) { return id == CURVE_BN254 ? bn254::OPS : bls12_381::OPS; }   // the table's slice of this unit (curve.h)
 struct PoolBuf {   // a block of the pool for the length of one call; freeing is ordered on the call's stream (devmem.hip)
     void* p;
     explicit PoolBuf(size_t n) : p(pool_alloc(n ? n : 4)) {}
@@ -106,30 +84,24 @@ struct PoolBuf {   // a block of the pool for the length of one call; freeing is
 };
 
 // n pairs (G1 n x 2 NL words, G2 n x 4 NL words, external layout) -> n GT values of 12 canonical Fq
-static void pairing_run(const PairingOps& o, const void* d_g1, const void* d_g2, u64 n, void* d_gt, int with_final_exp, hipStream_t st) {
+static void pairing_run(const Curve& cv, const void* d_g1, const void* d_g2, u64 n, void* d_gt, int with_final_exp, hipStream_t st) {
     if (!n) return;
+    const PairingOps& o = cv.pairing();
     PoolBuf lines(o.lines_bytes(n)), inf(4 * n), f(o.f12_bytes(n)), tab(with_final_exp ? o.tab_bytes(n) : 4);
-    o.g2_lines(d_g2, 4 * (u64)o.nl, n, lines.p, inf.p, st);
+    o.g2_lines(d_g2, cv.point_words(G2), n, lines.p, inf.p, st);
     MillerArgs a{};
     a.np = 1;
-    a.g1[0] = (const u32*)d_g1; a.g1_stride[0] = 2 * (u64)o.nl;
+    a.g1[0] = (const u32*)d_g1; a.g1_stride[0] = cv.point_words(G1);
     a.lines[0] = (const u32*)lines.p; a.lines_stride[0] = o.lines_bytes(1) / 4;
     a.inf[0] = (const u32*)inf.p; a.inf_stride[0] = 1;
     o.miller(a, n, f.p, st);
     o.final_exp(f.p, n, tab.p, d_gt, with_final_exp, st);
 }
-void pairing_dev(const char* curve, const void* d_g1, const void* d_g2, uint64_t n, void* d_gt, int with_final_exp, hipStream_t st) {
-    pairing_run(ops_of(curve), d_g1, d_g2, n, d_gt, with_final_exp, st);
+void pairing_dev(const Curve& cv, const void* d_g1, const void* d_g2, uint64_t n, void* d_gt, int with_final_exp, hipStream_t st) {
+    pairing_run(cv, d_g1, d_g2, n, d_gt, with_final_exp, st);
 }
 
 // ---- Groth16 -------------------------------------------------------------------------------------------------------------------
-struct Groth16Vk {
-    const PairingOps* o = nullptr;
-    std::string curve;
-    uint32_t n_ic = 0;
-    void *d_ic = nullptr, *d_lines = nullptr, *d_inf = nullptr, *d_ab = nullptr;   // IC (Montgomery), the lines of -gamma and -delta, e(alpha, beta)
-    ~Groth16Vk() { for (void* p : {d_ic, d_lines, d_inf, d_ab}) if (p) pool_free(p); }
-};
 // a decimal or 0x string -> little-endian 32-bit words; false when it does not fit
 static bool parse_int(const std::string& s, u32* w, int nw) {
     for (int i = 0; i < nw; ++i) w[i] = 0;
@@ -149,61 +121,64 @@ static bool parse_int(const std::string& s, u32* w, int nw) {
     return true;
 }
 static const std::string& jstr(const JVal& v) { ZK_REQUIRE(v.kind == JVal::Str || v.kind == JVal::Num, "groth16 verify: a number string expected"); return v.s; }
-static void parse_fq(const PairingOps& o, const JVal& v, u32* w) { ZK_REQUIRE(parse_int(jstr(v), w, o.nl), "groth16 verify: a coordinate does not fit the base field's width"); }
+static void parse_fq(const Curve& cv, const JVal& v, u32* w) { ZK_REQUIRE(parse_int(jstr(v), w, (int)cv.fq_words), "groth16 verify: a coordinate does not fit the base field's width"); }
 // {"x", "y"} -> 2 NL canonical words; pairing_ce's zero (0, 1) becomes the all-zero encoding
-static void parse_g1(const PairingOps& o, const JVal& v, u32* w) {
-    parse_fq(o, v.at("x"), w); parse_fq(o, v.at("y"), w + o.nl);
-    bool zero = w[o.nl] == 1;
-    for (int i = 0; i < 2 * o.nl; ++i) if (i != o.nl && w[i]) zero = false;
-    if (zero) w[o.nl] = 0;
+static void parse_g1(const Curve& cv, const JVal& v, u32* w) {
+    const int nl = (int)cv.fq_words;
+    parse_fq(cv, v.at("x"), w); parse_fq(cv, v.at("y"), w + nl);
+    bool zero = w[nl] == 1;
+    for (int i = 0; i < 2 * nl; ++i) if (i != nl && w[i]) zero = false;
+    if (zero) w[nl] = 0;
 }
-static void parse_g2(const PairingOps& o, const JVal& v, u32* w, bool negate) {
-    for (int c = 0; c < 2; ++c) { parse_fq(o, v.at("x").at(c), w + c * o.nl); parse_fq(o, v.at("y").at(c), w + (2 + c) * o.nl); }
-    bool zero = w[2 * o.nl] == 1;
-    for (int i = 0; i < 4 * o.nl; ++i) if (i != 2 * o.nl && w[i]) zero = false;
-    if (zero) w[2 * o.nl] = 0;
+static void parse_g2(const Curve& cv, const JVal& v, u32* w, bool negate) {
+    const int nl = (int)cv.fq_words;
+    for (int c = 0; c < 2; ++c) { parse_fq(cv, v.at("x").at(c), w + c * nl); parse_fq(cv, v.at("y").at(c), w + (2 + c) * nl); }
+    bool zero = w[2 * nl] == 1;
+    for (int i = 0; i < 4 * nl; ++i) if (i != 2 * nl && w[i]) zero = false;
+    if (zero) w[2 * nl] = 0;
     if (!negate || zero) return;
-    std::vector<u32> q(o.nl);
-    parse_int(std::string("0x") + o.q_hex, q.data(), o.nl);
+    std::vector<u32> q(nl);
+    parse_int(std::string("0x") + cv.pairing().q_hex, q.data(), nl);
     for (int c = 2; c < 4; ++c) {                          // y -> q - y (a coordinate >= q stays as it is and fails the curve check)
-        u32* y = w + c * o.nl;
+        u32* y = w + c * nl;
         bool nz = false, lt = false;
-        for (int i = 0; i < o.nl; ++i) nz |= y[i] != 0;
-        for (int i = o.nl - 1; i >= 0; --i) if (y[i] != q[i]) { lt = y[i] < q[i]; break; }
+        for (int i = 0; i < nl; ++i) nz |= y[i] != 0;
+        for (int i = nl - 1; i >= 0; --i) if (y[i] != q[i]) { lt = y[i] < q[i]; break; }
         if (!nz || !lt) continue;
         uint64_t br = 0;
-        for (int i = 0; i < o.nl; ++i) { const uint64_t d = (uint64_t)q[i] - y[i] - br; y[i] = (u32)d; br = (d >> 32) & 1; }
+        for (int i = 0; i < nl; ++i) { const uint64_t d = (uint64_t)q[i] - y[i] - br; y[i] = (u32)d; br = (d >> 32) & 1; }
     }
 }
-static void* upload_mont(const PairingOps& o, const std::vector<u32>& canon, hipStream_t st) {
+static void* upload_mont(const Curve& cv, const std::vector<u32>& canon, hipStream_t st) {
     void* d = pool_alloc(canon.size() * 4);
     try {
         h2d_sync(d, canon.data(), canon.size() * 4);
-        o.to_mont(d, canon.size() / o.nl, st);
+        cv.msm().fq_canon_to_mont_dev(d, canon.size() / cv.fq_words, st);
     } catch (...) { pool_free(d); throw; }
     return d;
 }
 
 Groth16Vk* groth16_vk_new(const char* curve, const char* vk_json) {
     ZK_REQUIRE(vk_json, "groth16 verify: null verification key");
-    const PairingOps& o = ops_of(curve);
+    const Curve& cv = curve_of(curve, PAIRING_NAMES);
+    const PairingOps& o = cv.pairing();
     const JVal js = JParser::parse(vk_json);
-    if (const JVal* c = js.find("curve")) ZK_REQUIRE(&ops_of(c->str().c_str()) == &o, "groth16 verify: the key is for curve " + c->str());
+    if (const JVal* c = js.find("curve")) ZK_REQUIRE(&curve_of(c->str().c_str(), PAIRING_NAMES) == &cv, "groth16 verify: the key is for curve " + c->str());
     const JVal& ic = js.at("IC");
     ZK_REQUIRE(ic.kind == JVal::Arr && ic.size() >= 1, "groth16 verify: IC must hold at least one point");
-    const int nl = o.nl;
+    const int nl = (int)cv.fq_words;
     std::vector<u32> g1((ic.size() + 1) * 2 * nl), g2(3 * 4 * nl);              // alpha, IC... ; beta, -gamma, -delta
-    parse_g1(o, js.at("vk_alpha_1"), g1.data());
-    for (size_t i = 0; i < ic.size(); ++i) parse_g1(o, ic.at(i), g1.data() + (i + 1) * 2 * nl);
-    parse_g2(o, js.at("vk_beta_2"), g2.data(), false);
-    parse_g2(o, js.at("vk_gamma_2"), g2.data() + 4 * nl, true);
-    parse_g2(o, js.at("vk_delta_2"), g2.data() + 8 * nl, true);
+    parse_g1(cv, js.at("vk_alpha_1"), g1.data());
+    for (size_t i = 0; i < ic.size(); ++i) parse_g1(cv, ic.at(i), g1.data() + (i + 1) * 2 * nl);
+    parse_g2(cv, js.at("vk_beta_2"), g2.data(), false);
+    parse_g2(cv, js.at("vk_gamma_2"), g2.data() + 4 * nl, true);
+    parse_g2(cv, js.at("vk_delta_2"), g2.data() + 8 * nl, true);
     hipStream_t st = cur_stream();
     auto vk = std::make_unique<Groth16Vk>();
-    vk->o = &o; vk->curve = curve; vk->n_ic = (uint32_t)ic.size();
+    vk->curve = &cv; vk->n_ic = (uint32_t)ic.size();
     PoolBuf dg1(g1.size() * 4), dg2(g2.size() * 4), status(4 * (g1.size() / (2 * nl) + 3));
     h2d_sync(dg1.p, g1.data(), g1.size() * 4); h2d_sync(dg2.p, g2.data(), g2.size() * 4);
-    o.to_mont(dg1.p, g1.size() / nl, st); o.to_mont(dg2.p, g2.size() / nl, st);
+    cv.msm().fq_canon_to_mont_dev(dg1.p, g1.size() / nl, st); cv.msm().fq_canon_to_mont_dev(dg2.p, g2.size() / nl, st);
     const u64 n1 = g1.size() / (2 * nl);
     ZK_HIP(hipMemsetD32Async((hipDeviceptr_t)status.p, 1, n1 + 3, st));
     o.g1_check(dg1.p, 2 * (u64)nl, n1, (int*)status.p, 1, st);
@@ -215,26 +190,25 @@ Groth16Vk* groth16_vk_new(const char* curve, const char* vk_json) {
     vk->d_ic = pool_alloc(ic.size() * 2 * nl * 4);
     ZK_HIP(hipMemcpyAsync(vk->d_ic, (const u32*)dg1.p + 2 * nl, ic.size() * 2 * nl * 4, hipMemcpyDeviceToDevice, st));
     vk->d_ab = pool_alloc(12 * nl * 4);
-    pairing_run(o, dg1.p, dg2.p, 1, vk->d_ab, 1, st);
+    pairing_run(cv, dg1.p, dg2.p, 1, vk->d_ab, 1, st);
     vk->d_lines = pool_alloc(o.lines_bytes(2)); vk->d_inf = pool_alloc(8);
     o.g2_lines((const u32*)dg2.p + 4 * nl, 4 * (u64)nl, 2, vk->d_lines, vk->d_inf, st);
     ZK_HIP(hipStreamSynchronize(st));
     return vk.release();
 }
-void groth16_vk_free(Groth16Vk* vk) { delete vk; }
 void groth16_vk_info(const Groth16Vk* vk, uint32_t* n_public, uint32_t* proof_bytes, uint32_t* gt_bytes) {
     ZK_REQUIRE(vk, "groth16 verify: null key");
     if (n_public) *n_public = vk->n_ic - 1;
-    if (proof_bytes) *proof_bytes = 8 * vk->o->nl * 4;
-    if (gt_bytes) *gt_bytes = 12 * vk->o->nl * 4;
+    if (proof_bytes) *proof_bytes = (uint32_t)(4 * vk->curve->proof_words());
+    if (gt_bytes) *gt_bytes = (uint32_t)vk->curve->gt_bytes();
 }
 // proofs: n x (A | B | C) in the layout zk_groth16_prove writes; publics: n x n_public x 8 words canonical; verdicts: n ints
 void groth16_verify_batch_dev(const Groth16Vk* vk, const void* d_proofs, const void* d_publics, uint64_t n, int* d_verdicts, hipStream_t st) {
     ZK_REQUIRE(vk, "groth16 verify: null key");
     if (!n) return;
     ZK_REQUIRE(d_proofs && d_verdicts && (d_publics || vk->n_ic == 1), "groth16 verify: null argument");
-    const PairingOps& o = *vk->o;
-    const u64 nl = o.nl, pw = 8 * nl;
+    const PairingOps& o = vk->curve->pairing();
+    const u64 nl = vk->curve->fq_words, pw = 8 * nl;
     const u32* pr = (const u32*)d_proofs;
     PoolBuf status(4 * n), acc(n * 2 * nl * 4), lines(o.lines_bytes(n)), inf(4 * n), f(o.f12_bytes(n)), tab(o.tab_bytes(n)), gt(n * 12 * nl * 4);
     ZK_HIP(hipMemsetD32Async((hipDeviceptr_t)status.p, 1, n, st));
@@ -257,7 +231,7 @@ void groth16_verify_batch(const Groth16Vk* vk, const void* proofs, const void* p
     ZK_REQUIRE(vk, "groth16 verify: null key");
     if (!n) return;
     ZK_REQUIRE(proofs && verdicts && (publics || vk->n_ic == 1), "groth16 verify: null argument");
-    const size_t pb = 8 * (size_t)vk->o->nl * 4, ub = (size_t)(vk->n_ic - 1) * 32;
+    const size_t pb = 4 * vk->curve->proof_words(), ub = (size_t)(vk->n_ic - 1) * 32;
     PoolBuf dp(n * pb), du(n * ub), dv(n * 4);
     h2d_sync(dp.p, proofs, n * pb);
     if (ub) h2d_sync(du.p, publics, n * ub);
@@ -267,16 +241,16 @@ void groth16_verify_batch(const Groth16Vk* vk, const void* proofs, const void* p
 // the file-level form (api.rs:302-341): proof.json and public_input.json -> verdict
 int groth16_verify_json(const Groth16Vk* vk, const char* proof_json, const char* public_json) {
     ZK_REQUIRE(vk && proof_json && public_json, "groth16 verify: null argument");
-    const PairingOps& o = *vk->o;
-    const int nl = o.nl;
+    const Curve& cv = *vk->curve;
+    const int nl = (int)cv.fq_words;
     const JVal pj = JParser::parse(proof_json), uj = JParser::parse(public_json);
     ZK_REQUIRE(uj.kind == JVal::Arr, "groth16 verify: public_input.json must be an array");
     if (uj.size() != vk->n_ic - 1) return -2;
     std::vector<u32> pts(8 * nl), pub(8 * uj.size() + 8);
-    parse_g1(o, pj.at("pi_a"), pts.data()); parse_g2(o, pj.at("pi_b"), pts.data() + 2 * nl, false); parse_g1(o, pj.at("pi_c"), pts.data() + 6 * nl);
+    parse_g1(cv, pj.at("pi_a"), pts.data()); parse_g2(cv, pj.at("pi_b"), pts.data() + 2 * nl, false); parse_g1(cv, pj.at("pi_c"), pts.data() + 6 * nl);
     for (size_t i = 0; i < uj.size(); ++i) if (!parse_int(jstr(uj.at(i)), pub.data() + 8 * i, 8)) return -1;
     hipStream_t st = cur_stream();
-    void* dp = upload_mont(o, pts, st);
+    void* dp = upload_mont(cv, pts, st);
     int verdict = 0;
     try {
         PoolBuf du(pub.size() * 4), dv(4);

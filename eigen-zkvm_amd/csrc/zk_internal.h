@@ -196,33 +196,6 @@ void pol_set_dev(u64* d_buf, uint64_t width, uint64_t offset, uint32_t dim, uint
 uint64_t h1h2_work_words(uint64_t n);
 void calculate_h1h2_dev(const u64* d_f, const u64* d_t, uint64_t n, u64* d_h1, u64* d_h2, u64* d_work, u64** d_missing, hipStream_t st);
 void calculate_z_dev(const u64* d_num, const u64* d_den, uint64_t n, u64* d_z, u64* d_work, u64* d_check, hipStream_t st);
-// ---- MSM (msm.hip): bases n*64 B affine Montgomery, scalars n*32 B canonical; d_out 17 u32 (x, y, inf flag)
-void msm_g1_bn254_dev(const void* d_bases, const void* d_scalars, uint64_t n, void* d_out, hipStream_t st);
-void g1_bn254_mul_generator_dev(const u64* d_k, uint64_t n, void* d_bases, hipStream_t st);  // P_i = [k_i]G, k_i != 0
-// BLS12-381: bases n*96 B, scalars n*32 B; d_out 25 u32 (x, y, inf flag)
-void msm_g1_bls12_381_dev(const void* d_bases, const void* d_scalars, uint64_t n, void* d_out, hipStream_t st);
-void g1_bls12_381_mul_generator_dev(const u64* d_k, uint64_t n, void* d_bases, hipStream_t st);
-// G2 (Fq2 coordinates: x.c0 || x.c1 || y.c0 || y.c1): 128 B / 192 B per point; d_out = that + a flag word
-void msm_g2_bn254_dev(const void* d_bases, const void* d_scalars, uint64_t n, void* d_out, hipStream_t st);
-void g2_bn254_mul_generator_dev(const u64* d_k, uint64_t n, void* d_bases, hipStream_t st);
-void msm_g2_bls12_381_dev(const void* d_bases, const void* d_scalars, uint64_t n, void* d_out, hipStream_t st);
-void g2_bls12_381_mul_generator_dev(const u64* d_k, uint64_t n, void* d_bases, hipStream_t st);
-// P_i = [k_i]G for n full-width scalars (4 x u64 canonical, < r; zero gives the all-zero encoding): a window table of the generator,
-// no doublings, one inversion per workgroup (fixedbase_impl.hip.h); the output layout of the *_mul_generator_dev above
-void g1_bn254_mul_generator_fr_dev(const u64* d_k, uint64_t n, void* d_bases, hipStream_t st);
-void g2_bn254_mul_generator_fr_dev(const u64* d_k, uint64_t n, void* d_bases, hipStream_t st);
-void g1_bls12_381_mul_generator_fr_dev(const u64* d_k, uint64_t n, void* d_bases, hipStream_t st);
-void g2_bls12_381_mul_generator_fr_dev(const u64* d_k, uint64_t n, void* d_bases, hipStream_t st);
-// window tables for fixed bases (msm_impl.hip.h): table[w * n + i] = 2^(16 w) P_i; a sum over points [off, off + n) of it
-#define ZK_MSM_FIXED_DECL(NAME)                                                                                             \
-    size_t msm_##NAME##_fixed_table_bytes(uint64_t n);                                                                      \
-    void msm_##NAME##_fixed_prepare_dev(const void* d_bases, uint64_t n, void* d_table, hipStream_t st);                     \
-    void msm_##NAME##_fixed_dev(const void* d_table, uint64_t table_n, uint64_t off, const void* d_scalars, uint64_t n, void* d_out, hipStream_t st);
-ZK_MSM_FIXED_DECL(g1_bn254)
-ZK_MSM_FIXED_DECL(g2_bn254)
-ZK_MSM_FIXED_DECL(g1_bls12_381)
-ZK_MSM_FIXED_DECL(g2_bls12_381)
-#undef ZK_MSM_FIXED_DECL
 // ---- BN128-field hashing (frhash.hip; reached through the field table of commit.h); digests = 4 raw (Montgomery, R = 2^256) limbs
 void bn128_load_constants(const char* path);
 std::string bn128_tables_selfcheck(const char* path);   // host only: the matrix-pipe tables (fr_mfma.hip.h) against the constants; "" or what is wrong
@@ -241,11 +214,6 @@ void bls12381_merkelize_dev(const u64* d_rows, uint32_t width, uint64_t height, 
 struct JVal;
 int stark_verify_impl(const JVal& info, const JVal& prog, const JVal& ss, const u64 const_root[4], const char* zkin_json, std::string& why);
 void qsplit_dev(const u64* d_qq1, uint32_t nbits, uint32_t q_dim, uint32_t q_deg, u64* d_qq2, hipStream_t st);
-// base-field elements in place: canonical integers <-> Montgomery (msm.hip); n = number of Fq elements
-void fq_bn254_canon_to_mont_dev(void* d, uint64_t n, hipStream_t st);
-void fq_bn254_mont_to_canon_dev(void* d, uint64_t n, hipStream_t st);
-void fq_bls12_381_canon_to_mont_dev(void* d, uint64_t n, hipStream_t st);
-void fq_bls12_381_mont_to_canon_dev(void* d, uint64_t n, hipStream_t st);
 
 // ---- compressor12 exec (compressor12.hip): witness -> committed trace [n_rows][12]
 struct C12Exec;
@@ -264,49 +232,6 @@ std::string c12_setup_exec(const C12Setup* s);
 void c12_setup_consts_dev(const C12Setup* s, u64* d_out, hipStream_t st);
 // the 12 S columns of any [n_used][12] map (0 = no wire) into columns [col0, col0 + 12) of a [2^n_bits][n_const] matrix
 void c12_sigma_dev(const u32* d_s_map, uint64_t n_used, uint32_t n_bits, uint32_t n_const, uint32_t col0, u64* d_out, hipStream_t st);
-// ---- Groth16 around the multi-scalar sums (groth16.hip): scalar-field transforms, the quotient, the prover ----
-// bellman's EvaluationDomain::{fft, ifft, coset_fft, icoset_fft} on 2^logn Fr elements (4 x u64 Montgomery), in place
-void fr_bn254_ntt_dev(u64* d_data, int logn, bool inverse, bool coset, hipStream_t st);
-void fr_bls12_381_ntt_dev(u64* d_data, int logn, bool inverse, bool coset, hipStream_t st);
-// a <- coefficients of (A B - C) / (X^n - 1) from the row evaluations a, b, c (prover.rs create_proof's h block)
-void fr_bn254_quotient_dev(u64* d_a, const u64* d_b, const u64* d_c, int logn, hipStream_t st);
-void fr_bls12_381_quotient_dev(u64* d_a, const u64* d_b, const u64* d_c, int logn, hipStream_t st);
-namespace g16 {
-struct Lc { std::vector<u32> col, coeff; };            // coeff: 8 x u32 canonical per term
-struct Row { Lc lc[3]; };
-struct R1cs { uint32_t n_wires = 0, n_pub_out = 0, n_pub_in = 0, n_prv_in = 0; std::vector<Row> rows; };
-struct PointVec { uint64_t n = 0; std::vector<u32> w; std::vector<char> inf; };   // canonical little-endian words
-struct Params { PointVec vk[6]; PointVec ic, h, l, a, b_g1, b_g2; };               // vk: alpha_g1 beta_g1 beta_g2 gamma_g2 delta_g1 delta_g2
-std::string words_to_dec(const u32* w, int n);
-}
-struct Groth16Setup {
-    virtual ~Groth16Setup() {}
-    // witness: n_wires x 32 B canonical (host or device); proof_out: A || B || C affine Montgomery words; d_h_out:
-    // optional device buffer for the quotient's (2^domain_log - 1) x 32 B canonical coefficients
-    virtual void prove(const void* witness, bool on_device, const u64 r[4], const u64 s[4], u32* proof_out, std::string* json, u64* d_h_out) = 0;
-    virtual uint32_t num_wires() const = 0;
-    virtual uint32_t num_inputs() const = 0;
-    virtual uint32_t domain_log() const = 0;
-    std::string curve;
-    std::vector<u32> modulus;     // Fr, 8 words
-    size_t proof_words = 0;
-};
-Groth16Setup* groth16_setup_new(const char* curve, const void* r1cs, size_t r1cs_len, const void* params, size_t params_len);
-void groth16_wtns_payload(const void* wtns, size_t len, const char* curve, uint64_t* offset, uint64_t* n);
-// Key generation (groth16_keygen_impl.hip.h; `zkit groth16_setup`, groth16/src/api.rs:42-66): the finished key as bellman's
-// Parameters::write lays it out.  trapdoor: 5 x 4 u64 (tau, alpha, beta, gamma, delta), or null to draw them from the OS.
-struct Groth16Key { std::string curve; std::vector<uint8_t> params; double ms[5] = {}; };   // ms: transform, column sums, G1 points, G2 points, serialisation
-Groth16Key* groth16_keygen_new(const char* curve, const void* r1cs, size_t r1cs_len, const uint64_t* trapdoor);
-std::string groth16_keygen_vk_json(const Groth16Key& k, bool to_hex);   // json_utils.rs:285-303 serialize_vk
-
-// ---- pairing.hip: the optimal ate pairing and Groth16 verification ("BN128" | "BLS12381") ----
-struct Groth16Vk;
-void pairing_dev(const char* curve, const void* d_g1, const void* d_g2, uint64_t n, void* d_gt, int with_final_exp, hipStream_t st);
-Groth16Vk* groth16_vk_new(const char* curve, const char* vk_json);
-void groth16_vk_free(Groth16Vk* vk);
-void groth16_vk_info(const Groth16Vk* vk, uint32_t* n_public, uint32_t* proof_bytes, uint32_t* gt_bytes);
-void groth16_verify_batch_dev(const Groth16Vk* vk, const void* d_proofs, const void* d_publics, uint64_t n, int* d_verdicts, hipStream_t st);
-void groth16_verify_batch(const Groth16Vk* vk, const void* proofs, const void* publics, uint64_t n, int* verdicts);
-int groth16_verify_json(const Groth16Vk* vk, const char* proof_json, const char* public_json);
+// (the curves -- multi-scalar sums, Groth16, pairings -- are declared in curve.h, for the four units that see it)
 
 }  // namespace zk
