@@ -58,6 +58,7 @@ EXPORTS = [
     "zk_pairing_bn254", "zk_pairing_bn254_dev", "zk_pairing_bls12_381", "zk_pairing_bls12_381_dev", "zk_groth16_vk_new", "zk_groth16_vk_info", "zk_groth16_vk_free",
     "zk_groth16_verify_batch", "zk_groth16_verify_batch_dev", "zk_groth16_verify_json", "zk_groth16_verdict_name",
     "zk_pil_check_new", "zk_pil_check_listing", "zk_pil_check_run", "zk_pil_check_run_dev", "zk_pil_check_free",
+    "zk_r1cs_check_new", "zk_r1cs_check_info", "zk_r1cs_check_run", "zk_r1cs_check_run_dev", "zk_r1cs_check_free",
 ]
 
 # include/zkgpu.h enums
@@ -318,6 +319,11 @@ def _load():
         "zk_pil_check_run": (vp, [vp, vp, vp, C.c_uint64]),
         "zk_pil_check_run_dev": (vp, [vp, vp, vp, C.c_uint64, vp]),
         "zk_pil_check_free": (C.c_int, [vp]),
+        "zk_r1cs_check_new": (vp, [C.c_char_p, vp, C.c_size_t]),
+        "zk_r1cs_check_info": (C.c_int, [vp, vp, vp, vp, vp]),
+        "zk_r1cs_check_run": (vp, [vp, vp, C.c_uint64, C.c_uint32]),
+        "zk_r1cs_check_run_dev": (vp, [vp, vp, C.c_uint64, C.c_uint32]),
+        "zk_r1cs_check_free": (C.c_int, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

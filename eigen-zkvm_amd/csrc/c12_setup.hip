@@ -14,6 +14,7 @@
 // identity value of its predecessor in the run and the head takes the tail's.  No cell is written twice and no order between
 // signals matters.  The sort is a stable LSD radix sort over 32-bit keys, 8 bits a pass, one wave per tile.
 #include "zk_internal.h"
+#include "r1cs_file.h"
 #include "poseidon_gl_constants.h"
 #include "../../tools/poseidong_round_constants.h"   // the 360 plain round constants + the 12 zeros of the output row
 #include <algorithm>
@@ -25,6 +26,7 @@
 #include <vector>
 
 namespace zk {
+using namespace c12;                                      // Lc, CustomGate, CustomUse, R1csGL: r1cs_file.h
 namespace {
 
 constexpr u64 GLP = 0xFFFFFFFF00000001ULL;
@@ -43,17 +45,9 @@ struct Rd {
     const uint8_t* take(size_t k) { need(k); const uint8_t* q = p + o; o += k; return q; }
     u64 field() { const u64 v = u64le(); if (v >= GLP) throw Error("r1cs: coefficient is not a canonical field element"); return v; }
 };
-using Lc = std::map<u64, u64>;                            // wire -> coefficient, ordered by wire as the reference's BTreeMap
-struct CustomGate { std::string name; std::vector<u64> params; };
-struct CustomUse { u64 id; std::vector<u64> signals; };
-struct R1csGL {
-    uint32_t n_wires = 0, n_pub_out = 0, n_pub_in = 0, n_prv_in = 0;
-    std::vector<std::array<Lc, 3>> rows;
-    std::vector<CustomGate> gates;
-    std::vector<CustomUse> uses;
-};
+}  // namespace
 
-R1csGL parse_r1cs_gl(const uint8_t* b, size_t len) {
+R1csGL c12::parse_r1cs_gl(const uint8_t* b, size_t len) {
     Rd rd{b, len};
     if (std::memcmp(rd.take(4), "r1cs", 4) != 0) throw Error("r1cs: Invalid magic number");
     if (rd.u32le() != 1) throw Error("r1cs: Unsupported version");
@@ -110,6 +104,8 @@ R1csGL parse_r1cs_gl(const uint8_t* b, size_t len) {
     }
     return rc;
 }
+
+namespace {
 
 // ---- R1CS -> PLONK (r1cs2plonk.rs:50-227) ---------------------------------------------------------------------------------------
 struct Gate { u64 s[3]; u64 q[5]; };                      // sl sr so | qm ql qr qo qc

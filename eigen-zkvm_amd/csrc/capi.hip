@@ -4,6 +4,7 @@
 #include "commit.h"
 #include "curve.h"
 #include "pil_check.h"
+#include "r1cs_check.h"
 #include "../../include/zkgpu.h"
 #include <algorithm>
 #include <map>
@@ -715,6 +716,45 @@ char* zk_pil_check_run(zk_pil_check_t* c, const uint64_t* const_pols, const uint
 }
 int zk_pil_check_free(zk_pil_check_t* c) {
     return guard([&] { if (c) { pil_check_free(c->impl); delete c; } });
+}
+
+// ---- wtns_check (r1cs_check.hip) ---------------------------------------------------------------------------------
+struct zk_r1cs_check { R1csCheck* impl; };
+zk_r1cs_check_t* zk_r1cs_check_new(const char* field, const void* r1cs, size_t len) {
+    zk_r1cs_check_t* h = nullptr;
+    if (guard([&] { R1csCheck* c = r1cs_check_new(field, r1cs, len); h = new zk_r1cs_check{c}; }) != 0) return nullptr;
+    return h;
+}
+int zk_r1cs_check_info(const zk_r1cs_check_t* c, uint32_t* n_wires, uint64_t* n_constraints, uint64_t* n_custom_uses, uint32_t* n_public) {
+    return guard([&] { ZK_REQUIRE(c && c->impl, "r1cs check: null handle"); r1cs_check_info(c->impl, n_wires, n_constraints, n_custom_uses, n_public); });
+}
+static char* r1cs_check_run_any(zk_r1cs_check_t* c, const void* witness, bool on_device, uint64_t n_values, uint32_t max_findings) {
+    char* out = nullptr;
+    if (guard([&] {
+            ZK_REQUIRE(c && c->impl, "r1cs check: null handle");
+            ZK_REQUIRE(witness, "r1cs check: null witness");
+            uint32_t n_wires = 0;
+            r1cs_check_info(c->impl, &n_wires, nullptr, nullptr, nullptr);
+            ZK_REQUIRE(n_values == n_wires, "r1cs check: the witness has " + std::to_string(n_values) + " values, the circuit has " + std::to_string(n_wires) + " wires");
+            if (on_device) { out = c12_dup(r1cs_check_run_dev(c->impl, witness, max_findings, cur_stream())); return; }
+            const size_t vb = r1cs_check_value_bytes(c->impl);
+            for (uint64_t i = 0; i < n_values; ++i)
+                ZK_REQUIRE(r1cs_check_value_canonical(c->impl, (const uint8_t*)witness + i * vb), "groth16: witness value " + std::to_string(i) + " is not a canonical field element");
+            DevBuf d_wit;
+            d_wit.reserve((size_t)n_values * vb);
+            h2d_sync(d_wit.p, witness, (size_t)n_values * vb);
+            out = c12_dup(r1cs_check_run_dev(c->impl, d_wit.p, max_findings, cur_stream()));
+        }) != 0) return nullptr;
+    return out;
+}
+char* zk_r1cs_check_run(zk_r1cs_check_t* c, const void* witness, uint64_t n_values, uint32_t max_findings) {
+    return r1cs_check_run_any(c, witness, false, n_values, max_findings);
+}
+char* zk_r1cs_check_run_dev(zk_r1cs_check_t* c, const void* d_witness, uint64_t n_values, uint32_t max_findings) {
+    return r1cs_check_run_any(c, d_witness, true, n_values, max_findings);
+}
+int zk_r1cs_check_free(zk_r1cs_check_t* c) {
+    return guard([&] { if (c) { r1cs_check_free(c->impl); delete c; } });
 }
 
 }  // extern "C"

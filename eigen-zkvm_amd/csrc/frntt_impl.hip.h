@@ -34,7 +34,7 @@ __device__ __forceinline__ fe fe_small(u32 v) {            // the plain value v 
     for (int i = 0; i < NR; ++i) c.l[i] = RRP29(i);
     return fe_mul(x, c);
 }
-__device__ __forceinline__ fe fe_renorm(const fe& a) { return fe_mul(a, fe_one()); }   // any value < 68q -> < 2q
+#include "fr_rows_impl.hip.h"   // fe_renorm, the witness conversion, the row sums of an R1CS, fe_store_canon
 
 // per-domain scalars and the square chains the table kernels multiply together
 struct FrDomainConsts {
@@ -181,29 +181,6 @@ __global__ __launch_bounds__(256) void frn_to_canon_kernel(const u32* __restrict
 #pragma unroll
     for (int k = 0; k < NL; ++k) out[i * NL + k] = w[k];
 }
-// canonical integers (8 x u32 each, < r) -> internal form, element-major (9 x u32 each): the witness
-__global__ __launch_bounds__(256) void frn_canon_to_fe_kernel(const u32* __restrict__ in, u32* __restrict__ out, u64 n) {
-    const u64 i = blockIdx.x * 256ull + threadIdx.x;
-    if (i >= n) return;
-    u32 w[NL];
-#pragma unroll
-    for (int k = 0; k < NL; ++k) w[k] = in[i * NL + k];
-    fe x;
-#pragma unroll
-    for (int k = 0; k < NR; ++k) {
-        const int bit = LB * k, wi = bit >> 5, s = bit & 31;
-        u32 v = wi < NL ? w[wi] >> s : 0;
-        if (s > 32 - LB && wi + 1 < NL) v |= w[wi + 1] << (32 - s);
-        x.l[k] = v & LMASK;
-    }
-    fe c;
-#pragma unroll
-    for (int k = 0; k < NR; ++k) c.l[k] = RRP29(k);
-    x = fe_mul(x, c);
-#pragma unroll
-    for (int k = 0; k < NR; ++k) out[i * NR + k] = x.l[k];
-}
-
 // ---- the quotient's pointwise step: a <- (a b - c) / Z on the coset (mul_assign, sub_assign, divide_by_z_on_coset)
 __global__ __launch_bounds__(256) void frn_quotient_pointwise_kernel(u32* __restrict__ a, const u32* __restrict__ b, const u32* __restrict__ c, const fe* __restrict__ zinv, u64 n) {
     const u64 i = blockIdx.x * 256ull + threadIdx.x;
@@ -219,32 +196,7 @@ __global__ __launch_bounds__(256) void frn_r1cs_eval_kernel(const u64* __restric
                                                             const u32* __restrict__ wit, u64 n_rows, u32* __restrict__ out, u64 n) {
     const u64 i = blockIdx.x * 256ull + threadIdx.x;
     if (i >= n) return;
-    fe acc = fe_zero();
-    if (i < n_rows) {
-        int pending = 0;
-        for (u64 k = row_ptr[i]; k < row_ptr[i + 1]; ++k) {
-            fe cf, x;
-            const u64 col = cols[k];
-#pragma unroll
-            for (int l = 0; l < NR; ++l) { cf.l[l] = coeffs[k * NR + l]; x.l[l] = wit[col * NR + l]; }
-            acc = fe_add(acc, fe_mul(cf, x));
-            if (++pending == 4) { acc = fe_renorm(acc); pending = 0; }   // < 2q + 4 * 2q between renormalisations
-        }
-        if (pending) acc = fe_renorm(acc);
-    }
-    soa_store(out, n, i, acc);
-}
-__device__ __forceinline__ void fe_store_canon(const fe& a /* Montgomery, < 68q */, u32* __restrict__ out) {
-    fe one = fe_zero(); one.l[0] = 1;
-    const fe x = fe_canon(fe_mul(a, one));
-#pragma unroll
-    for (int jj = 0; jj < NL; ++jj) {
-        const int bit = 32 * jj, k = bit / LB, s = bit % LB;
-        u32 v = x.l[k] >> s;
-        if (k + 1 < NR) v |= x.l[k + 1] << (LB - s);
-        if (k + 2 < NR && 2 * LB - s < 32) v |= x.l[k + 2] << (2 * LB - s);
-        out[jj] = v;
-    }
+    soa_store(out, n, i, i < n_rows ? frn_row_sum(row_ptr, cols, coeffs, wit, i) : fe_zero());
 }
 // density-indexed scalars (8 x u32 canonical each): out[i] = scale * w[idx[i]] (idx < 0: 0).  wit: canonical values,
 // wit_fe: the same in internal form (element-major), used when a scale is given

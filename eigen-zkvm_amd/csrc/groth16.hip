@@ -13,6 +13,7 @@
 // r and s are taken from the caller (the reference draws them from OsRng, api.rs:172); everything else is a
 // function of (key, circuit, witness).
 #include "curve.h"
+#include "r1cs_file.h"
 #include <algorithm>
 #include <cerrno>
 #include <chrono>
@@ -28,9 +29,7 @@
 namespace zk {
 namespace g16 {
 
-struct Lc { std::vector<u32> col, coeff; };            // coeff: 8 x u32 canonical per term
-struct Row { Lc lc[3]; };
-struct R1cs { uint32_t n_wires = 0, n_pub_out = 0, n_pub_in = 0, n_prv_in = 0; std::vector<Row> rows; };
+// Lc, Row, R1cs: r1cs_file.h
 struct PointVec { uint64_t n = 0; std::vector<u32> w; std::vector<char> inf; };   // canonical little-endian words
 struct Params { PointVec vk[6]; PointVec ic, h, l, a, b_g1, b_g2; };               // vk: alpha_g1 beta_g1 beta_g2 gamma_g2 delta_g1 delta_g2
 
@@ -45,7 +44,7 @@ struct Reader {
 };
 }  // namespace
 
-static std::string words_to_dec(const u32* w, int n) {
+std::string words_to_dec(const u32* w, int n) {
     std::vector<u32> v(w, w + n);
     std::string out;
     while (true) {
@@ -64,7 +63,7 @@ static std::string words_to_dec(const u32* w, int n) {
 }
 
 // r1cs_file.rs:185-270 from_reader (sections may come in any order; custom gates are not supported there either)
-static R1cs parse_r1cs(const uint8_t* b, size_t len, const Curve& cv) {
+R1cs parse_r1cs(const uint8_t* b, size_t len, const Curve& cv) {
     Reader rd{b, len, 0, "r1cs"};
     if (std::memcmp(rd.take(4), "r1cs", 4) != 0) throw std::runtime_error("r1cs: Invalid magic number");
     if (rd.u32le() != 1) throw std::runtime_error("r1cs: Unsupported version");

@@ -644,6 +644,41 @@ char* zk_pil_check_run(zk_pil_check_t* c, const uint64_t* const_pols, const uint
 char* zk_pil_check_run_dev(zk_pil_check_t* c, const uint64_t* d_const_pols, const uint64_t* d_cm_pols, uint64_t n_rows, void* stream);
 int zk_pil_check_free(zk_pil_check_t* c);
 
+/* ---- wtns_check: a witness against its R1CS (csrc/r1cs_check.hip) ----------------------------------------------------
+ * What `snarkjs wtns check` answers, on the device and for the three fields of this pipeline; neither the reference nor
+ * bellman checks a witness (the prover divides (A w)(B w) - C w by Z and drops the remainder).  No proving key is needed.
+ * field: "BN128" | "BLS12381" (the scalar fields, 32-byte values) | "GL" (Goldilocks, 8-byte values, the compressor's circuits).
+ * Checked: every constraint of the file's section 2 as written and in file order -- the rows the Groth16 circuit leaves
+ * unenforced included, bellman's appended `input * 0 = 0` rows not --, w[0] = 1, and over "GL" every use of the custom gates
+ * CMulAdd, Poseidon12, FFT4, EvPol4 (sections 4 and 5, resolved by template name as zk_c12_setup_new resolves them).
+ * zk_r1cs_check_new reads the file with the readers of zk_groth16_setup_new / zk_c12_setup_new (same error texts) and puts the
+ * three matrices on the device in CSR form.  zk_r1cs_check_info: n_public = public outputs + public inputs (wire 0 not counted).
+ * zk_r1cs_check_run: `witness` = n_values values, little-endian canonical, 32 B or 8 B each; _run_dev: the same already in HBM
+ * (taken as canonical, as zk_groth16_prove_dev takes its witness).  The report, JSON text (malloc'ed: zk_string_free):
+ *   {"field": "GL", "n_wires": n, "n_constraints": m,
+ *    "checked":   {"constraint": m, "cmuladd": a, "poseidon12": b, "fft4": c, "evpol4": d},
+ *    "n_failing": {"one_wire": 0 | 1, "constraint": ., "cmuladd": ., "poseidon12": ., "fft4": ., "evpol4": .},
+ *    "findings": [
+ *      {"kind": "one_wire", "value": "2"},
+ *      {"kind": "constraint", "index": 17, "a": "..", "b": "..", "c": "..",            the three row sums; a b != c
+ *       "wires": {"a": [[wire, "coefficient"], ..], "b": [..], "c": [..]}},           the row as the reader keeps it: by ascending wire
+ *      {"kind": "poseidon12", "use": u, "row": j, "column": i, "wire": w, "expected": "..", "value": ".."},
+ *      {"kind": "cmuladd" | "fft4" | "evpol4", "use": u, "position": k, "wire": w, "expected": "..", "value": ".."}]}
+ * Field values are decimal strings.  Kinds come in the order above; within a kind the findings ascend by index and there are at
+ * most max_findings of them; the n_failing counts are exact whatever max_findings is.  "use" counts the uses of section 5 in file
+ * order.  A gate finding names the first output that differs from what the use's inputs force: "position" counts the outputs
+ * (CMulAdd s[9 + k], FFT4 s[12 + k], EvPol4 s[18 + k]); Poseidon12 checks each of the 30 transitions from the witness' own
+ * row j and names (j, column) of the first wrong cell of row j + 1.  "wire" is the signal at that output.
+ * NULL + zk_last_error on error: n_values != n_wires, a host value that is not below the modulus (zk_groth16_prove's message),
+ * an unknown field, every fault of the readers, custom gates in a 32-byte-field file.  A handle is bound to the device
+ * current at its creation and is not re-entrant: one run at a time per handle. */
+typedef struct zk_r1cs_check zk_r1cs_check_t;
+zk_r1cs_check_t* zk_r1cs_check_new(const char* field, const void* r1cs, size_t len);
+int zk_r1cs_check_info(const zk_r1cs_check_t* c, uint32_t* n_wires, uint64_t* n_constraints, uint64_t* n_custom_uses, uint32_t* n_public);
+char* zk_r1cs_check_run(zk_r1cs_check_t* c, const void* witness, uint64_t n_values, uint32_t max_findings);
+char* zk_r1cs_check_run_dev(zk_r1cs_check_t* c, const void* d_witness, uint64_t n_values, uint32_t max_findings);
+int zk_r1cs_check_free(zk_r1cs_check_t* c);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,7 @@
   zkgpu_prove.py groth16_prove -c BN128 --r1cs circuit.r1cs -w witness.wtns -p g16.key --public-input public_input.json --proof proof.json [--verify verification_key.json]
   zkgpu_prove.py groth16_verify -c BN128 -v verification_key.json --public-input public_input.json --proof proof.json
   zkgpu_prove.py pil_verify -p circuit.pil.json --o circuit.const --m circuit.cm [--report out.json]
+  zkgpu_prove.py wtns_check -c BN128|BLS12381|GL --r1cs circuit.r1cs --wtns witness.wtns [--sym circuit.sym] [--report out.json] [--max-findings N]
   zkgpu_prove.py stark_verify -s starkStruct.json -p circuit.pil.json --o circuit.const --i zkin.json [--program FILE]
   zkgpu_prove.py compressor12_setup --r circuit.r1cs --c c12.const --p c12.pil --e c12.exec [--force_n_bits K] [--pil-json c12.pil.json]
   zkgpu_prove.py compressor12_exec --wtns witness.wtns --p c12.pil --e c12.exec --m c12.cm
@@ -29,6 +30,11 @@ starky/src/prove.rs:30-160, groth16/src/api.rs:144-205).  What differs, and why:
     verifyPil), on the device: one line `fileName:line: <kind> ...` per violated constraint, exit 0 when there is none and 1 otherwise;
     `--report` also writes the whole report as JSON.  `stark_prove --check-trace` runs it first and stops with the findings (exit 1)
     before any setup.
+  * wtns_check: `snarkjs wtns check` on the device (the reference has no counterpart): every constraint of the .r1cs as written, wire 0,
+    and over GL every use of the compressor's custom gates; one line per finding, exit 0 when there is none and 1 otherwise; `--sym` takes
+    circom's .sym file and prints every wire with its signal name; `--report` also writes the whole report as JSON.
+    `groth16_prove --check-witness` runs it first and stops with the findings (exit 1) before the proving key is read;
+    `compressor12_exec --check-witness R1CS` does the same in front of the exec.
   * stark_verify: the check alone, on a zkin file (the reference exposes it only inside stark_prove).
   * compressor12_setup: `--pil-json OUT` also writes the compiled PIL (tools/pilc.py; the reference leaves that step to pilcom), so
     that the next command can be stark_prove.  compressor12_exec: the witness comes as a `.wtns` with 8-byte field elements
@@ -106,6 +112,67 @@ def pil_verify(a):
     if report["findings"]:
         raise SystemExit(1)
     print("zkgpu_prove: %s satisfies %s (%d rows; %s)" % (a.cm_pols, a.piljson, report["n"], ", ".join("%d %s" % (v, k) for k, v in report["checked"].items())))
+
+
+def read_sym(text):
+    """circom's .sym file, one line per signal `label,wire,component,name` -> {wire: name}; a wire several names map to keeps
+    the first, lines of wire -1 (signals the compiler removed) are skipped"""
+    names = {}
+    for line in text.splitlines():
+        parts = line.strip().split(",", 3)
+        if len(parts) < 4:
+            continue
+        try:
+            wire = int(parts[1])
+        except ValueError:
+            continue
+        if wire >= 0:
+            names.setdefault(wire, parts[3])
+    return names
+
+
+def wtns_finding_line(f, names=None):
+    """one finding of a wtns_check report as a line; names: {wire: signal name} of a .sym file"""
+    wire = lambda w: "w%d (%s)" % (w, names[w]) if names and w in names else "w%d" % w
+    k = f["kind"]
+    if k == "one_wire":
+        return "one_wire: wire 0 holds %s, not 1" % f["value"]
+    if k == "constraint":
+        side = lambda lc: " + ".join("%s*%s" % (c, wire(w)) for w, c in lc) or "0"
+        return "constraint %d: a*b != c with a = %s, b = %s, c = %s; a: %s; b: %s; c: %s" % (
+            f["index"], f["a"], f["b"], f["c"], side(f["wires"]["a"]), side(f["wires"]["b"]), side(f["wires"]["c"]))
+    at = "row %d column %d" % (f["row"], f["column"]) if k == "poseidon12" else "output %d" % f["position"]
+    return "%s use %d: %s, %s holds %s, the inputs force %s" % (k, f["use"], at, wire(f["wire"]), f["value"], f["expected"])
+
+
+def _check_witness(field, r1cs_file, wtns_file, max_findings=16):
+    """-> the wtns_check report of the files"""
+    import importlib
+    dev = importlib.import_module("eigen_zkvm_amd.r1cs")
+    values, n = dev.wtns_payload(pathlib.Path(wtns_file).read_bytes(), field)
+    chk = dev.R1csCheck(field, pathlib.Path(r1cs_file).read_bytes())
+    try:
+        return chk.run(values, max_findings=max_findings, n_values=n), chk.info
+    finally:
+        chk.free()
+
+
+def _stop_on_findings(report, sym=None, out=sys.stderr):
+    names = read_sym(pathlib.Path(sym).read_text()) if sym else None
+    for f in report["findings"]:
+        print(wtns_finding_line(f, names), file=out)
+    if report["findings"] or any(report["n_failing"].values()):
+        raise SystemExit(1)
+
+
+def wtns_check(a):
+    _zk()
+    report, info = _check_witness(a.curve_type, a.circuit_file, a.wtns, a.max_findings)
+    if a.report:
+        with open(a.report, "w") as f:
+            json.dump(report, f, indent=1)
+    _stop_on_findings(report, a.sym, out=sys.stdout)
+    print("zkgpu_prove: %s satisfies %s (%d constraints, %d custom-gate uses)" % (a.wtns, a.circuit_file, info["n_constraints"], info["n_custom_uses"]))
 
 
 def stark_prove(a):
@@ -264,6 +331,8 @@ def compressor12_exec(a):
     dev = importlib.import_module("eigen_zkvm_amd.compressor12")
     if not a.wtns:
         raise SystemExit("zkgpu_prove: compressor12_exec needs --wtns FILE (running the .wasm on --i is out of scope)")
+    if a.check_witness:                                                    # nothing is executed for a bad witness
+        _stop_on_findings(_check_witness("GL", a.check_witness, a.wtns)[0])
     b = pathlib.Path(a.wtns).read_bytes()
     if b[:4] != b"wtns" or len(b) < 12:
         raise SystemExit("zkgpu_prove: %s is not a .wtns file" % a.wtns)
@@ -300,6 +369,8 @@ def groth16_prove(a):
     import importlib
     zk = _zk()
     dev = importlib.import_module("eigen_zkvm_amd.groth16")
+    if a.check_witness:                                                    # the proving key is not read for a bad witness
+        _stop_on_findings(_check_witness(a.curve_type, a.circuit_file, a.wasm_file)[0])
     r1cs, pk, wtns = (pathlib.Path(p).read_bytes() for p in (a.circuit_file, a.pk_file, a.wasm_file))
     if not wtns.startswith(b"wtns"):
         raise SystemExit("zkgpu_prove: -w must be the .wtns file of the witness calculator (running the .wasm is out of scope)")
@@ -361,6 +432,14 @@ def build_parser():
     pv.add_argument("--m", dest="cm_pols", default="pols.cm")
     pv.add_argument("--report", default=None, metavar="OUT.json", help="also write the whole report")
     pv.set_defaults(fn=pil_verify)
+    wc = sub.add_parser("wtns_check", help="check a witness against its R1CS, constraint by constraint (extension; `snarkjs wtns check`)")
+    wc.add_argument("-c", dest="curve_type", default="BN128", choices=["BN128", "BLS12381", "GL"])
+    wc.add_argument("--r1cs", dest="circuit_file", required=True)
+    wc.add_argument("--wtns", required=True)
+    wc.add_argument("--sym", default=None, help="circom's .sym file: wires are printed with their signal names")
+    wc.add_argument("--report", default=None, metavar="OUT.json", help="also write the whole report")
+    wc.add_argument("--max-findings", dest="max_findings", type=int, default=16, help="findings listed per kind (the counts are always exact)")
+    wc.set_defaults(fn=wtns_check)
     v = sub.add_parser("stark_verify", help="stark_verify.rs:20-136 on a zkin file (extension: the reference runs it inside stark_prove only)")
     v.add_argument("-s", "--stark_stuct", dest="stark_struct", default="stark_struct.json")
     v.add_argument("-p", "--piljson", default="pil.json")
@@ -394,6 +473,8 @@ def build_parser():
     ce.add_argument("--p", dest="pil_file", default="mycircuit.c12.pil")
     ce.add_argument("--e", dest="exec_file", default="mycircuit.c12.exec")
     ce.add_argument("--m", dest="commit_file", default="mycircuit.c12.cm")
+    ce.add_argument("--check-witness", dest="check_witness", default=None, metavar="R1CS",
+                    help="run wtns_check of the witness against this .r1cs first and stop with its findings (exit 1) before the exec (extension)")
     ce.set_defaults(fn=compressor12_exec)
     k = sub.add_parser("groth16_setup", help="Setup groth16 (zkit/src/main.rs:185-196)")
     k.add_argument("-c", dest="curve_type", default="BN128")
@@ -413,6 +494,8 @@ def build_parser():
     g.add_argument("-t", dest="to_hex", action="store_true")
     g.add_argument("--verify", dest="verify_vk", default=None, metavar="VK.json",
                    help="check the proof against this verification key before writing it (extension)")
+    g.add_argument("--check-witness", dest="check_witness", action="store_true",
+                   help="run wtns_check first and stop with its findings (exit 1) before the proving key is read (extension)")
     g.set_defaults(fn=groth16_prove)
     gv = sub.add_parser("groth16_verify", help="Verify with groth16 (zkit/src/main.rs:221-230)")
     gv.add_argument("-c", dest="curve_type", default="BN128")
