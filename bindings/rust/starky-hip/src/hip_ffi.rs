@@ -124,6 +124,12 @@ extern "C" {
     pub fn zk_stream_sync(stream: *mut c_void) -> c_int;
     pub fn zk_stream_free(stream: *mut c_void) -> c_int;
     pub fn zk_string_free(s: *mut c_char);
+    pub fn zk_groth16_key_check(curve: *const c_char, r1cs: *const c_void, r1cs_len: usize, params: *const c_void, params_len: usize,
+                                vk_json: *const c_char, seed: *const u8, max_findings: u32) -> *mut c_char;
+    pub fn zk_points_check_bn254(group: c_int, points: *const c_void, n: u64, plain: c_int, out: *mut u64) -> c_int;
+    pub fn zk_points_check_bn254_dev(group: c_int, d_points: *const c_void, n: u64, plain: c_int, d_out: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn zk_points_check_bls12_381(group: c_int, points: *const c_void, n: u64, plain: c_int, out: *mut u64) -> c_int;
+    pub fn zk_points_check_bls12_381_dev(group: c_int, d_points: *const c_void, n: u64, plain: c_int, d_out: *mut u64, stream: *mut c_void) -> c_int;
     pub fn zk_stark_setup_free(s: *mut zk_stark_setup_t) -> c_int;
     pub fn zk_bn128_load_constants(path: *const c_char) -> c_int;
     pub fn zk_bls12381_load_constants(path: *const c_char) -> c_int;

@@ -59,6 +59,7 @@ EXPORTS = [
     "zk_groth16_verify_batch", "zk_groth16_verify_batch_dev", "zk_groth16_verify_json", "zk_groth16_verdict_name",
     "zk_pil_check_new", "zk_pil_check_listing", "zk_pil_check_run", "zk_pil_check_run_dev", "zk_pil_check_free",
     "zk_r1cs_check_new", "zk_r1cs_check_info", "zk_r1cs_check_run", "zk_r1cs_check_run_dev", "zk_r1cs_check_free",
+    "zk_groth16_key_check", "zk_points_check_bn254", "zk_points_check_bn254_dev", "zk_points_check_bls12_381", "zk_points_check_bls12_381_dev",
 ]
 
 # include/zkgpu.h enums
@@ -324,6 +325,11 @@ def _load():
         "zk_r1cs_check_run": (vp, [vp, vp, C.c_uint64, C.c_uint32]),
         "zk_r1cs_check_run_dev": (vp, [vp, vp, C.c_uint64, C.c_uint32]),
         "zk_r1cs_check_free": (C.c_int, [vp]),
+        "zk_groth16_key_check": (vp, [C.c_char_p, vp, C.c_size_t, vp, C.c_size_t, C.c_char_p, vp, C.c_uint32]),
+        "zk_points_check_bn254": (C.c_int, [C.c_int, vp, C.c_uint64, C.c_int, vp]),
+        "zk_points_check_bn254_dev": (C.c_int, [C.c_int, vp, C.c_uint64, C.c_int, vp, vp]),
+        "zk_points_check_bls12_381": (C.c_int, [C.c_int, vp, C.c_uint64, C.c_int, vp]),
+        "zk_points_check_bls12_381_dev": (C.c_int, [C.c_int, vp, C.c_uint64, C.c_int, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

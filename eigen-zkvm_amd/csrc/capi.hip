@@ -348,6 +348,27 @@ static int pairing_host(CurveId id, const void* g1, const void* g2, uint64_t n, 
         d2h_sync(gt_out, dg.p, n * cv.gt_bytes());
     });
 }
+static int points_check_device(CurveId id, int group, const void* d_points, uint64_t n, int plain, uint64_t* d_out, void* stream) {
+    return guard([&] {
+        ZK_REQUIRE(group == 1 || group == 2, "points check: group must be 1 or 2");
+        ZK_REQUIRE(d_out && (d_points || n == 0), "points check: null argument");
+        const Group g = group == 1 ? G1 : G2;
+        curve(id).pairing().points_check[g](d_points, curve(id).point_words(g), n, plain != 0, 0, (u64*)d_out, on_stream((hipStream_t)stream));
+    });
+}
+static int points_check_host(CurveId id, int group, const void* points, uint64_t n, int plain, uint64_t* out) {
+    return guard([&] {
+        ZK_REQUIRE(group == 1 || group == 2, "points check: group must be 1 or 2");
+        ZK_REQUIRE(out && (points || n == 0), "points check: null argument");
+        const Curve& cv = curve(id);
+        const Group g = group == 1 ? G1 : G2;
+        DevBuf d, r;
+        d.reserve(n * cv.point_bytes(g) + 4); r.reserve(64);
+        if (n) h2d_sync(d.p, points, n * cv.point_bytes(g));
+        cv.pairing().points_check[g](d.p, cv.point_words(g), n, plain != 0, 0, r.u(), cur_stream());
+        d2h_sync(out, r.p, 64);
+    });
+}
 #define ZK_GROUP_API(GN, NAME, ID, G)                                                                                                         \
     int zk_msm_##GN##_##NAME(const void* bases, const void* scalars, uint64_t n, void* out, int* is_infinity) { return msm_host(ID, G, bases, scalars, n, out, is_infinity); } \
     int zk_msm_##GN##_##NAME##_dev(const void* d_bases, const void* d_scalars, uint64_t n, void* d_out, void* stream) { return msm_device(ID, G, d_bases, d_scalars, n, d_out, stream); } \
@@ -366,7 +387,9 @@ static int pairing_host(CurveId id, const void* g1, const void* g2, uint64_t n, 
     int zk_fr_##NAME##_quotient_dev(uint64_t* a, const uint64_t* b, const uint64_t* c, uint32_t log_n, void* stream) { return fr_quotient(ID, a, b, c, log_n, stream); } \
     int zk_fq_##NAME##_convert_dev(void* d, uint64_t n, int to_mont, void* stream) { return fq_convert(ID, d, n, to_mont, stream); }          \
     int zk_pairing_##NAME##_dev(const void* d_g1, const void* d_g2, uint64_t n, void* d_gt, int with_final_exp, void* stream) { return pairing_device(ID, d_g1, d_g2, n, d_gt, with_final_exp, stream); } \
-    int zk_pairing_##NAME(const void* g1, const void* g2, uint64_t n, void* gt_out, int with_final_exp) { return pairing_host(ID, g1, g2, n, gt_out, with_final_exp); }
+    int zk_pairing_##NAME(const void* g1, const void* g2, uint64_t n, void* gt_out, int with_final_exp) { return pairing_host(ID, g1, g2, n, gt_out, with_final_exp); } \
+    int zk_points_check_##NAME##_dev(int group, const void* d_points, uint64_t n, int plain, uint64_t* d_out, void* stream) { return points_check_device(ID, group, d_points, n, plain, d_out, stream); } \
+    int zk_points_check_##NAME(int group, const void* points, uint64_t n, int plain, uint64_t* out) { return points_check_host(ID, group, points, n, plain, out); }
 ZK_CURVE_API(bn254, CURVE_BN254)
 ZK_CURVE_API(bls12_381, CURVE_BLS12_381)
 #undef ZK_CURVE_API
@@ -569,6 +592,12 @@ int zk_c12_sigma_dev(const uint32_t* d_s_map, uint64_t n_used, uint32_t n_bits, 
 zk_groth16_setup_t* zk_groth16_setup_new(const char* curve, const void* r1cs, size_t r1cs_len, const void* params, size_t params_len) {
     zk_groth16_setup_t* out = nullptr;
     if (guard([&] { out = groth16_setup_new(curve, r1cs, r1cs_len, params, params_len); }) != 0) return nullptr;
+    return out;
+}
+char* zk_groth16_key_check(const char* curve, const void* r1cs, size_t r1cs_len, const void* params, size_t params_len, const char* vk_json,
+                           const uint8_t* seed, uint32_t max_findings) {
+    char* out = nullptr;
+    if (guard([&] { out = c12_dup(groth16_key_check(curve, r1cs, r1cs_len, params, params_len, vk_json, seed, max_findings)); }) != 0) return nullptr;
     return out;
 }
 int zk_groth16_setup_info(const zk_groth16_setup_t* s, uint32_t* n_wires, uint32_t* n_inputs, uint32_t* domain_log) {

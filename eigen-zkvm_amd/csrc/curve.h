@@ -61,6 +61,9 @@ struct PairingOps {
     void (*miller)(const MillerArgs&, u64, void*, hipStream_t);
     void (*final_exp)(const void*, u64, void*, void*, int, hipStream_t);
     void (*verdict)(const void*, const void*, u64, const int*, int*, hipStream_t);
+    // by Group (key_check_impl.hip.h): points, stride in words, n, plain, canon -> 4 x (count, first index) for infinity, coordinate_range,
+    // not_on_curve, not_in_subgroup
+    void (*points_check[2])(const void*, u64, u64, int, int, u64*, hipStream_t);
 };
 const MsmOps& msm_ops(CurveId id);
 const Groth16Ops& groth16_ops(CurveId id);
@@ -109,8 +112,17 @@ void groth16_wtns_payload(const void* wtns, size_t len, const char* curve, uint6
 Groth16Setup* groth16_setup_new(const char* curve, const void* r1cs, size_t r1cs_len, const void* params, size_t params_len);
 Groth16Key* groth16_keygen_new(const char* curve, const void* r1cs, size_t r1cs_len, const uint64_t* trapdoor);
 std::string groth16_keygen_vk_json(const Groth16Key& k, bool to_hex);   // json_utils.rs:285-303 serialize_vk
+// groth16_key_check (groth16.hip): the report as JSON text.  seed: 32 bytes for the random linear combination, for tests only -- null (the operating
+// system's randomness) anywhere else.
+std::string groth16_key_check(const char* curve, const void* r1cs, size_t r1cs_len, const void* params, size_t params_len, const char* vk_json,
+                              const uint8_t* seed, uint32_t max_findings);
 
 // ---- pairing.hip: the optimal ate pairing and Groth16 verification ----
+// one point of a verification_key.json or a proof ({"x", "y"}; G2: [c0, c1] pairs) -> 2 or 4 x fq_words canonical 32-bit words; pairing_ce's
+// zero (0, 1) becomes the all-zero encoding; negate: y -> q - y.  Throws on what is no number or does not fit the field's width.
+struct JVal;
+void groth16_json_g1(const Curve& cv, const JVal& v, uint32_t* w);
+void groth16_json_g2(const Curve& cv, const JVal& v, uint32_t* w, bool negate);
 void pairing_dev(const Curve& cv, const void* d_g1, const void* d_g2, uint64_t n, void* d_gt, int with_final_exp, hipStream_t st);
 Groth16Vk* groth16_vk_new(const char* curve, const char* vk_json);
 void groth16_vk_info(const Groth16Vk* vk, uint32_t* n_public, uint32_t* proof_bytes, uint32_t* gt_bytes);

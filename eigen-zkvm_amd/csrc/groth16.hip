@@ -14,9 +14,11 @@
 // function of (key, circuit, witness).
 #include "curve.h"
 #include "r1cs_file.h"
+#include "json_min.h"
 #include <algorithm>
 #include <cerrno>
 #include <chrono>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -324,6 +326,220 @@ std::string groth16_keygen_vk_json(const Groth16Key& k, bool to_hex) {
     js += ",\"IC\":[";
     for (u32 i = 0; i < n_ic; ++i) { if (i) js += ","; js += g1(); }
     return js + "]}";
+}
+
+// ---- groth16_key_check: a proving key against its circuit, before the prover takes it on faith -----------------------------------------
+// The one input of groth16_prove that is read unchecked (parse_params is the reference's read_pk_from_file(path, checked = false)).
+// Findings in a fixed order: section lengths against the circuit's; the class of every point (key_check_impl.hip.h: infinity --
+// bellman's Parameters::read refuses it in EVERY section, although the reference's own setup writes it for a wire no row mentions --,
+// a coordinate >= q, off the curve, outside the subgroup) with exact counts and first indices; the G1 and G2 copies of beta, delta and the
+// b query tied together by pairings (b: one random linear combination sum rho_i b_g1_i against sum rho_i b_g2_i, rho_i of 128 bits; a
+// wrong pair survives with probability 2^-128; on failure the smallest failing prefix by bisection); verification_key.json field by field.
+// What is NOT checked: h, l, ic and a against the circuit's polynomials -- that takes tau in G2 or the trapdoor.  "key ok" means well
+// formed and self-consistent; the functional test remains groth16_prove --verify.
+namespace g16 {
+// rho_i = the first 128 bits of ChaCha20(key = seed, counter = i, nonce = 0) as a 32 B canonical scalar
+__device__ __forceinline__ u32 kc_rotl(u32 v, int c) { return (v << c) | (v >> (32 - c)); }
+#define KC_QR(a, b, c, d) a += b; d = kc_rotl(d ^ a, 16); c += d; b = kc_rotl(b ^ c, 12); a += b; d = kc_rotl(d ^ a, 8); c += d; b = kc_rotl(b ^ c, 7);
+__global__ __launch_bounds__(256) void kc_rho_kernel(const u32* __restrict__ seed, u64 n, u32* __restrict__ out) {
+    const u64 i = blockIdx.x * 256ull + threadIdx.x;
+    if (i >= n) return;
+    u32 in[16] = {0x61707865u, 0x3320646eu, 0x79622d32u, 0x6b206574u, seed[0], seed[1], seed[2], seed[3], seed[4], seed[5], seed[6], seed[7],
+                  (u32)i, (u32)(i >> 32), 0u, 0u};
+    u32 x[16];
+    for (int k = 0; k < 16; ++k) x[k] = in[k];
+    for (int r = 0; r < 10; ++r) {
+        KC_QR(x[0], x[4], x[8], x[12]) KC_QR(x[1], x[5], x[9], x[13]) KC_QR(x[2], x[6], x[10], x[14]) KC_QR(x[3], x[7], x[11], x[15])
+        KC_QR(x[0], x[5], x[10], x[15]) KC_QR(x[1], x[6], x[11], x[12]) KC_QR(x[2], x[7], x[8], x[13]) KC_QR(x[3], x[4], x[9], x[14])
+    }
+    for (int k = 0; k < 4; ++k) { out[i * 8 + k] = x[k] + in[k]; out[i * 8 + 4 + k] = 0; }
+}
+#undef KC_QR
+
+static const char* const KC_CLASS_NAMES[4] = {"infinity", "coordinate_range", "not_on_curve", "not_in_subgroup"};
+struct KcSection { const char* name; Group g; const PointVec* pv; DevBuf d; };
+
+}  // namespace g16
+
+std::string groth16_key_check(const char* curve, const void* r1cs, size_t r1cs_len, const void* params, size_t params_len, const char* vk_json,
+                              const uint8_t* seed, uint32_t max_findings) {
+    using namespace g16;
+    using clk = std::chrono::steady_clock;
+    auto since = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    const Curve& cv = curve_of(curve, GROTH16_NAMES);
+    ZK_REQUIRE(r1cs && params, "groth16: null input");
+    const auto t0 = clk::now();
+    const R1cs rc = parse_r1cs((const uint8_t*)r1cs, r1cs_len, cv);
+    const Params pk = parse_params((const uint8_t*)params, params_len, 4 * (int)cv.fq_words);
+    const Circuit cir(rc);
+    const auto t1 = clk::now();
+    const int cw = (int)cv.fq_words;
+    const size_t P1 = cv.point_words(G1), P2 = cv.point_words(G2);
+    hipStream_t st = cur_stream();
+    const PairingOps& po = cv.pairing();
+
+    u64 na = cir.ni, nb = 0;
+    for (uint32_t j = cir.ni; j < cir.n_wires; ++j) na += cir.a_aux[j] ? 1 : 0;
+    for (uint32_t j = 0; j < cir.n_wires; ++j) nb += cir.b_any[j] ? 1 : 0;
+
+    std::string found[7], skipped;                          // by kind: size, the four classes, g1_g2_mismatch, vk_mismatch -- the report lists
+    u64 counts[7] = {};                                     // them kind by kind, whatever the order they are met in
+    auto add = [&](int kind, const std::string& body) {
+        if (counts[kind]++ < max_findings) { if (!found[kind].empty()) found[kind] += ","; found[kind] += body; }
+    };
+    auto skip = [&](const char* section, const char* reason) {
+        if (!skipped.empty()) skipped += ",";
+        skipped += std::string("{\"check\":\"g1_g2_mismatch\",\"section\":\"") + section + "\",\"reason\":\"" + reason + "\"}";
+    };
+    // 1. sizes
+    const struct { const char* name; u64 have, want; } sizes[6] = {{"ic", pk.ic.n, cir.ni}, {"h", pk.h.n, cir.m - 1}, {"l", pk.l.n, cir.n_aux},
+                                                                  {"a", pk.a.n, na}, {"b_g1", pk.b_g1.n, nb}, {"b_g2", pk.b_g2.n, nb}};
+    for (const auto& s : sizes)
+        if (s.have != s.want)
+            add(0, std::string("{\"kind\":\"size\",\"section\":\"") + s.name + "\",\"have\":" + std::to_string(s.have) + ",\"want\":" + std::to_string(s.want) + "}");
+    // 2. every point's class: canonical words up, one launch per section, 8 words per section back
+    static const char* const vk_names[6] = {"alpha_g1", "beta_g1", "beta_g2", "gamma_g2", "delta_g1", "delta_g2"};
+    static const Group vk_group[6] = {G1, G1, G2, G2, G1, G2};
+    KcSection sec[12];
+    for (int i = 0; i < 6; ++i) { sec[i].name = vk_names[i]; sec[i].g = vk_group[i]; sec[i].pv = &pk.vk[i]; }
+    const PointVec* qs[6] = {&pk.ic, &pk.h, &pk.l, &pk.a, &pk.b_g1, &pk.b_g2};
+    for (int i = 0; i < 6; ++i) { sec[6 + i].name = sizes[i].name; sec[6 + i].g = i == 5 ? G2 : G1; sec[6 + i].pv = qs[i]; }
+    DevBuf d_res; d_res.reserve(12 * 8 * 8);
+    u64 n_g1 = 0, n_g2 = 0;
+    for (int i = 0; i < 12; ++i) {
+        KcSection& s = sec[i];
+        const size_t pw = s.g == G1 ? P1 : P2;
+        s.d.reserve(s.pv->n * pw * 4 + 4);
+        if (s.pv->n) h2d_sync(s.d.p, s.pv->w.data(), s.pv->n * pw * 4);
+        po.points_check[s.g](s.d.p, pw, s.pv->n, 0, 1, d_res.u() + 8 * i, st);
+        (s.g == G1 ? n_g1 : n_g2) += s.pv->n;
+    }
+    u64 res[12][8];
+    d2h_sync(res, d_res.p, sizeof res);
+    const auto t2 = clk::now();
+    bool bad[12];
+    for (int i = 0; i < 12; ++i) {
+        bad[i] = false;
+        for (int c = 0; c < 4; ++c) {
+            if (!res[i][2 * c]) continue;
+            bad[i] = true;
+            add(1 + c, std::string("{\"kind\":\"") + KC_CLASS_NAMES[c] + "\",\"section\":\"" + sec[i].name + "\",\"n_points\":" + std::to_string(res[i][2 * c]) +
+                           ",\"first_index\":" + std::to_string(res[i][2 * c + 1]) + "}");
+        }
+    }
+    // 3. the G1 and G2 copies.  e(P1, G2) = e(G1, P2) as two reduced pairings compared (the product form e(P1, -G2) e(G1, P2) = 1 asks the same)
+    DevBuf d_gen1, d_gen2, d_one, d_p1, d_p2, d_gt;
+    d_gen1.reserve(P1 * 4); d_gen2.reserve(P2 * 4); d_one.reserve(8); d_p1.reserve(2 * P1 * 4); d_p2.reserve(2 * P2 * 4); d_gt.reserve(2 * cv.gt_bytes());
+    const u64 one = 1;
+    h2d_sync(d_one.p, &one, 8);
+    cv.group(G1).mul_generator_dev(d_one.u(), 1, d_gen1.p, st);
+    cv.group(G2).mul_generator_dev(d_one.u(), 1, d_gen2.p, st);
+    double ms_sum = 0, ms_pair = 0;
+    u64 pairs = 0;
+    // d_a: a G1 point, d_b: a G2 point (Montgomery; all zero = infinity) -> e(a, G2) == e(G1, b)
+    auto same_pair = [&](const void* d_a, const void* d_b) {
+        const auto ta = clk::now();
+        ZK_HIP(hipMemcpyAsync(d_p1.p, d_a, P1 * 4, hipMemcpyDeviceToDevice, st));
+        ZK_HIP(hipMemcpyAsync((u32*)d_p1.p + P1, d_gen1.p, P1 * 4, hipMemcpyDeviceToDevice, st));
+        ZK_HIP(hipMemcpyAsync(d_p2.p, d_gen2.p, P2 * 4, hipMemcpyDeviceToDevice, st));
+        ZK_HIP(hipMemcpyAsync((u32*)d_p2.p + P2, d_b, P2 * 4, hipMemcpyDeviceToDevice, st));
+        pairing_dev(cv, d_p1.p, d_p2.p, 2, d_gt.p, 1, st);
+        std::vector<uint8_t> gt(2 * cv.gt_bytes());
+        d2h_sync(gt.data(), d_gt.p, gt.size());
+        ms_pair += since(ta, clk::now());
+        return std::memcmp(gt.data(), gt.data() + cv.gt_bytes(), cv.gt_bytes()) == 0;
+    };
+    const int pair_idx[2][2] = {{1, 2}, {4, 5}};
+    static const char* const pair_name[2] = {"beta", "delta"};
+    for (int k = 0; k < 2; ++k) {
+        const int i1 = pair_idx[k][0], i2 = pair_idx[k][1];
+        if (bad[i1] || bad[i2]) { skip(pair_name[k], "an invalid point"); continue; }
+        cv.msm().fq_canon_to_mont_dev(sec[i1].d.p, P1 / cw, st); cv.msm().fq_canon_to_mont_dev(sec[i2].d.p, P2 / cw, st);
+        ++pairs;
+        if (!same_pair(sec[i1].d.p, sec[i2].d.p)) add(5, std::string("{\"kind\":\"g1_g2_mismatch\",\"section\":\"") + pair_name[k] + "\",\"first_index\":0}");
+    }
+    if (pk.b_g1.n != pk.b_g2.n) skip("b", "b_g1 and b_g2 differ in length");
+    else if (bad[10] || bad[11]) skip("b", "an invalid point");
+    else if (pk.b_g1.n) {
+        const u64 n = pk.b_g1.n;
+        pairs += n;
+        uint8_t sd[32];
+        if (seed) std::memcpy(sd, seed, 32);
+        else {
+            size_t got = 0;
+            while (got < 32) {
+                const ssize_t k = getrandom(sd + got, 32 - got, 0);
+                if (k < 0 && errno == EINTR) continue;
+                ZK_REQUIRE(k > 0, "groth16 key check: the operating system gave no random bytes");
+                got += (size_t)k;
+            }
+        }
+        DevBuf d_seed, d_rho, d_s1, d_s2;
+        d_seed.reserve(32); d_rho.reserve(n * 32); d_s1.reserve(P1 * 4 + 4); d_s2.reserve(P2 * 4 + 4);
+        h2d_sync(d_seed.p, sd, 32);
+        wipe(sd, 32);
+        hipLaunchKernelGGL(kc_rho_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const u32*)d_seed.p, n, (u32*)d_rho.p);
+        ZK_HIP(hipGetLastError());
+        cv.msm().fq_canon_to_mont_dev(sec[10].d.p, n * P1 / cw, st); cv.msm().fq_canon_to_mont_dev(sec[11].d.p, n * P2 / cw, st);
+        // the first len elements: sum rho_i b_g1_i against sum rho_i b_g2_i
+        auto prefix_ok = [&](u64 len) {
+            const auto ta = clk::now();
+            cv.group(G1).msm_dev(sec[10].d.p, d_rho.p, len, d_s1.p, st);
+            cv.group(G2).msm_dev(sec[11].d.p, d_rho.p, len, d_s2.p, st);
+            u32 f1 = 0, f2 = 0;
+            d2h_sync(&f1, (const u32*)d_s1.p + P1, 4); d2h_sync(&f2, (const u32*)d_s2.p + P2, 4);
+            ms_sum += since(ta, clk::now());
+            if (f1 || f2) return f1 && f2;
+            return same_pair(d_s1.p, d_s2.p);
+        };
+        if (!prefix_ok(n)) {
+            u64 lo = 0, hi = n;                             // the prefix of lo elements holds, that of hi fails
+            while (hi - lo > 1) { const u64 mid = lo + (hi - lo) / 2; if (prefix_ok(mid)) lo = mid; else hi = mid; }
+            add(5, "{\"kind\":\"g1_g2_mismatch\",\"section\":\"b\",\"first_index\":" + std::to_string(hi - 1) + "}");
+        }
+    }
+    // 4. verification_key.json against the embedded copy
+    if (vk_json) {
+        const JVal js = JParser::parse(vk_json);
+        static const struct { const char* field; int idx; bool g2, optional; } f[6] = {{"vk_alpha_1", 0, false, false}, {"vk_beta_1", 1, false, true}, {"vk_beta_2", 2, true, false},
+                                                                                       {"vk_gamma_2", 3, true, false}, {"vk_delta_1", 4, false, true}, {"vk_delta_2", 5, true, false}};
+        auto mismatch = [&](const std::string& field) { add(6, "{\"kind\":\"vk_mismatch\",\"field\":\"" + field + "\"}"); };
+        // the file's points through the verifier's own readers (pairing.hip; a field that is no point is their error), word for word
+        std::vector<u32> w(P2);
+        auto differs = [&](const JVal& v, bool g2, const u32* want) {
+            if (g2) groth16_json_g2(cv, v, w.data(), false); else groth16_json_g1(cv, v, w.data());
+            return std::memcmp(w.data(), want, (g2 ? P2 : P1) * 4) != 0;
+        };
+        for (const auto& e : f) {
+            if (e.optional && !js.find(e.field)) continue;
+            if (differs(js.at(e.field), e.g2, pk.vk[e.idx].w.data())) mismatch(e.field);
+        }
+        const JVal& ic = js.at("IC");
+        if (ic.kind != JVal::Arr || ic.size() != pk.ic.n) mismatch("IC");
+        else
+            for (size_t i = 0; i < ic.size(); ++i)
+                if (differs(ic.at(i), false, pk.ic.w.data() + i * P1)) mismatch("IC[" + std::to_string(i) + "]");
+    }
+    ZK_HIP(hipStreamSynchronize(st));
+    static const char* const kinds[7] = {"size", "infinity", "coordinate_range", "not_on_curve", "not_in_subgroup", "g1_g2_mismatch", "vk_mismatch"};
+    std::string js = std::string("{\"curve\":\"") + cv.name + "\",\"n_wires\":" + std::to_string(cir.n_wires) + ",\"n_public\":" + std::to_string(cir.ni - 1) +
+                     ",\"domain_log\":" + std::to_string(cir.logm) + ",\"sections\":{";
+    for (int i = 0; i < 6; ++i) js += std::string(i ? "," : "") + "\"" + sizes[i].name + "\":" + std::to_string(sizes[i].have);
+    js += "},\"checked\":{\"g1_points\":" + std::to_string(n_g1) + ",\"g2_points\":" + std::to_string(n_g2) + ",\"pairs\":" + std::to_string(pairs) + "},\"skipped\":[" + skipped + "],\"counts\":{";
+    for (int k = 0; k < 7; ++k) js += std::string(k ? "," : "") + "\"" + kinds[k] + "\":" + std::to_string(counts[k]);
+    js += "},\"findings\":[";
+    bool first = true;
+    for (int k = 0; k < 7; ++k)
+        if (!found[k].empty()) { js += (first ? "" : ",") + found[k]; first = false; }
+    js += "]";
+    // ZK_KEY_CHECK_TIMING (read per call, as ZK_STARK_TIMING is; tools/key_check_time.py sets it): the host's milliseconds of reading (both files
+    // and the circuit's three matrices), the point checks, the sums and the pairings
+    if (const char* env = getenv("ZK_KEY_CHECK_TIMING"); env && *env && strcmp(env, "0")) {
+        char buf[160];
+        snprintf(buf, sizeof buf, ",\"timing_ms\":{\"parse\":%.3f,\"point_checks\":%.3f,\"sums\":%.3f,\"pairings\":%.3f}", since(t0, t1), since(t1, t2), ms_sum, ms_pair);
+        js += buf;
+    }
+    return js + "}";
 }
 
 // reader.rs:86-137 load_witness_from_bin_reader: header checks, then n x 32 B little-endian canonical values

@@ -11,7 +11,7 @@
 //   3. final_exp_kernel   the same lanes: easy part with one inversion, hard part (q^4 - q^2 + 1)/r in a 4-bit window over
 //                         Granger-Scott squarings; the exact reduced pairing
 // and around them the input checks (curve, subgroup by [r]P = O, canonical public inputs), acc = IC_0 + sum x_j IC_j, and
-// the comparison with e(alpha, beta).  Stricter than the reference, which reads points unchecked (json_utils.rs:163-198).
+// the comparison with e(alpha, beta); the point checks at the scale of a proving key are key_check_impl.hip.h.  Stricter than the reference, which reads points unchecked (json_utils.rs:163-198).
 // Fq, Fq2 and the point formulas are the sums' (fe29_impl.hip.h, ecpt_impl.hip.h); fe_mul and the Fq2 product are real
 // functions here, and the loops over exponent bits stay loops: the code-size hazard recorded in msm.hip.
 #include "curve.h"
@@ -36,6 +36,7 @@ namespace pg1 {
 namespace {
 #include "ecpt_impl.hip.h"
 #include "pairing_impl.hip.h"
+#include "key_check_impl.hip.h"
 }
 }  // namespace pg1
 namespace pg2 {
@@ -43,6 +44,7 @@ namespace pg2 {
 namespace {
 #include "ecpt_impl.hip.h"
 #include "pairing_impl.hip.h"
+#include "key_check_impl.hip.h"
 }
 #undef MSM_G2
 #undef CF_MUL_ATTR
@@ -50,13 +52,15 @@ namespace {
 }  // namespace pg2
 static const PairingOps OPS = {"30644e72e131a029b85045b68181585d97816a916871ca8d3c208c16d87cfd47",
                                pg1::g1_check_dev, pg1::g16_acc_dev, pg2::g2_check_dev, pg2::g2_lines_bytes, pg2::g2_lines_dev, pg2::f12_bytes,
-                               pg2::final_exp_tab_bytes, pg2::miller_dev, pg2::final_exp_dev, pg2::g16_verdict_dev};
+                               pg2::final_exp_tab_bytes, pg2::miller_dev, pg2::final_exp_dev, pg2::g16_verdict_dev,
+                               {pg1::points_check_dev, pg2::points_check_dev}};
 }  // namespace bn254
 namespace bls12_381 {
 namespace pg1 {
 namespace {
 #include "ecpt_impl.hip.h"
 #include "pairing_impl.hip.h"
+#include "key_check_impl.hip.h"
 }
 }  // namespace pg1
 namespace pg2 {
@@ -64,6 +68,7 @@ namespace pg2 {
 namespace {
 #include "ecpt_impl.hip.h"
 #include "pairing_impl.hip.h"
+#include "key_check_impl.hip.h"
 }
 #undef MSM_G2
 #undef CF_MUL_ATTR
@@ -71,7 +76,8 @@ namespace {
 }  // namespace pg2
 static const PairingOps OPS = {"1a0111ea397fe69a4b1ba7b6434bacd764774b84f38512bf6730d2a0f6b0f6241eabfffeb153ffffb9feffffffffaaab",
                                pg1::g1_check_dev, pg1::g16_acc_dev, pg2::g2_check_dev, pg2::g2_lines_bytes, pg2::g2_lines_dev, pg2::f12_bytes,
-                               pg2::final_exp_tab_bytes, pg2::miller_dev, pg2::final_exp_dev, pg2::g16_verdict_dev};
+                               pg2::final_exp_tab_bytes, pg2::miller_dev, pg2::final_exp_dev, pg2::g16_verdict_dev,
+                               {pg1::points_check_dev, pg2::points_check_dev}};
 }  // namespace bls12_381
 #undef FQ_MUL_ATTR
 
@@ -122,15 +128,16 @@ static bool parse_int(const std::string& s, u32* w, int nw) {
 }
 static const std::string& jstr(const JVal& v) { ZK_REQUIRE(v.kind == JVal::Str || v.kind == JVal::Num, "groth16 verify: a number string expected"); return v.s; }
 static void parse_fq(const Curve& cv, const JVal& v, u32* w) { ZK_REQUIRE(parse_int(jstr(v), w, (int)cv.fq_words), "groth16 verify: a coordinate does not fit the base field's width"); }
-// {"x", "y"} -> 2 NL canonical words; pairing_ce's zero (0, 1) becomes the all-zero encoding
-static void parse_g1(const Curve& cv, const JVal& v, u32* w) {
+// {"x", "y"} -> 2 NL canonical words; pairing_ce's zero (0, 1) becomes the all-zero encoding (curve.h: groth16_key_check reads
+// verification_key.json with these two as well)
+void groth16_json_g1(const Curve& cv, const JVal& v, u32* w) {
     const int nl = (int)cv.fq_words;
     parse_fq(cv, v.at("x"), w); parse_fq(cv, v.at("y"), w + nl);
     bool zero = w[nl] == 1;
     for (int i = 0; i < 2 * nl; ++i) if (i != nl && w[i]) zero = false;
     if (zero) w[nl] = 0;
 }
-static void parse_g2(const Curve& cv, const JVal& v, u32* w, bool negate) {
+void groth16_json_g2(const Curve& cv, const JVal& v, u32* w, bool negate) {
     const int nl = (int)cv.fq_words;
     for (int c = 0; c < 2; ++c) { parse_fq(cv, v.at("x").at(c), w + c * nl); parse_fq(cv, v.at("y").at(c), w + (2 + c) * nl); }
     bool zero = w[2 * nl] == 1;
@@ -168,11 +175,11 @@ Groth16Vk* groth16_vk_new(const char* curve, const char* vk_json) {
     ZK_REQUIRE(ic.kind == JVal::Arr && ic.size() >= 1, "groth16 verify: IC must hold at least one point");
     const int nl = (int)cv.fq_words;
     std::vector<u32> g1((ic.size() + 1) * 2 * nl), g2(3 * 4 * nl);              // alpha, IC... ; beta, -gamma, -delta
-    parse_g1(cv, js.at("vk_alpha_1"), g1.data());
-    for (size_t i = 0; i < ic.size(); ++i) parse_g1(cv, ic.at(i), g1.data() + (i + 1) * 2 * nl);
-    parse_g2(cv, js.at("vk_beta_2"), g2.data(), false);
-    parse_g2(cv, js.at("vk_gamma_2"), g2.data() + 4 * nl, true);
-    parse_g2(cv, js.at("vk_delta_2"), g2.data() + 8 * nl, true);
+    groth16_json_g1(cv, js.at("vk_alpha_1"), g1.data());
+    for (size_t i = 0; i < ic.size(); ++i) groth16_json_g1(cv, ic.at(i), g1.data() + (i + 1) * 2 * nl);
+    groth16_json_g2(cv, js.at("vk_beta_2"), g2.data(), false);
+    groth16_json_g2(cv, js.at("vk_gamma_2"), g2.data() + 4 * nl, true);
+    groth16_json_g2(cv, js.at("vk_delta_2"), g2.data() + 8 * nl, true);
     hipStream_t st = cur_stream();
     auto vk = std::make_unique<Groth16Vk>();
     vk->curve = &cv; vk->n_ic = (uint32_t)ic.size();
@@ -247,7 +254,7 @@ int groth16_verify_json(const Groth16Vk* vk, const char* proof_json, const char*
     ZK_REQUIRE(uj.kind == JVal::Arr, "groth16 verify: public_input.json must be an array");
     if (uj.size() != vk->n_ic - 1) return -2;
     std::vector<u32> pts(8 * nl), pub(8 * uj.size() + 8);
-    parse_g1(cv, pj.at("pi_a"), pts.data()); parse_g2(cv, pj.at("pi_b"), pts.data() + 2 * nl, false); parse_g1(cv, pj.at("pi_c"), pts.data() + 6 * nl);
+    groth16_json_g1(cv, pj.at("pi_a"), pts.data()); groth16_json_g2(cv, pj.at("pi_b"), pts.data() + 2 * nl, false); groth16_json_g1(cv, pj.at("pi_c"), pts.data() + 6 * nl);
     for (size_t i = 0; i < uj.size(); ++i) if (!parse_int(jstr(uj.at(i)), pub.data() + 8 * i, 8)) return -1;
     hipStream_t st = cur_stream();
     void* dp = upload_mont(cv, pts, st);

@@ -9,6 +9,7 @@ import secrets
 import numpy as np
 
 from . import DevArray, ZkError, _check, _np, _ptr, lib
+from .key_check_lines import POINT_CLASSES, key_check_line, key_check_skipped_line  # noqa: F401
 
 _FR = {"BN128": 21888242871839275222246405745257275088548364400416034343698204186575808495617,
        "BLS12381": 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001}
@@ -213,3 +214,50 @@ class Groth16VerifyingKey:
             self.free()
         except Exception:
             pass
+
+
+# ---- groth16_key_check: a proving key against its circuit, before it is taken on faith ----
+
+
+def points_check(points, curve, group, plain=False):
+    """n affine points in the layout of the multi-scalar sums (u64 Montgomery words, all zero = infinity; a host array or a DevArray),
+    group "g1" | "g2" -> {class: (exact number of points, smallest index or None)} for POINT_CLASSES.  plain: [r]P = O bit by
+    bit instead of the endomorphism tests -- the same answer, the comparator."""
+    if curve not in _FR:
+        raise ZkError('groth16: unknown curve "%s" (BN128 | BLS12381)' % curve)
+    if group not in ("g1", "g2"):
+        raise ZkError('points check: group must be "g1" or "g2"')
+    pw = _FQ_WORDS[curve] * (2 if group == "g1" else 4)
+    fn = "zk_points_check_%s" % _NAME[curve]
+    out = np.zeros(8, np.uint64)
+    if isinstance(points, DevArray):
+        d_out = DevArray.from_host(out)
+        _check(getattr(lib(), fn + "_dev")(1 if group == "g1" else 2, points.ptr, points.n // pw, int(bool(plain)), d_out.ptr, 0))
+        out = d_out.to_host()
+    else:
+        a = np.ascontiguousarray(_np(points)).reshape(-1)
+        if a.size % pw:
+            raise ZkError("points check: the array does not hold whole points")
+        _check(getattr(lib(), fn)(1 if group == "g1" else 2, _ptr(a) if a.size else None, a.size // pw, int(bool(plain)), _ptr(out)))
+    return {k: (int(out[2 * i]), int(out[2 * i + 1]) if out[2 * i] else None) for i, k in enumerate(POINT_CLASSES)}
+
+
+def key_check(curve, r1cs_bytes, params_bytes, vk_json=None, seed=None, max_findings=16):
+    """zk_groth16_key_check (include/zkgpu.h): section lengths against the circuit, every point's class, the G1 / G2 copies tied by
+    pairings, verification_key.json against the embedded copy -> the report as a dict.  seed: 32 bytes, for tests only (None: the
+    operating system's randomness).  Not checked: h, l, ic and a against the circuit's polynomials -- `groth16_prove --verify` is
+    the functional test.  With ZK_KEY_CHECK_TIMING set in the environment the report also carries "timing_ms" (tools/key_check_time.py)."""
+    if curve not in _FR:
+        raise ZkError('groth16: unknown curve "%s" (BN128 | BLS12381)' % curve)
+    if seed is not None and len(seed) != 32:
+        raise ZkError("groth16 key check: the seed is 32 bytes")
+    r = np.frombuffer(r1cs_bytes, dtype=np.uint8); p = np.frombuffer(params_bytes, dtype=np.uint8)
+    text = None if vk_json is None else (vk_json if isinstance(vk_json, str) else json.dumps(vk_json)).encode()
+    sd = None if seed is None else np.frombuffer(bytes(seed), dtype=np.uint8)
+    s = lib().zk_groth16_key_check(curve.encode(), r.ctypes.data, r.size, p.ctypes.data, p.size, text, sd.ctypes.data if sd is not None else None, int(max_findings))
+    if not s:
+        raise ZkError(lib().zk_last_error().decode())
+    try:
+        return json.loads(C.string_at(s).decode())
+    finally:
+        lib().zk_string_free(s)

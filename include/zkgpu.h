@@ -679,6 +679,42 @@ char* zk_r1cs_check_run(zk_r1cs_check_t* c, const void* witness, uint64_t n_valu
 char* zk_r1cs_check_run_dev(zk_r1cs_check_t* c, const void* d_witness, uint64_t n_values, uint32_t max_findings);
 int zk_r1cs_check_free(zk_r1cs_check_t* c);
 
+/* ---- groth16_key_check: a Groth16 proving key against its circuit (csrc/groth16.hip, csrc/key_check_impl.hip.h) ----------
+ *
+ * zk_groth16_setup_new reads a key as the reference does (read_pk_from_file(path, checked = false)): no point is looked at.
+ * zk_groth16_key_check reads the same two files with the same readers (same error texts when a file cannot be parsed: NULL and
+ * zk_last_error) and returns a report as JSON text (zk_string_free):
+ *   {"curve", "n_wires", "n_public", "domain_log", "sections": {"ic", "h", "l", "a", "b_g1", "b_g2": lengths},
+ *    "checked": {"g1_points", "g2_points", "pairs"}, "skipped": [{"check", "section", "reason"}],
+ *    "counts": {kind: number of findings, exact}, "findings": [...at most max_findings per kind; kind by kind in the order below, and within a
+ *    kind in the order of the sections...]}
+ *   size              {"section", "have", "want"}: a section's length against the circuit's (ic = public wires + 1, l = the rest,
+ *                     h = 2^domain_log - 1, a / b_g1 / b_g2 = what bellman's density trackers count); the key of another circuit stops here
+ *   infinity, coordinate_range, not_on_curve, not_in_subgroup
+ *                     {"section", "n_points", "first_index"} per section: alpha_g1 beta_g1 beta_g2 gamma_g2 delta_g1 delta_g2 (one
+ *                     point each), ic, h, l, a, b_g1, b_g2.  A point has the first class that applies.  Infinity is a finding in every
+ *                     section, as bellman's Parameters::read refuses it there.
+ *   g1_g2_mismatch    {"section": "beta" | "delta" | "b", "first_index"}: e(P1, G2) != e(G1, P2).  b: one random linear combination
+ *                     of 128-bit factors over both queries (a wrong pair passes with probability 2^-128), then the smallest failing
+ *                     prefix by bisection.  Skipped (and listed under "skipped") when a section holds an invalid point or the lengths differ.
+ *   vk_mismatch       {"field"}: a field of verification_key.json (vk_json, may be NULL) against the key's embedded copy
+ * seed: 32 bytes from which the factors are expanded on the device.  FOR TESTS ONLY: pass NULL anywhere else, and the factors come from
+ * the operating system (getrandom); a caller who can predict them can make a wrong pair pass.
+ * NOT checked: h, l, ic and a against the circuit's polynomials.  That needs tau in G2 or the trapdoor; "no findings" means well formed
+ * and self-consistent, and the functional test remains a proof that verifies.
+ *
+ * zk_points_check_*: the per-point part on its own.  group: 1 = G1, 2 = G2; points: n affine points in the layout of the
+ * multi-scalar sums (Montgomery; all zero = infinity), as zk_pairing_* take them; plain != 0: [r]P = O bit by bit instead of the
+ * endomorphism tests (same answer; the comparator).  out: 4 x 2 words -- for ZK_POINT_INFINITY .. ZK_POINT_NOT_IN_SUBGROUP the
+ * exact number of points of the class and the smallest index of one (all ones when there is none). */
+enum { ZK_POINT_INFINITY = 0, ZK_POINT_COORDINATE_RANGE = 1, ZK_POINT_NOT_ON_CURVE = 2, ZK_POINT_NOT_IN_SUBGROUP = 3, ZK_POINT_CLASSES = 4 };
+char* zk_groth16_key_check(const char* curve, const void* r1cs, size_t r1cs_len, const void* params, size_t params_len, const char* vk_json,
+                           const uint8_t* seed, uint32_t max_findings);
+int zk_points_check_bn254(int group, const void* points, uint64_t n, int plain, uint64_t* out);
+int zk_points_check_bn254_dev(int group, const void* d_points, uint64_t n, int plain, uint64_t* d_out, void* stream);
+int zk_points_check_bls12_381(int group, const void* points, uint64_t n, int plain, uint64_t* out);
+int zk_points_check_bls12_381_dev(int group, const void* d_points, uint64_t n, int plain, uint64_t* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

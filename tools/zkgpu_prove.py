@@ -9,6 +9,7 @@
   zkgpu_prove.py groth16_verify -c BN128 -v verification_key.json --public-input public_input.json --proof proof.json
   zkgpu_prove.py pil_verify -p circuit.pil.json --o circuit.const --m circuit.cm [--report out.json]
   zkgpu_prove.py wtns_check -c BN128|BLS12381|GL --r1cs circuit.r1cs --wtns witness.wtns [--sym circuit.sym] [--report out.json] [--max-findings N]
+  zkgpu_prove.py groth16_key_check -c BN128|BLS12381 --r1cs circuit.r1cs -p g16.key [-v verification_key.json] [--report out.json] [--max-findings N]
   zkgpu_prove.py stark_verify -s starkStruct.json -p circuit.pil.json --o circuit.const --i zkin.json [--program FILE]
   zkgpu_prove.py compressor12_setup --r circuit.r1cs --c c12.const --p c12.pil --e c12.exec [--force_n_bits K] [--pil-json c12.pil.json]
   zkgpu_prove.py compressor12_exec --wtns witness.wtns --p c12.pil --e c12.exec --m c12.cm
@@ -30,6 +31,11 @@ starky/src/prove.rs:30-160, groth16/src/api.rs:144-205).  What differs, and why:
     verifyPil), on the device: one line `fileName:line: <kind> ...` per violated constraint, exit 0 when there is none and 1 otherwise;
     `--report` also writes the whole report as JSON.  `stark_prove --check-trace` runs it first and stops with the findings (exit 1)
     before any setup.
+  * groth16_key_check: the proving key against its circuit on the device (the reference reads keys unchecked): section lengths, every
+    point on its curve, in the subgroup and finite, b_g1 / b_g2 and the beta / delta pairs tied by pairings, `-v` against the embedded
+    verification key.  One line per finding, exit 1 with findings.  It cannot check h, l, ic and a against the circuit's polynomials:
+    `groth16_prove --verify` is the functional test.  `groth16_prove --check-key` runs it first and stops before the witness is touched;
+    `groth16_setup --check-key` runs it on the key it has just made.
   * wtns_check: `snarkjs wtns check` on the device (the reference has no counterpart): every constraint of the .r1cs as written, wire 0,
     and over GL every use of the compressor's custom gates; one line per finding, exit 0 when there is none and 1 otherwise; `--sym` takes
     circom's .sym file and prints every wire with its signal name; `--report` also writes the whole report as JSON.
@@ -354,21 +360,52 @@ def compressor12_exec(a):
     print("zkgpu_prove: %d wires -> 2^%s rows of 12 columns in %s" % (n, m.group(1), a.commit_file))
 
 
+def _check_key(curve, r1cs_bytes, pk_bytes, vk_text=None, max_findings=16, report_file=None, out=sys.stderr):
+    """groth16_key_check of the files' bytes: the finding lines and what was skipped, then exit 1 when there is a finding"""
+    import importlib
+    dev = importlib.import_module("eigen_zkvm_amd.groth16")
+    report = dev.key_check(curve, r1cs_bytes, pk_bytes, vk_json=vk_text, max_findings=max_findings)
+    if report_file:
+        with open(report_file, "w") as f:
+            json.dump(report, f, indent=1)
+    for f in report["findings"]:
+        print(dev.key_check_line(f), file=out)
+    for s in report["skipped"]:                                            # every reason to skip comes with a finding: say it before the exit
+        print(dev.key_check_skipped_line(s), file=out)
+    if any(report["counts"].values()):
+        raise SystemExit(1)
+    return report
+
+
+def groth16_key_check(a):
+    _zk()
+    rep = _check_key(a.curve_type, pathlib.Path(a.circuit_file).read_bytes(), pathlib.Path(a.pk_file).read_bytes(),
+                     pathlib.Path(a.vk_file).read_text() if a.vk_file else None, a.max_findings, a.report, out=sys.stdout)
+    print("zkgpu_prove: %s is a well-formed key of %s (%d G1 and %d G2 points, %d pairs; h, l, ic, a are not checked against the circuit's polynomials)"
+          % (a.pk_file, a.circuit_file, rep["checked"]["g1_points"], rep["checked"]["g2_points"], rep["checked"]["pairs"]))
+
+
 def groth16_setup(a):
     """groth16/src/api.rs:42-66: circuit_specific_setup, then the key and verification_key.json written to their files"""
     import importlib
     _zk()
     dev = importlib.import_module("eigen_zkvm_amd.groth16")
-    pk, vk = dev.keygen(a.curve_type, pathlib.Path(a.circuit_file).read_bytes(), to_hex=a.to_hex)
+    r1cs = pathlib.Path(a.circuit_file).read_bytes()
+    pk, vk = dev.keygen(a.curve_type, r1cs, to_hex=a.to_hex)
     pathlib.Path(a.pk_file).write_bytes(pk)
     pathlib.Path(a.vk_file).write_text(vk)
     print("zkgpu_prove: %s key written to %s (%d bytes), verification key to %s" % (a.curve_type, a.pk_file, len(pk), a.vk_file))
+    if a.check_key:
+        _check_key(a.curve_type, r1cs, pk, vk)
+        print("zkgpu_prove: the key passes groth16_key_check")
 
 
 def groth16_prove(a):
     import importlib
     zk = _zk()
     dev = importlib.import_module("eigen_zkvm_amd.groth16")
+    if a.check_key:                                                        # the witness is not touched for a bad key
+        _check_key(a.curve_type, pathlib.Path(a.circuit_file).read_bytes(), pathlib.Path(a.pk_file).read_bytes())
     if a.check_witness:                                                    # the proving key is not read for a bad witness
         _stop_on_findings(_check_witness(a.curve_type, a.circuit_file, a.wasm_file)[0])
     r1cs, pk, wtns = (pathlib.Path(p).read_bytes() for p in (a.circuit_file, a.pk_file, a.wasm_file))
@@ -482,7 +519,16 @@ def build_parser():
     k.add_argument("-p", dest="pk_file", default="g16.zkey")
     k.add_argument("-v", dest="vk_file", default="verification_key.json")
     k.add_argument("-t", dest="to_hex", action="store_true", help="coordinates of the verification key as 0x strings")
+    k.add_argument("--check-key", dest="check_key", action="store_true", help="run groth16_key_check on the key just made (extension)")
     k.set_defaults(fn=groth16_setup)
+    kc = sub.add_parser("groth16_key_check", help="check a proving key against its circuit: sizes, every point, the G1 / G2 copies (extension)")
+    kc.add_argument("-c", dest="curve_type", default="BN128")
+    kc.add_argument("--r1cs", dest="circuit_file", required=True)
+    kc.add_argument("-p", dest="pk_file", default="g16.zkey")
+    kc.add_argument("-v", dest="vk_file", default=None, help="a verification_key.json to compare with the key's embedded copy")
+    kc.add_argument("--report", default=None, metavar="OUT.json", help="also write the whole report")
+    kc.add_argument("--max-findings", dest="max_findings", type=int, default=16)
+    kc.set_defaults(fn=groth16_key_check)
     g = sub.add_parser("groth16_prove", help="Prove with groth16 (zkit/src/main.rs:199-217)")
     g.add_argument("-c", dest="curve_type", default="BN128")
     g.add_argument("--r1cs", dest="circuit_file", required=True)
@@ -496,6 +542,8 @@ def build_parser():
                    help="check the proof against this verification key before writing it (extension)")
     g.add_argument("--check-witness", dest="check_witness", action="store_true",
                    help="run wtns_check first and stop with its findings (exit 1) before the proving key is read (extension)")
+    g.add_argument("--check-key", dest="check_key", action="store_true",
+                   help="run groth16_key_check first and stop with its findings (exit 1) before the witness is touched (extension)")
     g.set_defaults(fn=groth16_prove)
     gv = sub.add_parser("groth16_verify", help="Verify with groth16 (zkit/src/main.rs:221-230)")
     gv.add_argument("-c", dest="curve_type", default="BN128")
