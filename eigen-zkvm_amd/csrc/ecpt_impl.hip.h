@@ -183,8 +183,8 @@ __device__ __forceinline__ xyzz pt_neg(const xyzz& p) {
 // The tails of a sum -- the bucket hierarchy and the final walk over the windows -- are chains of a few hundred dependent point
 // operations on a handful of lanes: latency, not throughput.  A doubling is 9 field products in 3 dependent stages, a full addition
 // 14 in 4; here the lanes of a quad hold the same point and lane q computes the q-th product of each stage, the results travel by
-// DPP quad broadcasts (a move per limb, no LDS).  The same formulas, the same operands, the same bounds: bit-identical results, in
-// a third of the dependent products.  Called by all four lanes of a quad with identical arguments.
+// DPP quad broadcasts (a move per limb, no LDS).  The same formulas, the same operands, the same bounds: bit-identical results
+// (tests/test_gpu_ecpt.py compares them limb for limb), in a third of the dependent products.  Called by all four lanes of a quad with identical arguments.
 __device__ __forceinline__ u32 quad_word(u32 v, int k) {            // lane k's value in every lane of the quad (k is uniform)
     switch (k) {
         case 0: return (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x00, 0xF, 0xF, false);
@@ -233,6 +233,18 @@ __device__ PT_COLD_ATTR void quad_stage(const cf& a0, const cf& b0, const cf& a1
     o0 = quad_cf(prod, 0); o1 = quad_cf(prod, 1); o2 = quad_cf(prod, 2); o3 = quad_cf(prod, 3);
     cf_opaque(o0); cf_opaque(o1); cf_opaque(o2); cf_opaque(o3);
 }
+#ifndef MSM_G2
+// G1's last stage of an addition: pt_finish has Y3 as ONE sum of two products (fe_mul2), so the quad does too -- lanes 0 and 1 compute
+// a b + c d, lanes 2 and 3 e f (fe_mul2 with a zero second product: the column sums, hence the limbs, of fe_mul(e, f))
+__device__ PT_COLD_ATTR void quad_stage_y(const cf& a, const cf& b, const cf& c, const cf& d, const cf& e, const cf& f, cf& o0, cf& o2) {
+    const int q = threadIdx.x & 3;
+    const cf z = cf_zero();
+    cf prod = fe_mul2(pick_cf(q, a, a, e, e), pick_cf(q, b, b, f, f), pick_cf(q, c, c, z, z), pick_cf(q, d, d, z, z));
+    cf_opaque(prod);
+    o0 = quad_cf(prod, 0); o2 = quad_cf(prod, 2);
+    cf_opaque(o0); cf_opaque(o2);
+}
+#endif
 __device__ PT_COLD_ATTR xyzz pt_dbl4(const xyzz& p) {   // pt_dbl, three stages
     if (pt_is_inf(p)) return p;
     const cf U = cf_dbl(p.Y);
@@ -249,7 +261,7 @@ __device__ PT_COLD_ATTR xyzz pt_dbl4(const xyzz& p) {   // pt_dbl, three stages
 __device__ PT_COLD_ATTR xyzz pt_add4(const xyzz& p, const xyzz& q) {   // pt_add, four stages
     if (pt_is_inf(p)) return q;
     if (pt_is_inf(q)) return p;
-    cf U1, U2, S1, S2, PP, RR, ZZ12, ZZZ12, PPP, Q, t1, t2, d0;
+    cf U1, U2, S1, S2, PP, RR, ZZ12, ZZZ12, PPP, Q, d0;
     quad_stage(p.X, q.ZZ, q.X, p.ZZ, p.Y, q.ZZZ, q.Y, p.ZZZ, U1, U2, S1, S2);
     const cf P = cf_sub<2>(U2, U1), Rr = cf_sub<2>(S2, S1);                      // < 4q
     quad_stage(P, P, Rr, Rr, p.ZZ, q.ZZ, p.ZZZ, q.ZZZ, PP, RR, ZZ12, ZZZ12);
@@ -257,8 +269,13 @@ __device__ PT_COLD_ATTR xyzz pt_add4(const xyzz& p, const xyzz& q) {   // pt_add
     xyzz r;
     quad_stage(P, PP, U1, PP, ZZ12, PP, P, PP, PPP, Q, r.ZZ, d0);
     r.X = cf_sub<4>(cf_sub<2>(RR, PPP), cf_dbl(Q));
+#ifdef MSM_G2
+    cf t1, t2;
     quad_stage(cf_sub<8>(Q, r.X), Rr, S1, PPP, ZZZ12, PPP, S1, PPP, t1, t2, r.ZZZ, d0);
     r.Y = cf_sub<2>(t1, t2);
+#else
+    quad_stage_y(cf_sub<8>(Q, r.X), Rr, cf_sub<4>(cf_zero(), S1), PPP, ZZZ12, PPP, r.Y, r.ZZZ);   // Y3 as pt_finish has it: < 2q
+#endif
     return r;
 }
 // affine (external layout) of a finite point: x = X/ZZ, y = Y/ZZZ; 1/ZZ = (ZZ/ZZZ)^2 because ZZ^3 = ZZZ^2

@@ -117,14 +117,17 @@ __device__ __forceinline__ fe fe_mul2(const fe& a, const fe& b, const fe& c, con
 // Deferred reduction for sums of products: partial products of up to FE_WIDE_MAX pairs accumulate in the 64-bit
 // columns ((FE_WIDE_MAX + 1) NR 2^58 <= 2^64 with the reduction's own products), then ONE Montgomery reduction.
 // Bounds: sum A_i B_i <= 168 (BN254 fields) / 68 (BLS12-381 Fr) for a result < 2q.  A dot product of n terms costs
-// n + ceil(n / 6) column passes instead of 2 n.
+// n + ceil(n / 6) column passes instead of 2 n.  The column bound holds for NR = 9 only (7 x 9 = 63 products of 2^58): with BLS12-381
+// Fq's 14 limbs a column would wrap, so fe_wide_mac does not compile there (it is a template for the assertion's sake alone).
 constexpr int FE_WIDE_MAX = 6;
 struct fe_wide { u64 t[2 * NR]; };
 __device__ __forceinline__ void fe_wide_zero(fe_wide& w) {
 #pragma unroll
     for (int i = 0; i < 2 * NR; ++i) w.t[i] = 0;
 }
+template <int N = NR>
 __device__ __forceinline__ void fe_wide_mac(fe_wide& w, const fe& a, const fe& b) {
+    static_assert((FE_WIDE_MAX + 1) * N <= 64, "fe_wide_*: (FE_WIDE_MAX + 1) NR products of 2^58 must fit a 64-bit column");
 #pragma unroll
     for (int i = 0; i < NR; ++i) {
 #pragma unroll
