@@ -25,6 +25,11 @@ pub struct zk_stark_ctx_t {
 pub struct zk_program_t {
     _private: [u8; 0],
 }
+/// a powers-of-tau file, read and measured (zk_srs_open)
+#[repr(C)]
+pub struct zk_srs_t {
+    _private: [u8; 0],
+}
 /// zk_operand / zk_instr of include/zkgpu.h (interpreter.rs:187-225: one Section with its Nodes resolved to addresses)
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
@@ -130,6 +135,14 @@ extern "C" {
     pub fn zk_points_check_bn254_dev(group: c_int, d_points: *const c_void, n: u64, plain: c_int, d_out: *mut u64, stream: *mut c_void) -> c_int;
     pub fn zk_points_check_bls12_381(group: c_int, points: *const c_void, n: u64, plain: c_int, out: *mut u64) -> c_int;
     pub fn zk_points_check_bls12_381_dev(group: c_int, d_points: *const c_void, n: u64, plain: c_int, d_out: *mut u64, stream: *mut c_void) -> c_int;
+    // a Groth16 key from a powers-of-tau file and contributions to it: the reports are JSON text (zk_string_free); keys are plain bytes
+    pub fn zk_srs_open(curve: *const c_char, path: *const c_char) -> *mut zk_srs_t;
+    pub fn zk_srs_info(s: *const zk_srs_t, power: *mut u32, ceremony_power: *mut u32) -> c_int;
+    pub fn zk_srs_check(s: *const zk_srs_t, seed: *const u8, max_findings: u32) -> *mut c_char;
+    pub fn zk_srs_free(s: *mut zk_srs_t) -> c_int;
+    pub fn zk_groth16_params_contribute(curve: *const c_char, params: *const c_void, len: usize, delta: *const u64, out: *mut c_void) -> c_int;
+    pub fn zk_groth16_contribution_check(curve: *const c_char, old_params: *const c_void, old_len: usize, new_params: *const c_void, new_len: usize,
+                                         seed: *const u8, max_findings: u32) -> *mut c_char;
     pub fn zk_stark_setup_free(s: *mut zk_stark_setup_t) -> c_int;
     pub fn zk_bn128_load_constants(path: *const c_char) -> c_int;
     pub fn zk_bls12381_load_constants(path: *const c_char) -> c_int;

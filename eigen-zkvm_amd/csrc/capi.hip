@@ -673,6 +673,65 @@ int zk_groth16_keygen_free(zk_groth16_keygen_t* k) {
     return guard([&] { delete k; });
 }
 
+// ---- a key from a powers-of-tau file, contributions to it (groth16_srs.hip.h, ecntt.hip) ----------------------------------------
+static char* dup_report(const std::string& js) {
+    char* out = (char*)malloc(js.size() + 1);
+    ZK_REQUIRE(out, "out of memory");
+    memcpy(out, js.c_str(), js.size() + 1);
+    return out;
+}
+zk_srs_t* zk_srs_open(const char* curve, const char* path) {
+    zk_srs_t* out = nullptr;
+    if (guard([&] { out = srs_open(curve, path); }) != 0) return nullptr;
+    return out;
+}
+int zk_srs_info(const zk_srs_t* s, uint32_t* power, uint32_t* ceremony_power) {
+    return guard([&] {
+        ZK_REQUIRE(s, "ptau: null handle");
+        if (power) *power = s->power;
+        if (ceremony_power) *ceremony_power = s->ceremony_power;
+    });
+}
+int zk_srs_free(zk_srs_t* s) {
+    return guard([&] { delete s; });
+}
+char* zk_srs_check(const zk_srs_t* s, const uint8_t* seed, uint32_t max_findings) {
+    char* out = nullptr;
+    if (guard([&] { ZK_REQUIRE(s, "ptau: null handle"); out = dup_report(srs_check(*s, seed, max_findings)); }) != 0) return nullptr;
+    return out;
+}
+zk_groth16_keygen_t* zk_groth16_keygen_from_srs(const char* curve, const void* r1cs, size_t r1cs_len, const zk_srs_t* srs) {
+    zk_groth16_keygen_t* out = nullptr;
+    if (guard([&] { out = groth16_keygen_from_srs(curve, r1cs, r1cs_len, srs); }) != 0) return nullptr;
+    return out;
+}
+int zk_groth16_params_contribute(const char* curve, const void* params, size_t len, const uint64_t* delta, void* out) {
+    return guard([&] { groth16_params_contribute(curve, params, len, delta, out); });
+}
+char* zk_groth16_contribution_check(const char* curve, const void* old_params, size_t old_len, const void* new_params, size_t new_len, const uint8_t* seed,
+                                    uint32_t max_findings) {
+    char* out = nullptr;
+    if (guard([&] { out = dup_report(groth16_contribution_check(curve, old_params, old_len, new_params, new_len, seed, max_findings)); }) != 0) return nullptr;
+    return out;
+}
+static int group_ntt_device(CurveId id, Group g, void* d_points, uint32_t log_n, int inverse, void* stream) {
+    return guard([&] { group_ntt_dev(curve(id), g, d_points, (int)log_n, inverse != 0, on_stream((hipStream_t)stream)); });
+}
+static int mul_scalar_device(CurveId id, Group g, const void* d_points, uint64_t n, const uint64_t* d_k, void* d_out, void* stream) {
+    return guard([&] {
+        ZK_REQUIRE(n == 0 || (d_points && d_k && d_out), "mul_scalar: null argument");
+        curve(id).ec().g[g].mul_scalar(d_points, n, (const u32*)d_k, d_out, on_stream((hipStream_t)stream));
+    });
+}
+#define ZK_EC_API(GN, NAME, ID, G)                                                                                                            \
+    int zk_##GN##_##NAME##_ntt_dev(void* d_points, uint32_t log_n, int inverse, void* stream) { return group_ntt_device(ID, G, d_points, log_n, inverse, stream); } \
+    int zk_##GN##_##NAME##_mul_scalar_dev(const void* d_points, uint64_t n, const uint64_t* d_k, void* d_out, void* stream) { return mul_scalar_device(ID, G, d_points, n, d_k, d_out, stream); }
+ZK_EC_API(g1, bn254, CURVE_BN254, G1)
+ZK_EC_API(g2, bn254, CURVE_BN254, G2)
+ZK_EC_API(g1, bls12_381, CURVE_BLS12_381, G1)
+ZK_EC_API(g2, bls12_381, CURVE_BLS12_381, G2)
+#undef ZK_EC_API
+
 // ---- pairings and Groth16 verification (pairing.hip) ----
 zk_groth16_vk_t* zk_groth16_vk_new(const char* curve, const char* vk_json) {
     zk_groth16_vk_t* h = nullptr;

@@ -8,12 +8,14 @@
 struct zk_groth16_setup;
 struct zk_groth16_keygen;
 struct zk_groth16_vk;
+struct zk_srs;
 
 namespace zk {
 
 using Groth16Setup = ::zk_groth16_setup;
 using Groth16Key = ::zk_groth16_keygen;
 using Groth16Vk = ::zk_groth16_vk;
+using Srs = ::zk_srs;
 namespace g16 { struct Circuit; struct Params; }
 struct MillerArgs;
 struct Curve;
@@ -65,7 +67,19 @@ struct PairingOps {
     // not_on_curve, not_in_subgroup
     void (*points_check[2])(const void*, u64, u64, int, int, u64*, hipStream_t);
 };
+// ---- ecntt.hip: transforms, column sums and scalar products whose elements are points (ecntt_impl.hip.h).  Points as for the sums; scalars and
+// coefficients 8 canonical words
+struct EcCsc { const u64* ptr; const u32* rows; const u32* coef; const u32* base; };   // one matrix by columns and the points its rows select
+struct EcGroupOps {
+    void (*ntt)(void* d_points, int logn, const u32* d_tw, const u32* d_scale, hipStream_t st);
+    void (*mul_scalar)(const void* d_points, u64 n, const u32* d_k, void* d_out, hipStream_t st);          // out_i = [k] P_i, one k
+    void (*diff)(const void* d_a, const void* d_b, u64 n, void* d_out, hipStream_t st);                    // out_i = a_i - b_i
+    // out_j = sum over the sets and the terms of column j of coef * base[row], j < n_wires; r: the scalar modulus
+    void (*column_sums)(const EcCsc* sets, int n_sets, const u32* r, u32 n_wires, void* d_out, hipStream_t st);
+};
+struct EcOps { EcGroupOps g[2]; };
 const MsmOps& msm_ops(CurveId id);
+const EcOps& ec_ops(CurveId id);
 const Groth16Ops& groth16_ops(CurveId id);
 const PairingOps& pairing_ops(CurveId id);
 
@@ -88,6 +102,7 @@ struct Curve {
     const GroupOps& group(Group g) const { return msm_ops(id).g[g]; }
     const Groth16Ops& groth16() const { return groth16_ops(id); }
     const PairingOps& pairing() const { return pairing_ops(id); }
+    const EcOps& ec() const { return ec_ops(id); }
 };
 inline const Curve CURVES[2] = {
     {CURVE_BN254, "BN128", "bn254", 8, {0xf0000001u, 0x43e1f593u, 0x79b97091u, 0x2833e848u, 0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u}},
@@ -112,6 +127,15 @@ void groth16_wtns_payload(const void* wtns, size_t len, const char* curve, uint6
 Groth16Setup* groth16_setup_new(const char* curve, const void* r1cs, size_t r1cs_len, const void* params, size_t params_len);
 Groth16Key* groth16_keygen_new(const char* curve, const void* r1cs, size_t r1cs_len, const uint64_t* trapdoor);
 std::string groth16_keygen_vk_json(const Groth16Key& k, bool to_hex);   // json_utils.rs:285-303 serialize_vk
+// A key from a powers-of-tau file instead of a trapdoor (groth16.hip; the group work is ecntt.hip's).  srs_open is host only.
+void group_ntt_dev(const Curve& cv, Group g, void* d_points, int logn, bool inverse, hipStream_t st);
+Srs* srs_open(const char* curve, const char* path);
+std::string srs_check(const Srs& srs, const uint8_t* seed, uint32_t max_findings);
+Groth16Key* groth16_keygen_from_srs(const char* curve, const void* r1cs, size_t r1cs_len, const Srs* srs);
+// delta: 4 canonical words, non-zero and below r, or null to draw it from the OS; out: len bytes
+void groth16_params_contribute(const char* curve, const void* params, size_t len, const uint64_t* delta, void* out);
+std::string groth16_contribution_check(const char* curve, const void* old_params, size_t old_len, const void* new_params, size_t new_len,
+                                       const uint8_t* seed, uint32_t max_findings);
 // groth16_key_check (groth16.hip): the report as JSON text.  seed: 32 bytes for the random linear combination, for tests only -- null (the operating
 // system's randomness) anywhere else.
 std::string groth16_key_check(const char* curve, const void* r1cs, size_t r1cs_len, const void* params, size_t params_len, const char* vk_json,
@@ -147,6 +171,12 @@ struct zk_groth16_keygen {   // a finished key
     const zk::Curve* curve = nullptr;
     std::vector<uint8_t> params;
     double ms[5] = {};       // transform, column sums, G1 points, G2 points, serialisation
+};
+struct zk_srs {              // a powers-of-tau file, read and measured; the sections stay in the file's bytes
+    const zk::Curve* curve = nullptr;
+    uint32_t power = 0, ceremony_power = 0;
+    std::vector<uint8_t> file;
+    size_t off[7] = {};      // by section id (2 tauG1, 3 tauG2, 4 alphaTauG1, 5 betaTauG1, 6 betaG2): where the payload starts
 };
 struct zk_groth16_vk {       // a verification key, checked and prepared
     const zk::Curve* curve = nullptr;

@@ -1,0 +1,232 @@
+// Transforms, column sums and scalar products whose elements are curve points: what a Groth16 key costs when it is made from a
+// powers-of-tau file instead of a trapdoor (groth16.hip keygen_from_srs).  Nothing can be computed on scalars and multiplied into the
+// generator there, so the work of groth16_keygen_impl.hip.h happens in the group.  Included once per (curve, group) by ecntt.hip inside
+// a namespace that has included ecpt_impl.hip.h; no include guard on purpose.
+//
+// Layouts.  Outside: affine (x, y), Montgomery, little-endian limbs, all zero = infinity (the layout of the sums).  Between kernels:
+// a work buffer of XYZZ points as raw internal limbs (EW words each), so a point is converted once on the way in and once on the way
+// out -- the way out shares one inversion per workgroup by the product tree of fb_mul_kernel (fixedbase_impl.hip.h).
+//
+// Transform: radix 2, decimation in time -- the load permutes by bit reversal, log n stage launches follow, one lane per butterfly
+// (a, b) -> (a + [w]b, a - [w]b).  [w]b is a double-and-add over the bits of w (canonical words from a table the host fills):
+// about 254 doublings and 127 additions of ~2 700 instructions each, next to which the 4 x EW words a butterfly moves are nothing, so
+// lanes are laid out for the arithmetic and not for the memory: butterfly t of stage s has twiddle index t / groups, which is the
+// same for all 64 lanes of a wave while the stage has 64 groups or more.  There the index is made wave-uniform (readfirstlane): the
+// scalar's words come through scalar loads and the branch on each bit is a scalar branch -- one recoding for the wave.  In the last
+// six stages the lanes of a wave hold different twiddles and the additions run under EXEC masks.  Twiddle 1 (index 0: every butterfly
+// of the first stage, one per group after that) skips the product altogether.
+// The point formulas are called through two real functions, so a kernel holds one copy of each (code size: see msm.hip).
+// pt_add is complete -- equal operands go to the doubling, opposite ones to infinity -- which a constant column of a file needs.
+constexpr int EW = 4 * CW_INT, AW = 2 * CW_STD;
+
+__device__ __forceinline__ xyzz ecn_ld(const u32* __restrict__ p) {
+    xyzz r;
+    r.X = cf_load_int(p); r.Y = cf_load_int(p + CW_INT); r.ZZ = cf_load_int(p + 2 * CW_INT); r.ZZZ = cf_load_int(p + 3 * CW_INT);
+    return r;
+}
+__device__ __forceinline__ void ecn_st(u32* __restrict__ p, const xyzz& r) {
+    cf_store_int(r.X, p); cf_store_int(r.Y, p + CW_INT); cf_store_int(r.ZZ, p + 2 * CW_INT); cf_store_int(r.ZZZ, p + 3 * CW_INT);
+}
+__device__ __forceinline__ xyzz ecn_load_ext(const u32* __restrict__ p) {
+    u32 w[AW], any = 0;
+#pragma unroll
+    for (int k = 0; k < AW; ++k) { w[k] = p[k]; any |= w[k]; }
+    if (!any) return pt_inf();
+    xyzz r;
+    r.X = cf_from_std(w); r.Y = cf_from_std(w + CW_STD); r.ZZ = cf_one(); r.ZZZ = cf_one();
+    return r;
+}
+__device__ __noinline__ xyzz ecn_add(const xyzz& p, const xyzz& q) { return pt_add(p, q); }
+__device__ __noinline__ xyzz ecn_dbl(const xyzz& p) { return pt_dbl(p); }
+// [k]b for k of 8 canonical words in memory, k < r; k = 0 or b = infinity gives infinity
+__device__ __forceinline__ xyzz ecn_mul(const xyzz& b, const u32* __restrict__ k) {
+    int top = -1;
+    for (int w = 7; w >= 0 && top < 0; --w)
+        if (k[w]) top = 32 * w + 31 - __clz((int)k[w]);
+    if (top < 0 || pt_is_inf(b)) return pt_inf();
+    xyzz acc = b;
+    for (int bit = top - 1; bit >= 0; --bit) {
+        acc = ecn_dbl(acc);
+        if ((k[bit >> 5] >> (bit & 31)) & 1) acc = ecn_add(acc, b);
+    }
+    return acc;
+}
+
+__global__ __launch_bounds__(64) void ecn_load_kernel(const u32* __restrict__ pts, u32 logn, u32* __restrict__ work) {
+    const u32 i = blockIdx.x * 64u + threadIdx.x;
+    if (i >> logn) return;
+    const u32 j = logn ? __brev(i) >> (32 - logn) : 0u;
+    ecn_st(work + (u64)j * EW, ecn_load_ext(pts + (u64)i * AW));
+}
+// stage s of logn: halves of 2^s, groups = 2^(logn - 1 - s); tw[k] = w_n^k for k < n / 2, 8 canonical words each
+__global__ __launch_bounds__(64) void ecn_stage_kernel(u32* __restrict__ work, const u32* __restrict__ tw, u32 logn, u32 s) {
+    const u32 t = blockIdx.x * 64u + threadIdx.x;
+    if (t >> (logn - 1)) return;
+    const u32 lg = logn - 1 - s;                                    // log2 of the number of groups
+    u32 j = t >> lg;
+    const u32 g = t & ((1u << lg) - 1);
+    if (lg >= 6) j = (u32)__builtin_amdgcn_readfirstlane((int)j);  // the wave's 64 butterflies share the twiddle
+    u32* p0 = work + (((u64)g << (s + 1)) + j) * EW;
+    u32* p1 = p0 + ((u64)EW << s);
+    const xyzz a = ecn_ld(p0);
+    xyzz b = ecn_ld(p1);
+    if (j) b = ecn_mul(b, tw + ((u64)j << lg) * 8);
+    ecn_st(p0, ecn_add(a, b));
+    ecn_st(p1, ecn_add(a, pt_neg(b)));
+}
+// work[i] = [k] work[i], one scalar for all (the 1 / n of the inverse transform)
+__global__ __launch_bounds__(64) void ecn_scale_kernel(u32* __restrict__ work, u64 n, const u32* __restrict__ k) {
+    const u64 i = blockIdx.x * 64ull + threadIdx.x;
+    if (i >= n) return;
+    ecn_st(work + i * EW, ecn_mul(ecn_ld(work + i * EW), k));
+}
+// work[i] = [k] pts[i]: every lane walks the same bits
+__global__ __launch_bounds__(64) void ecn_mul_scalar_kernel(const u32* __restrict__ pts, u64 n, const u32* __restrict__ k, u32* __restrict__ work) {
+    const u64 i = blockIdx.x * 64ull + threadIdx.x;
+    if (i >= n) return;
+    ecn_st(work + i * EW, ecn_mul(ecn_load_ext(pts + i * AW), k));
+}
+// work[i] = a[i] - b[i]
+__global__ __launch_bounds__(64) void ecn_diff_kernel(const u32* __restrict__ a, const u32* __restrict__ b, u64 n, u32* __restrict__ work) {
+    const u64 i = blockIdx.x * 64ull + threadIdx.x;
+    if (i >= n) return;
+    ecn_st(work + i * EW, ecn_add(ecn_load_ext(a + i * AW), pt_neg(ecn_load_ext(b + i * AW))));
+}
+
+// Column sums in the group: work[j] = sum over the sets q and the terms k of column j of coef[k] * base_q[rows[k]].  One wave per wire, as
+// kg_wire_sums_kernel has it (ONE can sit in every row, most wires in two or three): lane l takes the terms l, l + 64, ... of each set in
+// turn, then the 64 partial sums meet in a fixed order -- no atomics.  A coefficient of 1 or r - 1 (nearly all of a circom circuit's)
+// costs an addition; any other one a full product.
+struct EcnSums { EcCsc s[3]; int n_sets; u32 rm1[8]; };
+__device__ __forceinline__ xyzz ecn_shfl_down(const xyzz& p, int d) {
+    u32 w[EW];
+    ecn_st(w, p);
+#pragma unroll
+    for (int k = 0; k < EW; ++k) w[k] = __shfl_down(w[k], d, 64);
+    return ecn_ld(w);
+}
+__global__ __launch_bounds__(64) void ecn_column_sums_kernel(const EcnSums S, u32 n_wires, u32* __restrict__ work) {
+    const u32 j = blockIdx.x, lane = threadIdx.x;
+    if (j >= n_wires) return;
+    xyzz acc = pt_inf();
+    for (int q = 0; q < S.n_sets; ++q) {
+        const EcCsc& M = S.s[q];
+        for (u64 k = M.ptr[j] + lane; k < M.ptr[j + 1]; k += 64) {
+            xyzz b = ecn_load_ext(M.base + (u64)M.rows[k] * AW);
+            const u32* c = M.coef + k * 8;
+            u32 not_one = c[0] ^ 1u, not_m1 = 0;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) { if (i) not_one |= c[i]; not_m1 |= c[i] ^ S.rm1[i]; }
+            if (!not_m1) b = pt_neg(b);
+            else if (not_one) b = ecn_mul(b, c);
+            acc = ecn_add(acc, b);
+        }
+    }
+    for (int d = 32; d >= 1; d >>= 1) acc = ecn_add(acc, ecn_shfl_down(acc, d));   // lanes >= d add what nobody reads
+    if (lane == 0) ecn_st(work + (u64)j * EW, acc);
+}
+
+// ---- the way out: one inversion per workgroup (the tree of fb_mul_kernel) --------------------------------------------------------------
+__device__ __forceinline__ fe ecn_leaf(const xyzz& p) {            // ZZZ, or its norm over Fq2
+#ifndef MSM_G2
+    return p.ZZZ;
+#else
+    return fe_mul(fe_add(fe_sqr(p.ZZZ.c0), fe_sqr(p.ZZZ.c1)), fe_one());
+#endif
+}
+__device__ __noinline__ void ecn_store_affine(const xyzz& p, const fe& inv_leaf, u32* __restrict__ o) {
+#ifndef MSM_G2
+    const cf izzz = inv_leaf;
+#else
+    cf izzz; izzz.c0 = fe_mul(p.ZZZ.c0, inv_leaf); izzz.c1 = fe_mul(fe_sub<2>(fe_zero(), p.ZZZ.c1), inv_leaf);
+#endif
+    const cf s = cf_mul(p.ZZ, izzz), izz = cf_sqr(s);              // 1 / ZZ = (ZZ / ZZZ)^2
+    u32 x[CW_STD], y[CW_STD];
+    cf_to_std(cf_mul(p.X, izz), x); cf_to_std(cf_mul(p.Y, izzz), y);
+    for (int k = 0; k < CW_STD; ++k) { o[k] = x[k]; o[CW_STD + k] = y[k]; }
+}
+constexpr int ECN_BLOCK = 256;
+__global__ __launch_bounds__(ECN_BLOCK) void ecn_store_kernel(const u32* __restrict__ work, u64 n, u32* __restrict__ out) {
+    __shared__ fe node[2 * ECN_BLOCK];                              // heap order, leaves at ECN_BLOCK + lane
+    const u32 l = threadIdx.x;
+    const u64 i = (u64)blockIdx.x * ECN_BLOCK + l;
+    const bool live = i < n;
+    xyzz acc = pt_inf();
+    if (live) acc = ecn_ld(work + i * EW);
+    const bool finite = live && !pt_is_inf(acc);
+    node[ECN_BLOCK + l] = finite ? ecn_leaf(acc) : fe_one();
+    for (u32 s = ECN_BLOCK / 2; s >= 1; s >>= 1) {
+        __syncthreads();
+        if (l < s) node[s + l] = fe_mul(node[2 * (s + l)], node[2 * (s + l) + 1]);
+    }
+    __syncthreads();
+    if (l == 0) node[1] = fe_inv(node[1]);
+    for (u32 s = 1; s < (u32)ECN_BLOCK; s <<= 1) {
+        __syncthreads();
+        if (l < s) {
+            const u32 p = s + l;
+            const fe ip = node[p], a = node[2 * p], b = node[2 * p + 1];
+            node[2 * p] = fe_mul(ip, b); node[2 * p + 1] = fe_mul(ip, a);
+        }
+    }
+    __syncthreads();
+    if (!live) return;
+    u32* o = out + i * AW;
+    if (!finite) { for (int k = 0; k < AW; ++k) o[k] = 0; return; }
+    const fe inv_leaf = node[ECN_BLOCK + l];
+    ecn_store_affine(acc, inv_leaf, o);
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------------------------
+static unsigned ecn_blocks(u64 n, unsigned per) {
+    ZK_REQUIRE(n < (1ull << 31) * per, "group transform: too many points");
+    return (unsigned)((n + per - 1) / per);
+}
+static void ecn_store(const DevBuf& work, u64 n, void* d_out, hipStream_t st) {
+    hipLaunchKernelGGL(ecn_store_kernel, dim3(ecn_blocks(n, ECN_BLOCK)), dim3(ECN_BLOCK), 0, st, (const u32*)work.p, n, (u32*)d_out);
+    ZK_HIP(hipGetLastError());
+}
+// d_points: 2^logn points, in place.  d_tw: 2^(logn - 1) twiddles; d_scale: one scalar for the way out, or null
+void ntt_run(void* d_points, int logn, const u32* d_tw, const u32* d_scale, hipStream_t st) {
+    const u64 n = 1ull << logn;
+    DevBuf work; work.reserve(n * EW * 4);
+    hipLaunchKernelGGL(ecn_load_kernel, dim3(ecn_blocks(n, 64)), dim3(64), 0, st, (const u32*)d_points, (u32)logn, (u32*)work.p);
+    ZK_HIP(hipGetLastError());
+    for (int s = 0; s < logn; ++s) {
+        hipLaunchKernelGGL(ecn_stage_kernel, dim3(ecn_blocks(n / 2, 64)), dim3(64), 0, st, (u32*)work.p, d_tw, (u32)logn, (u32)s);
+        ZK_HIP(hipGetLastError());
+    }
+    if (d_scale) {
+        hipLaunchKernelGGL(ecn_scale_kernel, dim3(ecn_blocks(n, 64)), dim3(64), 0, st, (u32*)work.p, n, d_scale);
+        ZK_HIP(hipGetLastError());
+    }
+    ecn_store(work, n, d_points, st);
+}
+void mul_scalar_run(const void* d_pts, u64 n, const u32* d_k, void* d_out, hipStream_t st) {
+    if (n == 0) return;
+    DevBuf work; work.reserve(n * EW * 4);
+    hipLaunchKernelGGL(ecn_mul_scalar_kernel, dim3(ecn_blocks(n, 64)), dim3(64), 0, st, (const u32*)d_pts, n, d_k, (u32*)work.p);
+    ZK_HIP(hipGetLastError());
+    ecn_store(work, n, d_out, st);
+}
+void diff_run(const void* d_a, const void* d_b, u64 n, void* d_out, hipStream_t st) {
+    if (n == 0) return;
+    DevBuf work; work.reserve(n * EW * 4);
+    hipLaunchKernelGGL(ecn_diff_kernel, dim3(ecn_blocks(n, 64)), dim3(64), 0, st, (const u32*)d_a, (const u32*)d_b, n, (u32*)work.p);
+    ZK_HIP(hipGetLastError());
+    ecn_store(work, n, d_out, st);
+}
+void column_sums_run(const EcCsc* sets, int n_sets, const u32* r, u32 n_wires, void* d_out, hipStream_t st) {
+    if (n_wires == 0) return;
+    ZK_REQUIRE(n_sets >= 1 && n_sets <= 3, "column sums: one to three matrices");
+    EcnSums S;
+    for (int q = 0; q < n_sets; ++q) S.s[q] = sets[q];
+    for (int q = n_sets; q < 3; ++q) S.s[q] = sets[0];
+    S.n_sets = n_sets;
+    for (int i = 0; i < 8; ++i) S.rm1[i] = r[i];
+    S.rm1[0] -= 1;                                                  // r is odd
+    DevBuf work; work.reserve((u64)n_wires * EW * 4);
+    hipLaunchKernelGGL(ecn_column_sums_kernel, dim3(n_wires), dim3(64), 0, st, S, n_wires, (u32*)work.p);
+    ZK_HIP(hipGetLastError());
+    ecn_store(work, n_wires, d_out, st);
+}

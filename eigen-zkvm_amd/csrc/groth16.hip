@@ -9,10 +9,12 @@
 //   quotient         7 transforms over Fr + the pointwise step                  (frntt_impl.hip.h)
 //   h, l, a, b_g1, b_g2 sums and the final assembly through msm.hip
 //   proof.json       groth16/src/json_utils.rs:305-315
-// Key generation (`zkit groth16_setup`, groth16/src/api.rs:42-66) over the same circuit: groth16_keygen_impl.hip.h.
+// Key generation (`zkit groth16_setup`, groth16/src/api.rs:42-66) over the same circuit: groth16_keygen_impl.hip.h with a trapdoor,
+// groth16_srs.hip.h from a powers-of-tau file (and the contributions to such a key).
 // r and s are taken from the caller (the reference draws them from OsRng, api.rs:172); everything else is a
 // function of (key, circuit, witness).
 #include "curve.h"
+#include "fr_host.h"
 #include "r1cs_file.h"
 #include "json_min.h"
 #include <algorithm>
@@ -188,6 +190,41 @@ struct Circuit {
     }
 };
 
+// one matrix by columns, the rows of a column in increasing order: ptr (n_wires + 1 entries), the rows, and the coefficients (8 canonical words) beside them
+static void csc_of(const Circuit::Csr& M, u64 nw, std::vector<u64>& ptr, std::vector<u32>& rows, std::vector<u32>& coef) {
+    const size_t nt = M.cols.size();
+    ptr.assign(nw + 1, 0);
+    for (u32 c : M.cols) ++ptr[c + 1];
+    for (u64 j = 0; j < nw; ++j) ptr[j + 1] += ptr[j];
+    std::vector<u64> cur(ptr.begin(), ptr.end() - 1);
+    rows.resize(nt); coef.resize(nt * 8);
+    for (u64 r = 0; r + 1 < M.ptr.size(); ++r)
+        for (u64 k = M.ptr[r]; k < M.ptr[r + 1]; ++k) {
+            const u64 at = cur[M.cols[k]]++;
+            rows[at] = (u32)r;
+            std::memcpy(&coef[at * 8], &M.coef[k * 8], 32);
+        }
+}
+static void os_random(void* p, size_t n, const char* who) {
+    size_t got = 0;
+    while (got < n) {
+        const ssize_t k = getrandom((uint8_t*)p + got, n - got, 0);
+        if (k < 0 && errno == EINTR) continue;                              // a signal arrived before any byte: ask again
+        ZK_REQUIRE(k > 0, std::string(who) + ": the operating system gave no random bytes");
+        got += (size_t)k;
+    }
+}
+// uniform in [1, r): bytes from the operating system, cut to the modulus' bit length, drawn again while out of range
+static void draw_fr(const Curve& cv, u32* v, const char* who) {
+    const u32 top_mask = (1u << (cv.r_bits() - 224)) - 1;
+    for (;;) {
+        os_random(v, 32, who);
+        v[7] &= top_mask;
+        u32 any = 0; for (int i = 0; i < 8; ++i) any |= v[i];
+        if (any && cv.fr_canonical(v)) break;
+    }
+}
+
 // canonical little-endian coordinates (nc x cw words per point) -> pairing_ce's uncompressed encoding: every coordinate big-endian, G2 as
 // x.c1 || x.c0 || y.c1 || y.c0; the all-zero point (no finite point has x = y = 0) is infinity: bit 6 of byte 0, zeros behind it
 __global__ __launch_bounds__(256) void points_to_be_kernel(const u32* __restrict__ pts, u64 n, int cw, int g2, u32* __restrict__ out) {
@@ -207,6 +244,45 @@ static void points_to_be_dev(const u32* d_pts, u64 n, int cw, bool g2, u32* d_ou
     if (n == 0) return;
     hipLaunchKernelGGL(points_to_be_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_pts, n, cw, g2 ? 1 : 0, d_out);
     ZK_HIP(hipGetLastError());
+}
+// Parameters::write from the key's points on the device (affine, Montgomery): pts1 = [alpha beta delta | x (ic, then l) | h | a | b] over all wires,
+// pts2 = [beta gamma delta | b].  Canonical coordinates, then pairing_ce's uncompressed big-endian bytes; points at infinity are dropped from
+// a, b_g1, b_g2 (generator.rs), in wire order.  Consumes pts1 and pts2.
+static void write_params(const Curve& cv, const Circuit& C, DevBuf& pts1, DevBuf& pts2, std::vector<uint8_t>& out, hipStream_t st) {
+    const MsmOps& M = cv.msm();
+    const u64 nh = C.m - 1, nw = C.n_wires, n1 = 3 + 3 * nw + nh, n2 = 3 + nw;
+    const u64 o_x = 3, o_h = o_x + nw, o_a = o_h + nh, o_b = o_a + nw;
+    const size_t P1 = cv.point_words(G1), P2 = cv.point_words(G2);
+    DevBuf be1, be2;
+    M.fq_mont_to_canon_dev(pts1.p, n1 * 2, st); M.fq_mont_to_canon_dev(pts2.p, n2 * 4, st);
+    be1.reserve(n1 * P1 * 4); be2.reserve(n2 * P2 * 4);
+    points_to_be_dev((const u32*)pts1.p, n1, (int)cv.fq_words, false, (u32*)be1.p, st);
+    points_to_be_dev((const u32*)pts2.p, n2, (int)cv.fq_words, true, (u32*)be2.p, st);
+    ZK_HIP(hipStreamSynchronize(st));
+    pts1.release(); pts2.release();
+    std::vector<uint8_t> h1(n1 * P1 * 4), h2(n2 * P2 * 4);
+    d2h_sync(h1.data(), be1.p, h1.size()); d2h_sync(h2.data(), be2.p, h2.size());
+    const size_t B1 = P1 * 4, B2 = P2 * 4;
+    out.clear();
+    out.reserve(h1.size() + h2.size() + 24);
+    auto put = [&](const std::vector<uint8_t>& src, size_t pb, u64 at, u64 n) { out.insert(out.end(), src.begin() + at * pb, src.begin() + (at + n) * pb); };
+    auto count = [&](u64 n) { ZK_REQUIRE(n < (1ull << 32), "groth16 keygen: a query has 2^32 points or more"); const uint8_t b[4] = {(uint8_t)(n >> 24), (uint8_t)(n >> 16), (uint8_t)(n >> 8), (uint8_t)n}; out.insert(out.end(), b, b + 4); };
+    auto put_finite = [&](const std::vector<uint8_t>& src, size_t pb, u64 at, u64 n) {   // generator.rs drops the zero points of a, b_g1, b_g2
+        const size_t at_count = out.size();
+        count(0);
+        u64 kept = 0;
+        for (u64 i = 0; i < n; ++i)
+            if (!(src[(at + i) * pb] & 0x40)) { put(src, pb, at + i, 1); ++kept; }
+        const uint8_t b[4] = {(uint8_t)(kept >> 24), (uint8_t)(kept >> 16), (uint8_t)(kept >> 8), (uint8_t)kept};
+        std::memcpy(&out[at_count], b, 4);
+    };
+    put(h1, B1, 0, 2); put(h2, B2, 0, 2); put(h1, B1, 2, 1); put(h2, B2, 2, 1);   // alpha_g1 beta_g1 beta_g2 gamma_g2 delta_g1 delta_g2
+    count(C.ni); put(h1, B1, o_x, C.ni);
+    count(nh); put(h1, B1, o_h, nh);
+    count(C.n_aux); put(h1, B1, o_x + C.ni, C.n_aux);
+    put_finite(h1, B1, o_a, nw);
+    put_finite(h1, B1, o_b, nw);
+    put_finite(h2, B2, 3, nw);
 }
 // overwrite host memory that held a secret; the compiler may not drop the stores
 static void wipe(void* p, size_t n) { volatile uint8_t* q = (volatile uint8_t*)p; for (size_t i = 0; i < n; ++i) q[i] = 0; }
@@ -271,23 +347,7 @@ Groth16Key* groth16_keygen_new(const char* curve, const void* r1cs, size_t r1cs_
             ZK_REQUIRE(any, std::string("groth16 keygen: trapdoor component ") + names[c] + " is zero");
         }
     } else {
-        // uniform in [1, r): bytes from the operating system, cut to the modulus' bit length, drawn again while out of range
-        const u32 top_mask = (1u << (cv.r_bits() - 224)) - 1;
-        for (int c = 0; c < 5; ++c) {
-            u32* v = td + 8 * c;
-            for (;;) {
-                size_t got = 0;
-                while (got < 32) {
-                    const ssize_t k = getrandom((uint8_t*)v + got, 32 - got, 0);
-                    if (k < 0 && errno == EINTR) continue;                  // a signal arrived before any byte: ask again
-                    ZK_REQUIRE(k > 0, "groth16 keygen: the operating system gave no random bytes");
-                    got += (size_t)k;
-                }
-                v[7] &= top_mask;
-                u32 any = 0; for (int i = 0; i < 8; ++i) any |= v[i];
-                if (any && cv.fr_canonical(v)) break;
-            }
-        }
+        for (int c = 0; c < 5; ++c) g16::draw_fr(cv, td + 8 * c, "groth16 keygen");
     }
     auto key = std::make_unique<Groth16Key>();
     key->curve = &cv;
@@ -541,6 +601,8 @@ std::string groth16_key_check(const char* curve, const void* r1cs, size_t r1cs_l
     }
     return js + "}";
 }
+
+#include "groth16_srs.hip.h"
 
 // reader.rs:86-137 load_witness_from_bin_reader: header checks, then n x 32 B little-endian canonical values
 void groth16_wtns_payload(const void* wtns, size_t len, const char* curve, uint64_t* offset, uint64_t* n) {

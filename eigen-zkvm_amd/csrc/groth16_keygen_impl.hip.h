@@ -97,7 +97,7 @@ void keygen_run(const Curve& cv, const g16::Circuit& C, const u32* td, std::vect
     const u64 n1 = 3 + 3 * nw + nh, n2 = 3 + nw;
     // G1 scalars: [alpha beta delta | x (ic, then l) | h | a | b];  G2: [beta gamma delta], then the b of the G1 array
     const u64 o_x = 3, o_h = o_x + nw, o_a = o_h + nh, o_b = o_a + nw;
-    DevBuf d_td, d_kc, pw, tmp, sc1, sc2, csc_ptr[3], csc_rows[3], csc_coef[3], pts1, pts2, be1, be2;
+    DevBuf d_td, d_kc, pw, tmp, sc1, sc2, csc_ptr[3], csc_rows[3], csc_coef[3], pts1, pts2;
     d_td.reserve(40 * 4); d_kc.reserve(sizeof(KgConsts));
     pw.reserve(m * NR * 4); tmp.reserve(m * NR * 4); sc1.reserve(n1 * 32); sc2.reserve(3 * 32);
     struct Wipe {                                                       // also on the way out of an exception
@@ -132,19 +132,10 @@ void keygen_run(const Curve& cv, const g16::Circuit& C, const u32* td, std::vect
     DevBuf raw;                                                         // canonical coefficients on their way to the internal form: one block, reused
     raw.reserve(std::max({C.mat[0].cols.size(), C.mat[1].cols.size(), C.mat[2].cols.size()}) * 32 + 4);
     for (int w = 0; w < 3; ++w) {                                       // CSR -> CSC, rows of a column in increasing order; one host copy at a time
-        const auto& M = C.mat[w];
-        const size_t nt = M.cols.size();
-        std::vector<u64> ptr(nw + 1, 0);
-        for (u32 c : M.cols) ++ptr[c + 1];
-        for (u64 j = 0; j < nw; ++j) ptr[j + 1] += ptr[j];
-        std::vector<u64> cur(ptr.begin(), ptr.end() - 1);
-        std::vector<u32> rows(nt), coef(nt * 8);
-        for (u64 r = 0; r + 1 < M.ptr.size(); ++r)
-            for (u64 k = M.ptr[r]; k < M.ptr[r + 1]; ++k) {
-                const u64 at = cur[M.cols[k]]++;
-                rows[at] = (u32)r;
-                std::memcpy(&coef[at * 8], &M.coef[k * 8], 32);
-            }
+        std::vector<u64> ptr;
+        std::vector<u32> rows, coef;
+        g16::csc_of(C.mat[w], nw, ptr, rows, coef);
+        const size_t nt = rows.size();
         csc_ptr[w].reserve(ptr.size() * 8); csc_rows[w].reserve(nt * 4 + 4); csc_coef[w].reserve(nt * NR * 4 + 4);
         h2d_sync(csc_ptr[w].p, ptr.data(), ptr.size() * 8);
         if (nt) {
@@ -170,35 +161,6 @@ void keygen_run(const Curve& cv, const g16::Circuit& C, const u32* td, std::vect
     auto t4 = now();
     ms[3] = since(t3, t4);
 
-    // canonical coordinates, then pairing_ce's uncompressed big-endian bytes
-    M.fq_mont_to_canon_dev(pts1.p, n1 * 2, st); M.fq_mont_to_canon_dev(pts2.p, n2 * 4, st);
-    be1.reserve(n1 * P1 * 4); be2.reserve(n2 * P2 * 4);
-    g16::points_to_be_dev((const u32*)pts1.p, n1, (int)cv.fq_words, false, (u32*)be1.p, st);
-    g16::points_to_be_dev((const u32*)pts2.p, n2, (int)cv.fq_words, true, (u32*)be2.p, st);
-    ZK_HIP(hipStreamSynchronize(st));
-    pts1.release(); pts2.release();
-    std::vector<uint8_t> h1(n1 * P1 * 4), h2(n2 * P2 * 4);
-    d2h_sync(h1.data(), be1.p, h1.size()); d2h_sync(h2.data(), be2.p, h2.size());
-    const size_t B1 = P1 * 4, B2 = P2 * 4;
-    out.clear();
-    out.reserve(h1.size() + h2.size() + 24);
-    auto put = [&](const std::vector<uint8_t>& src, size_t pb, u64 at, u64 n) { out.insert(out.end(), src.begin() + at * pb, src.begin() + (at + n) * pb); };
-    auto count = [&](u64 n) { ZK_REQUIRE(n < (1ull << 32), "groth16 keygen: a query has 2^32 points or more"); const uint8_t b[4] = {(uint8_t)(n >> 24), (uint8_t)(n >> 16), (uint8_t)(n >> 8), (uint8_t)n}; out.insert(out.end(), b, b + 4); };
-    auto put_finite = [&](const std::vector<uint8_t>& src, size_t pb, u64 at, u64 n) {   // generator.rs drops the zero points of a, b_g1, b_g2
-        const size_t at_count = out.size();
-        count(0);
-        u64 kept = 0;
-        for (u64 i = 0; i < n; ++i)
-            if (!(src[(at + i) * pb] & 0x40)) { put(src, pb, at + i, 1); ++kept; }
-        const uint8_t b[4] = {(uint8_t)(kept >> 24), (uint8_t)(kept >> 16), (uint8_t)(kept >> 8), (uint8_t)kept};
-        std::memcpy(&out[at_count], b, 4);
-    };
-    put(h1, B1, 0, 2); put(h2, B2, 0, 2); put(h1, B1, 2, 1); put(h2, B2, 2, 1);   // alpha_g1 beta_g1 beta_g2 gamma_g2 delta_g1 delta_g2
-    count(C.ni); put(h1, B1, o_x, C.ni);
-    count(nh); put(h1, B1, o_h, nh);
-    count(C.n_aux); put(h1, B1, o_x + C.ni, C.n_aux);
-    put_finite(h1, B1, o_a, nw);
-    put_finite(h1, B1, o_b, nw);
-    put_finite(h2, B2, 3, nw);
+    g16::write_params(cv, C, pts1, pts2, out, st);
     ms[4] = since(t4, std::chrono::steady_clock::now());
 }

@@ -9,7 +9,7 @@ import secrets
 import numpy as np
 
 from . import DevArray, ZkError, _check, _np, _ptr, lib
-from .key_check_lines import POINT_CLASSES, key_check_line, key_check_skipped_line  # noqa: F401
+from .key_check_lines import POINT_CLASSES, contribution_check_line, key_check_line, key_check_skipped_line, srs_check_line  # noqa: F401
 
 _FR = {"BN128": 21888242871839275222246405745257275088548364400416034343698204186575808495617,
        "BLS12381": 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001}
@@ -95,20 +95,32 @@ class Groth16Setup:
             pass
 
 
-def keygen(curve, r1cs_bytes, trapdoor=None, to_hex=False, timing=None):
+def keygen(curve, r1cs_bytes, trapdoor=None, to_hex=False, timing=None, srs=None, check_srs=True):
     """`zkit groth16_setup` (groth16/src/api.rs:42-66): the circuit-specific key of an .r1cs, made on the device.
     trapdoor: (tau, alpha, beta, gamma, delta) as integers, or None to let the library draw them from the operating system
     (nothing of them survives the call).  -> (bellman Parameters bytes, verification_key.json text); `timing`, a list,
-    receives the milliseconds of the transform, the column sums, the G1 points, the G2 points and serialisation."""
+    receives the milliseconds of the transform, the column sums, the G1 points, the G2 points and serialisation.
+    srs: an Srs -- the key for (tau, alpha, beta, 1, 1) of that powers-of-tau file instead, made in the group (`timing` then: G1
+    transforms, G1 column sums, uploads and h, G2 transform and sums, serialisation).  check_srs: run Srs.check first and make no key from
+    a file with findings."""
     if curve not in _FR:
         raise ZkError('groth16: unknown curve "%s" (BN128 | BLS12381)' % curve)
+    if srs is not None and trapdoor is not None:
+        raise ZkError("groth16 keygen: a powers-of-tau file and a trapdoor exclude each other")
     td = None
     if trapdoor is not None:
         if len(trapdoor) != 5:
             raise ZkError("groth16 keygen: the trapdoor is (tau, alpha, beta, gamma, delta)")
         td = np.array([[(int(v) % _FR[curve] >> (64 * i)) & (2**64 - 1) for i in range(4)] for v in trapdoor], dtype=np.uint64).reshape(-1)
     r = np.frombuffer(r1cs_bytes, dtype=np.uint8)
-    h = lib().zk_groth16_keygen_new(curve.encode(), r.ctypes.data, r.size, _ptr(td) if td is not None else None)
+    if srs is not None:
+        if check_srs:
+            found = srs.check()["findings"]
+            if found:
+                raise ZkError("groth16 setup: the powers-of-tau file fails its check: " + "; ".join(srs_check_line(f) for f in found))
+        h = lib().zk_groth16_keygen_from_srs(curve.encode(), r.ctypes.data, r.size, srs._h)
+    else:
+        h = lib().zk_groth16_keygen_new(curve.encode(), r.ctypes.data, r.size, _ptr(td) if td is not None else None)
     if not h:
         raise ZkError(lib().zk_last_error().decode())
     try:
@@ -128,6 +140,97 @@ def keygen(curve, r1cs_bytes, trapdoor=None, to_hex=False, timing=None):
         return buf.tobytes(), vk
     finally:
         lib().zk_groth16_keygen_free(h)
+
+
+def _report(p):
+    if not p:
+        raise ZkError(lib().zk_last_error().decode())
+    try:
+        return json.loads(C.string_at(p).decode())
+    finally:
+        lib().zk_string_free(p)
+
+
+def _seed(seed, who):
+    if seed is not None and len(seed) != 32:
+        raise ZkError("%s: the seed is 32 bytes" % who)
+    return None if seed is None else np.frombuffer(bytes(seed), dtype=np.uint8)
+
+
+class Srs:
+    """A snarkjs powers-of-tau file (.ptau), opened on the host: sections tauG1, tauG2, alphaTauG1, betaTauG1, betaG2 of the curve's
+    points.  `power`: the file serves circuits of up to 2^power rows."""
+
+    def __init__(self, curve, path):
+        if curve not in _FR:
+            raise ZkError('groth16: unknown curve "%s" (BN128 | BLS12381)' % curve)
+        self.curve = curve
+        self._h = lib().zk_srs_open(curve.encode(), str(path).encode())
+        if not self._h:
+            raise ZkError(lib().zk_last_error().decode())
+        a, b = C.c_uint32(0), C.c_uint32(0)
+        _check(lib().zk_srs_info(self._h, C.byref(a), C.byref(b)))
+        self.power, self.ceremony_power = a.value, b.value
+
+    def check(self, seed=None, max_findings=16):
+        """every point's class and the sections' structure (zk_srs_check) -> the report as a dict; seed: 32 bytes, tests only"""
+        sd = _seed(seed, "srs check")
+        return _report(lib().zk_srs_check(self._h, sd.ctypes.data if sd is not None else None, int(max_findings)))
+
+    def free(self):
+        if self._h:
+            lib().zk_srs_free(self._h); self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def group_ntt(d_points, curve="BN128", group="g1", inverse=False, stream=0):
+    """EvaluationDomain::{fft, ifft} whose elements are points: a DevArray of 2^k affine points (u64 Montgomery words, all zero =
+    infinity), in place; natural order, the omega of fr_ntt, 1 / n in the inverse"""
+    pw = _FQ_WORDS[curve] * (2 if group == "g1" else 4)
+    n = d_points.n // pw
+    if n == 0 or n & (n - 1) or n * pw != d_points.n:
+        raise ZkError("group ntt: the array must hold a power of two of whole points")
+    _check(getattr(lib(), "zk_%s_%s_ntt_dev" % (group, _NAME[curve]))(d_points.ptr, n.bit_length() - 1, int(inverse), stream)); return d_points
+
+
+def mul_scalar(d_points, k, curve="BN128", group="g1", stream=0):
+    """[k] P_i for every point of a DevArray and one integer k -> a new DevArray"""
+    pw = _FQ_WORDS[curve] * (2 if group == "g1" else 4)
+    n = d_points.n // pw
+    kw = np.array([(int(k) % _FR[curve] >> (64 * i)) & (2**64 - 1) for i in range(4)], dtype=np.uint64)
+    out = DevArray(max(1, n) * pw)
+    _check(getattr(lib(), "zk_%s_%s_mul_scalar_dev" % (group, _NAME[curve]))(d_points.ptr, n, DevArray.from_host(kw).ptr, out.ptr, stream)); return out
+
+
+def contribute(curve, params_bytes, delta=None):
+    """One contribution to a key's delta: delta_g1, delta_g2 times delta, l and h divided by it, everything else copied -> the new key's
+    bytes.  delta: an integer in [1, r), or None to let the library draw it from the operating system (nothing of it survives the call)."""
+    if curve not in _FR:
+        raise ZkError('groth16: unknown curve "%s" (BN128 | BLS12381)' % curve)
+    dw = None
+    if delta is not None:
+        if not 0 < int(delta) < _FR[curve]:
+            raise ZkError("groth16 contribute: delta must be a non-zero canonical field element")
+        dw = np.array([(int(delta) >> (64 * i)) & (2**64 - 1) for i in range(4)], dtype=np.uint64)
+    p = np.frombuffer(params_bytes, dtype=np.uint8)
+    out = np.empty(p.size, np.uint8)
+    _check(lib().zk_groth16_params_contribute(curve.encode(), p.ctypes.data, p.size, _ptr(dw) if dw is not None else None, out.ctypes.data))
+    return out.tobytes()
+
+
+def contribution_check(curve, old_params, new_params, seed=None, max_findings=16):
+    """zk_groth16_contribution_check: what a contribution may and may not have changed between two keys -> the report as a dict"""
+    if curve not in _FR:
+        raise ZkError('groth16: unknown curve "%s" (BN128 | BLS12381)' % curve)
+    sd = _seed(seed, "groth16 contribution check")
+    a = np.frombuffer(old_params, dtype=np.uint8); b = np.frombuffer(new_params, dtype=np.uint8)
+    return _report(lib().zk_groth16_contribution_check(curve.encode(), a.ctypes.data, a.size, b.ctypes.data, b.size,
+                                                       sd.ctypes.data if sd is not None else None, int(max_findings)))
 
 
 def fq_convert(d_elems, curve="BN128", to_mont=True, stream=0):

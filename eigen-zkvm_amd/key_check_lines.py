@@ -18,3 +18,29 @@ def key_check_line(f):
 def key_check_skipped_line(s):
     """one entry of a report's "skipped" list"""
     return "skipped: %s of %s: %s" % (s["check"], s["section"], s["reason"])
+
+
+def srs_check_line(f):
+    """one finding of an Srs.check report"""
+    k = f["kind"]
+    if k in POINT_CLASSES:
+        return key_check_line(f)
+    if k == "not_generator":
+        return "not_generator: section %s does not start with the group's generator" % f["section"]
+    if k == "not_powers":
+        return "not_powers: section %s is not the sequence of powers of tau it claims to be" % f["section"]
+    return "beta_mismatch: %s is not the beta of betaTauG1" % f["section"]
+
+
+def contribution_check_line(f):
+    """one finding of a contribution_check report"""
+    k = f["kind"]
+    if k == "size":
+        return "size: section %s has %d points, the old key has %d" % (f["section"], f["have"], f["want"])
+    if k in POINT_CLASSES:
+        return key_check_line(f)
+    if k == "changed":
+        return "changed: section %s differs from the old key, first at index %d (a contribution touches delta, l and h only)" % (f["section"], f["first_index"])
+    if k == "delta_mismatch":
+        return "delta_mismatch: delta_g1 and delta_g2 of the new key hold different scalars"
+    return "not_scaled: section %s of the new key is not the old one divided by the ratio of the two deltas" % f["section"]

@@ -465,6 +465,47 @@ char* zk_groth16_keygen_vk_json(const zk_groth16_keygen_t* k, int to_hex);
 int zk_groth16_keygen_timing(const zk_groth16_keygen_t* k, double ms[5]);
 int zk_groth16_keygen_free(zk_groth16_keygen_t* k);
 
+/* ---- a Groth16 key from a powers-of-tau file, and contributions to it (csrc/groth16_srs.hip.h, csrc/ecntt.hip) ------------
+ * The key of zk_groth16_keygen_new is only as good as the promise that its trapdoor was forgotten.  These entry points make the key
+ * zk_groth16_keygen_new would make for (tau, alpha, beta, gamma = 1, delta = 1) from a ceremony's file, in which tau, alpha and beta
+ * exist only as points, and then let anybody multiply delta by a secret of their own.
+ * zk_srs_open reads a snarkjs .ptau container on the host (no GPU): magic "ptau", version 1, sections 1 (n8, the base field's modulus,
+ * power, ceremonyPower), 2 tauG1 (2 * 2^power - 1 points), 3 tauG2, 4 alphaTauG1, 5 betaTauG1 (2^power each), 6 betaG2 (one); other
+ * sections are ignored.  Points are uncompressed affine, little-endian Montgomery -- the layout of the multi-scalar sums.  curve: BN128 |
+ * BLS12381.  Errors (NULL, zk_last_error): wrong magic or version, a modulus that is not the curve's, a missing or wrong-sized section,
+ * a truncated file.  The layout is restated from snarkjs's writer; the reader has only met files tools/make_test_ptau.py wrote.
+ * zk_srs_check -> a JSON report (malloc'ed, zk_string_free) in the style of zk_groth16_key_check: every point's class; tauG1[0] = G1 and
+ * tauG2[0] = G2 ("not_generator"); each section a geometric sequence in tau, by one random linear combination and two pairings per section
+ * ("not_powers"); betaG2 against betaTauG1[0] ("beta_mismatch").  seed: 32 bytes, tests only; NULL = the operating system's randomness.
+ * zk_<g1|g2>_<curve>_ntt_dev: bellman's EvaluationDomain::{fft, ifft} on 2^log_n points in place -- natural order in and out, infinity
+ * allowed, the omega of zk_fr_<curve>_ntt, 1 / n in the inverse.  zk_<g1|g2>_<curve>_mul_scalar_dev: d_out[i] = [k] d_points[i] for one
+ * scalar k (4 x u64 canonical, below r) on the device; d_out may be d_points.
+ * zk_groth16_keygen_from_srs returns what zk_groth16_keygen_new returns (_params_size, _params, _vk_json, _timing and _free serve both;
+ * _timing here: G1 transforms, G1 column sums, uploads and the h differences, G2 transform and sums, serialisation).  It fails before any
+ * device work when the file's power is below the circuit's domain; a larger file is fine.
+ * zk_groth16_params_contribute: out (len bytes) = the key with delta_g1, delta_g2 multiplied by delta and every point of l and h by
+ * 1 / delta.  delta: 4 x u64 canonical, non-zero, or NULL to draw it from the operating system; it is overwritten on the host and on the
+ * device before the call returns.  zk_groth16_contribution_check -> a JSON report: sections that must be byte-equal ("changed", "size"),
+ * the classes of the new delta, l and h points, delta_g1 against delta_g2 ("delta_mismatch"), and l, h scaled by exactly the ratio of the
+ * two deltas ("not_scaled"). */
+typedef struct zk_srs zk_srs_t;
+zk_srs_t* zk_srs_open(const char* curve, const char* path);
+int zk_srs_info(const zk_srs_t* s, uint32_t* power, uint32_t* ceremony_power);
+char* zk_srs_check(const zk_srs_t* s, const uint8_t* seed, uint32_t max_findings);
+int zk_srs_free(zk_srs_t* s);
+int zk_g1_bn254_ntt_dev(void* d_points, uint32_t log_n, int inverse, void* stream);
+int zk_g2_bn254_ntt_dev(void* d_points, uint32_t log_n, int inverse, void* stream);
+int zk_g1_bls12_381_ntt_dev(void* d_points, uint32_t log_n, int inverse, void* stream);
+int zk_g2_bls12_381_ntt_dev(void* d_points, uint32_t log_n, int inverse, void* stream);
+int zk_g1_bn254_mul_scalar_dev(const void* d_points, uint64_t n, const uint64_t* d_k, void* d_out, void* stream);
+int zk_g2_bn254_mul_scalar_dev(const void* d_points, uint64_t n, const uint64_t* d_k, void* d_out, void* stream);
+int zk_g1_bls12_381_mul_scalar_dev(const void* d_points, uint64_t n, const uint64_t* d_k, void* d_out, void* stream);
+int zk_g2_bls12_381_mul_scalar_dev(const void* d_points, uint64_t n, const uint64_t* d_k, void* d_out, void* stream);
+zk_groth16_keygen_t* zk_groth16_keygen_from_srs(const char* curve, const void* r1cs, size_t r1cs_len, const zk_srs_t* srs);
+int zk_groth16_params_contribute(const char* curve, const void* params, size_t len, const uint64_t* delta, void* out);
+char* zk_groth16_contribution_check(const char* curve, const void* old_params, size_t old_len, const void* new_params, size_t new_len, const uint8_t* seed,
+                                    uint32_t max_findings);
+
 /* ---- pairings and Groth16 verification (`zkit groth16_verify`, zkit/src/main.rs:221-230, groth16/src/api.rs:302-341 ->
  * bellman's prepare_verifying_key + verify_proof) --------------------------------------------------------------------
  * zk_pairing_*: n pairs (g1[i], g2[i]) in the point layout of the multi-scalar sums (affine, Montgomery; the all-zero

@@ -9,6 +9,9 @@
   zkgpu_prove.py groth16_verify -c BN128 -v verification_key.json --public-input public_input.json --proof proof.json
   zkgpu_prove.py pil_verify -p circuit.pil.json --o circuit.const --m circuit.cm [--report out.json]
   zkgpu_prove.py wtns_check -c BN128|BLS12381|GL --r1cs circuit.r1cs --wtns witness.wtns [--sym circuit.sym] [--report out.json] [--max-findings N]
+  zkgpu_prove.py groth16_setup ... --ptau ceremony.ptau [--no-check-srs]
+  zkgpu_prove.py groth16_contribute -c BN128 -p in.key -o out.key [-v verification_key.json] [--check]
+  zkgpu_prove.py groth16_contribution_check -c BN128 --old a.key --new b.key
   zkgpu_prove.py groth16_key_check -c BN128|BLS12381 --r1cs circuit.r1cs -p g16.key [-v verification_key.json] [--report out.json] [--max-findings N]
   zkgpu_prove.py stark_verify -s starkStruct.json -p circuit.pil.json --o circuit.const --i zkin.json [--program FILE]
   zkgpu_prove.py compressor12_setup --r circuit.r1cs --c c12.const --p c12.pil --e c12.exec [--force_n_bits K] [--pil-json c12.pil.json]
@@ -388,16 +391,95 @@ def groth16_key_check(a):
 def groth16_setup(a):
     """groth16/src/api.rs:42-66: circuit_specific_setup, then the key and verification_key.json written to their files"""
     import importlib
+    if a.no_check_srs and not a.ptau:
+        raise SystemExit("zkgpu_prove: --no-check-srs says how to treat --ptau FILE and means nothing without it")
     _zk()
     dev = importlib.import_module("eigen_zkvm_amd.groth16")
     r1cs = pathlib.Path(a.circuit_file).read_bytes()
-    pk, vk = dev.keygen(a.curve_type, r1cs, to_hex=a.to_hex)
+    srs = None
+    if a.ptau:                                                            # extension: tau, alpha, beta from a ceremony's file, gamma = delta = 1
+        srs = dev.Srs(a.curve_type, a.ptau)
+        if not a.no_check_srs:                                            # a bad file makes no key
+            report = srs.check()
+            for f in report["findings"]:
+                print(dev.srs_check_line(f), file=sys.stderr)
+            for k in report["skipped"]:
+                print(dev.key_check_skipped_line(k), file=sys.stderr)
+            if any(report["counts"].values()):
+                raise SystemExit(1)
+            print("zkgpu_prove: %s is a well-formed powers-of-tau file of power %d (%d G1 and %d G2 points)"
+                  % (a.ptau, srs.power, report["checked"]["g1_points"], report["checked"]["g2_points"]))
+    pk, vk = dev.keygen(a.curve_type, r1cs, to_hex=a.to_hex, srs=srs, check_srs=False)   # checked above, line by line
+    if srs is not None:
+        srs.free()
+        print("zkgpu_prove: delta = 1 in this key: it needs at least one groth16_contribute before it is used")
     pathlib.Path(a.pk_file).write_bytes(pk)
     pathlib.Path(a.vk_file).write_text(vk)
     print("zkgpu_prove: %s key written to %s (%d bytes), verification key to %s" % (a.curve_type, a.pk_file, len(pk), a.vk_file))
     if a.check_key:
         _check_key(a.curve_type, r1cs, pk, vk)
         print("zkgpu_prove: the key passes groth16_key_check")
+
+
+def _vk_json_of_key(curve, pk, to_hex=False):
+    """verification_key.json of a key's bytes (json_utils.rs:285-303 over VerifyingKey::write's layout)"""
+    nb = 32 if curve == "BN128" else 48
+    o = 0
+    num = lambda b: ("0x" + b.hex()) if to_hex else str(int.from_bytes(b, "big"))
+
+    def g1():
+        nonlocal o
+        b = pk[o:o + 2 * nb]; o += 2 * nb
+        if b[0] & 0x40:
+            b = bytes(2 * nb - 1) + b"\x01"                               # CurveAffine::zero() is (0, 1)
+        return {"x": num(b[:nb]), "y": num(b[nb:])}
+
+    def g2():
+        nonlocal o
+        b = pk[o:o + 4 * nb]; o += 4 * nb
+        return {"x": [num(b[nb:2 * nb]), num(b[:nb])], "y": [num(b[3 * nb:]), num(b[2 * nb:3 * nb])]}
+    js = {"protocol": "groth16", "curve": curve}
+    for name, f in (("vk_alpha_1", g1), ("vk_beta_1", g1), ("vk_beta_2", g2), ("vk_gamma_2", g2), ("vk_delta_1", g1), ("vk_delta_2", g2)):
+        js[name] = f()
+    n = int.from_bytes(pk[o:o + 4], "big"); o += 4
+    js["IC"] = [g1() for _ in range(n)]
+    return json.dumps(js, separators=(",", ":"))
+
+
+def _check_contribution(curve, old, new, out=sys.stderr):
+    import importlib
+    dev = importlib.import_module("eigen_zkvm_amd.groth16")
+    report = dev.contribution_check(curve, old, new)
+    for f in report["findings"]:
+        print(dev.contribution_check_line(f), file=out)
+    for k in report["skipped"]:
+        print(dev.key_check_skipped_line(k), file=out)
+    if any(report["counts"].values()):
+        raise SystemExit(1)
+    return report
+
+
+def groth16_contribute(a):
+    """extension: one contribution to a key's delta, drawn from the operating system and forgotten"""
+    import importlib
+    _zk()
+    dev = importlib.import_module("eigen_zkvm_amd.groth16")
+    old = pathlib.Path(a.pk_file).read_bytes()
+    new = dev.contribute(a.curve_type, old)
+    if a.check:                                                           # nothing is written for a contribution that does not check
+        _check_contribution(a.curve_type, old, new)
+    pathlib.Path(a.out_file).write_bytes(new)
+    if a.vk_file:
+        pathlib.Path(a.vk_file).write_text(_vk_json_of_key(a.curve_type, new))
+    print("zkgpu_prove: %s key with one more contribution to delta written to %s (%d bytes)%s"
+          % (a.curve_type, a.out_file, len(new), ", verification key to %s" % a.vk_file if a.vk_file else ""))
+
+
+def groth16_contribution_check(a):
+    _zk()
+    rep = _check_contribution(a.curve_type, pathlib.Path(a.old_file).read_bytes(), pathlib.Path(a.new_file).read_bytes(), out=sys.stdout)
+    print("zkgpu_prove: %s is %s with a contribution to delta and nothing else changed (%d h and %d l points)"
+          % (a.new_file, a.old_file, rep["sections"]["h"], rep["sections"]["l"]))
 
 
 def groth16_prove(a):
@@ -520,7 +602,21 @@ def build_parser():
     k.add_argument("-v", dest="vk_file", default="verification_key.json")
     k.add_argument("-t", dest="to_hex", action="store_true", help="coordinates of the verification key as 0x strings")
     k.add_argument("--check-key", dest="check_key", action="store_true", help="run groth16_key_check on the key just made (extension)")
+    k.add_argument("--ptau", default=None, metavar="FILE", help="take tau, alpha, beta from a powers-of-tau file instead of drawing a trapdoor (extension)")
+    k.add_argument("--no-check-srs", dest="no_check_srs", action="store_true", help="with --ptau: skip the check of the file's points and structure")
     k.set_defaults(fn=groth16_setup)
+    gc = sub.add_parser("groth16_contribute", help="multiply a key's delta by a fresh secret (extension)")
+    gc.add_argument("-c", dest="curve_type", default="BN128")
+    gc.add_argument("-p", dest="pk_file", required=True)
+    gc.add_argument("-o", dest="out_file", required=True)
+    gc.add_argument("-v", dest="vk_file", default=None, help="write the new key's verification_key.json here")
+    gc.add_argument("--check", action="store_true", help="run groth16_contribution_check on the result before writing it")
+    gc.set_defaults(fn=groth16_contribute)
+    cc = sub.add_parser("groth16_contribution_check", help="check that a key is another one with a contribution to delta and no other change (extension)")
+    cc.add_argument("-c", dest="curve_type", default="BN128")
+    cc.add_argument("--old", dest="old_file", required=True)
+    cc.add_argument("--new", dest="new_file", required=True)
+    cc.set_defaults(fn=groth16_contribution_check)
     kc = sub.add_parser("groth16_key_check", help="check a proving key against its circuit: sizes, every point, the G1 / G2 copies (extension)")
     kc.add_argument("-c", dest="curve_type", default="BN128")
     kc.add_argument("--r1cs", dest="circuit_file", required=True)
