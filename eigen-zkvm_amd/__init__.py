@@ -63,6 +63,9 @@ EXPORTS = [
     "zk_g1_bn254_ntt_dev", "zk_g2_bn254_ntt_dev", "zk_g1_bls12_381_ntt_dev", "zk_g2_bls12_381_ntt_dev",
     "zk_g1_bn254_mul_scalar_dev", "zk_g2_bn254_mul_scalar_dev", "zk_g1_bls12_381_mul_scalar_dev", "zk_g2_bls12_381_mul_scalar_dev",
     "zk_groth16_key_check", "zk_points_check_bn254", "zk_points_check_bn254_dev", "zk_points_check_bls12_381", "zk_points_check_bls12_381_dev",
+    "zk_g1_bn254_mul_scalars_dev", "zk_g2_bn254_mul_scalars_dev", "zk_g1_bls12_381_mul_scalars_dev", "zk_g2_bls12_381_mul_scalars_dev",
+    "zk_pairing_product_bn254", "zk_pairing_product_bn254_dev", "zk_pairing_product_bls12_381", "zk_pairing_product_bls12_381_dev",
+    "zk_groth16_verify_aggregate", "zk_groth16_verify_aggregate_dev", "zk_groth16_verify_aggregate_timing", "zk_groth16_proof_words",
 ]
 
 # include/zkgpu.h enums
@@ -348,6 +351,18 @@ def _load():
         "zk_points_check_bn254_dev": (C.c_int, [C.c_int, vp, C.c_uint64, C.c_int, vp, vp]),
         "zk_points_check_bls12_381": (C.c_int, [C.c_int, vp, C.c_uint64, C.c_int, vp]),
         "zk_points_check_bls12_381_dev": (C.c_int, [C.c_int, vp, C.c_uint64, C.c_int, vp, vp]),
+        "zk_g1_bn254_mul_scalars_dev": (C.c_int, [vp, C.c_uint64, vp, vp, vp]),
+        "zk_g2_bn254_mul_scalars_dev": (C.c_int, [vp, C.c_uint64, vp, vp, vp]),
+        "zk_g1_bls12_381_mul_scalars_dev": (C.c_int, [vp, C.c_uint64, vp, vp, vp]),
+        "zk_g2_bls12_381_mul_scalars_dev": (C.c_int, [vp, C.c_uint64, vp, vp, vp]),
+        "zk_pairing_product_bn254": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_int]),
+        "zk_pairing_product_bn254_dev": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_int, vp]),
+        "zk_pairing_product_bls12_381": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_int]),
+        "zk_pairing_product_bls12_381_dev": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_int, vp]),
+        "zk_groth16_verify_aggregate": (C.c_int, [vp, vp, vp, C.c_uint64, vp, vp, vp]),
+        "zk_groth16_verify_aggregate_dev": (C.c_int, [vp, vp, vp, C.c_uint64, vp, vp, vp, vp]),
+        "zk_groth16_verify_aggregate_timing": (C.c_int, [vp]),
+        "zk_groth16_proof_words": (C.c_int, [vp, C.c_char_p, C.c_char_p, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -348,6 +348,23 @@ static int pairing_host(CurveId id, const void* g1, const void* g2, uint64_t n, 
         d2h_sync(gt_out, dg.p, n * cv.gt_bytes());
     });
 }
+static int pairing_product_device(CurveId id, const void* d_g1, const void* d_g2, uint64_t n, void* d_gt, int with_final_exp, void* stream) {
+    return guard([&] {
+        ZK_REQUIRE(d_gt && (n == 0 || (d_g1 && d_g2)), "pairing product: null argument");
+        pairing_product_dev(curve(id), d_g1, d_g2, n, d_gt, with_final_exp, on_stream((hipStream_t)stream));
+    });
+}
+static int pairing_product_host(CurveId id, const void* g1, const void* g2, uint64_t n, void* gt_out, int with_final_exp) {
+    return guard([&] {
+        ZK_REQUIRE(gt_out && (n == 0 || (g1 && g2)), "pairing product: null argument");
+        const Curve& cv = curve(id);
+        DevBuf d1, d2, dg;
+        d1.reserve(n * cv.point_bytes(G1) + 4); d2.reserve(n * cv.point_bytes(G2) + 4); dg.reserve(cv.gt_bytes());
+        if (n) { h2d_sync(d1.p, g1, n * cv.point_bytes(G1)); h2d_sync(d2.p, g2, n * cv.point_bytes(G2)); }
+        pairing_product_dev(cv, d1.p, d2.p, n, dg.p, with_final_exp, cur_stream());
+        d2h_sync(gt_out, dg.p, cv.gt_bytes());
+    });
+}
 static int points_check_device(CurveId id, int group, const void* d_points, uint64_t n, int plain, uint64_t* d_out, void* stream) {
     return guard([&] {
         ZK_REQUIRE(group == 1 || group == 2, "points check: group must be 1 or 2");
@@ -388,6 +405,8 @@ static int points_check_host(CurveId id, int group, const void* points, uint64_t
     int zk_fq_##NAME##_convert_dev(void* d, uint64_t n, int to_mont, void* stream) { return fq_convert(ID, d, n, to_mont, stream); }          \
     int zk_pairing_##NAME##_dev(const void* d_g1, const void* d_g2, uint64_t n, void* d_gt, int with_final_exp, void* stream) { return pairing_device(ID, d_g1, d_g2, n, d_gt, with_final_exp, stream); } \
     int zk_pairing_##NAME(const void* g1, const void* g2, uint64_t n, void* gt_out, int with_final_exp) { return pairing_host(ID, g1, g2, n, gt_out, with_final_exp); } \
+    int zk_pairing_product_##NAME##_dev(const void* d_g1, const void* d_g2, uint64_t n, void* d_gt, int with_final_exp, void* stream) { return pairing_product_device(ID, d_g1, d_g2, n, d_gt, with_final_exp, stream); } \
+    int zk_pairing_product_##NAME(const void* g1, const void* g2, uint64_t n, void* gt_out, int with_final_exp) { return pairing_product_host(ID, g1, g2, n, gt_out, with_final_exp); } \
     int zk_points_check_##NAME##_dev(int group, const void* d_points, uint64_t n, int plain, uint64_t* d_out, void* stream) { return points_check_device(ID, group, d_points, n, plain, d_out, stream); } \
     int zk_points_check_##NAME(int group, const void* points, uint64_t n, int plain, uint64_t* out) { return points_check_host(ID, group, points, n, plain, out); }
 ZK_CURVE_API(bn254, CURVE_BN254)
@@ -723,9 +742,16 @@ static int mul_scalar_device(CurveId id, Group g, const void* d_points, uint64_t
         curve(id).ec().g[g].mul_scalar(d_points, n, (const u32*)d_k, d_out, on_stream((hipStream_t)stream));
     });
 }
+static int mul_scalars_device(CurveId id, Group g, const void* d_points, uint64_t n, const uint64_t* d_k, void* d_out, void* stream) {
+    return guard([&] {
+        ZK_REQUIRE(n == 0 || (d_points && d_k && d_out), "mul_scalars: null argument");
+        curve(id).ec().g[g].mul_scalars(d_points, curve(id).point_words(g), n, (const u32*)d_k, d_out, on_stream((hipStream_t)stream));
+    });
+}
 #define ZK_EC_API(GN, NAME, ID, G)                                                                                                            \
     int zk_##GN##_##NAME##_ntt_dev(void* d_points, uint32_t log_n, int inverse, void* stream) { return group_ntt_device(ID, G, d_points, log_n, inverse, stream); } \
-    int zk_##GN##_##NAME##_mul_scalar_dev(const void* d_points, uint64_t n, const uint64_t* d_k, void* d_out, void* stream) { return mul_scalar_device(ID, G, d_points, n, d_k, d_out, stream); }
+    int zk_##GN##_##NAME##_mul_scalar_dev(const void* d_points, uint64_t n, const uint64_t* d_k, void* d_out, void* stream) { return mul_scalar_device(ID, G, d_points, n, d_k, d_out, stream); } \
+    int zk_##GN##_##NAME##_mul_scalars_dev(const void* d_points, uint64_t n, const uint64_t* d_k, void* d_out, void* stream) { return mul_scalars_device(ID, G, d_points, n, d_k, d_out, stream); }
 ZK_EC_API(g1, bn254, CURVE_BN254, G1)
 ZK_EC_API(g2, bn254, CURVE_BN254, G2)
 ZK_EC_API(g1, bls12_381, CURVE_BLS12_381, G1)
@@ -756,6 +782,30 @@ int zk_groth16_verify_batch_dev(const zk_groth16_vk_t* vk, const void* d_proofs,
 int zk_groth16_verify_json(const zk_groth16_vk_t* vk, const char* proof_json, const char* public_input_json) {
     int verdict = ZK_VERDICT_ERROR;
     if (guard([&] { ZK_REQUIRE(vk, "groth16 verify: null key"); verdict = groth16_verify_json(vk, proof_json, public_input_json); }) != 0)
+        return ZK_VERDICT_ERROR;
+    return verdict;
+}
+int zk_groth16_verify_aggregate(const zk_groth16_vk_t* vk, const void* proofs, const void* publics, uint64_t n, const uint8_t* seed, int* verdict, uint64_t* first_bad) {
+    return guard([&] {
+        ZK_REQUIRE(vk && verdict, "groth16 verify: null argument");
+        *verdict = ZK_VERDICT_ERROR;
+        groth16_verify_aggregate(vk, proofs, publics, n, seed, first_bad != nullptr, verdict, first_bad);
+    });
+}
+int zk_groth16_verify_aggregate_dev(const zk_groth16_vk_t* vk, const void* d_proofs, const void* d_publics, uint64_t n, const uint8_t* seed, int* verdict,
+                                    uint64_t* first_bad, void* stream) {
+    return guard([&] {
+        ZK_REQUIRE(vk && verdict, "groth16 verify: null argument");
+        *verdict = ZK_VERDICT_ERROR;
+        groth16_verify_aggregate_dev(vk, d_proofs, d_publics, n, seed, first_bad != nullptr, verdict, first_bad, on_stream((hipStream_t)stream));
+    });
+}
+int zk_groth16_verify_aggregate_timing(double* ms) {
+    return guard([&] { ZK_REQUIRE(ms, "groth16 verify: null argument"); groth16_verify_aggregate_timing(ms); });
+}
+int zk_groth16_proof_words(const zk_groth16_vk_t* vk, const char* proof_json, const char* public_input_json, void* proof_out, void* public_out) {
+    int verdict = ZK_VERDICT_ERROR;
+    if (guard([&] { ZK_REQUIRE(vk, "groth16 verify: null key"); verdict = groth16_proof_words(vk, proof_json, public_input_json, proof_out, public_out); }) != 0)
         return ZK_VERDICT_ERROR;
     return verdict;
 }

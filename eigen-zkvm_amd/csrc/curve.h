@@ -49,6 +49,9 @@ struct Groth16Ops {
     void (*fr_quotient_dev)(u64* d_a, const u64* d_b, const u64* d_c, int logn, hipStream_t st);
     Groth16Setup* (*setup_new)(const Curve& cv, const g16::Circuit& C, const g16::Params& pk);
     void (*keygen_run)(const Curve& cv, const g16::Circuit& C, const u32* td, std::vector<uint8_t>& out, double* ms);
+    // verify_sums_impl.hip.h: rho (n x 8 words) and inputs (n x n_pub x 8 canonical words) -> s_0 = sum rho_i, s_j = sum rho_i pub_ij mod r as
+    // (n_pub + 1) x 8 canonical words, then n_pub + 1 words: per column the number of inputs that are not below r
+    void (*verify_sums_dev)(const void* d_rho, const void* d_pub, uint64_t n, uint32_t n_pub, void* d_out, hipStream_t st);
 };
 // ---- pairing.hip: the steps of the optimal ate pairing and of Groth16 verification (pairing_impl.hip.h)
 struct PairingOps {
@@ -63,6 +66,9 @@ struct PairingOps {
     void (*miller)(const MillerArgs&, u64, void*, hipStream_t);
     void (*final_exp)(const void*, u64, void*, void*, int, hipStream_t);
     void (*verdict)(const void*, const void*, u64, const int*, int*, hipStream_t);
+    // the product of n Miller values (f12_bytes(1) each) as one: input, n, scratch of f12_prod_scratch(n) bytes, output; a fixed order
+    size_t (*f12_prod_scratch)(u64);
+    void (*f12_prod)(const void*, u64, void*, void*, hipStream_t);
     // by Group (key_check_impl.hip.h): points, stride in words, n, plain, canon -> 4 x (count, first index) for infinity, coordinate_range,
     // not_on_curve, not_in_subgroup
     void (*points_check[2])(const void*, u64, u64, int, int, u64*, hipStream_t);
@@ -73,6 +79,8 @@ struct EcCsc { const u64* ptr; const u32* rows; const u32* coef; const u32* base
 struct EcGroupOps {
     void (*ntt)(void* d_points, int logn, const u32* d_tw, const u32* d_scale, hipStream_t st);
     void (*mul_scalar)(const void* d_points, u64 n, const u32* d_k, void* d_out, hipStream_t st);          // out_i = [k] P_i, one k
+    // out_i = [k_i] P_i, one k per point; the points stride_words apart (a proof's A), the results packed; a walk from each scalar's top set bit
+    void (*mul_scalars)(const void* d_points, u64 stride_words, u64 n, const u32* d_k, void* d_out, hipStream_t st);
     void (*diff)(const void* d_a, const void* d_b, u64 n, void* d_out, hipStream_t st);                    // out_i = a_i - b_i
     // out_j = sum over the sets and the terms of column j of coef * base[row], j < n_wires; r: the scalar modulus
     void (*column_sums)(const EcCsc* sets, int n_sets, const u32* r, u32 n_wires, void* d_out, hipStream_t st);
@@ -141,6 +149,10 @@ std::string groth16_contribution_check(const char* curve, const void* old_params
 std::string groth16_key_check(const char* curve, const void* r1cs, size_t r1cs_len, const void* params, size_t params_len, const char* vk_json,
                               const uint8_t* seed, uint32_t max_findings);
 
+// n weights of 128 bits as 32 B canonical scalars: ChaCha20 of the seed on the device (kc_rho_kernel).  seed: 32 bytes, tests only; null = the
+// operating system's randomness.  Synchronises the stream.
+void groth16_rho_dev(const uint8_t* seed, uint64_t n, DevBuf& d_rho, hipStream_t st, const char* who);
+
 // ---- pairing.hip: the optimal ate pairing and Groth16 verification ----
 // one point of a verification_key.json or a proof ({"x", "y"}; G2: [c0, c1] pairs) -> 2 or 4 x fq_words canonical 32-bit words; pairing_ce's
 // zero (0, 1) becomes the all-zero encoding; negate: y -> q - y.  Throws on what is no number or does not fit the field's width.
@@ -153,6 +165,23 @@ void groth16_vk_info(const Groth16Vk* vk, uint32_t* n_public, uint32_t* proof_by
 void groth16_verify_batch_dev(const Groth16Vk* vk, const void* d_proofs, const void* d_publics, uint64_t n, int* d_verdicts, hipStream_t st);
 void groth16_verify_batch(const Groth16Vk* vk, const void* proofs, const void* publics, uint64_t n, int* verdicts);
 int groth16_verify_json(const Groth16Vk* vk, const char* proof_json, const char* public_json);
+// prod_i e(g1_i, g2_i) as ONE value of GT (the layout of pairing_dev): line tables, single-pair Miller loops, the product reduction, one final
+// exponentiation; n = 0 gives one.  In chunks, so that the tables of a large n are never allocated at once.
+void pairing_product_dev(const Curve& cv, const void* d_g1, const void* d_g2, uint64_t n, void* d_gt, int with_final_exp, hipStream_t st);
+// n proofs in one randomised check: accepted exactly when every proof is, except with probability about 2^-128 over the
+// weights.  seed: 32 bytes for the weights, for tests only -- null (the operating system's randomness) anywhere else.  locate: on refusal run
+// the per-proof path and report the first proof it does not accept (*first_bad, *verdict = its code); without it *verdict is REJECTED and
+// *first_bad is left at n.  Synchronises the stream.
+void groth16_verify_aggregate_dev(const Groth16Vk* vk, const void* d_proofs, const void* d_publics, uint64_t n, const uint8_t* seed, bool locate,
+                                  int* verdict, uint64_t* first_bad, hipStream_t st);
+void groth16_verify_aggregate(const Groth16Vk* vk, const void* proofs, const void* publics, uint64_t n, const uint8_t* seed, bool locate,
+                              int* verdict, uint64_t* first_bad);
+// proof.json and public_input.json -> the words groth16_verify_batch takes: proof_out A || B || C (Montgomery), public_out n_public x 8
+// canonical words.  -> 1, or the verdict the file-level form gives without looking at a point (INPUT_COUNT, INPUT_NOT_CANONICAL)
+int groth16_proof_words(const Groth16Vk* vk, const char* proof_json, const char* public_json, void* proof_out, void* public_out);
+// phases of the last aggregate call on this thread, host milliseconds around stream synchronisations, when ZK_VERIFY_AGG_TIMING is set:
+// checks, scalar products, lines and Miller loops, product, sums, tail
+void groth16_verify_aggregate_timing(double ms[6]);
 
 }  // namespace zk
 
@@ -181,7 +210,9 @@ struct zk_srs {              // a powers-of-tau file, read and measured; the sec
 struct zk_groth16_vk {       // a verification key, checked and prepared
     const zk::Curve* curve = nullptr;
     uint32_t n_ic = 0;
-    void *d_ic = nullptr, *d_lines = nullptr, *d_inf = nullptr, *d_ab = nullptr;   // IC (Montgomery), the lines of -gamma and -delta, e(alpha, beta)
+    void *d_ic = nullptr, *d_lines = nullptr, *d_inf = nullptr, *d_ab = nullptr;   // IC (Montgomery), the lines of -gamma, -delta and -beta, e(alpha, beta)
+    void* d_alpha = nullptr;                                                       // alpha (Montgomery), for the aggregate check
+    bool ic_has_infinity = false;                                                  // an IC point at infinity: the sums cannot take it
     zk_groth16_vk() = default; zk_groth16_vk(const zk_groth16_vk&) = delete; zk_groth16_vk& operator=(const zk_groth16_vk&) = delete;
-    ~zk_groth16_vk() { for (void* p : {d_ic, d_lines, d_inf, d_ab}) if (p) zk::pool_free(p); }
+    ~zk_groth16_vk() { for (void* p : {d_ic, d_lines, d_inf, d_ab, d_alpha}) if (p) zk::pool_free(p); }
 };

@@ -51,7 +51,7 @@ namespace {
 }  // namespace bls12_381
 
 // the table's slice of this unit (curve.h)
-#define ZK_EC_OPS(NS) {NS::ntt_run, NS::mul_scalar_run, NS::diff_run, NS::column_sums_run}
+#define ZK_EC_OPS(NS) {NS::ntt_run, NS::mul_scalar_run, NS::mul_scalars_run, NS::diff_run, NS::column_sums_run}
 const EcOps& ec_ops(CurveId id) {
     static const EcOps OPS[2] = {{{ZK_EC_OPS(bn254::ecntt_g1), ZK_EC_OPS(bn254::ecntt_g2)}}, {{ZK_EC_OPS(bls12_381::ecntt_g1), ZK_EC_OPS(bls12_381::ecntt_g2)}}};
     return OPS[id];

@@ -86,6 +86,13 @@ __global__ __launch_bounds__(64) void ecn_mul_scalar_kernel(const u32* __restric
     if (i >= n) return;
     ecn_st(work + i * EW, ecn_mul(ecn_load_ext(pts + i * AW), k));
 }
+// work[i] = [k_i] pts[i]: one scalar per point (8 canonical words each), points `stride` words apart.  Every lane starts at the top set
+// bit of its own scalar, so the wave walks as many bits as its longest scalar has: 128-bit scalars cost half of full-width ones.
+__global__ __launch_bounds__(64) void ecn_mul_scalars_kernel(const u32* __restrict__ pts, u64 stride, u64 n, const u32* __restrict__ k, u32* __restrict__ work) {
+    const u64 i = blockIdx.x * 64ull + threadIdx.x;
+    if (i >= n) return;
+    ecn_st(work + i * EW, ecn_mul(ecn_load_ext(pts + i * stride), k + i * 8));
+}
 // work[i] = a[i] - b[i]
 __global__ __launch_bounds__(64) void ecn_diff_kernel(const u32* __restrict__ a, const u32* __restrict__ b, u64 n, u32* __restrict__ work) {
     const u64 i = blockIdx.x * 64ull + threadIdx.x;
@@ -206,6 +213,13 @@ void mul_scalar_run(const void* d_pts, u64 n, const u32* d_k, void* d_out, hipSt
     if (n == 0) return;
     DevBuf work; work.reserve(n * EW * 4);
     hipLaunchKernelGGL(ecn_mul_scalar_kernel, dim3(ecn_blocks(n, 64)), dim3(64), 0, st, (const u32*)d_pts, n, d_k, (u32*)work.p);
+    ZK_HIP(hipGetLastError());
+    ecn_store(work, n, d_out, st);
+}
+void mul_scalars_run(const void* d_pts, u64 stride_words, u64 n, const u32* d_k, void* d_out, hipStream_t st) {
+    if (n == 0) return;
+    DevBuf work; work.reserve(n * EW * 4);
+    hipLaunchKernelGGL(ecn_mul_scalars_kernel, dim3(ecn_blocks(n, 64)), dim3(64), 0, st, (const u32*)d_pts, stride_words, n, d_k, (u32*)work.p);
     ZK_HIP(hipGetLastError());
     ecn_store(work, n, d_out, st);
 }

@@ -347,6 +347,35 @@ __global__ __launch_bounds__(64) void final_exp_kernel(const u32* __restrict__ f
         fe_to_canon_words(r.c0, o); fe_to_canon_words(r.c1, o + NL);
     }
 }
+// Product of n Fq12 values in the layout miller_kernel writes.  A launch of B blocks has 8 B groups; group g multiplies the items g, g + 8 B,
+// g + 16 B, ... (an idle group holds one), the eight groups of the block then meet through LDS as a tree (4, 2, 1: group j takes in group
+// j + s) and group 0 stores the block's product.  B = ceil(n / PR_PROD_BLOCK) capped at PR_PROD_MAX_BLOCKS; more than one block means a
+// second launch of one block over the B partial products.  The order is fixed by n alone and nothing is atomic: the same input gives the
+// same limbs.  All control flow around the barriers of f12_mul is uniform in the block (the trip count depends on n and gridDim only).
+constexpr int PR_PROD_SHARE = 8;                               // items a group takes before the launch opens another block
+constexpr int PR_PROD_BLOCK = PR_GROUPS * PR_PROD_SHARE;       // items per block at that point
+constexpr int PR_PROD_MAX_BLOCKS = 1024;
+__global__ __launch_bounds__(64) void f12_prod_kernel(const u32* __restrict__ f_in, u64 n, u32* __restrict__ f_out) {
+    __shared__ u32 sh_all[PR_GROUPS * PR_SH_WORDS];
+    __shared__ u32 meet[PR_GROUPS * PR_SLOT];
+    const f12ctx c = f12_ctx(sh_all);
+    const u32 grp = threadIdx.x / PR_GROUP;
+    const u64 tg = (u64)gridDim.x * PR_GROUPS, gg = (u64)blockIdx.x * PR_GROUPS + grp;
+    cf acc = gg < n ? cf_load_int(f_in + (gg * 6 + c.k) * CW_INT) : f12_one(c);
+    for (u64 base = tg; base < n; base += tg) {
+        const u64 i = base + gg;
+        const cf b = i < n ? cf_load_int(f_in + (i * 6 + c.k) * CW_INT) : f12_one(c);
+        acc = f12_mul(c, acc, b);
+    }
+    for (u32 s = PR_GROUPS / 2; s >= 1; s >>= 1) {
+        __syncthreads();
+        if (c.live) cf_store_int(acc, meet + grp * PR_SLOT + c.k * CW_INT);
+        __syncthreads();
+        const cf b = grp < s ? cf_load_int(meet + (grp + s) * PR_SLOT + c.k * CW_INT) : f12_one(c);
+        acc = f12_mul(c, acc, b);
+    }
+    if (grp == 0 && c.live) cf_store_int(acc, f_out + ((u64)blockIdx.x * 6 + c.k) * CW_INT);
+}
 __global__ __launch_bounds__(64) void g16_verdict_kernel(const u32* __restrict__ gt, const u32* __restrict__ want, u64 n, const int* __restrict__ status, int* __restrict__ verdict) {
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -377,6 +406,23 @@ void final_exp_dev(const void* f_in, u64 n, void* tab, void* gt_out, int do_exp,
     if (!n) return;
     hipLaunchKernelGGL(final_exp_kernel, dim3((unsigned)((n + PR_GROUPS - 1) / PR_GROUPS)), dim3(64), 0, st, (const u32*)f_in, n, (u32*)tab, (u32*)gt_out, do_exp);
     ZK_HIP(hipGetLastError());
+}
+// f_out: one value; scratch: f12_prod_scratch_bytes(n) for the partial products of a two-level run (unused below PR_PROD_BLOCK + 1 items).
+// f_out and scratch must not overlap f_in.
+size_t f12_prod_scratch_bytes(u64 n) {
+    const u64 b = (n + PR_PROD_BLOCK - 1) / PR_PROD_BLOCK;
+    return (size_t)(b < PR_PROD_MAX_BLOCKS ? b : PR_PROD_MAX_BLOCKS) * PR_SLOT * 4;
+}
+void f12_prod_dev(const void* f_in, u64 n, void* scratch, void* f_out, hipStream_t st) {
+    ZK_REQUIRE(n >= 1, "pairing product: nothing to multiply");
+    u64 blocks = (n + PR_PROD_BLOCK - 1) / PR_PROD_BLOCK;
+    if (blocks > PR_PROD_MAX_BLOCKS) blocks = PR_PROD_MAX_BLOCKS;
+    hipLaunchKernelGGL(f12_prod_kernel, dim3((unsigned)blocks), dim3(64), 0, st, (const u32*)f_in, n, (u32*)(blocks > 1 ? scratch : f_out));
+    ZK_HIP(hipGetLastError());
+    if (blocks > 1) {
+        hipLaunchKernelGGL(f12_prod_kernel, dim3(1), dim3(64), 0, st, (const u32*)scratch, blocks, (u32*)f_out);
+        ZK_HIP(hipGetLastError());
+    }
 }
 void g16_verdict_dev(const void* gt, const void* want, u64 n, const int* status, int* verdict, hipStream_t st) {
     if (!n) return;

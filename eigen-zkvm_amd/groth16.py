@@ -207,6 +207,20 @@ def mul_scalar(d_points, k, curve="BN128", group="g1", stream=0):
     _check(getattr(lib(), "zk_%s_%s_mul_scalar_dev" % (group, _NAME[curve]))(d_points.ptr, n, DevArray.from_host(kw).ptr, out.ptr, stream)); return out
 
 
+def mul_scalars(d_points, scalars, curve="BN128", group="g1", stream=0):
+    """[k_i] P_i for the points of a DevArray and one integer per point -> a new DevArray.  The walk starts at each scalar's top set
+    bit: short scalars are cheap.  A zero scalar or the all-zero point gives the all-zero encoding."""
+    pw = _FQ_WORDS[curve] * (2 if group == "g1" else 4)
+    n = d_points.n // pw
+    if n * pw != d_points.n or len(scalars) != n:
+        raise ZkError("mul_scalars: the array must hold whole points and one scalar for each")
+    kw = np.array([((int(k) % _FR[curve]) >> (64 * i)) & (2**64 - 1) for k in scalars for i in range(4)], dtype=np.uint64)
+    out = DevArray(max(1, n) * pw)
+    if n:
+        _check(getattr(lib(), "zk_%s_%s_mul_scalars_dev" % (group, _NAME[curve]))(d_points.ptr, n, DevArray.from_host(kw).ptr, out.ptr, stream))
+    return out
+
+
 def contribute(curve, params_bytes, delta=None):
     """One contribution to a key's delta: delta_g1, delta_g2 times delta, l and h divided by it, everything else copied -> the new key's
     bytes.  delta: an integer in [1, r), or None to let the library draw it from the operating system (nothing of it survives the call)."""
@@ -262,6 +276,20 @@ def pairing(g1, g2, curve="BN128", final_exp=True):
     return out
 
 
+def pairing_product(g1, g2, curve="BN128", final_exp=True):
+    """prod_i e(g1_i, g2_i) for n pairs in the layout `pairing` takes -> ONE GT value, 12 x (4 | 6) u64; n = 0 gives one"""
+    if curve not in _FR:
+        raise ZkError('pairing: unknown curve "%s" (BN128 | BLS12381)' % curve)
+    nl = _FQ_WORDS[curve]
+    a, b = np.ascontiguousarray(_np(g1)).reshape(-1), np.ascontiguousarray(_np(g2)).reshape(-1)
+    n = a.size // (2 * nl)
+    if a.size != n * 2 * nl or b.size != n * 4 * nl:
+        raise ZkError("pairing: g1 must hold n x 2 and g2 n x 4 base-field elements")
+    out = np.zeros((12, nl), np.uint64)
+    _check(getattr(lib(), "zk_pairing_product_%s" % _NAME[curve])(_ptr(a) if n else None, _ptr(b) if n else None, n, _ptr(out), int(bool(final_exp))))
+    return out
+
+
 class Groth16VerifyingKey:
     """bellman's PreparedVerifyingKey on the device: e(alpha, beta), the line tables of -gamma and -delta, the IC points.
     Stricter than the reference (which reads points unchecked): every point must be on its curve and of order r, every public
@@ -307,6 +335,43 @@ class Groth16VerifyingKey:
             _check(lib().zk_groth16_verify_batch(self._h, _ptr(sel), _ptr(pub) if pub.size else None, len(ok), _ptr(v)))
             out[ok] = v
         return out
+
+    def verify_aggregate(self, points, publics, seed=None, locate=True):
+        """All n proofs in one randomised pairing check (zk_groth16_verify_aggregate): -> (verdict, first_bad).  (ACCEPTED, None) when every
+        proof is good; a batch with a wrong proof is accepted with probability about 2^-128 over the secret weights.  Otherwise, with
+        locate, the per-proof path names the first proof it does not accept and its verdict; without it (REJECTED, None).
+        seed: 32 bytes, FOR TESTS ONLY -- None draws the weights from the operating system."""
+        pts = np.ascontiguousarray(_np(points)).reshape(-1)
+        n = pts.size * 8 // self.proof_bytes
+        if pts.size * 8 != n * self.proof_bytes or len(publics) != n:
+            raise ZkError("groth16 verify: points must hold n proofs and publics n input lists")
+        for i in range(n):                                   # what verify_batch settles on the host: the first such proof is the answer
+            if len(publics[i]) != self.n_public or not all(0 <= int(x) < 2**256 for x in publics[i]):
+                code = INPUT_COUNT if len(publics[i]) != self.n_public else INPUT_NOT_CANONICAL
+                if not locate:
+                    return REJECTED, None
+                if i:
+                    v, fb = self.verify_aggregate(pts.reshape(n, -1)[:i], publics[:i], seed, True)
+                    if v != ACCEPTED:
+                        return v, fb
+                return code, i
+        sd = _seed(seed, "groth16 verify")
+        pub = np.array([(int(x) >> (64 * k)) & (2**64 - 1) for row in publics for x in row for k in range(4)], dtype=np.uint64)
+        verdict, first = C.c_int(VERDICT_ERROR), C.c_uint64(0)
+        _check(lib().zk_groth16_verify_aggregate(self._h, _ptr(pts) if n else None, _ptr(pub) if pub.size else None, n,
+                                                 sd.ctypes.data if sd is not None else None, C.byref(verdict), C.byref(first) if locate else None))
+        return verdict.value, (int(first.value) if locate and verdict.value != ACCEPTED else None)
+
+    def proof_words(self, proof_json, public):
+        """proof.json and public_input.json (text) through the library's readers -> (points, inputs) as verify_batch takes them, or the
+        verdict (INPUT_COUNT, INPUT_NOT_CANONICAL) the file-level form gives without looking at a point"""
+        pts, pub = np.zeros(self.proof_bytes // 8, np.uint64), np.zeros(max(1, 4 * self.n_public), np.uint64)
+        v = lib().zk_groth16_proof_words(self._h, proof_json.encode(), public.encode(), _ptr(pts), _ptr(pub))
+        if v == VERDICT_ERROR:
+            raise ZkError(lib().zk_last_error().decode())
+        if v != ACCEPTED:
+            return v
+        return pts, [sum(int(pub[4 * j + k]) << (64 * k) for k in range(4)) for j in range(self.n_public)]
 
     def free(self):
         if self._h:

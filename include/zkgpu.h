@@ -479,7 +479,9 @@ int zk_groth16_keygen_free(zk_groth16_keygen_t* k);
  * ("not_powers"); betaG2 against betaTauG1[0] ("beta_mismatch").  seed: 32 bytes, tests only; NULL = the operating system's randomness.
  * zk_<g1|g2>_<curve>_ntt_dev: bellman's EvaluationDomain::{fft, ifft} on 2^log_n points in place -- natural order in and out, infinity
  * allowed, the omega of zk_fr_<curve>_ntt, 1 / n in the inverse.  zk_<g1|g2>_<curve>_mul_scalar_dev: d_out[i] = [k] d_points[i] for one
- * scalar k (4 x u64 canonical, below r) on the device; d_out may be d_points.
+ * scalar k (4 x u64 canonical, below r) on the device; d_out may be d_points.  zk_<g1|g2>_<curve>_mul_scalars_dev: d_out[i] =
+ * [d_k[i]] d_points[i], one scalar of 4 x u64 per point; the walk starts at each scalar's top set bit, so scalars of 128 bits cost half of
+ * full-width ones; a zero scalar or the all-zero point gives the all-zero encoding; d_out may be d_points.
  * zk_groth16_keygen_from_srs returns what zk_groth16_keygen_new returns (_params_size, _params, _vk_json, _timing and _free serve both;
  * _timing here: G1 transforms, G1 column sums, uploads and the h differences, G2 transform and sums, serialisation).  It fails before any
  * device work when the file's power is below the circuit's domain; a larger file is fine.
@@ -501,6 +503,10 @@ int zk_g1_bn254_mul_scalar_dev(const void* d_points, uint64_t n, const uint64_t*
 int zk_g2_bn254_mul_scalar_dev(const void* d_points, uint64_t n, const uint64_t* d_k, void* d_out, void* stream);
 int zk_g1_bls12_381_mul_scalar_dev(const void* d_points, uint64_t n, const uint64_t* d_k, void* d_out, void* stream);
 int zk_g2_bls12_381_mul_scalar_dev(const void* d_points, uint64_t n, const uint64_t* d_k, void* d_out, void* stream);
+int zk_g1_bn254_mul_scalars_dev(const void* d_points, uint64_t n, const uint64_t* d_k, void* d_out, void* stream);
+int zk_g2_bn254_mul_scalars_dev(const void* d_points, uint64_t n, const uint64_t* d_k, void* d_out, void* stream);
+int zk_g1_bls12_381_mul_scalars_dev(const void* d_points, uint64_t n, const uint64_t* d_k, void* d_out, void* stream);
+int zk_g2_bls12_381_mul_scalars_dev(const void* d_points, uint64_t n, const uint64_t* d_k, void* d_out, void* stream);
 zk_groth16_keygen_t* zk_groth16_keygen_from_srs(const char* curve, const void* r1cs, size_t r1cs_len, const zk_srs_t* srs);
 int zk_groth16_params_contribute(const char* curve, const void* params, size_t len, const uint64_t* delta, void* out);
 char* zk_groth16_contribution_check(const char* curve, const void* old_params, size_t old_len, const void* new_params, size_t new_len, const uint8_t* seed,
@@ -522,7 +528,25 @@ char* zk_groth16_contribution_check(const char* curve, const void* old_params, s
  * proof; the checks are stricter than the reference's, which reads points unchecked (json_utils.rs:163-198): proof points
  * must be on their curve and in the subgroup of order r ([r]P = O), inputs must be below r.
  * zk_groth16_verify_json: the file-level form, proof.json and public_input.json -> the verdict, or ZK_VERDICT_ERROR
- * (zk_last_error) when a file cannot be read as what it should be.                                                   */
+ * (zk_last_error) when a file cannot be read as what it should be.
+ * zk_pairing_product_*: prod_i e(g1[i], g2[i]) as ONE value of GT in the layout above (n = 0: one), through single-pair
+ * Miller loops, a product reduction in a fixed order and one final exponentiation.
+ * zk_groth16_verify_aggregate: the same n proofs and inputs as zk_groth16_verify_batch, ONE answer: *verdict =
+ * ZK_VERDICT_ACCEPTED when every proof is well formed and
+ *     prod_i e([rho_i]A_i, B_i) . e(sum_i rho_i X_i, -gamma) . e(sum_i rho_i C_i, -delta) . e([sum_i rho_i]alpha, -beta) = 1
+ * for secret weights rho_i of 128 bits (X_i = IC_0 + sum_j pub_ij IC_j): one short scalar product and one single-pair Miller
+ * loop per proof, one final exponentiation per batch.  A batch that holds a wrong proof is accepted with probability about
+ * 2^-128 over the weights.  seed: 32 bytes from which the weights are derived, FOR TESTS ONLY; NULL -- the only value to use
+ * anywhere else -- draws them from the operating system, and a caller who can predict them can make wrong proofs cancel.
+ * On refusal with first_bad != NULL the per-proof path runs: *first_bad = the index of the first proof it does not accept
+ * and *verdict = that proof's code; with first_bad == NULL nothing is located and *verdict = ZK_VERDICT_REJECTED.  Accepted
+ * batches leave *first_bad = n.  n = 0 is accepted.  The well-formedness rules and their codes are the per-proof path's.
+ * zk_groth16_verify_aggregate_timing: ms[6] = host milliseconds of the calling thread's last aggregate call spent in the
+ * checks, the scalar products, lines and Miller loops, the product, the sums, the tail -- measured (with a stream
+ * synchronisation after every phase) only while the environment holds ZK_VERIFY_AGG_TIMING.
+ * zk_groth16_proof_words: proof.json and public_input.json through the library's readers -> the words
+ * zk_groth16_verify_batch takes (proof_out: proof_bytes; public_out: n_public x 32 B); returns ZK_VERDICT_ACCEPTED, or
+ * ZK_VERDICT_INPUT_COUNT / ZK_VERDICT_INPUT_NOT_CANONICAL as zk_groth16_verify_json would, or ZK_VERDICT_ERROR.        */
 enum {
     ZK_VERDICT_ACCEPTED = 1,
     ZK_VERDICT_REJECTED = 0,              /* well-formed, the equation does not hold */
@@ -543,6 +567,15 @@ int zk_groth16_vk_free(zk_groth16_vk_t* vk);
 int zk_groth16_verify_batch(const zk_groth16_vk_t* vk, const void* proofs, const void* publics, uint64_t n, int* verdicts);
 int zk_groth16_verify_batch_dev(const zk_groth16_vk_t* vk, const void* d_proofs, const void* d_publics, uint64_t n, int* d_verdicts, void* stream);
 int zk_groth16_verify_json(const zk_groth16_vk_t* vk, const char* proof_json, const char* public_input_json);
+int zk_pairing_product_bn254(const void* g1, const void* g2, uint64_t n, void* gt_out, int with_final_exp);
+int zk_pairing_product_bn254_dev(const void* d_g1, const void* d_g2, uint64_t n, void* d_gt, int with_final_exp, void* stream);
+int zk_pairing_product_bls12_381(const void* g1, const void* g2, uint64_t n, void* gt_out, int with_final_exp);
+int zk_pairing_product_bls12_381_dev(const void* d_g1, const void* d_g2, uint64_t n, void* d_gt, int with_final_exp, void* stream);
+int zk_groth16_verify_aggregate(const zk_groth16_vk_t* vk, const void* proofs, const void* publics, uint64_t n, const uint8_t* seed, int* verdict, uint64_t* first_bad);
+int zk_groth16_verify_aggregate_dev(const zk_groth16_vk_t* vk, const void* d_proofs, const void* d_publics, uint64_t n, const uint8_t* seed, int* verdict,
+                                    uint64_t* first_bad, void* stream);
+int zk_groth16_verify_aggregate_timing(double* ms);
+int zk_groth16_proof_words(const zk_groth16_vk_t* vk, const char* proof_json, const char* public_input_json, void* proof_out, void* public_out);
 const char* zk_groth16_verdict_name(int verdict);
 
 /* ---- compressor12 exec (recursion/src/compressor12/compressor12_exec.rs:17-103) ----------------

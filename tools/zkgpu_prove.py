@@ -7,6 +7,7 @@
   zkgpu_prove.py groth16_setup -c BN128 --r1cs circuit.r1cs -p g16.key -v verification_key.json [-t]
   zkgpu_prove.py groth16_prove -c BN128 --r1cs circuit.r1cs -w witness.wtns -p g16.key --public-input public_input.json --proof proof.json [--verify verification_key.json]
   zkgpu_prove.py groth16_verify -c BN128 -v verification_key.json --public-input public_input.json --proof proof.json
+  zkgpu_prove.py groth16_verify -c BN128 -v verification_key.json --batch proofs.json
   zkgpu_prove.py pil_verify -p circuit.pil.json --o circuit.const --m circuit.cm [--report out.json]
   zkgpu_prove.py wtns_check -c BN128|BLS12381|GL --r1cs circuit.r1cs --wtns witness.wtns [--sym circuit.sym] [--report out.json] [--max-findings N]
   zkgpu_prove.py groth16_setup ... --ptau ceremony.ptau [--no-check-srs]
@@ -517,11 +518,49 @@ def groth16_verify(a):
     _zk()
     dev = importlib.import_module("eigen_zkvm_amd.groth16")
     vk = dev.Groth16VerifyingKey(a.curve_type, pathlib.Path(a.vk_file).read_text())
+    if a.batch:
+        return groth16_verify_list(a, dev, vk)
     verdict = vk.verify(pathlib.Path(a.proof_file).read_text(), pathlib.Path(a.public_input_file).read_text())
     vk.free()
     if verdict != dev.ACCEPTED:
         raise SystemExit("zkgpu_prove: verify failed: %s" % dev.verdict_name(verdict))
     print("zkgpu_prove: %s proof %s accepted" % (a.curve_type, a.proof_file))
+
+
+def groth16_verify_list(a, dev, vk):
+    """--batch LIST.json (extension): an array of [proof.json, public_input.json] path pairs, relative to the list's directory.  All of
+    them in one randomised pairing check; on refusal the per-proof path names every proof that is not accepted."""
+    import numpy as np
+    base = pathlib.Path(a.batch).resolve().parent
+    pairs = json.loads(pathlib.Path(a.batch).read_text())
+    if not isinstance(pairs, list) or not all(isinstance(e, list) and len(e) == 2 for e in pairs):
+        raise SystemExit("zkgpu_prove: %s must be an array of [proof.json, public_input.json] pairs" % a.batch)
+    early, pts, pubs = {}, [], []                               # verdicts the readers settle, and what goes to the device
+    for i, (pf, uf) in enumerate(pairs):
+        w = vk.proof_words((base / pf).read_text(), (base / uf).read_text())
+        if isinstance(w, tuple):
+            pts.append(w[0]); pubs.append(w[1])
+        else:
+            early[i] = w
+    rest = [i for i in range(len(pairs)) if i not in early]
+    verdict = dev.ACCEPTED
+    if rest:
+        allp = np.concatenate(pts)
+        verdict, _ = vk.verify_aggregate(allp, pubs, locate=False)
+    if verdict == dev.ACCEPTED and not early:
+        vk.free()
+        print("zkgpu_prove: %s all %d proofs of %s accepted" % (a.curve_type, len(pairs), a.batch))
+        return
+    each = dict(early)
+    if rest:
+        each.update(zip(rest, (int(v) for v in vk.verify_batch(allp, pubs))))
+    vk.free()
+    bad = [i for i in range(len(pairs)) if each[i] != dev.ACCEPTED]
+    if not bad:
+        raise RuntimeError("groth16_verify --batch: the aggregate check refused a batch whose proofs all pass one by one")
+    for i in bad:
+        print("zkgpu_prove: proof %d (%s): %s" % (i, pairs[i][0], dev.verdict_name(each[i])))
+    raise SystemExit("zkgpu_prove: verify failed: %d of %d proofs not accepted" % (len(bad), len(pairs)))
 
 
 def build_parser():
@@ -646,6 +685,8 @@ def build_parser():
     gv.add_argument("-v", dest="vk_file", default="verification_key.json")
     gv.add_argument("--public-input", dest="public_input_file", default="public_input.json")
     gv.add_argument("--proof", dest="proof_file", default="proof.json")
+    gv.add_argument("--batch", dest="batch", default=None, metavar="LIST.json",
+                    help="an array of [proof.json, public_input.json] path pairs, relative to the list: all of them in one randomised check (extension)")
     gv.set_defaults(fn=groth16_verify)
     return ap
 
