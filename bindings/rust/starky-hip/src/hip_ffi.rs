@@ -143,6 +143,8 @@ extern "C" {
     pub fn zk_groth16_params_contribute(curve: *const c_char, params: *const c_void, len: usize, delta: *const u64, out: *mut c_void) -> c_int;
     pub fn zk_groth16_contribution_check(curve: *const c_char, old_params: *const c_void, old_len: usize, new_params: *const c_void, new_len: usize,
                                          seed: *const u8, max_findings: u32) -> *mut c_char;
+    pub fn zk_groth16_key_check_srs(curve: *const c_char, r1cs: *const c_void, r1cs_len: usize, params: *const c_void, params_len: usize,
+                                    srs: *const zk_srs_t, seed: *const u8, max_findings: u32) -> *mut c_char;
     pub fn zk_stark_setup_free(s: *mut zk_stark_setup_t) -> c_int;
     pub fn zk_bn128_load_constants(path: *const c_char) -> c_int;
     pub fn zk_bls12381_load_constants(path: *const c_char) -> c_int;

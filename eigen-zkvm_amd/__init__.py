@@ -60,6 +60,7 @@ EXPORTS = [
     "zk_pil_check_new", "zk_pil_check_listing", "zk_pil_check_run", "zk_pil_check_run_dev", "zk_pil_check_free",
     "zk_r1cs_check_new", "zk_r1cs_check_info", "zk_r1cs_check_run", "zk_r1cs_check_run_dev", "zk_r1cs_check_free",
     "zk_srs_open", "zk_srs_info", "zk_srs_check", "zk_srs_free", "zk_groth16_keygen_from_srs", "zk_groth16_params_contribute", "zk_groth16_contribution_check",
+    "zk_groth16_key_check_srs",
     "zk_g1_bn254_ntt_dev", "zk_g2_bn254_ntt_dev", "zk_g1_bls12_381_ntt_dev", "zk_g2_bls12_381_ntt_dev",
     "zk_g1_bn254_mul_scalar_dev", "zk_g2_bn254_mul_scalar_dev", "zk_g1_bls12_381_mul_scalar_dev", "zk_g2_bls12_381_mul_scalar_dev",
     "zk_groth16_key_check", "zk_points_check_bn254", "zk_points_check_bn254_dev", "zk_points_check_bls12_381", "zk_points_check_bls12_381_dev",
@@ -338,6 +339,7 @@ def _load():
         "zk_groth16_keygen_from_srs": (vp, [C.c_char_p, vp, C.c_size_t, vp]),
         "zk_groth16_params_contribute": (C.c_int, [C.c_char_p, vp, C.c_size_t, vp, vp]),
         "zk_groth16_contribution_check": (vp, [C.c_char_p, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_uint32]),
+        "zk_groth16_key_check_srs": (vp, [C.c_char_p, vp, C.c_size_t, vp, C.c_size_t, vp, vp, C.c_uint32]),
         "zk_g1_bn254_ntt_dev": (C.c_int, [vp, C.c_uint32, C.c_int, vp]),
         "zk_g2_bn254_ntt_dev": (C.c_int, [vp, C.c_uint32, C.c_int, vp]),
         "zk_g1_bls12_381_ntt_dev": (C.c_int, [vp, C.c_uint32, C.c_int, vp]),

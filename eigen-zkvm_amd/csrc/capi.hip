@@ -733,6 +733,12 @@ char* zk_groth16_contribution_check(const char* curve, const void* old_params, s
     if (guard([&] { out = dup_report(groth16_contribution_check(curve, old_params, old_len, new_params, new_len, seed, max_findings)); }) != 0) return nullptr;
     return out;
 }
+char* zk_groth16_key_check_srs(const char* curve, const void* r1cs, size_t r1cs_len, const void* params, size_t params_len, const zk_srs_t* srs, const uint8_t* seed,
+                                uint32_t max_findings) {
+    char* out = nullptr;
+    if (guard([&] { out = dup_report(groth16_key_check_srs(curve, r1cs, r1cs_len, params, params_len, srs, seed, max_findings)); }) != 0) return nullptr;
+    return out;
+}
 static int group_ntt_device(CurveId id, Group g, void* d_points, uint32_t log_n, int inverse, void* stream) {
     return guard([&] { group_ntt_dev(curve(id), g, d_points, (int)log_n, inverse != 0, on_stream((hipStream_t)stream)); });
 }

@@ -42,6 +42,7 @@ struct MsmOps {
     void (*fq_mont_to_canon_dev)(void* d, uint64_t n, hipStream_t st);
 };
 // ---- groth16.hip: the scalar field's transforms and the prover / key generation built on them
+struct KcMatrix { const u64* ptr; const u32* cols; const u32* coef; u64 n_rows; };   // one matrix by rows on the device; coef as kc_coef_dev leaves it
 struct Groth16Ops {
     // bellman's EvaluationDomain::{fft, ifft, coset_fft, icoset_fft} on 2^logn Fr elements (4 x u64 Montgomery), in place
     void (*fr_ntt_dev)(u64* d_data, int logn, bool inverse, bool coset, hipStream_t st);
@@ -52,6 +53,11 @@ struct Groth16Ops {
     // verify_sums_impl.hip.h: rho (n x 8 words) and inputs (n x n_pub x 8 canonical words) -> s_0 = sum rho_i, s_j = sum rho_i pub_ij mod r as
     // (n_pub + 1) x 8 canonical words, then n_pub + 1 words: per column the number of inputs that are not below r
     void (*verify_sums_dev)(const void* d_rho, const void* d_pub, uint64_t n, uint32_t n_pub, void* d_out, hipStream_t st);
+    // key_check_srs_impl.hip.h: n coefficients of 8 canonical words -> the 9 words a term the row sums read; and for one matrix and the weights
+    // rho (8 words each, 128 bits) the coefficient vectors iNTT(M rho) over the public wires below bound, over the others below bound, and
+    // (d_sum, may be null) over both: 2^logm x 8 canonical words each.  ms (may be null): += milliseconds of the row sums, of the transforms
+    void (*kc_coef_dev)(const u32* d_canon, u64 n, u32* d_fe, hipStream_t st);
+    void (*kc_coeffs_dev)(const KcMatrix& M, const u32* d_rho, u32 ni, u32 bound, int logm, u32* d_pub, u32* d_aux, u32* d_sum, double* ms, hipStream_t st);
 };
 // ---- pairing.hip: the steps of the optimal ate pairing and of Groth16 verification (pairing_impl.hip.h)
 struct PairingOps {
@@ -144,6 +150,10 @@ Groth16Key* groth16_keygen_from_srs(const char* curve, const void* r1cs, size_t 
 void groth16_params_contribute(const char* curve, const void* params, size_t len, const uint64_t* delta, void* out);
 std::string groth16_contribution_check(const char* curve, const void* old_params, size_t old_len, const void* new_params, size_t new_len,
                                        const uint8_t* seed, uint32_t max_findings);
+// groth16_key_check_srs (key_check_srs.hip.h): every query of the key and alpha, beta against the circuit's polynomials at the tau
+// of a powers-of-tau file -> the report as JSON text.  seed as for groth16_key_check.
+std::string groth16_key_check_srs(const char* curve, const void* r1cs, size_t r1cs_len, const void* params, size_t params_len, const Srs* srs,
+                                  const uint8_t* seed, uint32_t max_findings);
 // groth16_key_check (groth16.hip): the report as JSON text.  seed: 32 bytes for the random linear combination, for tests only -- null (the operating
 // system's randomness) anywhere else.
 std::string groth16_key_check(const char* curve, const void* r1cs, size_t r1cs_len, const void* params, size_t params_len, const char* vk_json,

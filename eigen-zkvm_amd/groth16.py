@@ -9,7 +9,7 @@ import secrets
 import numpy as np
 
 from . import DevArray, ZkError, _check, _np, _ptr, lib
-from .key_check_lines import POINT_CLASSES, contribution_check_line, key_check_line, key_check_skipped_line, srs_check_line  # noqa: F401
+from .key_check_lines import POINT_CLASSES, contribution_check_line, key_check_line, key_check_skipped_line, key_check_srs_line, srs_check_line  # noqa: F401
 
 _FR = {"BN128": 21888242871839275222246405745257275088548364400416034343698204186575808495617,
        "BLS12381": 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001}
@@ -245,6 +245,21 @@ def contribution_check(curve, old_params, new_params, seed=None, max_findings=16
     a = np.frombuffer(old_params, dtype=np.uint8); b = np.frombuffer(new_params, dtype=np.uint8)
     return _report(lib().zk_groth16_contribution_check(curve.encode(), a.ctypes.data, a.size, b.ctypes.data, b.size,
                                                        sd.ctypes.data if sd is not None else None, int(max_findings)))
+
+
+def key_check_srs(curve, r1cs_bytes, params_bytes, srs, seed=None, max_findings=16):
+    """zk_groth16_key_check_srs (include/zkgpu.h): is this key a key for this circuit over this powers-of-tau file?  Every query against the
+    circuit's polynomials at the file's tau by random linear combinations, and alpha_g1, beta_g1, beta_g2 word for word -> the report as a
+    dict.  What key_check cannot see; it does not repeat key_check's findings (a section with an invalid point or a wrong length is listed
+    under "skipped") nor Srs.check's.  srs: an Srs of the same curve.  seed: 32 bytes, tests only."""
+    if curve not in _FR:
+        raise ZkError('groth16: unknown curve "%s" (BN128 | BLS12381)' % curve)
+    if not isinstance(srs, Srs) or not srs._h:
+        raise ZkError("groth16 key check: srs is an open Srs")
+    sd = _seed(seed, "groth16 key check")
+    r = np.frombuffer(r1cs_bytes, dtype=np.uint8); p = np.frombuffer(params_bytes, dtype=np.uint8)
+    return _report(lib().zk_groth16_key_check_srs(curve.encode(), r.ctypes.data, r.size, p.ctypes.data, p.size, srs._h,
+                                                  sd.ctypes.data if sd is not None else None, int(max_findings)))
 
 
 def fq_convert(d_elems, curve="BN128", to_mont=True, stream=0):

@@ -44,3 +44,11 @@ def contribution_check_line(f):
     if k == "delta_mismatch":
         return "delta_mismatch: delta_g1 and delta_g2 of the new key hold different scalars"
     return "not_scaled: section %s of the new key is not the old one divided by the ratio of the two deltas" % f["section"]
+
+
+def key_check_srs_line(f):
+    """one finding of a groth16.key_check_srs report"""
+    if f["kind"] == "query_mismatch":
+        where = "index %d" % f["first_index"] + (" (wire %d)" % f["wire"] if "wire" in f else "")
+        return "query_mismatch: section %s is not the circuit's over this powers-of-tau file, first at %s" % (f["section"], where)
+    return "vk_mismatch: %s differs from the powers-of-tau file's" % f["field"]

@@ -489,7 +489,18 @@ int zk_groth16_keygen_free(zk_groth16_keygen_t* k);
  * 1 / delta.  delta: 4 x u64 canonical, non-zero, or NULL to draw it from the operating system; it is overwritten on the host and on the
  * device before the call returns.  zk_groth16_contribution_check -> a JSON report: sections that must be byte-equal ("changed", "size"),
  * the classes of the new delta, l and h points, delta_g1 against delta_g2 ("delta_mismatch"), and l, h scaled by exactly the ratio of the
- * two deltas ("not_scaled"). */
+ * two deltas ("not_scaled").
+ * zk_groth16_key_check_srs -> a JSON report (malloc'ed, zk_string_free): is this key a key for this circuit over this file?  What
+ * zk_groth16_key_check cannot see: every query (a, b_g1, b_g2, ic, l, h) against the circuit's polynomials at the file's tau, each by one
+ * random linear combination over the wires (weights of 128 bits; a wrong section survives with probability 2^-128) -- multi-scalar sums
+ * against the file's sections as they stand, no group transform; ic and l are paired against the key's own gamma_g2 and delta_g2, h against
+ * delta_g2, so any gamma and any chain of contributions to delta pass.  Findings: {"kind":"query_mismatch","section":..,"first_index":k,
+ * "wire":j} (the first entry of the section that is wrong, by bisection; no "wire" for h) and {"kind":"vk_mismatch","field":"alpha_g1" |
+ * "beta_g1" | "beta_g2"} (word for word against alphaTauG1[0], betaTauG1[0], betaG2).  A section of the wrong length or with a point
+ * that is off its curve, outside the subgroup or out of range is not compared and is listed under "skipped"; run zk_groth16_key_check for
+ * those findings and zk_srs_check for the file's.  Errors (NULL, zk_last_error): the readers' texts, a file of a power below the circuit's
+ * domain, a file opened for another curve.  seed: 32 bytes, tests only; NULL = the operating system's randomness.  With
+ * ZK_KEY_CHECK_TIMING set the report carries "timing_ms" {parse, row_sums, transforms, sums, pairings}. */
 typedef struct zk_srs zk_srs_t;
 zk_srs_t* zk_srs_open(const char* curve, const char* path);
 int zk_srs_info(const zk_srs_t* s, uint32_t* power, uint32_t* ceremony_power);
@@ -511,6 +522,8 @@ zk_groth16_keygen_t* zk_groth16_keygen_from_srs(const char* curve, const void* r
 int zk_groth16_params_contribute(const char* curve, const void* params, size_t len, const uint64_t* delta, void* out);
 char* zk_groth16_contribution_check(const char* curve, const void* old_params, size_t old_len, const void* new_params, size_t new_len, const uint8_t* seed,
                                     uint32_t max_findings);
+char* zk_groth16_key_check_srs(const char* curve, const void* r1cs, size_t r1cs_len, const void* params, size_t params_len, const zk_srs_t* srs, const uint8_t* seed,
+                                uint32_t max_findings);
 
 /* ---- pairings and Groth16 verification (`zkit groth16_verify`, zkit/src/main.rs:221-230, groth16/src/api.rs:302-341 ->
  * bellman's prepare_verifying_key + verify_proof) --------------------------------------------------------------------

@@ -13,7 +13,7 @@
   zkgpu_prove.py groth16_setup ... --ptau ceremony.ptau [--no-check-srs]
   zkgpu_prove.py groth16_contribute -c BN128 -p in.key -o out.key [-v verification_key.json] [--check]
   zkgpu_prove.py groth16_contribution_check -c BN128 --old a.key --new b.key
-  zkgpu_prove.py groth16_key_check -c BN128|BLS12381 --r1cs circuit.r1cs -p g16.key [-v verification_key.json] [--report out.json] [--max-findings N]
+  zkgpu_prove.py groth16_key_check -c BN128|BLS12381 --r1cs circuit.r1cs -p g16.key [-v verification_key.json] [--ptau pot.ptau [--no-check-srs]] [--report out.json] [--max-findings N]
   zkgpu_prove.py stark_verify -s starkStruct.json -p circuit.pil.json --o circuit.const --i zkin.json [--program FILE]
   zkgpu_prove.py compressor12_setup --r circuit.r1cs --c c12.const --p c12.pil --e c12.exec [--force_n_bits K] [--pil-json c12.pil.json]
   zkgpu_prove.py compressor12_exec --wtns witness.wtns --p c12.pil --e c12.exec --m c12.cm
@@ -37,8 +37,10 @@ starky/src/prove.rs:30-160, groth16/src/api.rs:144-205).  What differs, and why:
     before any setup.
   * groth16_key_check: the proving key against its circuit on the device (the reference reads keys unchecked): section lengths, every
     point on its curve, in the subgroup and finite, b_g1 / b_g2 and the beta / delta pairs tied by pairings, `-v` against the embedded
-    verification key.  One line per finding, exit 1 with findings.  It cannot check h, l, ic and a against the circuit's polynomials:
-    `groth16_prove --verify` is the functional test.  `groth16_prove --check-key` runs it first and stops before the witness is touched;
+    verification key.  One line per finding, exit 1 with findings.  Without `--ptau` it cannot check h, l, ic and a against the circuit's
+    polynomials: `groth16_prove --verify` is the functional test.  With `--ptau FILE` (snarkjs's `zkey verify`) it then checks the file
+    (`--no-check-srs` skips that) and every query of the key, alpha and beta against the circuit over that file; `--report` then holds
+    the three reports.  `groth16_prove --check-key` runs it first and stops before the witness is touched;
     `groth16_setup --check-key` runs it on the key it has just made.
   * wtns_check: `snarkjs wtns check` on the device (the reference has no counterpart): every constraint of the .r1cs as written, wire 0,
     and over GL every use of the compressor's custom gates; one line per finding, exit 0 when there is none and 1 otherwise; `--sym` takes
@@ -381,8 +383,48 @@ def _check_key(curve, r1cs_bytes, pk_bytes, vk_text=None, max_findings=16, repor
     return report
 
 
+def _key_check_ptau(a):
+    """groth16_key_check --ptau: the key's own check, the file's (unless --no-check-srs), then the key against circuit and file; every
+    finding a line, the three reports side by side under --report, exit 1 when any of them has a finding"""
+    import importlib
+    dev = importlib.import_module("eigen_zkvm_amd.groth16")
+    r1cs, pk = pathlib.Path(a.circuit_file).read_bytes(), pathlib.Path(a.pk_file).read_bytes()
+    reports = {"key_check": dev.key_check(a.curve_type, r1cs, pk, vk_json=pathlib.Path(a.vk_file).read_text() if a.vk_file else None,
+                                          max_findings=a.max_findings), "srs_check": None}
+    srs = dev.Srs(a.curve_type, a.ptau)
+    try:
+        if not a.no_check_srs:
+            reports["srs_check"] = srs.check(max_findings=a.max_findings)
+        reports["key_check_srs"] = dev.key_check_srs(a.curve_type, r1cs, pk, srs, max_findings=a.max_findings)
+    finally:
+        srs.free()
+    if a.report:
+        with open(a.report, "w") as f:
+            json.dump(reports, f, indent=1)
+    lines = {"key_check": dev.key_check_line, "srs_check": dev.srs_check_line, "key_check_srs": dev.key_check_srs_line}
+    bad = False
+    for name, line in lines.items():
+        rep = reports[name]
+        if rep is None:
+            continue
+        for f in rep["findings"]:
+            print(line(f))
+        for k in rep["skipped"]:
+            print(dev.key_check_skipped_line(k))
+        bad = bad or any(rep["counts"].values())
+    if bad:
+        raise SystemExit(1)
+    c = reports["key_check_srs"]["checked"]
+    print("zkgpu_prove: %s is a key of %s over %s%s (%d row sums, %d transforms, %d sums, %d pairs)"
+          % (a.pk_file, a.circuit_file, a.ptau, " (the file itself was not checked)" if a.no_check_srs else "", c["row_sums"], c["transforms"], c["sums"], c["pairs"]))
+
+
 def groth16_key_check(a):
+    if a.no_check_srs and not a.ptau:
+        raise SystemExit("zkgpu_prove: --no-check-srs says how to treat --ptau FILE and means nothing without it")
     _zk()
+    if a.ptau:
+        return _key_check_ptau(a)
     rep = _check_key(a.curve_type, pathlib.Path(a.circuit_file).read_bytes(), pathlib.Path(a.pk_file).read_bytes(),
                      pathlib.Path(a.vk_file).read_text() if a.vk_file else None, a.max_findings, a.report, out=sys.stdout)
     print("zkgpu_prove: %s is a well-formed key of %s (%d G1 and %d G2 points, %d pairs; h, l, ic, a are not checked against the circuit's polynomials)"
@@ -663,6 +705,8 @@ def build_parser():
     kc.add_argument("-v", dest="vk_file", default=None, help="a verification_key.json to compare with the key's embedded copy")
     kc.add_argument("--report", default=None, metavar="OUT.json", help="also write the whole report")
     kc.add_argument("--max-findings", dest="max_findings", type=int, default=16)
+    kc.add_argument("--ptau", default=None, metavar="FILE", help="also check the key against the circuit's polynomials over this powers-of-tau file: h, l, ic, a, b and alpha, beta")
+    kc.add_argument("--no-check-srs", dest="no_check_srs", action="store_true", help="with --ptau: do not check the file itself first")
     kc.set_defaults(fn=groth16_key_check)
     g = sub.add_parser("groth16_prove", help="Prove with groth16 (zkit/src/main.rs:199-217)")
     g.add_argument("-c", dest="curve_type", default="BN128")
