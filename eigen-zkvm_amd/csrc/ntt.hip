@@ -17,9 +17,12 @@
 //     each thread owns 16 points: radix-2^LOGA DIF in registers -> twiddle -> ONE LDS
 //     transpose -> radix-2^LOGB DIF in registers -> inter-pass twiddle -> store.
 //     A 2^24 transform is three such passes (8+8+8 bits), 2 LDS accesses / element / pass.
-//   * twiddles w_N^e come from a two-level table (4096 + N/4096 entries, L2 resident); the factor of
-//     output RA kb + ka is A_ka * S_kb, S shared by the workgroup through LDS: 2 multiplies per element, none dependent on another.
-//   * HBM-bound: 16 B / element / pass; bytes per transform = 16 * passes * N * n_pols.
+//   * twiddles w_N^e come from a two-level table (4096 + N/4096 entries, L2 resident); the
+//     per-thread chain over the 16 outputs needs 2 lookups + 1 multiply per element.
+//   * HBM-bound: 16 B / element / pass; bytes per transform = 16 * passes * N * n_pols.  A pass reads every data word once, so the
+//     sixteen data loads of a lane are non-temporal (the tables, which are re-read, and the stores are plain): 2^24 points 75.9 -> 82.3
+//     GElem/s.  Measured on the same kernel and not kept: non-temporal stores (slower), LDS sized per launch, an XCD-contiguous
+//     block -> tile order (slower), a raised wave priority up to the last data load (profiles/r10/ntt_stream.md).
 #include "zk_internal.h"
 #include "ntt_reg.hip.h"
 #include <map>
@@ -48,7 +51,7 @@ struct PassParams {
     u32 dshift;
     const u64* sc_lo;  // optional output scaling c * g^k (k = output row): g^i * c, i < 4096
     const u64* sc_hi;  // g^(4096 i)
-    u64 sc_cinv;       // 1 / c: sc_lo carries c, so a product of two look-ups carries it twice
+    u64 sc_step;       // g^(RA * s)
     u64 out_scale;     // plain constant scaling (1 = none), used when sc_lo == nullptr
     u64 inner;         // (N/R) * n_pols : contiguous words per transform-axis index j
     u64 valid_in;      // words of `in` that exist; beyond that the input is implicit zero (LDE)
@@ -74,62 +77,9 @@ __global__ __launch_bounds__(NTT_TILE / 16) void ntt_pass_kernel(const PassParam
     constexpr int ROW = RB * C + PAD;
     static_assert(LOGR >= 4 && LOGR <= 8 && LOGA <= 4 && LOGB <= 4, "tile shape");
     __shared__ u64 lds[RA * ROW];
-    __shared__ u64 sfac[RB * C];            // S[kb][c], see below
 
     const int t = threadIdx.x;
     const u64 u0 = (u64)blockIdx.x * C;
-
-    // lane u -> p = u / (s n_pols) and the remainder: a shift for one column; a 32-bit division when the matrix has fewer than 2^32 words
-    // per transform-axis index (every size in use); the 64-bit division otherwise -- uniform branches, the general case cost ~100
-    // instructions per lane.  A lane past the matrix counts as lane 0.
-    auto split = [&](u64 u, u64& p, u64& rem) {
-        const u64 uc = u < P.inner ? u : 0;
-        if (P.np == 1) { p = uc >> P.log_s; rem = uc & (((u64)1 << P.log_s) - 1); }
-        else if ((P.inner >> 32) == 0) { const u32 p32 = (u32)uc / (u32)P.s_np; p = p32; rem = (u32)uc - p32 * (u32)P.s_np; }
-        else
-        { p = uc / P.s_np; rem = uc - p * P.s_np; }
-    };
-    auto row_of = [&](u64 rem) { return P.np == 1 ? rem : (P.inner >> 32) == 0 ? (u64)((u32)rem / P.np) : rem / P.np; };
-    // Whole matrix under 4 GiB (uniform): a lane's stores are then a uniform base plus a 32-bit byte offset, one add per store where the
-    // general form multiplies and adds in 64 bits.  (The same for the data loads of sub-step A gained nothing: 40 against 37 instructions.)
-    const bool small = ((P.inner * R) >> 29) == 0;
-    // sub-step B identity of this thread
-    int cB, tb;
-    if (KMODE) { tb = t % TG; cB = t / TG; } else { cB = t % C; tb = t / C; }
-
-    // The factor of output kappa = RA kb + ka of a lane (inter-pass twiddle w_L^(p kappa), or the extension's c g^row) is A_ka * S_kb:
-    //   twiddle: A = w_N^((p ka) s),       S = w_N^((p RA kb) s)        scaling: A = c g^(ka s + row_q),  S = g^(RA kb s)
-    // S does not depend on ka: the RB x C values a workgroup needs are computed once, GA per thread, and shared through LDS; A is one look-up
-    // per ka of the thread.  Both are two-level look-ups (tab2) whose loads go out here, beside the data loads, and are multiplied
-    // before the barrier; after the butterflies a lane has 15 independent products A S where it used to walk a chain f *= fstep.
-    // Every exponent is below N <= 2^32 (p kappa < L, row < N): 32-bit arithmetic is exact.
-    const bool split_f = (P.has_tw && !P.tw_mid) || P.sc_lo;
-    u64 fa_hi[GB], fa_lo[GB], fs_hi[GA], fs_lo[GA], fa[GB];
-#pragma unroll
-    for (int g = 0; g < GB; ++g) fa_hi[g] = fa_lo[g] = fa[g] = 1;
-#pragma unroll
-    for (int m = 0; m < GA; ++m) fs_hi[m] = fs_lo[m] = 1;
-    auto issue_factor_loads = [&]() {
-        const u64* __restrict__ lo = P.sc_lo ? P.sc_lo : P.tw_lo;
-        const u64* __restrict__ hi = P.sc_lo ? P.sc_hi : P.tw_hi;
-        u64 p, rem;
-        split(u0 + cB, p, rem);
-        const u32 rq = P.sc_lo ? (u32)row_of(rem) : 0;
-#pragma unroll
-        for (int g = 0; g < GB; ++g) {
-            const u32 ka = tb + g * TG;
-            const u32 e = P.sc_lo ? (ka << P.log_s) + rq : ((u32)p * ka) << P.log_s;
-            fa_hi[g] = hi[e >> TW_LO_BITS]; fa_lo[g] = lo[e & (TW_LO - 1)];
-        }
-#pragma unroll
-        for (int m = 0; m < GA; ++m) {
-            const int i = t + m * (NTT_TILE / 16);
-            const u32 kb = i / C;
-            split(u0 + i % C, p, rem);
-            const u32 e = P.sc_lo ? (RA * kb) << P.log_s : ((u32)p * (RA * kb)) << P.log_s;
-            fs_hi[m] = hi[e >> TW_LO_BITS]; fs_lo[m] = lo[e & (TW_LO - 1)];
-        }
-    };
 
     {   // ---- sub-step A: RA-point transforms over ja (j = ja*RB + jb), twiddle w_R^(jb*ka)
         const int c = t % C, ta = t / C;
@@ -140,13 +90,14 @@ __global__ __launch_bounds__(NTT_TILE / 16) void ntt_pass_kernel(const PassParam
         // issued back to back.  Otherwise (ragged last tile, or the zero-padded half of an extension's first forward
         // pass) every load still goes out unconditionally -- of word 0 where there is nothing to read -- and is zeroed afterwards: a
         // branch per element would serialise the loads behind each other's latency.
+        // The data loads are non-temporal: a pass reads each word once, and lines that do not linger in L2 leave it to the tables.
         const bool full = u0 + C <= P.inner && (u64)(R - 1) * P.inner + u0 + C <= P.valid_in;
         const u64* __restrict__ base = P.in + (u64)(ta * GA) * P.inner + (live ? u : 0);
         if (full) {
 #pragma unroll
             for (int g = 0; g < GA; ++g)
 #pragma unroll
-                for (int ja = 0; ja < RA; ++ja) x[g][ja] = base[(u64)(ja * RB + g) * P.inner];
+                for (int ja = 0; ja < RA; ++ja) x[g][ja] = __builtin_nontemporal_load(&base[(u64)(ja * RB + g) * P.inner]);
         } else {
 #pragma unroll
             for (int g = 0; g < GA; ++g)
@@ -154,12 +105,10 @@ __global__ __launch_bounds__(NTT_TILE / 16) void ntt_pass_kernel(const PassParam
                 for (int ja = 0; ja < RA; ++ja) {
                     const u64 off = (u64)(ja * RB + g) * P.inner;
                     const bool ok = live && (u64)(ta * GA) * P.inner + off + u < P.valid_in;
-                    const u64 v = *(ok ? base + off : P.in);       // word 0 always exists
+                    const u64 v = __builtin_nontemporal_load(ok ? base + off : P.in);      // word 0 always exists
                     x[g][ja] = ok ? v : 0;
                 }
         }
-        // (a uniform run-time branch, for the reason given at the tw_mid loads below)
-        if (split_f) issue_factor_loads();
 #pragma unroll
         for (int g = 0; g < GA; ++g) ntt_reg<LOGA, INV>(x[g]);
         // Passes of <= 6 bits: w_R is a power of two (w_64 = 2^39, ntt_reg.hip.h), so the twiddle w_R^(jb ka) between the two halves is a
@@ -198,19 +147,10 @@ __global__ __launch_bounds__(NTT_TILE / 16) void ntt_pass_kernel(const PassParam
             }
         }
     }
-    if (split_f) {
-#pragma unroll
-        for (int m = 0; m < GA; ++m) {
-            u64 sv = gl::mul_tw_nc(fs_hi[m], fs_lo[m]);
-            if (P.sc_lo) sv = gl::mul_tw_nc(sv, P.sc_cinv);
-            sfac[t + m * (NTT_TILE / 16)] = sv;
-        }
-#pragma unroll
-        for (int g = 0; g < GB; ++g) fa[g] = gl::mul_tw_nc(fa_hi[g], fa_lo[g]);
-    }
     __syncthreads();
     {   // ---- sub-step B: RB-point transforms over jb -> kappa = RA*kb + ka
-        const int c = cB;
+        int c, tb;
+        if (KMODE) { tb = t % TG; c = t / TG; } else { c = t % C; tb = t / C; }
         const u64 u = u0 + c;
         u64 y[GB][RB];
 #pragma unroll
@@ -219,8 +159,14 @@ __global__ __launch_bounds__(NTT_TILE / 16) void ntt_pass_kernel(const PassParam
 #pragma unroll
             for (int jb = 0; jb < RB; ++jb) y[g][jb] = lds[ka * ROW + jb * C + c];
         }
+        const u64 uc = u < P.inner ? u : 0;
+        // p = uc / (s n_pols): a shift for one column; a 32-bit division when the matrix has fewer than 2^32 words per transform-axis
+        // index (every size in use); the 64-bit division otherwise -- uniform branches, the general case cost ~100 instructions per lane
         u64 p, rem;
-        split(u, p, rem);
+        if (P.np == 1) { p = uc >> P.log_s; rem = uc & (((u64)1 << P.log_s) - 1); }
+        else if ((P.inner >> 32) == 0) { const u32 p32 = (u32)uc / (u32)P.s_np; p = p32; rem = (u32)uc - p32 * (u32)P.s_np; }
+        else
+        { p = uc / P.s_np; rem = uc - p * P.s_np; }
         u64 tw[GB][RB];
         if (P.tw_mid) {  // L <= 2^16: every twiddle w_L^(p*kappa) is one load from the 512 KB table (L2), no chain;
                          // issued here so that the radix-2^LOGB butterflies below hide the latency
@@ -240,44 +186,54 @@ __global__ __launch_bounds__(NTT_TILE / 16) void ntt_pass_kernel(const PassParam
         for (int g = 0; g < GB; ++g) ntt_reg<LOGB, INV>(y[g]);
         if (u >= P.inner) return;
 
-        // output kappa = RA kb + ka of the lane lies (RA kb + ka) s_np words past the lane's base: linear in kb
+        // output kappa = RA kb + ka of the lane lies (RA kb + ka) s_np words past the lane's base: linear in kb.  Whole matrix under 4 GiB
+        // (uniform): a lane's stores are then a uniform base plus a 32-bit byte offset, one add per store where the general form
+        // multiplies and adds in 64 bits.  (The same for the data loads of sub-step A gained nothing: 40 against 37 instructions.)
         auto finish = [&](auto small_c) {
             constexpr bool SMALL = decltype(small_c)::value;
             u64* __restrict__ outp = P.out + p * R * P.s_np + rem;
             const u64 kstride = P.s_np;                    // words between the outputs kappa and kappa + 1 of a lane
             const u32 b0 = ((u32)p * R * (u32)P.s_np + (u32)rem) * 8, bstep = RA * (u32)P.s_np * 8;
-            auto put = [&](int g, int kb, u64 v) {
-                const u32 ka = tb + g * TG;
+            auto put = [&](u32 ka, int kb, u64 v) {
                 if constexpr (SMALL) *(u64*)((char*)P.out + (u32)(b0 + ka * (u32)P.s_np * 8 + kb * bstep)) = v;
                 else outp[(u64)(RA * kb + ka) * kstride] = v;
             };
+            const u64 row_q = !P.sc_lo ? 0 : P.np == 1 ? rem : (P.inner >> 32) == 0 ? (u64)((u32)rem / P.np) : rem / P.np;  // output row = kappa*s + row_q (last pass: p == 0)
             if (P.tw_mid) {
 #pragma unroll
-                for (int g = 0; g < GB; ++g)
-#pragma unroll
-                    for (int kb = 0; kb < RB; ++kb) put(g, kb, gl::mul_tw(y[g][bitrev_c(kb, LOGB)], tw[g][kb]));
-            } else if (split_f) {
-#pragma unroll
-                for (int g = 0; g < GB; ++g)
+                for (int g = 0; g < GB; ++g) {
+                    const int ka = tb + g * TG;
 #pragma unroll
                     for (int kb = 0; kb < RB; ++kb) {
-                        const u64 f = kb == 0 ? fa[g] : gl::mul_tw_nc(fa[g], sfac[kb * C + c]);   // S_0 = 1
-                        put(g, kb, gl::mul_tw(y[g][bitrev_c(kb, LOGB)], f));                      // canonical: it is stored
+                        u64 v = y[g][bitrev_c(kb, LOGB)];
+                        v = gl::mul_tw(v, tw[g][kb]);
+                        put(ka, kb, v);
                     }
-            } else if (P.out_scale != 1) {
-                // last pass of a plain transform: no table factor (the inverse's 1 / N went in with sub-step A)
+                }
+                return;
+            }
+            u64 tw_step = 1;
+            if (P.has_tw) tw_step = tab2(P.tw_lo, P.tw_hi, (p * RA) << P.log_s);
 #pragma unroll
-                for (int g = 0; g < GB; ++g)
+            for (int g = 0; g < GB; ++g) {
+                const int ka = tb + g * TG;
+                u64 f = P.out_scale;
+                if (P.has_tw) f = tab2(P.tw_lo, P.tw_hi, (p * ka) << P.log_s);
+                if (P.sc_lo) f = tab2(P.sc_lo, P.sc_hi, ((u64)ka << P.log_s) + row_q);
+                const bool scaled = P.has_tw || P.sc_lo || P.out_scale != 1;
+                const u64 fstep = P.sc_lo ? P.sc_step : tw_step;
 #pragma unroll
-                    for (int kb = 0; kb < RB; ++kb) put(g, kb, gl::mul_tw(y[g][bitrev_c(kb, LOGB)], P.out_scale));
-            } else {
-#pragma unroll
-                for (int g = 0; g < GB; ++g)
-#pragma unroll
-                    for (int kb = 0; kb < RB; ++kb) put(g, kb, y[g][bitrev_c(kb, LOGB)]);
+                for (int kb = 0; kb < RB; ++kb) {
+                    u64 v = y[g][bitrev_c(kb, LOGB)];
+                    if (scaled) {
+                        v = gl::mul_tw(v, f);                               // canonical: it is stored
+                        if (kb + 1 < RB) f = gl::mul_tw_nc(f, fstep);       // the running factor only ever feeds products
+                    }
+                    put(ka, kb, v);
+                }
             }
         };
-        if (small) finish(std::true_type{});
+        if (((P.inner * R) >> 29) == 0) finish(std::true_type{});
         else finish(std::false_type{});
     }
 }
@@ -428,7 +384,8 @@ void run_transform(const u64* in, u64* a, u64* b, /* ping-pong, result must land
         P.w256 = T.w256.u(); P.tw_lo = T.lo.u(); P.tw_hi = T.hi.u();
         P.sc_lo = (last && sc.on) ? S->lo.u() : nullptr;
         P.sc_hi = (last && sc.on) ? S->hi.u() : nullptr;
-        P.sc_cinv = (last && sc.on) ? gl::hinv(sc.cst) : 1;
+        const int loga = (logr + 1) / 2;
+        P.sc_step = (last && sc.on) ? gl::hpow(sc.g, (1ull << loga) << log_s) : 1;
         P.out_scale = 1; P.pre_scale = 1;
         if (last && !sc.on && out_scale != 1) {
             // the only constant scaling in use is the inverse transform's 1/N (ntt_dev)
