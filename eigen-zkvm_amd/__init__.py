@@ -60,11 +60,13 @@ EXPORTS = [
     "zk_pil_check_new", "zk_pil_check_listing", "zk_pil_check_run", "zk_pil_check_run_dev", "zk_pil_check_free",
     "zk_r1cs_check_new", "zk_r1cs_check_info", "zk_r1cs_check_run", "zk_r1cs_check_run_dev", "zk_r1cs_check_free",
     "zk_srs_open", "zk_srs_info", "zk_srs_check", "zk_srs_free", "zk_groth16_keygen_from_srs", "zk_groth16_params_contribute", "zk_groth16_contribution_check",
-    "zk_groth16_key_check_srs",
+    "zk_groth16_key_check_srs", "zk_srs_new", "zk_srs_contribute", "zk_srs_verify", "zk_srs_transcript_count",
+    "zk_groth16_key_transcript_size", "zk_groth16_params_contribute_pok", "zk_groth16_key_transcript_check",
     "zk_g1_bn254_ntt_dev", "zk_g2_bn254_ntt_dev", "zk_g1_bls12_381_ntt_dev", "zk_g2_bls12_381_ntt_dev",
     "zk_g1_bn254_mul_scalar_dev", "zk_g2_bn254_mul_scalar_dev", "zk_g1_bls12_381_mul_scalar_dev", "zk_g2_bls12_381_mul_scalar_dev",
     "zk_groth16_key_check", "zk_points_check_bn254", "zk_points_check_bn254_dev", "zk_points_check_bls12_381", "zk_points_check_bls12_381_dev",
     "zk_g1_bn254_mul_scalars_dev", "zk_g2_bn254_mul_scalars_dev", "zk_g1_bls12_381_mul_scalars_dev", "zk_g2_bls12_381_mul_scalars_dev",
+    "zk_g1_bn254_mul_scalars_glv_dev", "zk_g1_bls12_381_mul_scalars_glv_dev",
     "zk_pairing_product_bn254", "zk_pairing_product_bn254_dev", "zk_pairing_product_bls12_381", "zk_pairing_product_bls12_381_dev",
     "zk_groth16_verify_aggregate", "zk_groth16_verify_aggregate_dev", "zk_groth16_verify_aggregate_timing", "zk_groth16_proof_words",
 ]
@@ -336,6 +338,13 @@ def _load():
         "zk_srs_info": (C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
         "zk_srs_check": (vp, [vp, vp, C.c_uint32]),
         "zk_srs_free": (C.c_int, [vp]),
+        "zk_srs_new": (C.c_int, [C.c_char_p, C.c_uint32, C.c_char_p]),
+        "zk_srs_contribute": (C.c_int, [vp, C.c_char_p, vp, vp, C.c_uint32]),
+        "zk_srs_verify": (vp, [vp, vp, C.c_uint32]),
+        "zk_srs_transcript_count": (C.c_int, [vp, C.POINTER(C.c_int64)]),
+        "zk_groth16_key_transcript_size": (C.c_size_t, [C.c_char_p, C.c_uint32]),
+        "zk_groth16_params_contribute_pok": (C.c_int, [C.c_char_p, vp, C.c_size_t, vp, vp, C.c_size_t, vp, vp]),
+        "zk_groth16_key_transcript_check": (vp, [C.c_char_p, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_uint32]),
         "zk_groth16_keygen_from_srs": (vp, [C.c_char_p, vp, C.c_size_t, vp]),
         "zk_groth16_params_contribute": (C.c_int, [C.c_char_p, vp, C.c_size_t, vp, vp]),
         "zk_groth16_contribution_check": (vp, [C.c_char_p, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_uint32]),
@@ -357,6 +366,8 @@ def _load():
         "zk_g2_bn254_mul_scalars_dev": (C.c_int, [vp, C.c_uint64, vp, vp, vp]),
         "zk_g1_bls12_381_mul_scalars_dev": (C.c_int, [vp, C.c_uint64, vp, vp, vp]),
         "zk_g2_bls12_381_mul_scalars_dev": (C.c_int, [vp, C.c_uint64, vp, vp, vp]),
+        "zk_g1_bn254_mul_scalars_glv_dev": (C.c_int, [vp, C.c_uint64, vp, vp, vp]),
+        "zk_g1_bls12_381_mul_scalars_glv_dev": (C.c_int, [vp, C.c_uint64, vp, vp, vp]),
         "zk_pairing_product_bn254": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_int]),
         "zk_pairing_product_bn254_dev": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_int, vp]),
         "zk_pairing_product_bls12_381": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_int]),

@@ -719,6 +719,20 @@ char* zk_srs_check(const zk_srs_t* s, const uint8_t* seed, uint32_t max_findings
     if (guard([&] { ZK_REQUIRE(s, "ptau: null handle"); out = dup_report(srs_check(*s, seed, max_findings)); }) != 0) return nullptr;
     return out;
 }
+int zk_srs_new(const char* curve, uint32_t power, const char* path) {
+    return guard([&] { srs_new(curve, power, path); });
+}
+int zk_srs_contribute(const zk_srs_t* s, const char* out_path, const uint64_t* secrets, const uint8_t* beacon_seed, uint32_t beacon_iter_log) {
+    return guard([&] { ZK_REQUIRE(s, "ptau: null handle"); srs_contribute(*s, out_path, secrets, beacon_seed, beacon_iter_log); });
+}
+char* zk_srs_verify(const zk_srs_t* s, const uint8_t* seed, uint32_t max_findings) {
+    char* out = nullptr;
+    if (guard([&] { ZK_REQUIRE(s, "ptau: null handle"); out = dup_report(srs_verify(*s, seed, max_findings)); }) != 0) return nullptr;
+    return out;
+}
+int zk_srs_transcript_count(const zk_srs_t* s, int64_t* count) {
+    return guard([&] { ZK_REQUIRE(s && count, "ptau: null argument"); *count = srs_transcript_count(*s); });
+}
 zk_groth16_keygen_t* zk_groth16_keygen_from_srs(const char* curve, const void* r1cs, size_t r1cs_len, const zk_srs_t* srs) {
     zk_groth16_keygen_t* out = nullptr;
     if (guard([&] { out = groth16_keygen_from_srs(curve, r1cs, r1cs_len, srs); }) != 0) return nullptr;
@@ -731,6 +745,21 @@ char* zk_groth16_contribution_check(const char* curve, const void* old_params, s
                                     uint32_t max_findings) {
     char* out = nullptr;
     if (guard([&] { out = dup_report(groth16_contribution_check(curve, old_params, old_len, new_params, new_len, seed, max_findings)); }) != 0) return nullptr;
+    return out;
+}
+size_t zk_groth16_key_transcript_size(const char* curve, uint32_t count) {
+    size_t out = 0;
+    if (guard([&] { out = groth16_key_transcript_size(curve, count); }) != 0) return 0;
+    return out;
+}
+int zk_groth16_params_contribute_pok(const char* curve, const void* params, size_t len, const uint64_t* delta, const void* transcript, size_t t_len, void* out_params,
+                                     void* out_transcript) {
+    return guard([&] { groth16_params_contribute_pok(curve, params, len, delta, transcript, t_len, out_params, out_transcript); });
+}
+char* zk_groth16_key_transcript_check(const char* curve, const void* initial, size_t initial_len, const void* final_key, size_t final_len, const void* transcript,
+                                      size_t t_len, const uint8_t* seed, uint32_t max_findings) {
+    char* out = nullptr;
+    if (guard([&] { out = dup_report(groth16_key_transcript_check(curve, initial, initial_len, final_key, final_len, transcript, t_len, seed, max_findings)); }) != 0) return nullptr;
     return out;
 }
 char* zk_groth16_key_check_srs(const char* curve, const void* r1cs, size_t r1cs_len, const void* params, size_t params_len, const zk_srs_t* srs, const uint8_t* seed,
@@ -754,6 +783,14 @@ static int mul_scalars_device(CurveId id, Group g, const void* d_points, uint64_
         curve(id).ec().g[g].mul_scalars(d_points, curve(id).point_words(g), n, (const u32*)d_k, d_out, on_stream((hipStream_t)stream));
     });
 }
+static int mul_scalars_glv_device(CurveId id, const void* d_points, uint64_t n, const uint64_t* d_k, void* d_out, void* stream) {
+    return guard([&] {
+        ZK_REQUIRE(n == 0 || (d_points && d_k && d_out), "mul_scalars_glv: null argument");
+        curve(id).ec().g[G1].mul_scalars_glv(d_points, curve(id).point_words(G1), n, (const u32*)d_k, d_out, on_stream((hipStream_t)stream));
+    });
+}
+int zk_g1_bn254_mul_scalars_glv_dev(const void* d_points, uint64_t n, const uint64_t* d_k, void* d_out, void* stream) { return mul_scalars_glv_device(CURVE_BN254, d_points, n, d_k, d_out, stream); }
+int zk_g1_bls12_381_mul_scalars_glv_dev(const void* d_points, uint64_t n, const uint64_t* d_k, void* d_out, void* stream) { return mul_scalars_glv_device(CURVE_BLS12_381, d_points, n, d_k, d_out, stream); }
 #define ZK_EC_API(GN, NAME, ID, G)                                                                                                            \
     int zk_##GN##_##NAME##_ntt_dev(void* d_points, uint32_t log_n, int inverse, void* stream) { return group_ntt_device(ID, G, d_points, log_n, inverse, stream); } \
     int zk_##GN##_##NAME##_mul_scalar_dev(const void* d_points, uint64_t n, const uint64_t* d_k, void* d_out, void* stream) { return mul_scalar_device(ID, G, d_points, n, d_k, d_out, stream); } \

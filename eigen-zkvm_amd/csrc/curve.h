@@ -35,6 +35,7 @@ struct GroupOps {
     size_t (*fixed_table_bytes)(uint64_t n);
     void (*fixed_prepare_dev)(const void* d_bases, uint64_t n, void* d_table, hipStream_t st);
     void (*fixed_dev)(const void* d_table, uint64_t table_n, uint64_t off, const void* d_scalars, uint64_t n, void* d_out, hipStream_t st);
+    void (*generator_words)(u32* out);                                     // host: the generator as one affine point in the layout of the sums
 };
 struct MsmOps {
     GroupOps g[2];                                                          // by Group
@@ -58,6 +59,8 @@ struct Groth16Ops {
     // (d_sum, may be null) over both: 2^logm x 8 canonical words each.  ms (may be null): += milliseconds of the row sums, of the transforms
     void (*kc_coef_dev)(const u32* d_canon, u64 n, u32* d_fe, hipStream_t st);
     void (*kc_coeffs_dev)(const KcMatrix& M, const u32* d_rho, u32 ni, u32 bound, int logm, u32* d_pub, u32* d_aux, u32* d_sum, double* ms, hipStream_t st);
+    // ceremony_impl.hip.h: out_i = s t^(i0 + i), i < n, as 8 canonical words each; d_tab: 30 x 8 words Montgomery (fr_host.h): s, then t^(2^j), j < 29
+    void (*powers_dev)(const u32* d_tab, u64 i0, u64 n, u32* d_out, hipStream_t st);
 };
 // ---- pairing.hip: the steps of the optimal ate pairing and of Groth16 verification (pairing_impl.hip.h)
 struct PairingOps {
@@ -87,6 +90,8 @@ struct EcGroupOps {
     void (*mul_scalar)(const void* d_points, u64 n, const u32* d_k, void* d_out, hipStream_t st);          // out_i = [k] P_i, one k
     // out_i = [k_i] P_i, one k per point; the points stride_words apart (a proof's A), the results packed; a walk from each scalar's top set bit
     void (*mul_scalars)(const void* d_points, u64 stride_words, u64 n, const u32* d_k, void* d_out, hipStream_t st);
+    // the same through the endomorphism split of G1 (one joint walk over two 128-bit halves; points of the subgroup of order r); null for G2
+    void (*mul_scalars_glv)(const void* d_points, u64 stride_words, u64 n, const u32* d_k, void* d_out, hipStream_t st);
     void (*diff)(const void* d_a, const void* d_b, u64 n, void* d_out, hipStream_t st);                    // out_i = a_i - b_i
     // out_j = sum over the sets and the terms of column j of coef * base[row], j < n_wires; r: the scalar modulus
     void (*column_sums)(const EcCsc* sets, int n_sets, const u32* r, u32 n_wires, void* d_out, hipStream_t st);
@@ -146,10 +151,23 @@ void group_ntt_dev(const Curve& cv, Group g, void* d_points, int logn, bool inve
 Srs* srs_open(const char* curve, const char* path);
 std::string srs_check(const Srs& srs, const uint8_t* seed, uint32_t max_findings);
 Groth16Key* groth16_keygen_from_srs(const char* curve, const void* r1cs, size_t r1cs_len, const Srs* srs);
+// A powers-of-tau ceremony (groth16_ceremony.hip.h).  srs_new and srs_transcript_count are host only.
+void srs_new(const char* curve, uint32_t power, const char* path);
+// secrets: 3 x 4 canonical words (tau, alpha, beta factors), or null to draw them; beacon_seed: 32 bytes for a beacon (then no secrets), or null
+void srs_contribute(const Srs& srs, const char* out_path, const uint64_t* secrets, const uint8_t* beacon_seed, uint32_t beacon_iter_log);
+std::string srs_verify(const Srs& srs, const uint8_t* seed, uint32_t max_findings);
+int64_t srs_transcript_count(const Srs& srs);                              // records of the file's transcript, -1 without one
 // delta: 4 canonical words, non-zero and below r, or null to draw it from the OS; out: len bytes
 void groth16_params_contribute(const char* curve, const void* params, size_t len, const uint64_t* delta, void* out);
 std::string groth16_contribution_check(const char* curve, const void* old_params, size_t old_len, const void* new_params, size_t new_len,
                                        const uint8_t* seed, uint32_t max_findings);
+// contributions with proofs of knowledge and their transcript (groth16_ceremony.hip.h): groth16_params_contribute plus one
+// record appended to the transcript (t_len = 0 starts one at this key); out_transcript: groth16_key_transcript_size(count + 1) bytes
+size_t groth16_key_transcript_size(const char* curve, uint32_t count);
+void groth16_params_contribute_pok(const char* curve, const void* params, size_t len, const uint64_t* delta, const void* transcript, size_t t_len,
+                                   void* out_params, void* out_transcript);
+std::string groth16_key_transcript_check(const char* curve, const void* initial, size_t initial_len, const void* final_key, size_t final_len,
+                                         const void* transcript, size_t t_len, const uint8_t* seed, uint32_t max_findings);
 // groth16_key_check_srs (key_check_srs.hip.h): every query of the key and alpha, beta against the circuit's polynomials at the tau
 // of a powers-of-tau file -> the report as JSON text.  seed as for groth16_key_check.
 std::string groth16_key_check_srs(const char* curve, const void* r1cs, size_t r1cs_len, const void* params, size_t params_len, const Srs* srs,

@@ -11,10 +11,12 @@
 namespace zk {
 namespace bn254 {
 namespace ecntt_g1 {
+#define GLV_CURVE_BN254             // G1 has the endomorphism split (glv_split.hip.h): the per-point product through it
 namespace {
 #include "ecpt_impl.hip.h"
 #include "ecntt_impl.hip.h"
 }
+#undef GLV_CURVE_BN254
 }  // namespace ecntt_g1
 namespace ecntt_g2 {
 #define MSM_G2_INLINE_CF
@@ -32,10 +34,12 @@ namespace {
 }  // namespace bn254
 namespace bls12_381 {
 namespace ecntt_g1 {
+#define GLV_CURVE_BLS12_381
 namespace {
 #include "ecpt_impl.hip.h"
 #include "ecntt_impl.hip.h"
 }
+#undef GLV_CURVE_BLS12_381
 }  // namespace ecntt_g1
 namespace ecntt_g2 {
 #define MSM_G2
@@ -51,7 +55,7 @@ namespace {
 }  // namespace bls12_381
 
 // the table's slice of this unit (curve.h)
-#define ZK_EC_OPS(NS) {NS::ntt_run, NS::mul_scalar_run, NS::mul_scalars_run, NS::diff_run, NS::column_sums_run}
+#define ZK_EC_OPS(NS) {NS::ntt_run, NS::mul_scalar_run, NS::mul_scalars_run, NS::mul_scalars_glv_run, NS::diff_run, NS::column_sums_run}
 const EcOps& ec_ops(CurveId id) {
     static const EcOps OPS[2] = {{{ZK_EC_OPS(bn254::ecntt_g1), ZK_EC_OPS(bn254::ecntt_g2)}}, {{ZK_EC_OPS(bls12_381::ecntt_g1), ZK_EC_OPS(bls12_381::ecntt_g2)}}};
     return OPS[id];

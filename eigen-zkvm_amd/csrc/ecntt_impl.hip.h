@@ -18,6 +18,10 @@
 // The point formulas are called through two real functions, so a kernel holds one copy of each (code size: see msm.hip).
 // pt_add is complete -- equal operands go to the doubling, opposite ones to infinity -- which a constant column of a file needs.
 constexpr int EW = 4 * CW_INT, AW = 2 * CW_STD;
+#if !defined(MSM_G2) && (defined(GLV_CURVE_BN254) || defined(GLV_CURVE_BLS12_381))
+#define ECN_GLV 1
+#include "glv_split.hip.h"
+#endif
 
 __device__ __forceinline__ xyzz ecn_ld(const u32* __restrict__ p) {
     xyzz r;
@@ -93,6 +97,62 @@ __global__ __launch_bounds__(64) void ecn_mul_scalars_kernel(const u32* __restri
     if (i >= n) return;
     ecn_st(work + i * EW, ecn_mul(ecn_load_ext(pts + i * stride), k + i * 8));
 }
+#ifdef ECN_GLV
+// work[i] = [k_i] pts[i] through the curve's endomorphism (G1 only; the points must lie in the subgroup of order r, where phi = [lambda]).
+// k = s1 |k1| + s2 |k2| lambda with both halves below 2^128 (glv_split), so [k]P = [|k1|]P1 + [|k2|]P2 with P1 = s1 P and
+// P2 = s2 phi(P) = (beta x, s2 y): one joint (Straus) walk over the two halves from the higher top bit down -- a doubling per step and
+// the addition of P1, P2 or P1 + P2 as the two bits say.  The addend is picked by masks from named values (a branch per table entry would
+// make a wave run up to three additions per step; an array indexed by the digit would live in scratch), and the one addition of a step is
+// skipped by the lanes whose digit is 00.  The halves are kept as two 128-bit shift registers, top bit first, for the same reason.
+// Point operations a wave executes per product, counted from the code below: 1 addition for P1 + P2, then per step 1 doubling and 1
+// addition, and the steps are as many as the longest half of the wave has bits: at most 128 doublings + 129 additions (with 64 lanes a
+// step in which every digit is 00 does not happen: 4^-64).  The bit walk of ecn_mul_scalars_kernel executes 253 doublings and, under
+// divergence, 253 additions for scalars of full width.  The affine answers are the same bytes: the way out is ecn_store_kernel's.
+__device__ __forceinline__ cf ecn_pick(u32 m1, u32 m2, u32 m3, const cf& a1, const cf& a2, const cf& a3) {
+    cf r;
+#pragma unroll
+    for (int i = 0; i < NR; ++i) r.l[i] = (a1.l[i] & m1) | (a2.l[i] & m2) | (a3.l[i] & m3);
+    return r;
+}
+__global__ __launch_bounds__(64) void ecn_mul_scalars_glv_kernel(const u32* __restrict__ pts, u64 stride, u64 n, const u32* __restrict__ k, u32* __restrict__ work) {
+    const u64 i = blockIdx.x * 64ull + threadIdx.x;
+    if (i >= n) return;
+    const xyzz b = ecn_load_ext(pts + i * stride);
+    u32 kk[8], k1[8], k2[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) kk[j] = k[i * 8 + j];
+    bool n1, n2;
+    glv_split(kk, k1, k2, n1, n2);
+    unsigned __int128 h1 = ((unsigned __int128)(((u64)k1[3] << 32) | k1[2]) << 64) | (((u64)k1[1] << 32) | k1[0]);
+    unsigned __int128 h2 = ((unsigned __int128)(((u64)k2[3] << 32) | k2[2]) << 64) | (((u64)k2[1] << 32) | k2[0]);
+    const u64 hi = (u64)((h1 | h2) >> 64), lo = (u64)(h1 | h2);
+    if (!(hi | lo) || pt_is_inf(b)) { ecn_st(work + i * EW, pt_inf()); return; }
+    const int steps = hi ? 128 - __clzll((long long)hi) : 64 - __clzll((long long)lo);
+    h1 <<= 128 - steps; h2 <<= 128 - steps;                            // the top bit of the longer half at bit 127
+    // the table: P1 = (x, y1), P2 = (beta x, y2), both with ZZ = ZZZ = 1, and P3 = P1 + P2
+    const cf ny = cf_sub<4>(cf_zero(), b.Y), one = cf_one();
+    xyzz p1 = b, p2 = b;
+    if (n1) p1.Y = ny;
+    if (n2) p2.Y = ny;
+    p2.X = cf_mul(b.X, glv_beta());
+    const xyzz p3 = ecn_add(p1, p2);
+    xyzz acc = pt_inf();
+    for (int s = 0; s < steps; ++s) {
+        acc = ecn_dbl(acc);                                             // infinity returns at once
+        const u32 d = (u32)(h1 >> 127) | ((u32)(h2 >> 127) << 1);
+        h1 <<= 1; h2 <<= 1;
+        if (d) {
+            u32 m1 = d == 1 ? ~0u : 0u, m2 = d == 2 ? ~0u : 0u, m3 = d == 3 ? ~0u : 0u;
+            asm volatile("" : "+v"(m1), "+v"(m2), "+v"(m3));            // masks, not `?:` between structures (ecpt_impl.hip.h pick_fe)
+            xyzz q;
+            q.X = ecn_pick(m1, m2, m3, p1.X, p2.X, p3.X); q.Y = ecn_pick(m1, m2, m3, p1.Y, p2.Y, p3.Y);
+            q.ZZ = ecn_pick(m1, m2, m3, one, one, p3.ZZ); q.ZZZ = ecn_pick(m1, m2, m3, one, one, p3.ZZZ);
+            acc = ecn_add(acc, q);
+        }
+    }
+    ecn_st(work + i * EW, acc);
+}
+#endif
 // work[i] = a[i] - b[i]
 __global__ __launch_bounds__(64) void ecn_diff_kernel(const u32* __restrict__ a, const u32* __restrict__ b, u64 n, u32* __restrict__ work) {
     const u64 i = blockIdx.x * 64ull + threadIdx.x;
@@ -223,6 +283,18 @@ void mul_scalars_run(const void* d_pts, u64 stride_words, u64 n, const u32* d_k,
     ZK_HIP(hipGetLastError());
     ecn_store(work, n, d_out, st);
 }
+#ifdef ECN_GLV
+void mul_scalars_glv_run(const void* d_pts, u64 stride_words, u64 n, const u32* d_k, void* d_out, hipStream_t st) {
+    if (n == 0) return;
+    DevBuf work; work.reserve(n * EW * 4);
+    hipLaunchKernelGGL(ecn_mul_scalars_glv_kernel, dim3(ecn_blocks(n, 64)), dim3(64), 0, st, (const u32*)d_pts, stride_words, n, d_k, (u32*)work.p);
+    ZK_HIP(hipGetLastError());
+    ecn_store(work, n, d_out, st);
+}
+#undef ECN_GLV
+#else
+constexpr auto mul_scalars_glv_run = nullptr;                       // no endomorphism in this group
+#endif
 void diff_run(const void* d_a, const void* d_b, u64 n, void* d_out, hipStream_t st) {
     if (n == 0) return;
     DevBuf work; work.reserve(n * EW * 4);

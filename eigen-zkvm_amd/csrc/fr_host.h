@@ -1,5 +1,6 @@
 // The scalar field of a curve on the host: 4 x 64-bit Montgomery arithmetic for the handful of values that are cheaper to make here than
-// to launch a kernel for -- the twiddles of a group transform (ecntt.hip) and the inverse of a contribution's delta (groth16.hip).
+// to launch a kernel for -- the twiddles of a group transform (ecntt.hip), the inverse of a contribution's delta and the responses of
+// a ceremony's proofs of knowledge (groth16.hip).
 // Not constant time, so secrets pass through it only where the caller wipes them (FrHost::wipe).
 #pragma once
 #include "curve.h"
@@ -34,6 +35,13 @@ struct FrHost {
         for (int i = 3; i > 0; --i) a[i] = (a[i] << 1) | (a[i - 1] >> 63);
         a[0] <<= 1;
         if (geq_p(a)) sub_p(a);
+    }
+    // out = a + b mod r for a, b < r (either form); out may alias an operand
+    void add(const u64* a, const u64* b, u64* out) const {
+        u64 t[4]; u128 c = 0;
+        for (int i = 0; i < 4; ++i) { c += (u128)a[i] + b[i]; t[i] = (u64)c; c >>= 64; }
+        if (geq_p(t)) sub_p(t);                                     // r < 2^255: the sum fits
+        std::memcpy(out, t, 32);
     }
     // out = a b / 2^256 mod r (CIOS); out may alias an operand
     void mul(const u64* a, const u64* b, u64* out) const {

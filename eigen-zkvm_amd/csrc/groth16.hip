@@ -17,6 +17,7 @@
 #include "fr_host.h"
 #include "r1cs_file.h"
 #include "json_min.h"
+#include "ceremony_host.h"
 #include <algorithm>
 #include <cerrno>
 #include <chrono>
@@ -300,6 +301,7 @@ namespace bn254fr {
 #include "groth16_keygen_impl.hip.h"
 #include "verify_sums_impl.hip.h"
 #include "key_check_srs_impl.hip.h"
+#include "ceremony_impl.hip.h"
 #undef FRN_S
 #undef FRN_ROOT
 }  // namespace bn254fr
@@ -315,12 +317,13 @@ namespace bls12381fr {
 #include "groth16_keygen_impl.hip.h"
 #include "verify_sums_impl.hip.h"
 #include "key_check_srs_impl.hip.h"
+#include "ceremony_impl.hip.h"
 }  // namespace bls12381fr
 
 const Groth16Ops& groth16_ops(CurveId id) {   // the table's slice of this unit (curve.h)
-    static const Groth16Ops OPS[2] = {{bn254fr::ntt_dev, bn254fr::quotient_dev, bn254fr::setup_new, bn254fr::keygen_run, bn254fr::verify_sums_dev, bn254fr::kc_coef_dev, bn254fr::kc_coeffs_dev},
+    static const Groth16Ops OPS[2] = {{bn254fr::ntt_dev, bn254fr::quotient_dev, bn254fr::setup_new, bn254fr::keygen_run, bn254fr::verify_sums_dev, bn254fr::kc_coef_dev, bn254fr::kc_coeffs_dev, bn254fr::powers_dev},
                                       {bls12381fr::ntt_dev, bls12381fr::quotient_dev, bls12381fr::setup_new, bls12381fr::keygen_run, bls12381fr::verify_sums_dev,
-                                       bls12381fr::kc_coef_dev, bls12381fr::kc_coeffs_dev}};
+                                       bls12381fr::kc_coef_dev, bls12381fr::kc_coeffs_dev, bls12381fr::powers_dev}};
     return OPS[id];
 }
 
@@ -609,6 +612,7 @@ std::string groth16_key_check(const char* curve, const void* r1cs, size_t r1cs_l
 
 #include "groth16_srs.hip.h"
 #include "key_check_srs.hip.h"
+#include "groth16_ceremony.hip.h"
 // the weights of the aggregate verification (pairing.hip): rho_dev for a caller outside this unit
 void groth16_rho_dev(const uint8_t* seed, uint64_t n, DevBuf& d_rho, hipStream_t st, const char* who) { g16::rho_dev(seed, n, d_rho, st, who); }
 

@@ -11,7 +11,7 @@
 namespace g16 {
 static const char* const SRS_SECTION[7] = {"", "header", "tauG1", "tauG2", "alphaTauG1", "betaTauG1", "betaG2"};
 static const Group SRS_GROUP[7] = {G1, G1, G1, G2, G1, G1, G2};
-static u64 srs_count(uint32_t power, int id) { const u64 n = 1ull << power; return id == 2 ? 2 * n - 1 : id == 6 ? 1 : n; }
+static u64 srs_count(uint32_t power, int id) { return cer::section_count(power, id); }   // ceremony_host.h: the writer counts the same way
 
 // e(a1, a2) == e(b1, b2) for device points in the layout of the sums (all zero = infinity)
 struct PairEq {
@@ -74,6 +74,17 @@ struct Findings {
         return js + "]";
     }
 };
+static std::vector<uint8_t> q_bytes(const Curve& cv) {               // the base field's modulus, little-endian, as the header carries it
+    const size_t qb = 4 * (size_t)cv.fq_words;
+    std::vector<uint8_t> q(qb, 0);
+    const std::string qh = cv.pairing().q_hex;
+    for (size_t i = 0; i < qh.size() && i < 2 * qb; ++i) {
+        const char c = qh[qh.size() - 1 - i];
+        const int d = c >= '0' && c <= '9' ? c - '0' : (c | 0x20) - 'a' + 10;
+        q[i / 2] |= (uint8_t)(d << (4 * (i & 1)));
+    }
+    return q;
+}
 static std::string skipped_entry(const char* check, const char* section, const char* reason) {
     return std::string("{\"check\":\"") + check + "\",\"section\":\"" + section + "\",\"reason\":\"" + reason + "\"}";
 }
@@ -108,14 +119,8 @@ Srs* srs_open(const char* curve, const char* path) {
     if (!sec.count(1)) throw std::runtime_error(missing(1));
     g16::Reader h{s->file.data() + sec[1].first, (size_t)sec[1].second, 0, "ptau header"};
     const uint32_t n8 = h.u32le();
-    const size_t qb = 4 * (size_t)cv.fq_words;
-    std::vector<uint8_t> q(qb, 0);
-    const std::string qh = cv.pairing().q_hex;
-    for (size_t i = 0; i < qh.size() && i < 2 * qb; ++i) {
-        const char c = qh[qh.size() - 1 - i];
-        const int d = c >= '0' && c <= '9' ? c - '0' : (c | 0x20) - 'a' + 10;
-        q[i / 2] |= (uint8_t)(d << (4 * (i & 1)));
-    }
+    const std::vector<uint8_t> q = g16::q_bytes(cv);
+    const size_t qb = q.size();
     if (n8 != qb || sec[1].second != 12 + (uint64_t)n8 || std::memcmp(h.take(n8), q.data(), qb) != 0)
         throw std::runtime_error(std::string("ptau: the file's prime is not the base field of ") + cv.name);
     s->power = h.u32le(); s->ceremony_power = h.u32le();

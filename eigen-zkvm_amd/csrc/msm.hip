@@ -47,28 +47,14 @@ namespace {
 }
 }  // namespace g1half
 namespace g1 {
-// phi(x, y) = (beta x, y) = [lambda](x, y) on y^2 = x^3 + 3: beta = 2203960485148121921418603742825762020974279258880205651966 (beta^3 = 1 in
-// Fq), lambda = 4407920970296243842393367215006156084916469457145843978461; lattice basis a1 = b2 = 9931322734385697763,
-// -b1 = 147946756881789319000765030803803410728, a2 = 147946756881789319010696353538189108491 (tools/glv_constants.py derives and checks them)
-#define GLV_BETA_STD 0xd782e155u, 0x71930c11u, 0xffbe3323u, 0xa6bb947cu, 0xd4741444u, 0xaa303344u, 0x26594943u, 0x2c3b3f0du
-#define GLV_G1 0xc7e0b3d7u, 0xd91d232eu, 0x00000002u
-#define GLV_G2 0x391eb18du, 0x7a7bd9d4u, 0xa773d2cfu, 0x4ccef014u, 0x00000002u
-#define GLV_A1 0x94d213e3u, 0x89d32568u
-#define GLV_A2 0x1221250bu, 0x0be4e154u, 0xeeb859fdu, 0x6f4d8248u
-#define GLV_NB1 0x7d4f1128u, 0x8211bbebu, 0xeeb859fcu, 0x6f4d8248u
-#define GLV_B2 0x94d213e3u, 0x89d32568u
+// the endomorphism split: constants and derivation in glv_split.hip.h
+#define GLV_CURVE_BN254
 #define MSM_GLV g1half
 namespace {
 #include "msm_impl.hip.h"
 }
 #undef MSM_GLV
-#undef GLV_BETA_STD
-#undef GLV_G1
-#undef GLV_G2
-#undef GLV_A1
-#undef GLV_A2
-#undef GLV_NB1
-#undef GLV_B2
+#undef GLV_CURVE_BN254
 }  // namespace g1
 namespace g2 {   // the twist y^2 = x^3 + 3/(9 + u) over Fq2 = Fq[u]/(u^2 + 1); generator of EIP-197, x = c0 + c1 u
 __host__ __device__ constexpr u32 GEN_X(int i) {
@@ -123,22 +109,13 @@ namespace {
 }
 }  // namespace g1half
 namespace g1 {
-// phi(x, y) = (beta x, y) = [lambda](x, y) on y^2 = x^3 + 4 with lambda = z^2 - 1 = 0xac45a4010001a40200000000ffffffff (z the curve parameter):
-// lambda^2 + lambda + 1 = 0 mod r, so k = k1 + k2 lambda by division; beta =
-// 4002409555221667392624310435006688643935503118305586438271171395842971157480381377015405980053539358417135540939436
-#define GLV_BETA_STD 0x8671f071u, 0xcd03c9e4u, 0x1fcda5d2u, 0x5dab2246u, 0xd3851b95u, 0x587042afu, 0x01bacb9eu, 0x8eb60ebeu, 0x83d050d2u, 0x03f97d6eu, 0x54638741u, 0x18f02065u
-#define GLV_LAMBDA 0xffffffffu, 0x00000000u, 0x0001a402u, 0xac45a401u
-#define GLV_G 0xf6cfee30u, 0x63f6e522u, 0xe01faaddu, 0x7c6becf1u, 0x00000001u
-#define GLV_R 0x00000001u, 0xffffffffu, 0xfffe5bfeu, 0x53bda402u, 0x09a1d805u, 0x3339d808u, 0x299d7d48u, 0x73eda753u
+#define GLV_CURVE_BLS12_381
 #define MSM_GLV g1half
 namespace {
 #include "msm_impl.hip.h"
 }
 #undef MSM_GLV
-#undef GLV_BETA_STD
-#undef GLV_LAMBDA
-#undef GLV_G
-#undef GLV_R
+#undef GLV_CURVE_BLS12_381
 }  // namespace g1
 namespace g2 {   // the twist y^2 = x^3 + 4(1 + u) over Fq2 = Fq[u]/(u^2 + 1); G2 generator of the BLS12-381 specification
 __host__ __device__ constexpr u32 GEN_X(int i) {
@@ -169,7 +146,7 @@ namespace {
 }  // namespace bls12_381
 
 // the table's slice of this unit (curve.h)
-#define ZK_GROUP_OPS(NS) {NS::msm_g1_dev, NS::g1_mul_generator_dev, NS::mul_generator_fr_dev, NS::msm_fixed_table_bytes, NS::msm_fixed_prepare_dev, NS::msm_fixed_dev}
+#define ZK_GROUP_OPS(NS) {NS::msm_g1_dev, NS::g1_mul_generator_dev, NS::mul_generator_fr_dev, NS::msm_fixed_table_bytes, NS::msm_fixed_prepare_dev, NS::msm_fixed_dev, NS::generator_words}
 const MsmOps& msm_ops(CurveId id) {
     static const MsmOps OPS[2] = {
         {{ZK_GROUP_OPS(bn254::g1), ZK_GROUP_OPS(bn254::g2)}, bn254::g1::fq_canon_to_mont_dev, bn254::g1::fq_mont_to_canon_dev},

@@ -615,90 +615,26 @@ static void msm_core(const void* d_bases, const void* d_table, uint64_t table_n,
     ZK_HIP(hipGetLastError());
 }   // the pooled scratch above is released here, stream-ordered: the sum is asynchronous on `st` like every other _dev entry point
 
+void generator_words(u32* out) { for (int j = 0; j < CW_STD; ++j) { out[j] = GEN_X(j); out[CW_STD + j] = GEN_Y(j); } }   // host: G as the sums lay a point out
 void msm_preconv_dev(const void* d_points, const void* d_scalars, uint64_t n, void* d_out, hipStream_t st) { msm_core(nullptr, nullptr, 0, 0, d_scalars, n, d_out, st, d_points); }
 #ifdef MSM_GLV
 // ---- the curve's endomorphism phi(x, y) = (beta x, y) = [lambda](x, y): k P = k1 P + k2 phi(P) with |k1|, |k2| < 2^128, so a sum
 // over n points with 254-bit scalars becomes a sum over 2n points with 128-bit scalars: the same number of bucket additions, half
 // the windows -- half the bucket hierarchy and half of the doublings of the final Horner walk, the two serial tails of a sum.
-// (k1, k2) = k - c1 (a1, b1) - c2 (a2, b2) with c1 = floor(k g1 / 2^256), c2 = floor(k g2 / 2^256), g1 = floor(2^256 b2 / r),
-// g2 = floor(-2^256 b1 / r) for the short basis (a1, b1), (a2, b2) of {(x, y): x + y lambda = 0 mod r}; any integers c1, c2 give
-// a correct split, these keep both halves below 2^128 (checked over the edge scalars and 2 * 10^5 random ones when the constants
-// were derived, tools/glv_constants.py).  One kernel splits the scalar, converts the base and writes (+-P, |k1|), (+-phi(P), |k2|).
-template <int NA, int NB, int NO>
-__device__ __forceinline__ void glv_mul(const u32 (&a)[NA], const u32 (&b)[NB], u32 (&out)[NO], int from) {   // words [from, from + NO) of a * b
-    u64 acc = 0;
-    u32 carry_hi = 0;
-    for (int k = 0; k < from + NO; ++k) {       // column k; (acc, carry_hi) is a 96-bit running sum
-        for (int i = 0; i < NA; ++i) {
-            const int j = k - i;
-            if (j < 0 || j >= NB) continue;
-            const u64 p = (u64)a[i] * b[j];
-            acc += p;
-            carry_hi += acc < p;
-        }
-        if (k >= from) out[k - from] = (u32)acc;
-        acc = (acc >> 32) | ((u64)carry_hi << 32);
-        carry_hi = 0;
-    }
-}
+// The split itself is glv_split (glv_split.hip.h).  One kernel splits the scalar, converts the base and writes (+-P, |k1|), (+-phi(P), |k2|).
+#include "glv_split.hip.h"
 __global__ __launch_bounds__(256) void glv_split_kernel(const u32* __restrict__ bases, const u32* __restrict__ scalars, u64 n,
                                                         u32* __restrict__ conv2 /* 2n points */, u32* __restrict__ sc2 /* 2n x 4 words */) {
     __shared__ cf beta_s;                                              // beta in the internal form, converted once per block
-    if (threadIdx.x == 0) { const u32 BETA[NL] = {GLV_BETA_STD}; beta_s = cf_from_std(BETA); }
+    if (threadIdx.x == 0) beta_s = glv_beta();
     __syncthreads();
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     u32 k[8], k1[8], k2[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) k[j] = scalars[i * 8 + j];
-    bool n1 = false, n2 = false;
-#ifdef GLV_LAMBDA
-    // lambda^2 + lambda + 1 = 0 (mod r) with lambda < 2^128: k = k1 + k2 lambda by plain division, both halves non-negative.  A scalar
-    // is brought below r first (k2 <= lambda + 1 needs it); the quotient from the reciprocal g = floor(2^256 / lambda) is at most
-    // one short, made up by one conditional step
-    const u32 LAMBDA[4] = {GLV_LAMBDA}, GG[5] = {GLV_G}, RMOD[8] = {GLV_R};
-    for (int rep = 0; rep < 2; ++rep) {
-        u32 t[8]; u64 br = 0;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { const u64 d = (u64)k[j] - RMOD[j] - br; t[j] = (u32)d; br = (d >> 32) & 1; }
-        if (!br) { for (int j = 0; j < 8; ++j) k[j] = t[j]; }
-    }
-    u32 c[5], t8[8];
-    glv_mul<8, 5, 5>(k, GG, c, 8);
-    glv_mul<5, 4, 8>(c, LAMBDA, t8, 0);
-    u64 br = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { const u64 d = (u64)k[j] - t8[j] - br; k1[j] = (u32)d; br = (d >> 32) & 1; }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) k2[j] = j < 5 ? c[j] : 0;
-    {   // k1 >= lambda: one more lambda goes to k2
-        u32 t[8]; u64 b2 = 0;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { const u64 d = (u64)k1[j] - (j < 4 ? LAMBDA[j] : 0u) - b2; t[j] = (u32)d; b2 = (d >> 32) & 1; }
-        if (!b2) {
-            for (int j = 0; j < 8; ++j) k1[j] = t[j];
-            u64 cy = 1;
-            for (int j = 0; j < 8; ++j) { cy += k2[j]; k2[j] = (u32)cy; cy >>= 32; }
-        }
-    }
-#else
-    const u32 G1[3] = {GLV_G1}, G2[5] = {GLV_G2}, A1[2] = {GLV_A1}, A2[4] = {GLV_A2}, NB1[4] = {GLV_NB1}, B2[2] = {GLV_B2};
-    u32 c1[3], c2[5];
-    glv_mul<8, 3, 3>(k, G1, c1, 8);
-    glv_mul<8, 5, 5>(k, G2, c2, 8);
-    u32 t1[8], t2[8];
-    glv_mul<3, 2, 8>(c1, A1, t1, 0); glv_mul<5, 4, 8>(c2, A2, t2, 0);          // k1 = k - c1 a1 - c2 a2  (mod 2^256, two's complement)
-    u64 br = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { const u64 d = (u64)k[j] - t1[j] - t2[j] - br; k1[j] = (u32)d; br = (0 - (d >> 32)) & 3; }
-    glv_mul<3, 4, 8>(c1, NB1, t1, 0); glv_mul<5, 2, 8>(c2, B2, t2, 0);         // k2 = c1 |b1| - c2 b2
-    br = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { const u64 d = (u64)t1[j] - t2[j] - br; k2[j] = (u32)d; br = (0 - (d >> 32)) & 1; }
-    n1 = k1[7] >> 31; n2 = k2[7] >> 31;
-    if (n1) { u64 c = 1; for (int j = 0; j < 8; ++j) { c += (u32)~k1[j]; k1[j] = (u32)c; c >>= 32; } }
-    if (n2) { u64 c = 1; for (int j = 0; j < 8; ++j) { c += (u32)~k2[j]; k2[j] = (u32)c; c >>= 32; } }
-#endif
+    bool n1, n2;
+    glv_split(k, k1, k2, n1, n2);
 #pragma unroll
     for (int j = 0; j < 4; ++j) { sc2[(2 * i) * 4 + j] = k1[j]; sc2[(2 * i + 1) * 4 + j] = k2[j]; }
     u32 w[2 * CW_STD];

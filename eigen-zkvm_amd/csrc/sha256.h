@@ -1,11 +1,12 @@
-// SHA-256 (FIPS 180-4) of a byte string, as lower-case hex: names the on-disk code objects of the run-time compiled kernels.
+// SHA-256 (FIPS 180-4) of a byte string: as 32 bytes for the ceremonies' transcripts, as lower-case hex for the names of the on-disk
+// code objects of the run-time compiled kernels.
 #pragma once
 #include <cstdint>
 #include <cstring>
 #include <string>
 
 namespace zk {
-inline std::string sha256_hex(const void* data, size_t len) {
+inline void sha256_raw(const void* data, size_t len, uint8_t* out /* 32 bytes */) {
     static const uint32_t K[64] = {
         0x428a2f98, 0x71374491, 0xb5c0fbcf, 0xe9b5dba5, 0x3956c25b, 0x59f111f1, 0x923f82a4, 0xab1c5ed5, 0xd807aa98, 0x12835b01, 0x243185be,
         0x550c7dc3, 0x72be5d74, 0x80deb1fe, 0x9bdc06a7, 0xc19bf174, 0xe49b69c1, 0xefbe4786, 0x0fc19dc6, 0x240ca1cc, 0x2de92c6f, 0x4a7484aa,
@@ -41,13 +42,15 @@ inline std::string sha256_hex(const void* data, size_t len) {
     for (int i = 0; i < 8; ++i) tail[tl - 1 - i] = (uint8_t)(bits >> (8 * i));
     block(tail);
     if (tl == 128) block(tail + 64);
+    for (int i = 0; i < 8; ++i)
+        for (int j = 0; j < 4; ++j) out[4 * i + j] = (uint8_t)(h[i] >> (24 - 8 * j));
+}
+inline std::string sha256_hex(const void* data, size_t len) {
+    uint8_t d[32];
+    sha256_raw(data, len, d);
     static const char* hex = "0123456789abcdef";
     std::string out(64, '0');
-    for (int i = 0; i < 8; ++i)
-        for (int j = 0; j < 4; ++j) {
-            const uint8_t byte = (uint8_t)(h[i] >> (24 - 8 * j));
-            out[8 * i + 2 * j] = hex[byte >> 4]; out[8 * i + 2 * j + 1] = hex[byte & 15];
-        }
+    for (int i = 0; i < 32; ++i) { out[2 * i] = hex[d[i] >> 4]; out[2 * i + 1] = hex[d[i] & 15]; }
     return out;
 }
 }  // namespace zk

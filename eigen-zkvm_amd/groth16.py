@@ -177,6 +177,37 @@ class Srs:
         sd = _seed(seed, "srs check")
         return _report(lib().zk_srs_check(self._h, sd.ctypes.data if sd is not None else None, int(max_findings)))
 
+    def transcript_count(self):
+        """the records of the file's transcript of contributions (host only); -1: the file has none"""
+        n = C.c_int64(0)
+        _check(lib().zk_srs_transcript_count(self._h, C.byref(n)))
+        return n.value
+
+    def contribute(self, out_path, secrets=None, beacon=None):
+        """zk_srs_contribute: write to out_path this file with tau, alpha, beta multiplied by three factors, and one more record in its
+        transcript.  secrets: (t, a, b) integers in [1, r) -- tests only; None lets the library draw them from the operating system and
+        nothing of them survives the call.  beacon: (seed of 32 bytes, iter_log) for a contribution whose factors anyone can recompute."""
+        if secrets is not None and beacon is not None:
+            raise ZkError("ptau contribute: a beacon takes no secrets")
+        sw = sd = None
+        it = 0
+        if secrets is not None:
+            if len(secrets) != 3 or not all(0 < int(v) < _FR[self.curve] for v in secrets):
+                raise ZkError("ptau contribute: three factors in [1, r)")
+            sw = np.array([(int(v) >> (64 * i)) & (2**64 - 1) for v in secrets for i in range(4)], dtype=np.uint64)
+        if beacon is not None:
+            sd, it = _seed(beacon[0], "ptau beacon"), int(beacon[1])
+            if not 0 <= it <= 40:
+                raise ZkError("ptau beacon: iter_log in [0, 40]")
+        _check(lib().zk_srs_contribute(self._h, str(out_path).encode(), _ptr(sw) if sw is not None else None,
+                                       sd.ctypes.data if sd is not None else None, it))
+
+    def verify(self, seed=None, max_findings=16):
+        """zk_srs_verify: Srs.check's report under "file", the transcript's hash chain, every proof of knowledge and beacon, and the last
+        record's images against the file -> the report as a dict; seed: 32 bytes, tests only"""
+        sd = _seed(seed, "srs verify")
+        return _report(lib().zk_srs_verify(self._h, sd.ctypes.data if sd is not None else None, int(max_findings)))
+
     def free(self):
         if self._h:
             lib().zk_srs_free(self._h); self._h = None
@@ -186,6 +217,28 @@ class Srs:
             self.free()
         except Exception:
             pass
+
+
+def srs_new(curve, power, path):
+    """zk_srs_new (host only): the powers-of-tau file of tau = alpha = beta = 1 with an empty transcript, where a ceremony starts"""
+    if curve not in _FR:
+        raise ZkError('groth16: unknown curve "%s" (BN128 | BLS12381)' % curve)
+    _check(lib().zk_srs_new(curve.encode(), int(power), str(path).encode()))
+
+
+def srs_verify_lines(report):
+    """one line per finding of Srs.verify's report, the file's own findings (Srs.check) first"""
+    out = []
+    for f in report["file"]["findings"]:
+        out.append("ptau file: %s %s" % (f["kind"], " ".join("%s=%s" % (k, v) for k, v in f.items() if k != "kind")))
+    text = {"no_transcript": "the file has no transcript of contributions (section %(section)s)",
+            "chain_hash": "contribution %(contribution)s: the chain hash is not the hash of the records before it",
+            "pok_invalid": "contribution %(contribution)s: no valid proof of knowledge of the %(which)s factor",
+            "beacon_mismatch": "contribution %(contribution)s: the %(which)s image is not the beacon's recomputed factor times the image before",
+            "image_mismatch": "the file's %(which)s point is not the image of the last contribution (%(contribution)s)"}
+    for f in report["findings"]:
+        out.append("ptau transcript: " + text[f["kind"]] % f)
+    return out
 
 
 def group_ntt(d_points, curve="BN128", group="g1", inverse=False, stream=0):
@@ -207,9 +260,12 @@ def mul_scalar(d_points, k, curve="BN128", group="g1", stream=0):
     _check(getattr(lib(), "zk_%s_%s_mul_scalar_dev" % (group, _NAME[curve]))(d_points.ptr, n, DevArray.from_host(kw).ptr, out.ptr, stream)); return out
 
 
-def mul_scalars(d_points, scalars, curve="BN128", group="g1", stream=0):
+def mul_scalars(d_points, scalars, curve="BN128", group="g1", stream=0, glv=False):
     """[k_i] P_i for the points of a DevArray and one integer per point -> a new DevArray.  The walk starts at each scalar's top set
-    bit: short scalars are cheap.  A zero scalar or the all-zero point gives the all-zero encoding."""
+    bit: short scalars are cheap.  A zero scalar or the all-zero point gives the all-zero encoding.  glv=True (G1 only, points of the
+    subgroup of order r): the same bytes through the endomorphism split, about half the point operations for full-width scalars."""
+    if glv and group != "g1":
+        raise ZkError("mul_scalars: the endomorphism split exists for g1 only")
     pw = _FQ_WORDS[curve] * (2 if group == "g1" else 4)
     n = d_points.n // pw
     if n * pw != d_points.n or len(scalars) != n:
@@ -217,7 +273,8 @@ def mul_scalars(d_points, scalars, curve="BN128", group="g1", stream=0):
     kw = np.array([((int(k) % _FR[curve]) >> (64 * i)) & (2**64 - 1) for k in scalars for i in range(4)], dtype=np.uint64)
     out = DevArray(max(1, n) * pw)
     if n:
-        _check(getattr(lib(), "zk_%s_%s_mul_scalars_dev" % (group, _NAME[curve]))(d_points.ptr, n, DevArray.from_host(kw).ptr, out.ptr, stream))
+        fn = "zk_%s_%s_mul_scalars%s_dev" % (group, _NAME[curve], "_glv" if glv else "")
+        _check(getattr(lib(), fn)(d_points.ptr, n, DevArray.from_host(kw).ptr, out.ptr, stream))
     return out
 
 
@@ -235,6 +292,49 @@ def contribute(curve, params_bytes, delta=None):
     out = np.empty(p.size, np.uint8)
     _check(lib().zk_groth16_params_contribute(curve.encode(), p.ctypes.data, p.size, _ptr(dw) if dw is not None else None, out.ctypes.data))
     return out.tobytes()
+
+
+def contribute_pok(curve, params_bytes, transcript=b"", delta=None):
+    """zk_groth16_params_contribute_pok: contribute() plus a proof of knowledge of the ratio of the two deltas, appended to the key's
+    transcript -> (the new key's bytes, the new transcript's bytes).  transcript: the bytes so far, or empty to start one at this key."""
+    if curve not in _FR:
+        raise ZkError('groth16: unknown curve "%s" (BN128 | BLS12381)' % curve)
+    dw = None
+    if delta is not None:
+        if not 0 < int(delta) < _FR[curve]:
+            raise ZkError("groth16 contribute: delta must be a non-zero canonical field element")
+        dw = np.array([(int(delta) >> (64 * i)) & (2**64 - 1) for i in range(4)], dtype=np.uint64)
+    p = np.frombuffer(params_bytes, dtype=np.uint8)
+    t = np.frombuffer(bytes(transcript), dtype=np.uint8)
+    head, rec = 48, 96 + 4 * 8 * _FQ_WORDS[curve]
+    count = max(0, t.size - head) // rec + 1
+    out = np.empty(p.size, np.uint8)
+    out_t = np.empty(lib().zk_groth16_key_transcript_size(curve.encode(), count), np.uint8)
+    _check(lib().zk_groth16_params_contribute_pok(curve.encode(), p.ctypes.data, p.size, _ptr(dw) if dw is not None else None,
+                                                  t.ctypes.data if t.size else None, t.size, out.ctypes.data, out_t.ctypes.data))
+    return out.tobytes(), out_t.tobytes()
+
+
+def key_transcript_check(curve, initial_bytes, final_bytes, transcript, seed=None, max_findings=16):
+    """zk_groth16_key_transcript_check: the transcript's chain and proofs from the initial key's delta_g1 to the final key's, and
+    contribution_check(initial, final) under "keys" -> the report as a dict.  Whether the initial key is a delta = 1 key of its circuit is
+    key_check_srs's question.  seed: 32 bytes, tests only."""
+    if curve not in _FR:
+        raise ZkError('groth16: unknown curve "%s" (BN128 | BLS12381)' % curve)
+    a, b, t = (np.frombuffer(bytes(x), dtype=np.uint8) for x in (initial_bytes, final_bytes, transcript))
+    sd = _seed(seed, "groth16 key transcript")
+    return _report(lib().zk_groth16_key_transcript_check(curve.encode(), a.ctypes.data, a.size, b.ctypes.data, b.size, t.ctypes.data, t.size,
+                                                         sd.ctypes.data if sd is not None else None, int(max_findings)))
+
+
+def key_transcript_lines(report):
+    """one line per finding of key_transcript_check's report, the two keys' own findings (contribution_check) first"""
+    out = ["keys: %s %s" % (f["kind"], " ".join("%s=%s" % (k, v) for k, v in f.items() if k != "kind")) for f in report["keys"]["findings"]]
+    text = {"initial_key_mismatch": "the transcript starts at another key than the initial one",
+            "chain_hash": "contribution %(contribution)s: the chain hash is not the hash of the records before it",
+            "pok_invalid": "contribution %(contribution)s: no valid proof of knowledge of the ratio of the two deltas",
+            "final_key_mismatch": "the transcript does not end at the final key (%(what)s)"}
+    return out + ["key transcript: " + text[f["kind"]] % f for f in report["findings"]]
 
 
 def contribution_check(curve, old_params, new_params, seed=None, max_findings=16):

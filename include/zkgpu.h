@@ -482,6 +482,25 @@ int zk_groth16_keygen_free(zk_groth16_keygen_t* k);
  * scalar k (4 x u64 canonical, below r) on the device; d_out may be d_points.  zk_<g1|g2>_<curve>_mul_scalars_dev: d_out[i] =
  * [d_k[i]] d_points[i], one scalar of 4 x u64 per point; the walk starts at each scalar's top set bit, so scalars of 128 bits cost half of
  * full-width ones; a zero scalar or the all-zero point gives the all-zero encoding; d_out may be d_points.
+ * zk_g1_<curve>_mul_scalars_glv_dev: the same contract and the same bytes for points of the subgroup of order r, through the curve's
+ * endomorphism: each scalar is split into two halves below 2^128 and one joint walk serves both, about half the point operations of the
+ * walk above for full-width scalars and no gain for scalars of 128 bits or fewer.  G1 only: G2 has no such split here.
+ * A ceremony.  zk_srs_new (host only, no device) writes the file of tau = alpha = beta = 1 -- every point its group's generator -- with an
+ * empty transcript.  zk_srs_contribute writes to out_path the file for (tau t, alpha a, beta b): tauG1[i] t^i, tauG2[i] t^i, alphaTauG1[i] a t^i,
+ * betaTauG1[i] b t^i, betaG2 b, the old transcript and one new record.  secrets: 3 x 4 u64 canonical and non-zero (t, a, b), or NULL to draw
+ * them from the operating system; they and the proofs' nonces are overwritten on the host and on the device before the call returns.
+ * beacon_seed (32 bytes, then secrets must be NULL): a contribution whose factors anyone can recompute -- d = SHA-256 iterated
+ * 2^beacon_iter_log times over the seed, factor j = SHA-256(d | u8 j) as a little-endian integer cut to 253 bits.  The work goes section by
+ * section in chunks of 2^20 points through one device buffer, each chunk straight into the file.  The transcript is section 64 of the
+ * container -- a layout of this project (csrc/ceremony_host.h), not snarkjs's contribution section; zk_srs_open walks over it, so a
+ * contributed file serves zk_groth16_keygen_from_srs and zk_groth16_key_check_srs as it is.  Each record holds the three images after
+ * the contribution (tauG1[1], alphaTauG1[0], betaTauG1[0]), a Schnorr proof of knowledge of each factor over the previous record's image
+ * (G1 for the first) and a hash chained over all records before it.  zk_srs_transcript_count (host only): the records of the file's
+ * transcript, -1 without one.  zk_srs_verify -> a JSON report (malloc'ed, zk_string_free): zk_srs_check's whole report under "file", and
+ * the findings "no_transcript", "chain_hash" {contribution}, "pok_invalid" {contribution, which: tau | alpha | beta} (the proof's equation,
+ * or an image that is infinity or no point of the group), "beacon_mismatch" (a beacon record's images are not its recomputed factors'),
+ * "image_mismatch" (the last record's images are not the file's, byte for byte).  The transcript proves that somebody knew every factor
+ * from G1 to the last images; "file" proves that every section is the powers of that tau with those alpha and beta.
  * zk_groth16_keygen_from_srs returns what zk_groth16_keygen_new returns (_params_size, _params, _vk_json, _timing and _free serve both;
  * _timing here: G1 transforms, G1 column sums, uploads and the h differences, G2 transform and sums, serialisation).  It fails before any
  * device work when the file's power is below the circuit's domain; a larger file is fine.
@@ -490,6 +509,17 @@ int zk_groth16_keygen_free(zk_groth16_keygen_t* k);
  * device before the call returns.  zk_groth16_contribution_check -> a JSON report: sections that must be byte-equal ("changed", "size"),
  * the classes of the new delta, l and h points, delta_g1 against delta_g2 ("delta_mismatch"), and l, h scaled by exactly the ratio of the
  * two deltas ("not_scaled").
+ * zk_groth16_contribution_check holds for ANY ratio of the two deltas that its presenter knows -- the delta = 1 key scaled by a known k passes
+ * as the successor of any key -- so a chain of contributions carries proofs of knowledge in a transcript beside the key (bellman's layout
+ * has no room for one): "zkgk", u32 version = 1, u32 n8, u32 count, SHA-256 of the initial key; per contribution SHA-256 of the new key,
+ * delta_g1 after, R, z (32 B canonical little-endian) and a chain hash; points in the key's encoding; the proof is Schnorr's over base
+ * delta_g1 before and image delta_g1 after (csrc/groth16_ceremony.hip.h has the hashes).  zk_groth16_params_contribute_pok is
+ * zk_groth16_params_contribute plus the appended record: t_len = 0 starts a transcript with this key as the initial one, otherwise the
+ * transcript must end at this key; out_transcript takes zk_groth16_key_transcript_size(curve, count + 1) bytes; out_params may be params.
+ * zk_groth16_key_transcript_check -> a JSON report (malloc'ed, zk_string_free): "initial_key_mismatch" (the transcript starts at another
+ * key), "chain_hash" {contribution}, "pok_invalid" {contribution}, "final_key_mismatch" (the last delta_g1, or the last key hash, is not
+ * the final key's), and zk_groth16_contribution_check(initial, final) under "keys" -- that check holds for any ratio, so the intermediate
+ * keys are not needed.  Whether the initial key is a delta = 1 key of its circuit stays zk_groth16_key_check_srs's question.
  * zk_groth16_key_check_srs -> a JSON report (malloc'ed, zk_string_free): is this key a key for this circuit over this file?  What
  * zk_groth16_key_check cannot see: every query (a, b_g1, b_g2, ic, l, h) against the circuit's polynomials at the file's tau, each by one
  * random linear combination over the wires (weights of 128 bits; a wrong section survives with probability 2^-128) -- multi-scalar sums
@@ -506,6 +536,10 @@ zk_srs_t* zk_srs_open(const char* curve, const char* path);
 int zk_srs_info(const zk_srs_t* s, uint32_t* power, uint32_t* ceremony_power);
 char* zk_srs_check(const zk_srs_t* s, const uint8_t* seed, uint32_t max_findings);
 int zk_srs_free(zk_srs_t* s);
+int zk_srs_new(const char* curve, uint32_t power, const char* path);
+int zk_srs_contribute(const zk_srs_t* s, const char* out_path, const uint64_t* secrets, const uint8_t* beacon_seed, uint32_t beacon_iter_log);
+char* zk_srs_verify(const zk_srs_t* s, const uint8_t* seed, uint32_t max_findings);
+int zk_srs_transcript_count(const zk_srs_t* s, int64_t* count);
 int zk_g1_bn254_ntt_dev(void* d_points, uint32_t log_n, int inverse, void* stream);
 int zk_g2_bn254_ntt_dev(void* d_points, uint32_t log_n, int inverse, void* stream);
 int zk_g1_bls12_381_ntt_dev(void* d_points, uint32_t log_n, int inverse, void* stream);
@@ -518,8 +552,15 @@ int zk_g1_bn254_mul_scalars_dev(const void* d_points, uint64_t n, const uint64_t
 int zk_g2_bn254_mul_scalars_dev(const void* d_points, uint64_t n, const uint64_t* d_k, void* d_out, void* stream);
 int zk_g1_bls12_381_mul_scalars_dev(const void* d_points, uint64_t n, const uint64_t* d_k, void* d_out, void* stream);
 int zk_g2_bls12_381_mul_scalars_dev(const void* d_points, uint64_t n, const uint64_t* d_k, void* d_out, void* stream);
+int zk_g1_bn254_mul_scalars_glv_dev(const void* d_points, uint64_t n, const uint64_t* d_k, void* d_out, void* stream);
+int zk_g1_bls12_381_mul_scalars_glv_dev(const void* d_points, uint64_t n, const uint64_t* d_k, void* d_out, void* stream);
 zk_groth16_keygen_t* zk_groth16_keygen_from_srs(const char* curve, const void* r1cs, size_t r1cs_len, const zk_srs_t* srs);
 int zk_groth16_params_contribute(const char* curve, const void* params, size_t len, const uint64_t* delta, void* out);
+size_t zk_groth16_key_transcript_size(const char* curve, uint32_t count);
+int zk_groth16_params_contribute_pok(const char* curve, const void* params, size_t len, const uint64_t* delta, const void* transcript, size_t t_len, void* out_params,
+                                     void* out_transcript);
+char* zk_groth16_key_transcript_check(const char* curve, const void* initial, size_t initial_len, const void* final_key, size_t final_len, const void* transcript,
+                                      size_t t_len, const uint8_t* seed, uint32_t max_findings);
 char* zk_groth16_contribution_check(const char* curve, const void* old_params, size_t old_len, const void* new_params, size_t new_len, const uint8_t* seed,
                                     uint32_t max_findings);
 char* zk_groth16_key_check_srs(const char* curve, const void* r1cs, size_t r1cs_len, const void* params, size_t params_len, const zk_srs_t* srs, const uint8_t* seed,
