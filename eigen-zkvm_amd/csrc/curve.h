@@ -17,7 +17,13 @@ using Groth16Key = ::zk_groth16_keygen;
 using Groth16Vk = ::zk_groth16_vk;
 using Srs = ::zk_srs;
 namespace g16 { struct Circuit; struct Params; }
-struct MillerArgs;
+// what miller_kernel takes (pairing_impl.hip.h): up to three pairs per item -- G1 points, line tables and infinity words with their strides
+struct MillerArgs {
+    const u32* g1[3]; u64 g1_stride[3];
+    const u32* lines[3]; u64 lines_stride[3];
+    const u32* inf[3]; u64 inf_stride[3];
+    int np;
+};
 struct Curve;
 
 enum CurveId { CURVE_BN254, CURVE_BLS12_381 };

@@ -26,12 +26,6 @@
 
 namespace zk {
 
-struct MillerArgs {
-    const u32* g1[3]; u64 g1_stride[3];
-    const u32* lines[3]; u64 lines_stride[3];
-    const u32* inf[3]; u64 inf_stride[3];
-    int np;
-};
 #define FQ_MUL_ATTR __noinline__
 
 namespace bn254 {

@@ -185,7 +185,7 @@ __device__ __noinline__ cf f12_dot(const u32* A, const u32* B, const u32* BX, in
     for (int i = 0; i < 6; ++i) {
         const int j = k - i;
         const cf b = j < 0 ? f12_get(BX, j + 6) : f12_get(B, j);
-        acc = cf_add(acc, cf_mul(b, f12_get(A, i)));                                     // b < 8q first, a < 2q
+        acc = cf_add(acc, cf_mul(b, f12_get(A, i)));                                     // b < 8q first, a <= 2q (2q itself: a coefficient f12_conj6 negated)
     }
     return cf_red(acc);                                                                  // < 12q -> < 2q
 }
@@ -233,7 +233,7 @@ __device__ __noinline__ cf f12_cyc_sqr(const f12ctx& c, const cf& a) {
     const cf s3 = cf_add(cf_dbl(s), s), a2 = cf_dbl(a);                                  // < 24q, < 4q
     return cf_red((c.k & 1) ? cf_add(s3, a2) : cf_sub<4>(s3, a2));
 }
-__device__ __forceinline__ cf f12_conj6(const f12ctx& c, const cf& a) { return (c.k & 1) ? cf_neg(a) : a; }
+__device__ __forceinline__ cf f12_conj6(const f12ctx& c, const cf& a) { return (c.k & 1) ? cf_neg(a) : a; }   // odd k: 2q - a, up to 2q itself
 __device__ __forceinline__ cf f12_frob2(const f12ctx& c, const cf& a) { return cf_scale(a, pr_const(PAIR_GAMMA2[c.k])); }
 __device__ __forceinline__ cf f12_one(const f12ctx& c) { return c.k == 0 ? cf_one() : cf_zero(); }
 __device__ __forceinline__ f12ctx f12_ctx(u32* sh_all) {

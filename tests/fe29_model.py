@@ -312,16 +312,26 @@ class Model:
         NL, NR = self.NL, self.NR
         p = self.mul(a, self.const(self.COUT, a.shape[1]))
         need(_all(self.F.val(p) < 2 * self.q), "fe_to_std: fe_canon's operand reaches 2q")
-        x = self.canon(p)
-        w = np.empty((NL, a.shape[1]), dtype=object)
+        return self.words(self.canon(p), "fe_to_std")
+
+    def words(self, x, what):
+        """canonical limbs -> (NL, n) 32-bit words, as fe_to_std and fe_to_canon_words repack them"""
+        NL, NR = self.NL, self.NR
+        w = np.empty((NL, x.shape[1]), dtype=object)
         for j in range(NL):
             bit = 32 * j; k = bit // LB; s = bit % LB
             v = x[k] >> s
             if k + 1 < NR: v = v | ((x[k + 1] << (LB - s)) & M32)
             if k + 2 < NR and 2 * LB - s < 32: v = v | ((x[k + 2] << (2 * LB - s)) & M32)
             w[j] = v & M32
-        need(_all(sum(w[i] << (32 * i) for i in range(NL)) == self.F.val(x)), "fe_to_std: the words are not the canonical limbs' integer")
+        need(_all(sum(w[i] << (32 * i) for i in range(NL)) == self.F.val(x)), f"{what}: the words are not the canonical limbs' integer")
         return w
+
+    def to_canon_words(self, a):
+        """pairing_impl.hip.h's fe_to_canon_words: the product with the plain integer 1 leaves Montgomery form"""
+        p = self.mul(a, self.const([1] + [0] * (self.NR - 1), a.shape[1]))
+        need(_all(self.F.val(p) < 2 * self.q), "fe_to_canon_words: fe_canon's operand reaches 2q")
+        return self.words(self.canon(p), "fe_to_canon_words")
 
 
 # ---- values with bounds: the call sites of ecpt_impl.hip.h -----------------------------------------------------------------------
@@ -427,12 +437,22 @@ class Curve:
             return self.B.is_zero_m(a, site)
         return self.B.is_zero_m(a[0], site) & self.B.is_zero_m(a[1], site)
 
-    def cf_inv(self, a):
+    def cf_inv(self, a, replay=False):
         B = self.B
         if not self.g2:
-            return B.inv(a)
-        n = B.inv(B.renorm(B.add(B.mul(a[0], a[0], "cf_inv: "), B.mul(a[1], a[1], "cf_inv: "))))
+            return B.inv(a, replay)
+        n = B.inv(B.renorm(B.add(B.mul(a[0], a[0], "cf_inv: "), B.mul(a[1], a[1], "cf_inv: "))), replay)
         return (B.mul(a[0], n, "cf_inv: "), B.mul(B.sub(2, B.zero(self.n_of(a)), a[1], "cf_inv: "), n, "cf_inv: "))
+
+    # -- pairing_impl.hip.h's additions to cf (the twist only) --
+    def cf_red(self, a): return (self.B.renorm(a[0]), self.B.renorm(a[1]))
+    def cf_neg(self, a, site=""): return self.cf_sub(2, self.cf_zero(self.n_of(a)), a, site + "cf_neg: ")
+    def cf_scale(self, a, s, site=""): return (self.B.mul(a[0], s, site + "cf_scale: "), self.B.mul(a[1], s, site + "cf_scale: "))
+
+    def to_canon_words(self, a, site=""):
+        """one Fq value (a V) -> (NL, n) canonical words"""
+        need(a.ub <= self.B.cap, f"{site}fe_to_canon_words: the operand is too large for the product with 1")
+        return self.B.m.to_canon_words(a.l)
 
     def cf_val(self, a):
         """residues mod q: an (n,) array (G1) or a pair of them"""

@@ -94,3 +94,17 @@ def test_batches_of_1_and_9_equal_single_calls(dev, tag):
     for i in (0, 4, 7, 8):
         assert pair(dev, tag, [pairs[i]])[0] == batch[i]
     assert len({tuple(x) for x in batch}) == 9
+
+
+@pytest.mark.parametrize("tag", list(CURVES))
+def test_nine_random_pairs_equal_the_model_miller_value_and_its_exponentiation(dev, tag):
+    """[a]G1, [b]G2 with a, b uniform below r: the value miller_kernel leaves is pairing_constants.Model.miller's exactly (the same line
+    scalings), and Model.final_exp of it is the full call.  Milliseconds on the host, where the oracle costs seconds."""
+    C, _, nl = CURVES[tag]
+    M = pc.Model(C)
+    rng = random.Random(254 + nl)
+    pairs = [(C.g1_mul(rng.randrange(C.r), C.g1), C.g2_mul(rng.randrange(C.r), C.g2)) for _ in range(9)]
+    f, e = pair(dev, tag, pairs, final_exp=False), pair(dev, tag, pairs)
+    for i, pq in enumerate(pairs):
+        assert f12(f[i]) == M.miller([pq]), f"pair {i}: the Miller value"
+        assert M.final_exp(f12(f[i])) == f12(e[i]), f"pair {i}: the exponentiation"

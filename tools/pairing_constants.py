@@ -152,30 +152,42 @@ class Model:
         sign = [-1, 1, -1, 1, -1, 1]
         return [C.f2add(C.f2scale(src[k], 3), C.f2scale(a[k], 2 * sign[k])) for k in range(6)]
 
+    def line_dbl(self, T):
+        """one doubling step on the Jacobian T = (X, Y, Z): ([2]T, the line's (cY, cX, c0))"""
+        C = self.C
+        m, s, sc = C.f2mul, C.f2sub, C.f2scale
+        X, Y, Z = T
+        A, B, ZZ = m(X, X), m(Y, Y), m(Z, Z)
+        S = sc(m(X, B), 4); M = sc(A, 3)
+        X3 = s(m(M, M), sc(S, 2)); Z3 = sc(m(Y, Z), 2)
+        Y3 = s(m(M, s(S, X3)), sc(m(B, B), 8))
+        return (X3, Y3, Z3), (m(Z3, ZZ), C.f2neg(m(M, ZZ)), s(m(M, X), sc(B, 2)))
+    def line_add(self, T, x2, y2):
+        """one addition step: (T + (x2, y2), the line's (cY, cX, c0))"""
+        C = self.C
+        m, s, sc = C.f2mul, C.f2sub, C.f2scale
+        X, Y, Z = T
+        ZZ = m(Z, Z)
+        H, Rr = s(m(x2, ZZ), X), s(m(y2, m(ZZ, Z)), Y)
+        HH = m(H, H); HHH = m(H, HH); V = m(X, HH)
+        X3 = s(s(m(Rr, Rr), HHH), sc(V, 2)); Z3 = m(Z, H)
+        Y3 = s(m(Rr, s(V, X3)), m(Y, HHH))
+        return (X3, Y3, Z3), (Z3, C.f2neg(Rr), s(m(Rr, x2), m(y2, Z3)))
     def lines(self, Q):
         """the line coefficients (cY, cX, c0) of every step of the loop for the twist point Q = (x, y): Jacobian steps, no inversion"""
         C = self.C
-        m, s, a, sc = C.f2mul, C.f2sub, C.f2add, C.f2scale
+        m, sc = C.f2mul, C.f2scale
         xq, yq = Q
-        T = [xq, yq, (1, 0)]
+        T = (xq, yq, (1, 0))
         out = []
         def dbl():
-            X, Y, Z = T
-            A, B, ZZ = m(X, X), m(Y, Y), m(Z, Z)
-            S = sc(m(X, B), 4); M = sc(A, 3)
-            X3 = s(m(M, M), sc(S, 2)); Z3 = sc(m(Y, Z), 2)
-            Y3 = s(m(M, s(S, X3)), sc(m(B, B), 8))
-            out.append((m(Z3, ZZ), C.f2neg(m(M, ZZ)), s(m(M, X), sc(B, 2))))
-            T[:] = [X3, Y3, Z3]
+            nonlocal T
+            T, ln = self.line_dbl(T)
+            out.append(ln)
         def add(x2, y2):
-            X, Y, Z = T
-            ZZ = m(Z, Z)
-            H, Rr = s(m(x2, ZZ), X), s(m(y2, m(ZZ, Z)), Y)
-            HH = m(H, H); HHH = m(H, HH); V = m(X, HH)
-            X3 = s(s(m(Rr, Rr), HHH), sc(V, 2)); Z3 = m(Z, H)
-            Y3 = s(m(Rr, s(V, X3)), m(Y, HHH))
-            out.append((Z3, C.f2neg(Rr), s(m(Rr, x2), m(y2, Z3))))
-            T[:] = [X3, Y3, Z3]
+            nonlocal T
+            T, ln = self.line_add(T, x2, y2)
+            out.append(ln)
         for i in range(C.loop.bit_length() - 2, -1, -1):
             dbl()
             if (C.loop >> i) & 1: add(xq, yq)
