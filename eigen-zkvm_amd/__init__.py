@@ -69,6 +69,9 @@ EXPORTS = [
     "zk_g1_bn254_mul_scalars_glv_dev", "zk_g1_bls12_381_mul_scalars_glv_dev",
     "zk_pairing_product_bn254", "zk_pairing_product_bn254_dev", "zk_pairing_product_bls12_381", "zk_pairing_product_bls12_381_dev",
     "zk_groth16_verify_aggregate", "zk_groth16_verify_aggregate_dev", "zk_groth16_verify_aggregate_timing", "zk_groth16_proof_words",
+    "zk_kzg_tile_elems", "zk_kzg_aggregate_span", "zk_kzg_bn254_divide_dev", "zk_kzg_bls12_381_divide_dev", "zk_kzg_bn254_lincomb_dev", "zk_kzg_bls12_381_lincomb_dev",
+    "zk_kzg_new", "zk_kzg_free", "zk_kzg_info", "zk_kzg_commit_dev", "zk_kzg_commit_evals_dev", "zk_kzg_eval_dev", "zk_kzg_open_dev", "zk_kzg_open_many_dev",
+    "zk_kzg_fold_commitments", "zk_kzg_verify", "zk_kzg_verify_dev",
 ]
 
 # include/zkgpu.h enums
@@ -376,6 +379,22 @@ def _load():
         "zk_groth16_verify_aggregate_dev": (C.c_int, [vp, vp, vp, C.c_uint64, vp, vp, vp, vp]),
         "zk_groth16_verify_aggregate_timing": (C.c_int, [vp]),
         "zk_groth16_proof_words": (C.c_int, [vp, C.c_char_p, C.c_char_p, vp, vp]),
+        "zk_kzg_tile_elems": (C.c_uint64, []), "zk_kzg_aggregate_span": (C.c_uint64, []),
+        "zk_kzg_bn254_divide_dev": (C.c_int, [vp, C.c_uint64, vp, vp, vp, vp]),
+        "zk_kzg_bls12_381_divide_dev": (C.c_int, [vp, C.c_uint64, vp, vp, vp, vp]),
+        "zk_kzg_bn254_lincomb_dev": (C.c_int, [vp, vp, C.c_uint32, vp, vp, vp]),
+        "zk_kzg_bls12_381_lincomb_dev": (C.c_int, [vp, vp, C.c_uint32, vp, vp, vp]),
+        "zk_kzg_new": (vp, [vp, C.c_uint64]),
+        "zk_kzg_free": (C.c_int, [vp]),
+        "zk_kzg_info": (C.c_int, [vp, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "zk_kzg_commit_dev": (C.c_int, [vp, vp, C.c_uint64, vp, vp]),
+        "zk_kzg_commit_evals_dev": (C.c_int, [vp, vp, C.c_uint32, vp, vp]),
+        "zk_kzg_eval_dev": (C.c_int, [vp, vp, C.c_uint64, vp, vp, vp]),
+        "zk_kzg_open_dev": (C.c_int, [vp, vp, C.c_uint64, vp, vp, vp, vp]),
+        "zk_kzg_open_many_dev": (C.c_int, [vp, vp, vp, C.c_uint32, vp, vp, vp, vp, vp]),
+        "zk_kzg_fold_commitments": (C.c_int, [vp, vp, C.c_uint32, vp, vp]),
+        "zk_kzg_verify": (C.c_int, [vp, vp, C.c_uint64, vp, C.POINTER(C.c_int), vp]),
+        "zk_kzg_verify_dev": (C.c_int, [vp, vp, C.c_uint64, vp, C.POINTER(C.c_int), vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -398,6 +417,9 @@ def __getattr__(name):
     if name == "PilCheck":
         import importlib
         return importlib.import_module(__name__ + ".stark").PilCheck
+    if name in ("Kzg", "divide"):                       # kzg.py (KZG commitments over a powers-of-tau file), fetched the same way
+        import importlib
+        return getattr(importlib.import_module(__name__ + ".kzg"), name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 

@@ -843,6 +843,70 @@ int zk_groth16_verify_aggregate_dev(const zk_groth16_vk_t* vk, const void* d_pro
         groth16_verify_aggregate_dev(vk, d_proofs, d_publics, n, seed, first_bad != nullptr, verdict, first_bad, on_stream((hipStream_t)stream));
     });
 }
+// ---- KZG commitments over a powers-of-tau file (kzg.hip) ----
+uint64_t zk_kzg_tile_elems(void) { return KZG_TILE; }
+uint64_t zk_kzg_aggregate_span(void) { return KZG_SPAN; }
+#define ZK_KZG_API(NAME, ID)                                                                                                                  \
+    int zk_kzg_##NAME##_divide_dev(const uint64_t* d_coeffs, uint64_t n, const uint64_t* z, uint64_t* d_q, uint64_t* d_y, void* stream) {     \
+        return guard([&] { kzg_divide_dev(curve(ID), d_coeffs, n, z, d_q, d_y, on_stream((hipStream_t)stream)); });                           \
+    }                                                                                                                                         \
+    int zk_kzg_##NAME##_lincomb_dev(const uint64_t* const* d_polys, const uint64_t* n, uint32_t k, const uint64_t* gamma, uint64_t* d_out, void* stream) { \
+        return guard([&] { kzg_lincomb_dev(curve(ID), d_polys, n, k, gamma, d_out, on_stream((hipStream_t)stream)); });                       \
+    }
+ZK_KZG_API(bn254, CURVE_BN254)
+ZK_KZG_API(bls12_381, CURVE_BLS12_381)
+#undef ZK_KZG_API
+zk_kzg_t* zk_kzg_new(const zk_srs_t* srs, uint64_t max_coeffs) {
+    zk_kzg_t* out = nullptr;
+    if (guard([&] { out = kzg_new(srs, max_coeffs); }) != 0) return nullptr;
+    return out;
+}
+int zk_kzg_free(zk_kzg_t* k) {
+    return guard([&] { delete k; });
+}
+int zk_kzg_info(const zk_kzg_t* k, const char** curve, uint64_t* max_coeffs, uint32_t* power, uint32_t* point_bytes, uint32_t* opening_bytes) {
+    return guard([&] {
+        ZK_REQUIRE(k, "kzg: null handle");
+        if (curve) *curve = k->curve->name;
+        if (max_coeffs) *max_coeffs = k->max_coeffs;
+        if (power) *power = k->power;
+        if (point_bytes) *point_bytes = (uint32_t)k->curve->point_bytes(G1);
+        if (opening_bytes) *opening_bytes = (uint32_t)(2 * k->curve->point_bytes(G1) + 64);
+    });
+}
+int zk_kzg_commit_dev(zk_kzg_t* k, const uint64_t* d_coeffs, uint64_t n, void* d_out, void* stream) {
+    return guard([&] { ZK_REQUIRE(k, "kzg: null handle"); kzg_commit_dev(*k, d_coeffs, n, d_out, on_stream((hipStream_t)stream)); });
+}
+int zk_kzg_commit_evals_dev(zk_kzg_t* k, const uint64_t* d_evals, uint32_t log_n, void* d_out, void* stream) {
+    return guard([&] { ZK_REQUIRE(k, "kzg: null handle"); kzg_commit_evals_dev(*k, d_evals, log_n, d_out, on_stream((hipStream_t)stream)); });
+}
+int zk_kzg_eval_dev(zk_kzg_t* k, const uint64_t* d_coeffs, uint64_t n, const uint64_t* z, uint64_t* d_y_out, void* stream) {
+    return guard([&] { ZK_REQUIRE(k, "kzg: null handle"); kzg_divide_dev(*k->curve, d_coeffs, n, z, nullptr, d_y_out, on_stream((hipStream_t)stream)); });
+}
+int zk_kzg_open_dev(zk_kzg_t* k, const uint64_t* d_coeffs, uint64_t n, const uint64_t* z, uint64_t* d_y_out, void* d_w_out, void* stream) {
+    return guard([&] { ZK_REQUIRE(k, "kzg: null handle"); kzg_open_dev(*k, d_coeffs, n, z, d_y_out, d_w_out, on_stream((hipStream_t)stream)); });
+}
+int zk_kzg_open_many_dev(zk_kzg_t* k, const uint64_t* const* d_polys, const uint64_t* n, uint32_t n_polys, const uint64_t* z, const uint64_t* gamma,
+                         uint64_t* d_ys_out, void* d_w_out, void* stream) {
+    return guard([&] { ZK_REQUIRE(k, "kzg: null handle"); kzg_open_many_dev(*k, d_polys, n, n_polys, z, gamma, d_ys_out, d_w_out, on_stream((hipStream_t)stream)); });
+}
+int zk_kzg_fold_commitments(zk_kzg_t* k, const void* commitments, uint32_t n, const uint64_t* gamma, void* out) {
+    return guard([&] { ZK_REQUIRE(k, "kzg: null handle"); kzg_fold_commitments(*k, commitments, n, gamma, out); });
+}
+int zk_kzg_verify(zk_kzg_t* k, const void* openings, uint64_t m, const uint8_t* seed, int* verdict, uint64_t* first_bad) {
+    return guard([&] {
+        ZK_REQUIRE(k && verdict, "kzg verify: null argument");
+        *verdict = ZK_VERDICT_ERROR;
+        kzg_verify(*k, openings, m, seed, first_bad != nullptr, verdict, first_bad);
+    });
+}
+int zk_kzg_verify_dev(zk_kzg_t* k, const void* d_openings, uint64_t m, const uint8_t* seed, int* verdict, uint64_t* first_bad, void* stream) {
+    return guard([&] {
+        ZK_REQUIRE(k && verdict, "kzg verify: null argument");
+        *verdict = ZK_VERDICT_ERROR;
+        kzg_verify_dev(*k, d_openings, m, seed, first_bad != nullptr, verdict, first_bad, on_stream((hipStream_t)stream));
+    });
+}
 int zk_groth16_verify_aggregate_timing(double* ms) {
     return guard([&] { ZK_REQUIRE(ms, "groth16 verify: null argument"); groth16_verify_aggregate_timing(ms); });
 }

@@ -9,6 +9,7 @@ struct zk_groth16_setup;
 struct zk_groth16_keygen;
 struct zk_groth16_vk;
 struct zk_srs;
+struct zk_kzg;
 
 namespace zk {
 
@@ -16,6 +17,7 @@ using Groth16Setup = ::zk_groth16_setup;
 using Groth16Key = ::zk_groth16_keygen;
 using Groth16Vk = ::zk_groth16_vk;
 using Srs = ::zk_srs;
+using Kzg = ::zk_kzg;
 namespace g16 { struct Circuit; struct Params; }
 // what miller_kernel takes (pairing_impl.hip.h): up to three pairs per item -- G1 points, line tables and infinity words with their strides
 struct MillerArgs {
@@ -67,7 +69,26 @@ struct Groth16Ops {
     void (*kc_coeffs_dev)(const KcMatrix& M, const u32* d_rho, u32 ni, u32 bound, int logm, u32* d_pub, u32* d_aux, u32* d_sum, double* ms, hipStream_t st);
     // ceremony_impl.hip.h: out_i = s t^(i0 + i), i < n, as 8 canonical words each; d_tab: 30 x 8 words Montgomery (fr_host.h): s, then t^(2^j), j < 29
     void (*powers_dev)(const u32* d_tab, u64 i0, u64 n, u32* d_out, hipStream_t st);
+    // n Fr elements (4 x u64 Montgomery, the transforms' layout) -> the canonical scalars the sums take (8 words each): the prover's two
+    // layout kernels back to back (frntt_impl.hip.h)
+    void (*fr_to_canon_dev)(const u64* d_mont, u64 n, u32* d_canon, hipStream_t st);
 };
+// ---- kzg.hip: the polynomial side of a KZG opening over the scalar field (kzg_impl.hip.h)
+struct KzgOps {
+    // y = p(z) (8 canonical words, device) and, when d_q is not null, q_j = sum_{i > j} c_i z^(i - j - 1), j < n - 1: Montgomery words as the
+    // coefficients are, or with q_canon the canonical scalars of the sums.  z: 8 canonical words on the host, below r
+    // d_table: the block table_dev made for the same z (table_bytes() bytes: the square chain of z and z^0 .. z^(T-1)), or null to make one for this call
+    void (*divide_dev)(const u64* d_coeffs, u64 n, const u32* z, const void* d_table, u64* d_q, bool q_canon, u32* d_y, hipStream_t st);
+    size_t (*table_bytes)();
+    void (*table_dev)(const u32* z, void* d_table, hipStream_t st);
+    // out_j = sum_i gamma^i p_i[j], j < n_max; d_polys / d_lens: k pointers and lengths in device memory
+    void (*lincomb_dev)(const u64* const* d_polys, const u64* d_lens, u32 k, u64 n_max, const u32* gamma, u64* d_out, hipStream_t st);
+    // m openings `stride` words apart, z at word z_off and y behind it: d_rz_j = rho_j z_j mod r, d_y_j = y_j packed (8 canonical words each),
+    // d_flag_j = 1 when z_j is not below r
+    void (*weights_dev)(const u32* d_open, u64 stride, u64 z_off, u64 m, const u32* d_rho, u32* d_rz, u32* d_y, u32* d_flag, hipStream_t st);
+};
+const KzgOps& kzg_ops(CurveId id);
+constexpr uint64_t KZG_TILE = 2048, KZG_SPAN = 512;   // coefficients per workgroup; tile aggregates per step of the combining workgroup
 // ---- pairing.hip: the steps of the optimal ate pairing and of Groth16 verification (pairing_impl.hip.h)
 struct PairingOps {
     const char* q_hex;                                                      // the base field's modulus
@@ -128,6 +149,7 @@ struct Curve {
     const Groth16Ops& groth16() const { return groth16_ops(id); }
     const PairingOps& pairing() const { return pairing_ops(id); }
     const EcOps& ec() const { return ec_ops(id); }
+    const KzgOps& kzg() const { return kzg_ops(id); }
 };
 inline const Curve CURVES[2] = {
     {CURVE_BN254, "BN128", "bn254", 8, {0xf0000001u, 0x43e1f593u, 0x79b97091u, 0x2833e848u, 0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u}},
@@ -217,6 +239,20 @@ int groth16_proof_words(const Groth16Vk* vk, const char* proof_json, const char*
 // checks, scalar products, lines and Miller loops, product, sums, tail
 void groth16_verify_aggregate_timing(double ms[6]);
 
+// ---- kzg.hip: KZG commitments over a powers-of-tau file.  Polynomials: coefficients in the transforms' layout; z, gamma: 8
+// canonical words on the host; results as include/zkgpu.h states them
+Kzg* kzg_new(const Srs* srs, uint64_t max_coeffs);
+void kzg_divide_dev(const Curve& cv, const uint64_t* d_coeffs, uint64_t n, const uint64_t* z, uint64_t* d_q, uint64_t* d_y, hipStream_t st);
+void kzg_lincomb_dev(const Curve& cv, const uint64_t* const* d_polys, const uint64_t* n, uint32_t k, const uint64_t* gamma, uint64_t* d_out, hipStream_t st);
+void kzg_commit_dev(Kzg& k, const uint64_t* d_coeffs, uint64_t n, void* d_out, hipStream_t st);
+void kzg_commit_evals_dev(Kzg& k, const uint64_t* d_evals, uint32_t log_n, void* d_out, hipStream_t st);
+void kzg_open_dev(Kzg& k, const uint64_t* d_coeffs, uint64_t n, const uint64_t* z, uint64_t* d_y_out, void* d_w_out, hipStream_t st);
+void kzg_open_many_dev(Kzg& k, const uint64_t* const* d_polys, const uint64_t* n, uint32_t n_polys, const uint64_t* z, const uint64_t* gamma, uint64_t* d_ys_out, void* d_w_out,
+                       hipStream_t st);
+void kzg_fold_commitments(Kzg& k, const void* commitments, uint32_t n, const uint64_t* gamma, void* out);
+void kzg_verify_dev(Kzg& k, const void* d_openings, uint64_t m, const uint8_t* seed, bool locate, int* verdict, uint64_t* first_bad, hipStream_t st);
+void kzg_verify(Kzg& k, const void* openings, uint64_t m, const uint8_t* seed, bool locate, int* verdict, uint64_t* first_bad);
+
 }  // namespace zk
 
 // the opaque handles of include/zkgpu.h
@@ -240,6 +276,16 @@ struct zk_srs {              // a powers-of-tau file, read and measured; the sec
     uint32_t power = 0, ceremony_power = 0;
     std::vector<uint8_t> file;
     size_t off[7] = {};      // by section id (2 tauG1, 3 tauG2, 4 alphaTauG1, 5 betaTauG1, 6 betaG2): where the payload starts
+};
+struct zk_kzg {              // the G1 powers of a file on the device, and what verification pairs against (kzg.hip)
+    const zk::Curve* curve = nullptr;
+    uint32_t power = 0;
+    uint64_t max_coeffs = 0;
+    void *d_tau = nullptr, *d_table = nullptr;       // tauG1[0, max_coeffs) as the sums take it; its window tables, when built
+    void *d_gen1 = nullptr, *d_g2 = nullptr;         // G1; G2 || -tauG2[1]
+    void* d_lagrange[32] = {};                       // by log_n: iNTT(tauG1[0, 2^log_n)), made and waited for on first use; like every handle, one call at a time
+    zk_kzg() = default; zk_kzg(const zk_kzg&) = delete; zk_kzg& operator=(const zk_kzg&) = delete;
+    ~zk_kzg() { for (void* p : {d_tau, d_table, d_gen1, d_g2}) if (p) zk::pool_free(p); for (void* p : d_lagrange) if (p) zk::pool_free(p); }
 };
 struct zk_groth16_vk {       // a verification key, checked and prepared
     const zk::Curve* curve = nullptr;

@@ -332,6 +332,16 @@ void FRN_FN(ntt_dev)(u64* d_data, int logn, bool inverse, bool coset, hipStream_
     ZK_HIP(hipStreamSynchronize(st));   // A, B go back to the pool
 }
 
+// Fr elements as the transforms take them (4 x u64 Montgomery, element-major) -> canonical scalars for the sums: the two layout kernels above
+void FRN_FN(fr_to_canon_dev)(const u64* d_mont, u64 n, u32* d_canon, hipStream_t st) {
+    if (!n) return;
+    DevBuf A;
+    A.reserve(n * NR * 4);
+    hipLaunchKernelGGL(frn_from_std_kernel, dim3(frn_blocks(n)), dim3(256), 0, st, (const u32*)d_mont, (u32*)A.p, n, n);
+    hipLaunchKernelGGL(frn_to_canon_kernel, dim3(frn_blocks(n)), dim3(256), 0, st, (const u32*)A.p, d_canon, n, n);
+    ZK_HIP(hipGetLastError());
+}
+
 // prover.rs create_proof's `h` block on limb-major a, b, c (row evaluations, values < 2q): on return the buffer
 // returned holds the n coefficients of (A B - C)/Z (the last one is zero for a satisfied system and is dropped by
 // the caller).  t0..t2: scratch of the same size.

@@ -321,9 +321,9 @@ namespace bls12381fr {
 }  // namespace bls12381fr
 
 const Groth16Ops& groth16_ops(CurveId id) {   // the table's slice of this unit (curve.h)
-    static const Groth16Ops OPS[2] = {{bn254fr::ntt_dev, bn254fr::quotient_dev, bn254fr::setup_new, bn254fr::keygen_run, bn254fr::verify_sums_dev, bn254fr::kc_coef_dev, bn254fr::kc_coeffs_dev, bn254fr::powers_dev},
+    static const Groth16Ops OPS[2] = {{bn254fr::ntt_dev, bn254fr::quotient_dev, bn254fr::setup_new, bn254fr::keygen_run, bn254fr::verify_sums_dev, bn254fr::kc_coef_dev, bn254fr::kc_coeffs_dev, bn254fr::powers_dev, bn254fr::fr_to_canon_dev},
                                       {bls12381fr::ntt_dev, bls12381fr::quotient_dev, bls12381fr::setup_new, bls12381fr::keygen_run, bls12381fr::verify_sums_dev,
-                                       bls12381fr::kc_coef_dev, bls12381fr::kc_coeffs_dev, bls12381fr::powers_dev}};
+                                       bls12381fr::kc_coef_dev, bls12381fr::kc_coeffs_dev, bls12381fr::powers_dev, bls12381fr::fr_to_canon_dev}};
     return OPS[id];
 }
 

@@ -843,6 +843,59 @@ int zk_points_check_bn254_dev(int group, const void* d_points, uint64_t n, int p
 int zk_points_check_bls12_381(int group, const void* points, uint64_t n, int plain, uint64_t* out);
 int zk_points_check_bls12_381_dev(int group, const void* d_points, uint64_t n, int plain, uint64_t* d_out, void* stream);
 
+/* ---- KZG commitments over a powers-of-tau file: commit, open, verify (csrc/kzg.hip, csrc/kzg_impl.hip.h) ----------
+ * The family of snarkjs `ffs` / `fff` / `ffv` (test/snark_verifier.sh:67-106: PLONK, fflonk) stands on two operations over the tauG1
+ * section of a .ptau file: C = [p(tau)] G1, and for a point z the value y = p(z) with the witness W = [q(tau)] G1, q = (p - y) / (X - z).
+ * Commitments are in G1 and are NOT hiding: no blinding term is added, C is a function of p alone.
+ * Polynomials are coefficient vectors, lowest degree first, in the layout zk_fr_<curve>_ntt_dev keeps (4 x u64 Montgomery R = 2^256 per
+ * coefficient).  A point z and a value y are 32 B canonical little-endian, below r.  A commitment or witness on the device is the point
+ * in the layout of the sums followed by the 4-byte infinity word (zk_msm_*_dev's d_out); on the host the all-zero encoding is infinity.
+ * zk_kzg_<curve>_divide_dev needs no file: d_q[j] = sum_{i > j} d_coeffs[i] z^(i - j - 1) for j < n - 1 (same layout as d_coeffs; may be
+ *   NULL: evaluation only, nothing but y is written) and d_y = p(z) (32 B canonical, device).  z is read from HOST memory before the call
+ *   returns.  A tiled scan of affine maps (z^len, value): zk_kzg_tile_elems() coefficients per workgroup, the tile aggregates combined by
+ *   one workgroup that walks them zk_kzg_aggregate_span() at a time.  No inverse of z (z = 0 is fine), no atomics, bit-exact.
+ * zk_kzg_<curve>_lincomb_dev: d_out[j] = sum_i gamma^i p_i[j] for j < max n_i; d_polys, n: HOST arrays of k device pointers / lengths;
+ *   shorter polynomials count as zero-padded; gamma 32 B canonical on the host.
+ * zk_kzg_new uploads tauG1[0, max_coeffs) of the file once (max_coeffs = 0: all 2^(power + 1) - 1; more than the file has is an error
+ *   raised before any device work), keeps G2 and -tauG2[1], and builds window tables for the sums when there are fewer than 2^24 points
+ *   (the policy of zk_groth16_setup_new).  The file is trusted as zk_groth16_keygen_from_srs trusts it: run zk_srs_check first.
+ * zk_kzg_commit_dev: n <= max_coeffs; n = 0 and the zero polynomial give infinity.  zk_kzg_commit_evals_dev: the commitment to the
+ *   polynomial of degree < 2^log_n whose values on the domain of zk_fr_<curve>_ntt are d_evals (same layout), through the Lagrange basis
+ *   iNTT(tauG1[0, 2^log_n)) in the group, made on first use of a log_n and cached in the handle; 2^log_n <= max_coeffs, log_n <= power.
+ * zk_kzg_open_dev: d_y_out (32 B canonical, device) and d_w_out = [q(tau)] G1; n <= 1 gives W = infinity.
+ * zk_kzg_open_many_dev: d_ys_out = the k values p_i(z) and one witness for f = sum_i gamma^i p_i.  The verifier folds: C = sum gamma^i C_i
+ *   (zk_kzg_fold_commitments: host points in, one host point out; an all-zero point is infinity), y = sum gamma^i y_i.
+ * zk_kzg_verify: m openings, each C || z || y || W (point_bytes + 32 + 32 + point_bytes, host; _dev: device).  With weights rho_j
+ *   (m = 1: rho = 1; m > 1: secret, 128 bits) L = sum rho_j C_j - [sum rho_j y_j] G1 + sum [rho_j z_j] W_j, R = sum rho_j W_j, and the
+ *   batch is accepted when e(L, G2) e(R, -tau G2) = 1: two Miller loops and one final exponentiation whatever m is.  A batch that holds a
+ *   wrong opening is accepted with probability about 2^-128 over the weights.  seed: as in zk_groth16_verify_aggregate -- 32 bytes, FOR
+ *   TESTS ONLY, NULL anywhere else.  Verdicts are the ZK_VERDICT_* codes: C and W must be on the curve (a coordinate >= q counts as off
+ *   it) and in the subgroup, infinity is legal for both, z and y must be below r (ZK_VERDICT_INPUT_NOT_CANONICAL).  On refusal with
+ *   first_bad != NULL the openings are checked one by one: *first_bad = the first one not accepted, *verdict = its code; with first_bad ==
+ *   NULL *verdict = ZK_VERDICT_REJECTED.  Accepted batches leave *first_bad = m.  m = 0 is accepted.  Both forms synchronise.
+ * A handle is bound to the device current at its creation and is not re-entrant: one call at a time per handle, from any thread or stream
+ *   (the Lagrange basis of a log_n is made, and waited for, inside the first zk_kzg_commit_evals_dev that asks for it).
+ * Not built: hiding commitments, commitments in G2, openings of one polynomial at several points.                                    */
+typedef struct zk_kzg zk_kzg_t;
+uint64_t zk_kzg_tile_elems(void);
+uint64_t zk_kzg_aggregate_span(void);
+int zk_kzg_bn254_divide_dev(const uint64_t* d_coeffs, uint64_t n, const uint64_t* z, uint64_t* d_q, uint64_t* d_y, void* stream);
+int zk_kzg_bls12_381_divide_dev(const uint64_t* d_coeffs, uint64_t n, const uint64_t* z, uint64_t* d_q, uint64_t* d_y, void* stream);
+int zk_kzg_bn254_lincomb_dev(const uint64_t* const* d_polys, const uint64_t* n, uint32_t k, const uint64_t* gamma, uint64_t* d_out, void* stream);
+int zk_kzg_bls12_381_lincomb_dev(const uint64_t* const* d_polys, const uint64_t* n, uint32_t k, const uint64_t* gamma, uint64_t* d_out, void* stream);
+zk_kzg_t* zk_kzg_new(const zk_srs_t* srs, uint64_t max_coeffs);
+int zk_kzg_free(zk_kzg_t* k);
+int zk_kzg_info(const zk_kzg_t* k, const char** curve, uint64_t* max_coeffs, uint32_t* power, uint32_t* point_bytes, uint32_t* opening_bytes);
+int zk_kzg_commit_dev(zk_kzg_t* k, const uint64_t* d_coeffs, uint64_t n, void* d_out, void* stream);
+int zk_kzg_commit_evals_dev(zk_kzg_t* k, const uint64_t* d_evals, uint32_t log_n, void* d_out, void* stream);
+int zk_kzg_eval_dev(zk_kzg_t* k, const uint64_t* d_coeffs, uint64_t n, const uint64_t* z, uint64_t* d_y_out, void* stream);
+int zk_kzg_open_dev(zk_kzg_t* k, const uint64_t* d_coeffs, uint64_t n, const uint64_t* z, uint64_t* d_y_out, void* d_w_out, void* stream);
+int zk_kzg_open_many_dev(zk_kzg_t* k, const uint64_t* const* d_polys, const uint64_t* n, uint32_t n_polys, const uint64_t* z, const uint64_t* gamma,
+                         uint64_t* d_ys_out, void* d_w_out, void* stream);
+int zk_kzg_fold_commitments(zk_kzg_t* k, const void* commitments, uint32_t n, const uint64_t* gamma, void* out);
+int zk_kzg_verify(zk_kzg_t* k, const void* openings, uint64_t m, const uint8_t* seed, int* verdict, uint64_t* first_bad);
+int zk_kzg_verify_dev(zk_kzg_t* k, const void* d_openings, uint64_t m, const uint8_t* seed, int* verdict, uint64_t* first_bad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
