@@ -72,6 +72,8 @@ EXPORTS = [
     "zk_kzg_tile_elems", "zk_kzg_aggregate_span", "zk_kzg_bn254_divide_dev", "zk_kzg_bls12_381_divide_dev", "zk_kzg_bn254_lincomb_dev", "zk_kzg_bls12_381_lincomb_dev",
     "zk_kzg_new", "zk_kzg_free", "zk_kzg_info", "zk_kzg_commit_dev", "zk_kzg_commit_evals_dev", "zk_kzg_eval_dev", "zk_kzg_open_dev", "zk_kzg_open_many_dev",
     "zk_kzg_fold_commitments", "zk_kzg_verify", "zk_kzg_verify_dev",
+    "zk_kzg_bn254_divide_acc_dev", "zk_kzg_bls12_381_divide_acc_dev", "zk_kzg_bn254_interleave_dev", "zk_kzg_bls12_381_interleave_dev",
+    "zk_kzg_multi_begin", "zk_kzg_multi_quotient", "zk_kzg_multi_finish", "zk_kzg_multi_free", "zk_kzg_multi_verify", "zk_kzg_multi_verify_dev",
 ]
 
 # include/zkgpu.h enums
@@ -395,6 +397,16 @@ def _load():
         "zk_kzg_fold_commitments": (C.c_int, [vp, vp, C.c_uint32, vp, vp]),
         "zk_kzg_verify": (C.c_int, [vp, vp, C.c_uint64, vp, C.POINTER(C.c_int), vp]),
         "zk_kzg_verify_dev": (C.c_int, [vp, vp, C.c_uint64, vp, C.POINTER(C.c_int), vp, vp]),
+        "zk_kzg_bn254_divide_acc_dev": (C.c_int, [vp, C.c_uint64, vp, vp, vp, vp, vp]),
+        "zk_kzg_bls12_381_divide_acc_dev": (C.c_int, [vp, C.c_uint64, vp, vp, vp, vp, vp]),
+        "zk_kzg_bn254_interleave_dev": (C.c_int, [vp, vp, C.c_uint32, vp, vp]),
+        "zk_kzg_bls12_381_interleave_dev": (C.c_int, [vp, vp, C.c_uint32, vp, vp]),
+        "zk_kzg_multi_begin": (vp, [vp, vp, vp, C.c_uint32, vp, vp, vp, vp]),
+        "zk_kzg_multi_quotient": (C.c_int, [vp, vp, vp, vp]),
+        "zk_kzg_multi_finish": (C.c_int, [vp, vp, vp, vp]),
+        "zk_kzg_multi_free": (C.c_int, [vp]),
+        "zk_kzg_multi_verify": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, vp, C.POINTER(C.c_int), vp]),
+        "zk_kzg_multi_verify_dev": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, vp, C.POINTER(C.c_int), vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -417,7 +429,7 @@ def __getattr__(name):
     if name == "PilCheck":
         import importlib
         return importlib.import_module(__name__ + ".stark").PilCheck
-    if name in ("Kzg", "divide"):                       # kzg.py (KZG commitments over a powers-of-tau file), fetched the same way
+    if name in ("Kzg", "divide", "divide_acc", "interleave"):   # kzg.py (KZG commitments over a powers-of-tau file), fetched the same way
         import importlib
         return getattr(importlib.import_module(__name__ + ".kzg"), name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

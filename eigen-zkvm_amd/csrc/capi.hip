@@ -907,6 +907,54 @@ int zk_kzg_verify_dev(zk_kzg_t* k, const void* d_openings, uint64_t m, const uin
         kzg_verify_dev(*k, d_openings, m, seed, first_bad != nullptr, verdict, first_bad, on_stream((hipStream_t)stream));
     });
 }
+// ---- KZG: several polynomials at several points in one two-point proof (kzg.hip) ----
+#define ZK_KZG_MULTI_API(NAME, ID)                                                                                                            \
+    int zk_kzg_##NAME##_divide_acc_dev(const uint64_t* d_coeffs, uint64_t n, const uint64_t* z, const uint64_t* w, uint64_t* d_acc_inout, uint64_t* d_y, \
+                                       void* stream) {                                                                                        \
+        return guard([&] { kzg_divide_acc_dev(curve(ID), d_coeffs, n, z, w, d_acc_inout, d_y, on_stream((hipStream_t)stream)); });            \
+    }                                                                                                                                         \
+    int zk_kzg_##NAME##_interleave_dev(const uint64_t* const* d_polys, const uint64_t* n, uint32_t k, uint64_t* d_out, void* stream) {        \
+        return guard([&] { kzg_interleave_dev(curve(ID), d_polys, n, k, d_out, on_stream((hipStream_t)stream)); });                           \
+    }
+ZK_KZG_MULTI_API(bn254, CURVE_BN254)
+ZK_KZG_MULTI_API(bls12_381, CURVE_BLS12_381)
+#undef ZK_KZG_MULTI_API
+zk_kzg_multi_t* zk_kzg_multi_begin(zk_kzg_t* k, const uint64_t* const* d_polys, const uint64_t* n, uint32_t n_polys, const uint64_t* points,
+                                   const uint32_t* set_sizes, uint64_t* d_values_out, void* stream) {
+    zk_kzg_multi_t* out = nullptr;
+    if (guard([&] {
+            ZK_REQUIRE(k, "kzg: null handle");
+            out = kzg_multi_begin(*k, d_polys, n, n_polys, points, set_sizes, d_values_out, on_stream((hipStream_t)stream));
+        }) != 0)
+        return nullptr;
+    return out;
+}
+int zk_kzg_multi_quotient(zk_kzg_multi_t* m, const uint64_t* gamma, void* d_w1_out, void* stream) {
+    return guard([&] { ZK_REQUIRE(m, "kzg multi: null handle"); kzg_multi_quotient(*m, gamma, d_w1_out, on_stream((hipStream_t)stream)); });
+}
+int zk_kzg_multi_finish(zk_kzg_multi_t* m, const uint64_t* z, void* d_w2_out, void* stream) {
+    return guard([&] { ZK_REQUIRE(m, "kzg multi: null handle"); kzg_multi_finish(*m, z, d_w2_out, on_stream((hipStream_t)stream)); });
+}
+int zk_kzg_multi_free(zk_kzg_multi_t* m) {
+    return guard([&] { delete m; });
+}
+int zk_kzg_multi_verify(zk_kzg_t* k, const void* proofs, uint64_t bytes, uint64_t m, const uint8_t* seed, int* verdict, uint64_t* first_bad) {
+    return guard([&] {
+        ZK_REQUIRE(k && verdict, "kzg multi verify: null argument");
+        *verdict = ZK_VERDICT_ERROR;
+        kzg_multi_verify(*k, proofs, bytes, m, seed, first_bad != nullptr, verdict, first_bad, cur_stream());
+    });
+}
+int zk_kzg_multi_verify_dev(zk_kzg_t* k, const void* d_proofs, uint64_t bytes, uint64_t m, const uint8_t* seed, int* verdict, uint64_t* first_bad, void* stream) {
+    return guard([&] {
+        ZK_REQUIRE(k && verdict && (d_proofs || !bytes), "kzg multi verify: null argument");
+        *verdict = ZK_VERDICT_ERROR;
+        hipStream_t st = on_stream((hipStream_t)stream);
+        std::vector<uint8_t> host(bytes);                                   // the scalars of a proof are derived on the host: the sets are tiny
+        if (bytes) { ZK_HIP(hipMemcpyAsync(host.data(), d_proofs, bytes, hipMemcpyDeviceToHost, st)); ZK_HIP(hipStreamSynchronize(st)); }
+        kzg_multi_verify(*k, host.data(), bytes, m, seed, first_bad != nullptr, verdict, first_bad, st);
+    });
+}
 int zk_groth16_verify_aggregate_timing(double* ms) {
     return guard([&] { ZK_REQUIRE(ms, "groth16 verify: null argument"); groth16_verify_aggregate_timing(ms); });
 }

@@ -10,6 +10,7 @@ struct zk_groth16_keygen;
 struct zk_groth16_vk;
 struct zk_srs;
 struct zk_kzg;
+struct zk_kzg_multi;
 
 namespace zk {
 
@@ -18,6 +19,7 @@ using Groth16Key = ::zk_groth16_keygen;
 using Groth16Vk = ::zk_groth16_vk;
 using Srs = ::zk_srs;
 using Kzg = ::zk_kzg;
+using KzgMulti = ::zk_kzg_multi;
 namespace g16 { struct Circuit; struct Params; }
 // what miller_kernel takes (pairing_impl.hip.h): up to three pairs per item -- G1 points, line tables and infinity words with their strides
 struct MillerArgs {
@@ -86,6 +88,10 @@ struct KzgOps {
     // m openings `stride` words apart, z at word z_off and y behind it: d_rz_j = rho_j z_j mod r, d_y_j = y_j packed (8 canonical words each),
     // d_flag_j = 1 when z_j is not below r
     void (*weights_dev)(const u32* d_open, u64 stride, u64 z_off, u64 m, const u32* d_rho, u32* d_rz, u32* d_y, u32* d_flag, hipStream_t st);
+    // divide_dev's phases 1 and 2, then d_out[j] = d_acc[j] + w q_j for j < n - 1 (Montgomery words; d_out may be d_acc); w: 8 canonical words, host
+    void (*divide_acc_dev)(const u64* d_coeffs, u64 n, const u32* z, const void* d_table, const u32* w, const u64* d_acc, u64* d_out, u32* d_y, hipStream_t st);
+    // d_out[j k + i] = p_i[j], j < n_max, zero where p_i is shorter; d_polys / d_lens as for lincomb_dev
+    void (*interleave_dev)(const u64* const* d_polys, const u64* d_lens, u32 k, u64 n_max, u64* d_out, hipStream_t st);
 };
 const KzgOps& kzg_ops(CurveId id);
 constexpr uint64_t KZG_TILE = 2048, KZG_SPAN = 512;   // coefficients per workgroup; tile aggregates per step of the combining workgroup
@@ -252,6 +258,14 @@ void kzg_open_many_dev(Kzg& k, const uint64_t* const* d_polys, const uint64_t* n
 void kzg_fold_commitments(Kzg& k, const void* commitments, uint32_t n, const uint64_t* gamma, void* out);
 void kzg_verify_dev(Kzg& k, const void* d_openings, uint64_t m, const uint8_t* seed, bool locate, int* verdict, uint64_t* first_bad, hipStream_t st);
 void kzg_verify(Kzg& k, const void* openings, uint64_t m, const uint8_t* seed, bool locate, int* verdict, uint64_t* first_bad);
+// several polynomials at several points in one two-point proof; w as z
+void kzg_divide_acc_dev(const Curve& cv, const uint64_t* d_coeffs, uint64_t n, const uint64_t* z, const uint64_t* w, uint64_t* d_acc, uint64_t* d_y, hipStream_t st);
+void kzg_interleave_dev(const Curve& cv, const uint64_t* const* d_polys, const uint64_t* n, uint32_t k, uint64_t* d_out, hipStream_t st);
+KzgMulti* kzg_multi_begin(Kzg& k, const uint64_t* const* d_polys, const uint64_t* n, uint32_t n_polys, const uint64_t* points, const uint32_t* set_sizes,
+                          uint64_t* d_values_out, hipStream_t st);
+void kzg_multi_quotient(KzgMulti& m, const uint64_t* gamma, void* d_w1_out, hipStream_t st);
+void kzg_multi_finish(KzgMulti& m, const uint64_t* z, void* d_w2_out, hipStream_t st);
+void kzg_multi_verify(Kzg& k, const void* proofs, uint64_t bytes, uint64_t m, const uint8_t* seed, bool locate, int* verdict, uint64_t* first_bad, hipStream_t st);
 
 }  // namespace zk
 
@@ -286,6 +300,19 @@ struct zk_kzg {              // the G1 powers of a file on the device, and what 
     void* d_lagrange[32] = {};                       // by log_n: iNTT(tauG1[0, 2^log_n)), made and waited for on first use; like every handle, one call at a time
     zk_kzg() = default; zk_kzg(const zk_kzg&) = delete; zk_kzg& operator=(const zk_kzg&) = delete;
     ~zk_kzg() { for (void* p : {d_tau, d_table, d_gen1, d_g2}) if (p) zk::pool_free(p); for (void* p : d_lagrange) if (p) zk::pool_free(p); }
+};
+struct zk_kzg_multi {        // an opening at several points between its stages (kzg.hip)
+    zk_kzg* k = nullptr;
+    std::vector<const uint64_t*> polys;              // the caller's, on the device, until finish
+    std::vector<uint64_t> n;
+    std::vector<uint32_t> sizes;                     // |S_i|
+    std::vector<uint64_t> points, values, gamma;     // 4 canonical words each: the sets one after another, f_i(s) in the same order
+    std::vector<uint32_t> table_of;                  // per point: its block of d_tables (one per distinct point, table_bytes() each)
+    void *d_tables = nullptr, *d_q = nullptr;        // q: nq coefficients, Montgomery words
+    uint64_t nq = 0;
+    int stage = 0;                                   // 1 after begin, 2 after quotient, 3 after finish
+    zk_kzg_multi() = default; zk_kzg_multi(const zk_kzg_multi&) = delete; zk_kzg_multi& operator=(const zk_kzg_multi&) = delete;
+    ~zk_kzg_multi() { for (void* p : {d_tables, d_q}) if (p) zk::pool_free(p); }
 };
 struct zk_groth16_vk {       // a verification key, checked and prepared
     const zk::Curve* curve = nullptr;

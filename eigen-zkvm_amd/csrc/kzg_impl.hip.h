@@ -13,7 +13,9 @@
 //                           time, carrying h across the steps; it leaves carry_b = h_((b+1)T) per tile and y.  Evaluation stops here
 //                           (carry of the last tile is h past the end, zero: the host zeroes the buffer, the kernel need not meet that entry)
 //   3. kz_fixup_kernel      per tile again: the suffixes of a lane's 8 coefficients in registers (Horner), the lanes' suffixes by a scan in LDS with
-//                           the tile's carry folded into the last lane, then every element fixed up by z^k . (what comes in from above)
+//                           the tile's carry folded into the last lane, then every element fixed up by z^k . (what comes in from above);
+//                           kz_fixup_acc_kernel is the same body adding w q to a running sum (openings at several points)
+//      kz_interleave_kernel stands apart: the permutation that combines k polynomials into one, sum_i f_i(X^k) X^i
 // Value bounds (fe29_impl.hip.h: A B <= 68 for a product of a < A r, b < B r): loaded coefficients, table entries and products are < 2r;
 // Horner suffixes < 4r; a scanned value grows by 2r per step from < 6r to < 22r, and meets only factors < 2r (44).
 constexpr int KZ_E = 8, KZ_BLOCK = 256, KZ_LOGT = 11, KZ_T = KZ_E * KZ_BLOCK, KZ_S = 512;
@@ -182,10 +184,17 @@ __global__ __launch_bounds__(KZ_BLOCK) void kz_combine_kernel(const u32* __restr
     }
 }
 
-// 3. q_j = h_(j+1) for the tile's elements.  CANON: 8 canonical words (the scalars of the sums) instead of Montgomery words
-template <bool CANON>
-__global__ __launch_bounds__(KZ_BLOCK) void kz_fixup_kernel(const u32* __restrict__ c, u64 n, const u32* __restrict__ tab, const KzConsts* __restrict__ kc,
-                                                            const u32* __restrict__ carry, u32* __restrict__ q) {
+// 3. q_j = h_(j+1) for the tile's elements, as one body for three ways of leaving them:
+//   KZ_Q_MONT   Montgomery words, as the coefficients are
+//   KZ_Q_CANON  8 canonical words (the scalars of the sums)
+//   KZ_Q_ACC    out_j = acc_j + w h_(j+1), Montgomery words in and out: the quotient by a vanishing polynomial is a weighted sum of quotients
+//               by X - s, and this mode adds one of them to the running sum.  Element j is read and written by the one lane that
+//               owns h_(j+1), so acc and out may be the same buffer (neither is __restrict__ in kz_fixup_acc_kernel).  Bounds: h < 6r meets
+//               w < 2r (12 <= 68), the product is < 2r; acc's words are any integer below 2^256 < 6r against CIN < r, so acc is < 2r on load;
+//               the sum < 4r meets COUT < r in fe_to_std, which leaves the canonical value.
+enum { KZ_Q_MONT = 0, KZ_Q_CANON = 1, KZ_Q_ACC = 2 };
+template <int MODE>
+__device__ __forceinline__ void kz_fixup_body(const u32* c, u64 n, const u32* tab, const KzConsts* kc, const u32* carry, u32* q, const u32* acc, const fe* wt) {
     __shared__ fe sh[KZ_BLOCK];
     const int t = threadIdx.x;
     const u64 base = (u64)blockIdx.x * KZ_T + (u64)t * KZ_E;
@@ -218,10 +227,46 @@ __global__ __launch_bounds__(KZ_BLOCK) void kz_fixup_kernel(const u32* __restric
         if (i >= 1 && i < n) {
             const fe h = fe_add(loc[k], fe_mul(k == 0 ? zE : kz_tab(tab, KZ_E - k, 0), inc));
             u32 w[NL];
-            if (CANON) fe_store_canon(h, w); else fe_to_std(h, w);
+            if constexpr (MODE == KZ_Q_ACC) {
+                kz_load_words(acc, i - 1, w);
+                fe_to_std(fe_add(fe_from_std(w), fe_mul(*wt, h)), w);
+            } else if constexpr (MODE == KZ_Q_CANON) fe_store_canon(h, w);
+            else fe_to_std(h, w);
             kz_store_words(q, i - 1, w);
         }
     });
+}
+template <bool CANON>
+__global__ __launch_bounds__(KZ_BLOCK) void kz_fixup_kernel(const u32* __restrict__ c, u64 n, const u32* __restrict__ tab, const KzConsts* __restrict__ kc,
+                                                            const u32* __restrict__ carry, u32* __restrict__ q) {
+    kz_fixup_body<CANON ? KZ_Q_CANON : KZ_Q_MONT>(c, n, tab, kc, carry, q, nullptr, nullptr);
+}
+__global__ __launch_bounds__(KZ_BLOCK) void kz_fixup_acc_kernel(const u32* __restrict__ c, u64 n, const u32* __restrict__ tab, const KzConsts* __restrict__ kc,
+                                                                const u32* __restrict__ carry, const fe* __restrict__ wt, const u32* acc, u32* out) {
+    kz_fixup_body<KZ_Q_ACC>(c, n, tab, kc, carry, out, acc, wt);
+}
+// the weight of an accumulating division, 8 canonical words -> internal form, < 2r
+__global__ void kz_weight_kernel(const KzWords w, fe* __restrict__ wt) {
+    if (threadIdx.x || blockIdx.x) return;
+    bool ok;
+    *wt = fe_mul(kz_split(w.w, ok), kz_rr2());
+}
+
+// Sum_i f_i(X^k) X^i, the combination of fflonk: out[j k + i] = f_i[j] for j < n_max, zero where f_i is shorter.  A permutation of 32-byte
+// elements; one lane per OUTPUT element, so a wave's stores are 2 KiB in a row and its loads are k strided streams that the neighbouring
+// waves complete.  The block's first element is divided by k once (uniform); a lane then divides a value below k + KZ_BLOCK.
+__global__ __launch_bounds__(KZ_BLOCK) void kz_interleave_kernel(const u64* const* __restrict__ polys, const u64* __restrict__ lens, u32 k, u64 total,
+                                                                 u32* __restrict__ out) {
+    const u64 e0 = (u64)blockIdx.x * KZ_BLOCK, e = e0 + threadIdx.x;
+    if (e >= total) return;
+    const u32 off = (u32)(e0 % k) + threadIdx.x;
+    const u64 j = e0 / k + off / k;
+    const u32 i = off % k;
+    u32 w[NL];
+#pragma unroll
+    for (int l = 0; l < NL; ++l) w[l] = 0;
+    if (j < lens[i]) kz_load_words((const u32*)polys[i], j, w);
+    kz_store_words(out, e, w);
 }
 
 // out_j = sum_i gamma^i p_i[j], Montgomery words in and out.  The words of x R are taken as the plain integer they are (< 2^256 < 6r) and
@@ -272,14 +317,14 @@ void table_dev(const u32* z, void* d_table, hipStream_t st) {
     hipLaunchKernelGGL(kz_table_kernel, dim3(KZ_T / KZ_BLOCK), dim3(KZ_BLOCK), 0, st, (const KzConsts*)d_table, (u32*)((uint8_t*)d_table + KZ_TAB_OFF));
     ZK_HIP(hipGetLastError());
 }
-// d_table: table_dev's block for this z, or null to build one for this call
-void divide_dev(const u64* d_coeffs, u64 n, const u32* z, const void* d_table, u64* d_q, bool q_canon, u32* d_y, hipStream_t st) {
+// The three phases.  mode: one of KZ_Q_*; d_q null: evaluation alone.  KZ_Q_ACC: d_q[j] = d_acc[j] + w h_(j+1) with w 8 canonical words on the host
+static void kz_divide(const u64* d_coeffs, u64 n, const u32* z, const void* d_table, u64* d_q, int mode, const u64* d_acc, const u32* w, u32* d_y, hipStream_t st) {
     ZK_REQUIRE(n < (1ull << 40), "kzg: more than 2^40 coefficients");
     if (n == 0) { ZK_HIP(hipMemsetAsync(d_y, 0, 4 * NL, st)); return; }
-    ZK_REQUIRE(((uintptr_t)d_coeffs | (uintptr_t)d_q) % 16 == 0, "kzg: coefficient vectors must be 16-byte aligned");
+    ZK_REQUIRE(((uintptr_t)d_coeffs | (uintptr_t)d_q | (uintptr_t)d_acc) % 16 == 0, "kzg: coefficient vectors must be 16-byte aligned");
     const u64 tiles = (n + KZ_T - 1) / KZ_T;
     const bool want_q = d_q && n > 1;
-    DevBuf own, agg, carry;
+    DevBuf own, agg, carry, wt;
     if (!d_table) { own.reserve(table_bytes()); table_dev(z, own.p, st); d_table = own.p; }
     const KzConsts* kc = (const KzConsts*)d_table;
     const u32* tab = (const u32*)((const uint8_t*)d_table + KZ_TAB_OFF);
@@ -293,9 +338,29 @@ void divide_dev(const u64* d_coeffs, u64 n, const u32* z, const void* d_table, u
     }
     hipLaunchKernelGGL(kz_combine_kernel, dim3(1), dim3(KZ_BLOCK), 0, st, (const u32*)agg.p, tiles, kc, want_q ? (u32*)carry.p : (u32*)nullptr, d_y);
     if (want_q) {
-        if (q_canon) hipLaunchKernelGGL(kz_fixup_kernel<true>, dim3((unsigned)tiles), dim3(KZ_BLOCK), 0, st, (const u32*)d_coeffs, n, tab, kc, (const u32*)carry.p, (u32*)d_q);
+        if (mode == KZ_Q_ACC) {
+            wt.reserve(sizeof(fe));
+            hipLaunchKernelGGL(kz_weight_kernel, dim3(1), dim3(64), 0, st, kz_words(w), (fe*)wt.p);
+            hipLaunchKernelGGL(kz_fixup_acc_kernel, dim3((unsigned)tiles), dim3(KZ_BLOCK), 0, st, (const u32*)d_coeffs, n, tab, kc, (const u32*)carry.p, (const fe*)wt.p,
+                               (const u32*)d_acc, (u32*)d_q);
+        } else if (mode == KZ_Q_CANON)
+            hipLaunchKernelGGL(kz_fixup_kernel<true>, dim3((unsigned)tiles), dim3(KZ_BLOCK), 0, st, (const u32*)d_coeffs, n, tab, kc, (const u32*)carry.p, (u32*)d_q);
         else hipLaunchKernelGGL(kz_fixup_kernel<false>, dim3((unsigned)tiles), dim3(KZ_BLOCK), 0, st, (const u32*)d_coeffs, n, tab, kc, (const u32*)carry.p, (u32*)d_q);
     }
+    ZK_HIP(hipGetLastError());
+}
+// d_table: table_dev's block for this z, or null to build one for this call
+void divide_dev(const u64* d_coeffs, u64 n, const u32* z, const void* d_table, u64* d_q, bool q_canon, u32* d_y, hipStream_t st) {
+    kz_divide(d_coeffs, n, z, d_table, d_q, q_canon ? KZ_Q_CANON : KZ_Q_MONT, nullptr, nullptr, d_y, st);
+}
+// d_out[j] = d_acc[j] + w q_j for j < n - 1 (Montgomery words; d_out may be d_acc) and y = p(z): phases 1 and 2 as divide_dev runs them
+void divide_acc_dev(const u64* d_coeffs, u64 n, const u32* z, const void* d_table, const u32* w, const u64* d_acc, u64* d_out, u32* d_y, hipStream_t st) {
+    kz_divide(d_coeffs, n, z, d_table, d_out, KZ_Q_ACC, d_acc, w, d_y, st);
+}
+// d_out[j k + i] = p_i[j] for j < n_max; d_polys, d_lens: k device pointers / lengths, on the device
+void interleave_dev(const u64* const* d_polys, const u64* d_lens, u32 k, u64 n_max, u64* d_out, hipStream_t st) {
+    if (n_max == 0) return;
+    hipLaunchKernelGGL(kz_interleave_kernel, dim3(kz_blocks(n_max * k)), dim3(KZ_BLOCK), 0, st, d_polys, d_lens, k, n_max * k, (u32*)d_out);
     ZK_HIP(hipGetLastError());
 }
 

@@ -875,7 +875,7 @@ int zk_points_check_bls12_381_dev(int group, const void* d_points, uint64_t n, i
  *   NULL *verdict = ZK_VERDICT_REJECTED.  Accepted batches leave *first_bad = m.  m = 0 is accepted.  Both forms synchronise.
  * A handle is bound to the device current at its creation and is not re-entrant: one call at a time per handle, from any thread or stream
  *   (the Lagrange basis of a log_n is made, and waited for, inside the first zk_kzg_commit_evals_dev that asks for it).
- * Not built: hiding commitments, commitments in G2, openings of one polynomial at several points.                                    */
+ * Not built: hiding commitments, commitments in G2.  Openings at several points: the next section.                                   */
 typedef struct zk_kzg zk_kzg_t;
 uint64_t zk_kzg_tile_elems(void);
 uint64_t zk_kzg_aggregate_span(void);
@@ -895,6 +895,57 @@ int zk_kzg_open_many_dev(zk_kzg_t* k, const uint64_t* const* d_polys, const uint
 int zk_kzg_fold_commitments(zk_kzg_t* k, const void* commitments, uint32_t n, const uint64_t* gamma, void* out);
 int zk_kzg_verify(zk_kzg_t* k, const void* openings, uint64_t m, const uint8_t* seed, int* verdict, uint64_t* first_bad);
 int zk_kzg_verify_dev(zk_kzg_t* k, const void* d_openings, uint64_t m, const uint8_t* seed, int* verdict, uint64_t* first_bad, void* stream);
+
+/* ---- KZG: several polynomials at several points in one two-point proof (csrc/kzg.hip) ---------------------------------
+ * The opening of Boneh, Drake, Fisch, Gabizon 2020 section 4 ("Shplonk"), which is the whole commitment scheme of snarkjs `ffs` / `fff` /
+ * `ffv` (fflonk; test/snark_verifier.sh:81-105): polynomials f_0 .. f_(k-1) with commitments C_i, each opened on its own set S_i of
+ * 1 .. ZK_KZG_MULTI_MAX_POINTS distinct points; T is the union of the sets.  With r_i the interpolant of the values on S_i and Z_S the
+ * vanishing polynomial of S:
+ *   W1 = [q(tau)] G1,              q = sum_i gamma^i (f_i - r_i) / Z_(S_i)
+ *   W2 = [(L / (X - z))(tau)] G1,  L = sum_i w_i (f_i - r_i(z)) - Z_T(z) q,  w_i = gamma^i Z_(T \ S_i)(z),  for a z outside T
+ *   verifier: F = sum_i w_i C_i - [sum_i w_i r_i(z)] G1 - Z_T(z) W1 and e(F + z W2, G2) e(-W2, tau G2) = 1
+ * The quotient by Z_S is never formed as such: (f - r_S) / Z_S = sum_(s in S) a_s (f - f(s)) / (X - s) with a_s = 1 / prod_(s' != s) (s - s'),
+ * so every term is the single-point division of the section above, added into a running sum by its last phase.
+ * Building blocks (no file):
+ * zk_kzg_<curve>_divide_acc_dev: d_acc_inout[j] += w q_j for j < n - 1, q = (p - p(z)) / (X - z), and d_y = p(z) (32 B canonical, device).
+ *   d_acc_inout is in the layout of d_coeffs and holds at least n - 1 elements; elements from n - 1 on are not touched.  z, w: 32 B canonical
+ *   on the host, read before the call returns.  n <= 1 writes d_y alone.
+ * zk_kzg_<curve>_interleave_dev: d_out[j k + i] = p_i[j] for j < max n_i, zero where p_i is shorter: sum_i p_i(X^k) X^i, fflonk's
+ *   combination.  d_polys, n: HOST arrays of k device pointers / lengths (k <= 65536); d_out holds k max n_i elements and overlaps no input.
+ * The prover is staged because z is a challenge that depends on W1 (the style of zk_stark_new .. finish):
+ * zk_kzg_multi_begin: d_polys, n: HOST arrays of k device pointers / lengths; the polynomials stay where they are, unchanged, until
+ *   zk_kzg_multi_finish has returned.  points: the sets one after another, 32 B canonical each, HOST; set_sizes: k counts.  d_values_out
+ *   (device, may be NULL) receives f_i(s) in the order of `points`, 32 B canonical each.  Returns NULL -- before any device work -- for k = 0,
+ *   an empty set, a set of more than ZK_KZG_MULTI_MAX_POINTS points, a point >= r, a point repeated within a set, a polynomial longer than
+ *   the handle's max_coeffs.  The powers table of every point is kept for the next stage.
+ * zk_kzg_multi_quotient: gamma 32 B canonical, HOST; d_w1_out = W1 (a sum's result slot).  A polynomial with n_i <= |S_i| is its own
+ *   interpolant and adds nothing; q = 0 gives infinity.  q stays in the handle.
+ * zk_kzg_multi_finish: z 32 B canonical, HOST; refused when z is in T.  d_w2_out = W2.  Before it returns it checks on the host, from the
+ *   evaluations the divisions leave, that L(z) = sum w_i f_i(z) - Z_T(z) q(z) - sum w_i r_i(z) is zero, and fails with an internal-error
+ *   text when it is not.  The stages run once each, in this order, and synchronise; a handle is used by one call at a time, and the zk_kzg_t
+ *   it was made from outlives it.
+ * zk_kzg_multi_verify: m proofs, one after another in `bytes` bytes (HOST; _dev: device memory, copied first).  One proof is
+ *     u64 k | k x C_i (point_bytes) | k x u64 |S_i| | P x point (32 B) | P x value (32 B) | gamma (32 B) | z (32 B) | W1 | W2
+ *   with P = sum |S_i|, points and values set by set, integers little-endian, scalars canonical, points as zk_kzg_verify takes them (all
+ *   zero: infinity, legal for C_i, W1 and W2).  The host derives w_i, sum w_i r_i(z) and Z_T(z); one small sum per proof gives F_j; the
+ *   openings (F_j, z_j, 0, W2_j) go through the batched check of zk_kzg_verify (rho = 1 for m = 1, 128-bit weights otherwise; seed FOR
+ *   TESTS ONLY).  Verdicts: k = 0, a set size outside 1 .. ZK_KZG_MULTI_MAX_POINTS, a point repeated within a set and z in T give
+ *   ZK_VERDICT_INPUT_COUNT; a point, value, gamma or z >= r gives ZK_VERDICT_INPUT_NOT_CANONICAL; then the points' classes as in
+ *   zk_kzg_verify; then ZK_VERDICT_REJECTED.  first_bad as in zk_kzg_verify: the proofs one by one, the first not accepted.  A buffer that
+ *   ends inside a proof, or after the m-th, is an error of the call.                                                                      */
+#define ZK_KZG_MULTI_MAX_POINTS 16
+typedef struct zk_kzg_multi zk_kzg_multi_t;
+int zk_kzg_bn254_divide_acc_dev(const uint64_t* d_coeffs, uint64_t n, const uint64_t* z, const uint64_t* w, uint64_t* d_acc_inout, uint64_t* d_y, void* stream);
+int zk_kzg_bls12_381_divide_acc_dev(const uint64_t* d_coeffs, uint64_t n, const uint64_t* z, const uint64_t* w, uint64_t* d_acc_inout, uint64_t* d_y, void* stream);
+int zk_kzg_bn254_interleave_dev(const uint64_t* const* d_polys, const uint64_t* n, uint32_t k, uint64_t* d_out, void* stream);
+int zk_kzg_bls12_381_interleave_dev(const uint64_t* const* d_polys, const uint64_t* n, uint32_t k, uint64_t* d_out, void* stream);
+zk_kzg_multi_t* zk_kzg_multi_begin(zk_kzg_t* k, const uint64_t* const* d_polys, const uint64_t* n, uint32_t n_polys, const uint64_t* points,
+                                   const uint32_t* set_sizes, uint64_t* d_values_out, void* stream);
+int zk_kzg_multi_quotient(zk_kzg_multi_t* m, const uint64_t* gamma, void* d_w1_out, void* stream);
+int zk_kzg_multi_finish(zk_kzg_multi_t* m, const uint64_t* z, void* d_w2_out, void* stream);
+int zk_kzg_multi_free(zk_kzg_multi_t* m);
+int zk_kzg_multi_verify(zk_kzg_t* k, const void* proofs, uint64_t bytes, uint64_t m, const uint8_t* seed, int* verdict, uint64_t* first_bad);
+int zk_kzg_multi_verify_dev(zk_kzg_t* k, const void* d_proofs, uint64_t bytes, uint64_t m, const uint8_t* seed, int* verdict, uint64_t* first_bad, void* stream);
 
 #ifdef __cplusplus
 }
