@@ -229,6 +229,46 @@ __device__ __forceinline__ u64 add_nc(u64 a, u64 b) {
     return mk64(r0, r1);
 }
 
+// ---- the NTT passes' sums, differences and canonicalising tail, with the fix-ups as multiply-adds.  A multiply-add adds a 64-bit pair in
+// ONE instruction and hands out its carry as a lane mask, where the two-limb forms spend a v_add_co / v_addc_co (v_sub_co / v_subb_co)
+// pair; bit for bit what gl::add, gl::sub and gl::mad_eps return.  One instruction fewer per call; in the pass kernel that is 1 854 -> 1 688
+// vector instructions per lane up to the last twiddles and 2 % of the 2^24 transform (profiles/r20/ntt_issue_slots.md, which also has why
+// gl::sub itself stays as it is).  The wait states between a flag's producer and its consumer are written out (s_nop 1): the compiler
+// cannot add them inside asm.  Every asm below is as opaque to the optimiser as GL_OPAQUE makes the operands of gl::add.
+// a + b, canonical in -> canonical out.  t = s + 2^32 - 1 = s - p (mod 2^64) is `1 * (2^32 - 1) + s`; its carry-out <=> s >= p.
+__device__ __forceinline__ u64 add_m(u64 a, u64 b) {
+    u32 s0, s1, r0, r1; u64 c1, d1, t;
+    asm("v_add_co_u32 %0, vcc, %3, %5\n\ts_nop 1\n\tv_addc_co_u32 %1, %2, %4, %6, vcc"
+        : "=&v"(s0), "=&v"(s1), "=&s"(c1) : "v"((u32)a), "v"((u32)(a >> 32)), "v"((u32)b), "v"((u32)(b >> 32)) : "vcc");
+    asm("v_mad_u64_u32 %0, %1, 1, -1, %2" : "=&v"(t), "=&s"(d1) : "v"(mk64(s0, s1)));
+    asm("s_or_b64 %2, %2, %3\n\tv_cndmask_b32_e64 %0, %4, %6, %2\n\tv_cndmask_b32_e64 %1, %5, %7, %2"
+        : "=&v"(r0), "=v"(r1), "+s"(d1) : "s"(c1), "v"(s0), "v"(s1), "v"((u32)t), "v"((u32)(t >> 32)) : "scc");
+    return mk64(r0, r1);
+}
+// d - (2^32 - 1) if `borrowed` (a lane mask in vcc at the end of the asm that made d0, d1; m = borrowed ? -65537 : 0 comes from there):
+// -(2^32 - 1) = -65537 * 65535, a product of two signed words, so the fix-up is ONE v_mad_i64_i32 on the pair
+__device__ __forceinline__ u64 sub_eps_if(u32 m, u32 d0, u32 d1) {
+    u64 r, cc;
+    asm("v_mad_i64_i32 %0, %1, %2, %3, %4" : "=v"(r), "=s"(cc) : "v"(m), "s"(65535), "v"(mk64(d0, d1)));
+    return r;
+}
+// a - b, canonical in -> canonical out: d = a - b + 2^64 if it borrowed, and d + p = d - (2^32 - 1) (mod 2^64) then lies in [1, p - 1]
+__device__ __forceinline__ u64 sub_m(u64 a, u64 b) {
+    u32 d0, d1, m;
+    asm("v_sub_co_u32 %0, vcc, %3, %5\n\ts_nop 1\n\tv_subb_co_u32 %1, vcc, %4, %6, vcc\n\ts_nop 1\n\tv_cndmask_b32_e64 %2, 0, %7, vcc"
+        : "=&v"(d0), "=&v"(d1), "=v"(m) : "v"((u32)a), "v"((u32)(a >> 32)), "v"((u32)b), "v"((u32)(b >> 32)), "v"(-65537) : "vcc");
+    return sub_eps_if(m, d0, d1);
+}
+// gl::mad_eps with the last step (u >= p ? u - p : u) as in add_m
+__device__ __forceinline__ u64 mad_eps_m(u32 r2, u64 t) {
+    const u64 u = mad_eps_nc(r2, t);
+    u64 v, ge; u32 r0, r1;
+    asm("v_mad_u64_u32 %0, %1, 1, -1, %2" : "=&v"(v), "=&s"(ge) : "v"(u));
+    asm("s_nop 1\n\tv_cndmask_b32_e64 %0, %3, %5, %2\n\tv_cndmask_b32_e64 %1, %4, %6, %2"
+        : "=&v"(r0), "=v"(r1) : "s"(ge), "v"((u32)u), "v"((u32)(u >> 32)), "v"((u32)v), "v"((u32)(v >> 32)));
+    return mk64(r0, r1);
+}
+
 // ---- the NTT passes' twiddle product: a 64 x 64 product whose four multiply-adds take the 32-bit halves directly.
 // gl::mul chains its multiply-adds through the HIGH word of the one before (p1 = a0 b1 + (p0 >> 32), ...): a 64-bit
 // addend has to be a register pair, so every link costs a move beside a zero register (4 moves and a 64-bit add per product).
@@ -236,8 +276,8 @@ __device__ __forceinline__ u64 add_nc(u64 a, u64 b) {
 // 32-bit carry adds, and the last carry rides as the borrow-in of the 2^96 fold instead of being added to r3 first:
 //   a b = L + 2^32 (c:M) + 2^64 H,  L = a0 b0, c:M = a0 b1 + a1 b0 (65 bits), H = a1 b1
 //   w0 = L0, w1 = L1 + M0 -> k1, r2 = M1 + H0 + k1 -> k2, r3 = H1 + c + k2   (H1 <= 2^32 - 2: H1 + c cannot wrap)
-// Returns (w1:w0) - r3 folded as sub_word_fold does (minus 2^32 - 1 more if that borrowed) and r2 for mad_eps / mad_eps_nc:
-// 12 instructions where the plain product and sub_word_fold spend 14.  Any u64 operands.  The asm is as opaque to the
+// Returns (w1:w0) - r3 folded as sub_word_fold does (minus 2^32 - 1 more if that borrowed, as ONE multiply-add: sub_eps_if) and r2 for
+// mad_eps_m / mad_eps_nc: 11 instructions where the plain product and sub_word_fold spend 14.  Any u64 operands.  The asm is as opaque to the
 // optimiser as GL_OPAQUE makes the operands of gl::mul.  The cross products come first: their carry c, an SGPR pair, has the
 // two other multiply-adds between its producer and its consumer.  That distance is load-bearing: on the gfx940 family (gfx950
 // included) an SGPR written by a VALU instruction may be read by a VALU instruction only 2 wait states later, the compiler cannot
@@ -261,17 +301,14 @@ __device__ __forceinline__ u64 mul_fold96(u64 a, u64 b, u32& r2) {
         "s_nop 1\n\t"
         "v_subbrev_co_u32 %1, vcc, 0, %4, vcc\n\t"
         "s_nop 1\n\t"
-        "v_cndmask_b32_e64 %2, 0, -1, vcc\n\t"
-        "v_sub_co_u32 %0, vcc, %0, %2\n\t"
-        "s_nop 1\n\t"
-        "v_subbrev_co_u32 %1, vcc, 0, %1, vcc"
+        "v_cndmask_b32_e64 %2, 0, %13, vcc"
         : "=&v"(t0), "=&v"(t1), "=&v"(mb), "=&v"(h1), "=&v"(w1), "=&v"(r2)
-        : "v"((u32)(l >> 32)), "v"((u32)m), "v"((u32)(m >> 32)), "v"((u32)h), "v"((u32)(h >> 32)), "s"(c), "v"((u32)l) : "vcc");
-    return mk64(t0, t1);
+        : "v"((u32)(l >> 32)), "v"((u32)m), "v"((u32)(m >> 32)), "v"((u32)h), "v"((u32)(h >> 32)), "s"(c), "v"((u32)l), "v"(-65537) : "vcc");
+    return sub_eps_if(mb, t0, t1);
 }
-// x * w mod p, any u64 in, canonical out: bit for bit what gl::mul returns (19 instructions against 21 and no zero register pair)
-__device__ __forceinline__ u64 mul_tw(u64 x, u64 w) { u32 r2; const u64 t = mul_fold96(x, w, r2); return mad_eps(r2, t); }
-// the same without the final canonicalisation (15 instructions): for a product that feeds only other products
+// x * w mod p, any u64 in, canonical out: bit for bit what gl::mul returns (17 instructions against 21 and no zero register pair)
+__device__ __forceinline__ u64 mul_tw(u64 x, u64 w) { u32 r2; const u64 t = mul_fold96(x, w, r2); return mad_eps_m(r2, t); }
+// the same without the final canonicalisation (14 instructions): for a product that feeds only other products
 __device__ __forceinline__ u64 mul_tw_nc(u64 x, u64 w) { u32 r2; const u64 t = mul_fold96(x, w, r2); return mad_eps_nc(r2, t); }
 
 // x * 2^E mod p for a compile-time 0 <= E < 96, canonical x -> canonical result.  2 has order 192
@@ -285,7 +322,7 @@ __device__ __forceinline__ u64 mul_pow2(u64 x) {
     if constexpr (E == 0) {
         return x;
     } else if constexpr (E <= 32) {                       // lo + top*2^64, top < 2^32
-        return mad_eps((u32)(x >> (64 - E)), x << E);
+        return mad_eps_m((u32)(x >> (64 - E)), x << E);
     } else if constexpr (E < 64) {
         // E = 32 + r: x 2^r = t2:t1:t0 (t2 < 2^r), so x 2^E = t0 2^32 + t1 2^64 + t2 2^96 = t0 2^32 + t1 (2^32 - 1) - t2.  With the addend
         // (t0 : ~t2) = t0 2^32 + (2^32 - 1) - t2 one multiply-add gives u + carry 2^64 = value + 2^32 - 1, i.e. value = u if it carried
@@ -305,7 +342,7 @@ __device__ __forceinline__ u64 mul_pow2(u64 x) {
         const u32 t0 = (u32)x << r;
         u64 m = ((u64)t0 << 32) - t0;                     // t0*(2^32-1) < p
         u64 s = r == 0 ? (x >> 32) : (x >> (32 - r));     // < p
-        return sub(m, s);
+        return sub_m(m, s);
     }
 }
 

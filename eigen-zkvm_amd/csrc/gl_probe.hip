@@ -1,5 +1,6 @@
 // Test hooks for the field operations that have no entry point of their own: the NTT passes' twiddle product (gl::mul_tw, gl::mul_tw_nc)
-// applied to operand pairs from the host, and the shift twiddle gl::mul_pow2<E> for every exponent (tests/test_gpu_ntt_lean.py); every
+// applied to operand pairs from the host, and the shift twiddle gl::mul_pow2<E> for every exponent (tests/test_gpu_ntt_lean.py); the
+// passes' multiply-add forms gl::add_m, gl::sub_m, gl::mad_eps_m beside gl::sub and gl::add_nc (tests/test_gpu_ntt_issue_slots.py); every
 // other primitive of gl.hip.h, the carry-free accumulators of acc6.hip.h and the matrix-pipe product of gl_mfma.hip.h on operands from
 // the host (tests/test_gpu_field_ops.py).  Not part of include/zkgpu.h; the tests bind them by name.  Every probe writes what the
 // primitive returned, unreduced.
@@ -61,6 +62,25 @@ __global__ void scalar_probe_kernel(const u64* __restrict__ pa, const u64* __res
     const u64 x2 = gl::sqr_nc(a), x3 = gl::mul_nc(x2, a), x6 = gl::sqr_nc(x3);
     o[15 * n] = gl::mul_nc(x6, a);                                   // pow7 of poseidon.hip: a^7
     o[16 * n] = gl::mul_add_nc(gl::mul_nc(a, b), gl::sqr_nc(c), gl::add_nc(gl::mul_nc(a, c), cb));   // a b c^2 + a c + b
+}
+
+// The NTT passes' own forms (gl::add_m, gl::sub_m, gl::mad_eps_m) beside the ones they stand in for, and a non-canonical sum as the
+// operand of a twiddle product.  Rows of n: add_m(a mod p, b mod p), sub_m(same), sub(same), add_nc(a, b mod p) as returned,
+// mul_tw(add_nc(a, b mod p), w), mad_eps_m((u32)w, a) = a + (u32)w (2^32 - 1) mod p, mul_tw(a, w)   (tests/test_gpu_ntt_issue_slots.py)
+constexpr int NTT_ARITH_ROWS = 7;
+__global__ void ntt_arith_probe_kernel(const u64* __restrict__ pa, const u64* __restrict__ pb, const u64* __restrict__ pw, u64* __restrict__ out, u64 n) {
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const u64 a = pa[i], w = pw[i], ca = canon(a), cb = canon(pb[i]);
+    u64* __restrict__ o = out + i;
+    o[0 * n] = gl::add_m(ca, cb);
+    o[1 * n] = gl::sub_m(ca, cb);
+    o[2 * n] = gl::sub(ca, cb);
+    const u64 s = gl::add_nc(a, cb);
+    o[3 * n] = s;
+    o[4 * n] = gl::mul_tw(s, w);
+    o[5 * n] = gl::mad_eps_m((u32)w, a);
+    o[6 * n] = gl::mul_tw(a, w);
 }
 
 // rows of 3 n words: f3_add(x, y), f3_sub(x, y), f3_mul(x, y), f3_muls(x, s), f3_inv(x); x, y canonical, s any u64
@@ -149,6 +169,22 @@ extern "C" int zk_gl_scalar_probe(const uint64_t* a, const uint64_t* b, const ui
         hipLaunchKernelGGL(scalar_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, da.u(), db.u(), dc.u(), dout.u(), (u64)n);
         ZK_HIP(hipGetLastError());
         ZK_HIP(hipMemcpy(out, dout.p, SCALAR_ROWS * n * 8, hipMemcpyDeviceToHost));
+    });
+}
+
+// a, b, w: n host words each (any u64); out: 7 n host words, one row per form (ntt_arith_probe_kernel)
+extern "C" int zk_gl_ntt_arith_probe(const uint64_t* a, const uint64_t* b, const uint64_t* w, uint64_t* out, size_t n) {
+    using namespace zk;
+    return guard([&] {
+        ZK_REQUIRE(a && b && w && out && n > 0 && n <= ((size_t)1 << 20), "zk_gl_ntt_arith_probe: bad arguments");
+        DevBuf da, db, dw, dout;
+        da.reserve(n * 8); db.reserve(n * 8); dw.reserve(n * 8); dout.reserve(NTT_ARITH_ROWS * n * 8);
+        ZK_HIP(hipMemcpy(da.p, a, n * 8, hipMemcpyHostToDevice));
+        ZK_HIP(hipMemcpy(db.p, b, n * 8, hipMemcpyHostToDevice));
+        ZK_HIP(hipMemcpy(dw.p, w, n * 8, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(ntt_arith_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, da.u(), db.u(), dw.u(), dout.u(), (u64)n);
+        ZK_HIP(hipGetLastError());
+        ZK_HIP(hipMemcpy(out, dout.p, NTT_ARITH_ROWS * n * 8, hipMemcpyDeviceToHost));
     });
 }
 

@@ -38,9 +38,9 @@ __device__ __forceinline__ void ntt_reg(u64 (&x)[1 << LOG]) {
 #pragma unroll
             for (int blk = 0; blk < n; blk += 2 * half) {
                 const u64 a = x[blk + j], b = x[blk + j + half];
-                x[blk + j] = gl::add(a, b);
-                if constexpr (e >= 96) x[blk + j + half] = gl::mul_pow2<e - 96>(gl::sub(b, a));
-                else                   x[blk + j + half] = gl::mul_pow2<e>(gl::sub(a, b));
+                x[blk + j] = gl::add_m(a, b);
+                if constexpr (e >= 96) x[blk + j + half] = gl::mul_pow2<e - 96>(gl::sub_m(b, a));
+                else                   x[blk + j + half] = gl::mul_pow2<e>(gl::sub_m(a, b));
             }
         });
     });
