@@ -74,7 +74,9 @@ EXPORTS = [
     "zk_kzg_fold_commitments", "zk_kzg_verify", "zk_kzg_verify_dev",
     "zk_kzg_bn254_divide_acc_dev", "zk_kzg_bls12_381_divide_acc_dev", "zk_kzg_bn254_interleave_dev", "zk_kzg_bls12_381_interleave_dev",
     "zk_kzg_multi_begin", "zk_kzg_multi_quotient", "zk_kzg_multi_finish", "zk_kzg_multi_free", "zk_kzg_multi_verify", "zk_kzg_multi_verify_dev",
-]
+    "zk_frpoly_tile_elems", "zk_frpoly_span",
+] + ["zk_fr_%s_%s_dev" % (c, f) for c in ("bn254", "bls12_381")
+     for f in ("prefix_product", "batch_inverse", "pointwise", "powers", "terms", "grand_product", "poly_mul", "divmod_zh", "divide_zh_coset")]
 
 # include/zkgpu.h enums
 OP_ADD, OP_SUB, OP_MUL, OP_COPY = 0, 1, 2, 3
@@ -407,7 +409,20 @@ def _load():
         "zk_kzg_multi_free": (C.c_int, [vp]),
         "zk_kzg_multi_verify": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, vp, C.POINTER(C.c_int), vp]),
         "zk_kzg_multi_verify_dev": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, vp, C.POINTER(C.c_int), vp, vp]),
+        "zk_frpoly_tile_elems": (C.c_uint64, []), "zk_frpoly_span": (C.c_uint64, []),
     }
+    for c in ("bn254", "bls12_381"):                    # polynomial arithmetic over the scalar field (frpoly.py)
+        sig.update({
+            "zk_fr_%s_prefix_product_dev" % c: (C.c_int, [vp, C.c_uint64, C.c_int, vp, vp, vp]),
+            "zk_fr_%s_batch_inverse_dev" % c: (C.c_int, [vp, C.c_uint64, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp]),
+            "zk_fr_%s_pointwise_dev" % c: (C.c_int, [C.c_int, vp, vp, vp, C.c_uint64, vp]),
+            "zk_fr_%s_powers_dev" % c: (C.c_int, [vp, vp, C.c_uint64, vp, vp]),
+            "zk_fr_%s_terms_dev" % c: (C.c_int, [vp, vp, C.c_uint32, C.c_uint64, vp, vp, vp, vp]),
+            "zk_fr_%s_grand_product_dev" % c: (C.c_int, [vp, vp, C.c_uint64, vp, vp, vp]),
+            "zk_fr_%s_poly_mul_dev" % c: (C.c_int, [vp, C.c_uint64, vp, C.c_uint64, vp, vp]),
+            "zk_fr_%s_divmod_zh_dev" % c: (C.c_int, [vp, C.c_uint64, C.c_uint32, vp, vp, C.POINTER(C.c_uint64), vp]),
+            "zk_fr_%s_divide_zh_coset_dev" % c: (C.c_int, [vp, C.c_uint32, C.c_uint32, vp]),
+        })
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args

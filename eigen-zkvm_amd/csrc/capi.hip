@@ -955,6 +955,43 @@ int zk_kzg_multi_verify_dev(zk_kzg_t* k, const void* d_proofs, uint64_t bytes, u
         kzg_multi_verify(*k, host.data(), bytes, m, seed, first_bad != nullptr, verdict, first_bad, st);
     });
 }
+// ---- polynomial arithmetic over the scalar field (frpoly_impl.hip.h through groth16.hip) ----
+uint64_t zk_frpoly_tile_elems(void) { return FRPOLY_TILE; }
+uint64_t zk_frpoly_span(void) { return FRPOLY_SPAN; }
+#define ZK_FRPOLY_API(NAME, ID)                                                                                                               \
+    int zk_fr_##NAME##_prefix_product_dev(const uint64_t* d_in, uint64_t n, int inclusive, uint64_t* d_out, uint64_t* total_out, void* stream) { \
+        return guard([&] { curve(ID).frpoly().prefix_product_dev((const u64*)d_in, n, inclusive != 0, (u64*)d_out, (u64*)total_out, on_stream((hipStream_t)stream)); }); \
+    }                                                                                                                                         \
+    int zk_fr_##NAME##_batch_inverse_dev(const uint64_t* d_in, uint64_t n, uint64_t* d_out, uint64_t* n_zero, uint64_t* first_zero, void* stream) { \
+        return guard([&] { curve(ID).frpoly().batch_inverse_dev((const u64*)d_in, n, (u64*)d_out, (u64*)n_zero, (u64*)first_zero, on_stream((hipStream_t)stream)); }); \
+    }                                                                                                                                         \
+    int zk_fr_##NAME##_pointwise_dev(int op, const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_out, uint64_t n, void* stream) {           \
+        return guard([&] { curve(ID).frpoly().pointwise_dev(op, (const u64*)d_a, (const u64*)d_b, (u64*)d_out, n, on_stream((hipStream_t)stream)); }); \
+    }                                                                                                                                         \
+    int zk_fr_##NAME##_powers_dev(const uint64_t* base, const uint64_t* scale, uint64_t n, uint64_t* d_out, void* stream) {                   \
+        return guard([&] { curve(ID).frpoly().powers_dev((const u64*)base, (const u64*)scale, n, (u64*)d_out, on_stream((hipStream_t)stream)); }); \
+    }                                                                                                                                         \
+    int zk_fr_##NAME##_terms_dev(const uint64_t* const* d_cols, const uint64_t* const* d_labels, uint32_t k, uint64_t n, const uint64_t* beta, \
+                                 const uint64_t* gamma, uint64_t* d_out, void* stream) {                                                      \
+        return guard([&] {                                                                                                                    \
+            curve(ID).frpoly().terms_dev((const u64* const*)d_cols, (const u64* const*)d_labels, k, n, (const u64*)beta, (const u64*)gamma, (u64*)d_out, on_stream((hipStream_t)stream)); \
+        });                                                                                                                                   \
+    }                                                                                                                                         \
+    int zk_fr_##NAME##_grand_product_dev(const uint64_t* d_num, const uint64_t* d_den, uint64_t n, uint64_t* d_z, uint64_t* last_out, void* stream) { \
+        return guard([&] { curve(ID).frpoly().grand_product_dev((const u64*)d_num, (const u64*)d_den, n, (u64*)d_z, (u64*)last_out, on_stream((hipStream_t)stream)); }); \
+    }                                                                                                                                         \
+    int zk_fr_##NAME##_poly_mul_dev(const uint64_t* d_a, uint64_t na, const uint64_t* d_b, uint64_t nb, uint64_t* d_out, void* stream) {      \
+        return guard([&] { curve(ID).frpoly().poly_mul_dev((const u64*)d_a, na, (const u64*)d_b, nb, (u64*)d_out, on_stream((hipStream_t)stream)); }); \
+    }                                                                                                                                         \
+    int zk_fr_##NAME##_divmod_zh_dev(const uint64_t* d_p, uint64_t n_p, uint32_t log_n, uint64_t* d_q, uint64_t* d_rem, uint64_t* rem_nonzero, void* stream) { \
+        return guard([&] { curve(ID).frpoly().divmod_zh_dev((const u64*)d_p, n_p, log_n, (u64*)d_q, (u64*)d_rem, (u64*)rem_nonzero, on_stream((hipStream_t)stream)); }); \
+    }                                                                                                                                         \
+    int zk_fr_##NAME##_divide_zh_coset_dev(uint64_t* d_evals, uint32_t log_m, uint32_t log_n, void* stream) {                                 \
+        return guard([&] { curve(ID).frpoly().divide_zh_coset_dev((u64*)d_evals, log_m, log_n, on_stream((hipStream_t)stream)); });           \
+    }
+ZK_FRPOLY_API(bn254, CURVE_BN254)
+ZK_FRPOLY_API(bls12_381, CURVE_BLS12_381)
+#undef ZK_FRPOLY_API
 int zk_groth16_verify_aggregate_timing(double* ms) {
     return guard([&] { ZK_REQUIRE(ms, "groth16 verify: null argument"); groth16_verify_aggregate_timing(ms); });
 }

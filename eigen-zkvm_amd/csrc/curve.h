@@ -95,6 +95,22 @@ struct KzgOps {
 };
 const KzgOps& kzg_ops(CurveId id);
 constexpr uint64_t KZG_TILE = 2048, KZG_SPAN = 512;   // coefficients per workgroup; tile aggregates per step of the combining workgroup
+// ---- groth16.hip: polynomial arithmetic over the scalar field (frpoly_impl.hip.h).  Vectors: n x 4 u64 Montgomery words on the
+// device, the transforms' layout; scalars and host results: 4 canonical u64 words on the host.  What include/zkgpu.h states for
+// zk_fr_<curve>_<name>_dev holds for each of these
+struct FrPolyOps {
+    void (*prefix_product_dev)(const u64* d_in, u64 n, bool inclusive, u64* d_out, u64* total_out, hipStream_t st);
+    void (*batch_inverse_dev)(const u64* d_in, u64 n, u64* d_out, u64* n_zero, u64* first_zero, hipStream_t st);
+    void (*pointwise_dev)(int op, const u64* d_a, const u64* d_b, u64* d_out, u64 n, hipStream_t st);
+    void (*powers_dev)(const u64* base, const u64* scale, u64 n, u64* d_out, hipStream_t st);
+    void (*terms_dev)(const u64* const* d_cols, const u64* const* d_labels, u32 k, u64 n, const u64* beta, const u64* gamma, u64* d_out, hipStream_t st);
+    void (*grand_product_dev)(const u64* d_num, const u64* d_den, u64 n, u64* d_z, u64* last_out, hipStream_t st);
+    void (*poly_mul_dev)(const u64* d_a, u64 na, const u64* d_b, u64 nb, u64* d_out, hipStream_t st);
+    void (*divmod_zh_dev)(const u64* d_p, u64 n_p, u32 log_n, u64* d_q, u64* d_rem, u64* rem_nonzero, hipStream_t st);
+    void (*divide_zh_coset_dev)(u64* d_evals, u32 log_m, u32 log_n, hipStream_t st);
+};
+const FrPolyOps& frpoly_ops(CurveId id);
+constexpr uint64_t FRPOLY_TILE = 2048, FRPOLY_SPAN = 512;   // elements per workgroup of the running product; tile aggregates per step of the combining workgroup
 // ---- pairing.hip: the steps of the optimal ate pairing and of Groth16 verification (pairing_impl.hip.h)
 struct PairingOps {
     const char* q_hex;                                                      // the base field's modulus
@@ -156,6 +172,7 @@ struct Curve {
     const PairingOps& pairing() const { return pairing_ops(id); }
     const EcOps& ec() const { return ec_ops(id); }
     const KzgOps& kzg() const { return kzg_ops(id); }
+    const FrPolyOps& frpoly() const { return frpoly_ops(id); }
 };
 inline const Curve CURVES[2] = {
     {CURVE_BN254, "BN128", "bn254", 8, {0xf0000001u, 0x43e1f593u, 0x79b97091u, 0x2833e848u, 0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u}},

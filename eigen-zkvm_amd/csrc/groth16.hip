@@ -8,6 +8,8 @@
 //   row evaluations  one lane per row of the three CSR matrices                 (frntt_impl.hip.h)
 //   quotient         7 transforms over Fr + the pointwise step                  (frntt_impl.hip.h)
 //   h, l, a, b_g1, b_g2 sums and the final assembly through msm.hip
+// This unit owns the scalar field's transforms, so the polynomial layer that runs them batched in their own layout lives here too
+// (frpoly_impl.hip.h, DESIGN.md 3.20: zk_fr_<curve>_poly_mul_dev and its siblings; no protocol).
 //   proof.json       groth16/src/json_utils.rs:305-315
 // Key generation (`zkit groth16_setup`, groth16/src/api.rs:42-66) over the same circuit: groth16_keygen_impl.hip.h with a trapdoor,
 // groth16_srs.hip.h from a powers-of-tau file (and the contributions to such a key).
@@ -18,6 +20,7 @@
 #include "r1cs_file.h"
 #include "json_min.h"
 #include "ceremony_host.h"
+#include "../../include/zkgpu.h"
 #include <algorithm>
 #include <cerrno>
 #include <chrono>
@@ -296,7 +299,9 @@ namespace bn254fr {
 #define FRN_S 28
 #define FRN_ROOT 0xb639feb8u, 0x9632c7c5u, 0x0d0ff299u, 0x985ce340u, 0x01b0ecd8u, 0xb2dd8800u, 0x6d98ce29u, 0x1d69070du   // 7^((r-1)/2^28) * 2^256
 #define FRN_FN(name) name
+#define FRP_CURVE CURVE_BN254
 #include "frntt_impl.hip.h"
+#include "frpoly_impl.hip.h"
 #include "groth16_impl.hip.h"
 #include "groth16_keygen_impl.hip.h"
 #include "verify_sums_impl.hip.h"
@@ -304,6 +309,7 @@ namespace bn254fr {
 #include "ceremony_impl.hip.h"
 #undef FRN_S
 #undef FRN_ROOT
+#undef FRP_CURVE
 }  // namespace bn254fr
 
 namespace bls12381fr {
@@ -312,7 +318,9 @@ namespace bls12381fr {
 #include "fe29_impl.hip.h"
 #define FRN_S 32
 #define FRN_ROOT 0x5f0e466au, 0xb9b58d8cu, 0x1819d7ecu, 0x5b1b4c80u, 0x52a31e64u, 0x0af53ae3u, 0x19e9b27bu, 0x5bf3addau   // 7^((r-1)/2^32) * 2^256
+#define FRP_CURVE CURVE_BLS12_381
 #include "frntt_impl.hip.h"
+#include "frpoly_impl.hip.h"
 #include "groth16_impl.hip.h"
 #include "groth16_keygen_impl.hip.h"
 #include "verify_sums_impl.hip.h"
@@ -324,6 +332,14 @@ const Groth16Ops& groth16_ops(CurveId id) {   // the table's slice of this unit 
     static const Groth16Ops OPS[2] = {{bn254fr::ntt_dev, bn254fr::quotient_dev, bn254fr::setup_new, bn254fr::keygen_run, bn254fr::verify_sums_dev, bn254fr::kc_coef_dev, bn254fr::kc_coeffs_dev, bn254fr::powers_dev, bn254fr::fr_to_canon_dev},
                                       {bls12381fr::ntt_dev, bls12381fr::quotient_dev, bls12381fr::setup_new, bls12381fr::keygen_run, bls12381fr::verify_sums_dev,
                                        bls12381fr::kc_coef_dev, bls12381fr::kc_coeffs_dev, bls12381fr::powers_dev, bls12381fr::fr_to_canon_dev}};
+    return OPS[id];
+}
+
+const FrPolyOps& frpoly_ops(CurveId id) {     // frpoly_impl.hip.h, per scalar field
+#define ZK_FRPOLY_OPS(NS) {NS::fp_prefix_product_dev, NS::fp_batch_inverse_dev, NS::fp_pointwise_dev, NS::fp_powers_dev, NS::fp_terms_dev, NS::fp_grand_product_dev, \
+                           NS::fp_poly_mul_dev, NS::fp_divmod_zh_dev, NS::fp_divide_zh_coset_dev}
+    static const FrPolyOps OPS[2] = {ZK_FRPOLY_OPS(bn254fr), ZK_FRPOLY_OPS(bls12381fr)};
+#undef ZK_FRPOLY_OPS
     return OPS[id];
 }
 

@@ -947,6 +947,60 @@ int zk_kzg_multi_free(zk_kzg_multi_t* m);
 int zk_kzg_multi_verify(zk_kzg_t* k, const void* proofs, uint64_t bytes, uint64_t m, const uint8_t* seed, int* verdict, uint64_t* first_bad);
 int zk_kzg_multi_verify_dev(zk_kzg_t* k, const void* d_proofs, uint64_t bytes, uint64_t m, const uint8_t* seed, int* verdict, uint64_t* first_bad, void* stream);
 
+/* ---- Polynomial arithmetic over the scalar field (csrc/frpoly_impl.hip.h) ----------------------------------------------
+ * What a PLONK-family prover, a lookup argument or a batched opening is made of, and nothing of a protocol: no transcript, no soundness
+ * claim.  <curve> is bn254 or bls12_381.  A vector is n x 4 u64 Montgomery words (R = 2^256), element-major, on the device and 16-byte
+ * aligned: the layout of zk_fr_<curve>_ntt_dev and zk_kzg_<curve>_divide_dev; input words may be anything those leave.  EVERY OUTPUT
+ * VECTOR HOLDS THE CANONICAL REPRESENTATIVE (< r): results are bit-exact and the same on every run.  A scalar argument (base, scale, beta,
+ * gamma) is 4 canonical u64 words on the HOST; one that is not below r is refused before any device work.  A host result (total_out,
+ * last_out) is 4 canonical words of the plain integer, not Montgomery; a call that fills a host result waits for the stream.
+ * zk_fr_<curve>_prefix_product_dev: out[i] = prod_{j < i} in[j] (inclusive = 0, so out[0] = 1) or prod_{j <= i} in[j]; total_out = prod in.
+ *   d_out == NULL: the total alone.  n = 0: total 1.  d_out may be d_in.  A zero element is an ordinary value.  A tiled scan:
+ *   zk_frpoly_tile_elems() elements per workgroup, the tile aggregates combined by one workgroup that walks them zk_frpoly_span() at a time.
+ * zk_fr_<curve>_batch_inverse_dev: out[i] = 1 / in[i]; a zero stays zero and does not disturb its neighbours.  n_zero, first_zero (HOST,
+ *   either may be NULL): how many zeros, the index of the first (UINT64_MAX when none).  d_out may be d_in.  One inversion per tile.
+ * zk_fr_<curve>_pointwise_dev: out[i] = a[i] op b[i], op one of ZK_FR_MUL, ZK_FR_ADD, ZK_FR_SUB; d_out may be either operand.
+ * zk_fr_<curve>_powers_dev: out[i] = scale base^i; base = 0 gives scale, 0, 0, ...
+ * zk_fr_<curve>_terms_dev: out[i] = prod_{c < k} (cols_c[i] + beta labels_c[i] + gamma), 1 <= k <= 16; d_cols, d_labels: HOST arrays of k
+ *   device pointers; d_labels == NULL drops the beta term.
+ * zk_fr_<curve>_grand_product_dev: z_0 = 1, z_(i+1) = z_i num_i / den_i; d_z receives z_0 .. z_(n-1), last_out z_n: "the two products
+ *   agree" is last_out == 1, which the caller compares.  A zero denominator is refused with its first row named and d_z untouched.  d_z may
+ *   be d_num.
+ * zk_fr_<curve>_poly_mul_dev: the na + nb - 1 coefficients of a b (na, nb >= 1; leading zeros kept) by two forward transforms of the next
+ *   power of two, a pointwise product and one inverse transform; a length beyond the field's 2-adicity is refused.  d_out overlaps no input.
+ * zk_fr_<curve>_divmod_zh_dev: p = q (X^N - 1) + rem for N = 2^log_n, exactly: rem (N elements, zero-padded when n_p < N) and q
+ *   (max(n_p - N, 0) elements); d_q or d_rem may be NULL, d_q overlaps no input.  rem_nonzero (HOST): the number of non-zero remainder
+ *   coefficients -- zero exactly when X^N - 1 divides p.  Additions only.  ceil(n_p / N) > ZK_FRPOLY_MAX_RATIO is refused.
+ * zk_fr_<curve>_divide_zh_coset_dev: d_evals holds values on the coset 7 H_m in the order zk_fr_<curve>_ntt_dev(.., coset = 1) leaves them,
+ *   m = 2^log_m >= N = 2^log_n; element i is multiplied in place by 1 / (7^N w_m^(iN) - 1), the m / N distinct factors made on the device.
+ * Not built: the prover that stands on this (gate constraints, transcript, blinding).                                                    */
+#define ZK_FR_MUL 0
+#define ZK_FR_ADD 1
+#define ZK_FR_SUB 2
+#define ZK_FRPOLY_MAX_RATIO 4096
+uint64_t zk_frpoly_tile_elems(void);
+uint64_t zk_frpoly_span(void);
+int zk_fr_bn254_prefix_product_dev(const uint64_t* d_in, uint64_t n, int inclusive, uint64_t* d_out, uint64_t* total_out, void* stream);
+int zk_fr_bls12_381_prefix_product_dev(const uint64_t* d_in, uint64_t n, int inclusive, uint64_t* d_out, uint64_t* total_out, void* stream);
+int zk_fr_bn254_batch_inverse_dev(const uint64_t* d_in, uint64_t n, uint64_t* d_out, uint64_t* n_zero, uint64_t* first_zero, void* stream);
+int zk_fr_bls12_381_batch_inverse_dev(const uint64_t* d_in, uint64_t n, uint64_t* d_out, uint64_t* n_zero, uint64_t* first_zero, void* stream);
+int zk_fr_bn254_pointwise_dev(int op, const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_out, uint64_t n, void* stream);
+int zk_fr_bls12_381_pointwise_dev(int op, const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_out, uint64_t n, void* stream);
+int zk_fr_bn254_powers_dev(const uint64_t* base, const uint64_t* scale, uint64_t n, uint64_t* d_out, void* stream);
+int zk_fr_bls12_381_powers_dev(const uint64_t* base, const uint64_t* scale, uint64_t n, uint64_t* d_out, void* stream);
+int zk_fr_bn254_terms_dev(const uint64_t* const* d_cols, const uint64_t* const* d_labels, uint32_t k, uint64_t n, const uint64_t* beta, const uint64_t* gamma,
+                          uint64_t* d_out, void* stream);
+int zk_fr_bls12_381_terms_dev(const uint64_t* const* d_cols, const uint64_t* const* d_labels, uint32_t k, uint64_t n, const uint64_t* beta, const uint64_t* gamma,
+                              uint64_t* d_out, void* stream);
+int zk_fr_bn254_grand_product_dev(const uint64_t* d_num, const uint64_t* d_den, uint64_t n, uint64_t* d_z, uint64_t* last_out, void* stream);
+int zk_fr_bls12_381_grand_product_dev(const uint64_t* d_num, const uint64_t* d_den, uint64_t n, uint64_t* d_z, uint64_t* last_out, void* stream);
+int zk_fr_bn254_poly_mul_dev(const uint64_t* d_a, uint64_t na, const uint64_t* d_b, uint64_t nb, uint64_t* d_out, void* stream);
+int zk_fr_bls12_381_poly_mul_dev(const uint64_t* d_a, uint64_t na, const uint64_t* d_b, uint64_t nb, uint64_t* d_out, void* stream);
+int zk_fr_bn254_divmod_zh_dev(const uint64_t* d_p, uint64_t n_p, uint32_t log_n, uint64_t* d_q, uint64_t* d_rem, uint64_t* rem_nonzero, void* stream);
+int zk_fr_bls12_381_divmod_zh_dev(const uint64_t* d_p, uint64_t n_p, uint32_t log_n, uint64_t* d_q, uint64_t* d_rem, uint64_t* rem_nonzero, void* stream);
+int zk_fr_bn254_divide_zh_coset_dev(uint64_t* d_evals, uint32_t log_m, uint32_t log_n, void* stream);
+int zk_fr_bls12_381_divide_zh_coset_dev(uint64_t* d_evals, uint32_t log_m, uint32_t log_n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
