@@ -76,7 +76,8 @@ EXPORTS = [
     "zk_kzg_multi_begin", "zk_kzg_multi_quotient", "zk_kzg_multi_finish", "zk_kzg_multi_free", "zk_kzg_multi_verify", "zk_kzg_multi_verify_dev",
     "zk_frpoly_tile_elems", "zk_frpoly_span",
 ] + ["zk_fr_%s_%s_dev" % (c, f) for c in ("bn254", "bls12_381")
-     for f in ("prefix_product", "batch_inverse", "pointwise", "powers", "terms", "grand_product", "poly_mul", "divmod_zh", "divide_zh_coset")]
+     for f in ("prefix_product", "batch_inverse", "pointwise", "powers", "terms", "grand_product", "poly_mul", "divmod_zh", "divide_zh_coset")
+     ] + [n % c for c in ("bn254", "bls12_381") for n in ("zk_plonk_%s_quotient_dev", "zk_plonk_%s_gate_check_dev", "zk_fr_%s_gather_dev")]
 
 # include/zkgpu.h enums
 OP_ADD, OP_SUB, OP_MUL, OP_COPY = 0, 1, 2, 3
@@ -422,6 +423,10 @@ def _load():
             "zk_fr_%s_poly_mul_dev" % c: (C.c_int, [vp, C.c_uint64, vp, C.c_uint64, vp, vp]),
             "zk_fr_%s_divmod_zh_dev" % c: (C.c_int, [vp, C.c_uint64, C.c_uint32, vp, vp, C.POINTER(C.c_uint64), vp]),
             "zk_fr_%s_divide_zh_coset_dev" % c: (C.c_int, [vp, C.c_uint32, C.c_uint32, vp]),
+            # the device side of the PLONK prover (plonk.py)
+            "zk_plonk_%s_quotient_dev" % c: (C.c_int, [vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp]),
+            "zk_plonk_%s_gate_check_dev" % c: (C.c_int, [vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp]),
+            "zk_fr_%s_gather_dev" % c: (C.c_int, [vp, C.c_uint64, vp, C.c_uint64, vp, vp]),
         })
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -447,6 +452,9 @@ def __getattr__(name):
     if name in ("Kzg", "divide", "divide_acc", "interleave"):   # kzg.py (KZG commitments over a powers-of-tau file), fetched the same way
         import importlib
         return getattr(importlib.import_module(__name__ + ".kzg"), name)
+    if name in ("Circuit", "PlonkKey"):                         # plonk.py (the PLONK prover and verifier over kzg.py and frpoly.py)
+        import importlib
+        return getattr(importlib.import_module(__name__ + ".plonk"), name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 

@@ -992,6 +992,24 @@ uint64_t zk_frpoly_span(void) { return FRPOLY_SPAN; }
 ZK_FRPOLY_API(bn254, CURVE_BN254)
 ZK_FRPOLY_API(bls12_381, CURVE_BLS12_381)
 #undef ZK_FRPOLY_API
+// ---- the device side of the PLONK prover (plonk_impl.hip.h through groth16.hip) ----
+#define ZK_PLONK_API(NAME, ID)                                                                                                                \
+    int zk_plonk_##NAME##_quotient_dev(const uint64_t* const* d_cols, uint32_t log_n, const uint64_t* alpha, const uint64_t* beta, const uint64_t* gamma, \
+                                       const uint64_t* k1, const uint64_t* k2, uint64_t* d_out, void* stream) {                               \
+        return guard([&] {                                                                                                                    \
+            curve(ID).plonk().quotient_dev((const u64* const*)d_cols, log_n, (const u64*)alpha, (const u64*)beta, (const u64*)gamma, (const u64*)k1, (const u64*)k2, (u64*)d_out, \
+                                           on_stream((hipStream_t)stream));                                                                   \
+        });                                                                                                                                   \
+    }                                                                                                                                         \
+    int zk_plonk_##NAME##_gate_check_dev(const uint64_t* const* d_cols, uint64_t n, uint64_t* n_bad, uint64_t* first_bad, void* stream) {      \
+        return guard([&] { curve(ID).plonk().gate_check_dev((const u64* const*)d_cols, n, (u64*)n_bad, (u64*)first_bad, on_stream((hipStream_t)stream)); }); \
+    }                                                                                                                                         \
+    int zk_fr_##NAME##_gather_dev(const uint64_t* d_src, uint64_t n_src, const uint32_t* d_idx, uint64_t n, uint64_t* d_out, void* stream) {   \
+        return guard([&] { curve(ID).plonk().gather_dev((const u64*)d_src, n_src, d_idx, n, (u64*)d_out, on_stream((hipStream_t)stream)); }); \
+    }
+ZK_PLONK_API(bn254, CURVE_BN254)
+ZK_PLONK_API(bls12_381, CURVE_BLS12_381)
+#undef ZK_PLONK_API
 int zk_groth16_verify_aggregate_timing(double* ms) {
     return guard([&] { ZK_REQUIRE(ms, "groth16 verify: null argument"); groth16_verify_aggregate_timing(ms); });
 }

@@ -111,6 +111,14 @@ struct FrPolyOps {
 };
 const FrPolyOps& frpoly_ops(CurveId id);
 constexpr uint64_t FRPOLY_TILE = 2048, FRPOLY_SPAN = 512;   // elements per workgroup of the running product; tile aggregates per step of the combining workgroup
+// ---- groth16.hip: the device side of the PLONK prover (plonk_impl.hip.h).  Vectors and scalars as for FrPolyOps; what
+// include/zkgpu.h states for zk_plonk_<curve>_quotient_dev, zk_plonk_<curve>_gate_check_dev and zk_fr_<curve>_gather_dev holds for these
+struct PlonkOps {
+    void (*quotient_dev)(const u64* const* d_cols, u32 log_n, const u64* alpha, const u64* beta, const u64* gamma, const u64* k1, const u64* k2, u64* d_out, hipStream_t st);
+    void (*gate_check_dev)(const u64* const* d_cols, u64 n, u64* n_bad, u64* first_bad, hipStream_t st);
+    void (*gather_dev)(const u64* d_src, u64 n_src, const u32* d_idx, u64 n, u64* d_out, hipStream_t st);
+};
+const PlonkOps& plonk_ops(CurveId id);
 // ---- pairing.hip: the steps of the optimal ate pairing and of Groth16 verification (pairing_impl.hip.h)
 struct PairingOps {
     const char* q_hex;                                                      // the base field's modulus
@@ -173,6 +181,7 @@ struct Curve {
     const EcOps& ec() const { return ec_ops(id); }
     const KzgOps& kzg() const { return kzg_ops(id); }
     const FrPolyOps& frpoly() const { return frpoly_ops(id); }
+    const PlonkOps& plonk() const { return plonk_ops(id); }
 };
 inline const Curve CURVES[2] = {
     {CURVE_BN254, "BN128", "bn254", 8, {0xf0000001u, 0x43e1f593u, 0x79b97091u, 0x2833e848u, 0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u}},

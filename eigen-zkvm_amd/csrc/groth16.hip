@@ -9,7 +9,8 @@
 //   quotient         7 transforms over Fr + the pointwise step                  (frntt_impl.hip.h)
 //   h, l, a, b_g1, b_g2 sums and the final assembly through msm.hip
 // This unit owns the scalar field's transforms, so the polynomial layer that runs them batched in their own layout lives here too
-// (frpoly_impl.hip.h, DESIGN.md 3.20: zk_fr_<curve>_poly_mul_dev and its siblings; no protocol).
+// (frpoly_impl.hip.h, DESIGN.md 3.20: zk_fr_<curve>_poly_mul_dev and its siblings; no protocol), and after it the three kernels of the
+// PLONK prover (plonk_impl.hip.h, DESIGN.md 3.21: the fused numerator of the quotient, the gate check, the gather).
 //   proof.json       groth16/src/json_utils.rs:305-315
 // Key generation (`zkit groth16_setup`, groth16/src/api.rs:42-66) over the same circuit: groth16_keygen_impl.hip.h with a trapdoor,
 // groth16_srs.hip.h from a powers-of-tau file (and the contributions to such a key).
@@ -302,6 +303,7 @@ namespace bn254fr {
 #define FRP_CURVE CURVE_BN254
 #include "frntt_impl.hip.h"
 #include "frpoly_impl.hip.h"
+#include "plonk_impl.hip.h"
 #include "groth16_impl.hip.h"
 #include "groth16_keygen_impl.hip.h"
 #include "verify_sums_impl.hip.h"
@@ -321,6 +323,7 @@ namespace bls12381fr {
 #define FRP_CURVE CURVE_BLS12_381
 #include "frntt_impl.hip.h"
 #include "frpoly_impl.hip.h"
+#include "plonk_impl.hip.h"
 #include "groth16_impl.hip.h"
 #include "groth16_keygen_impl.hip.h"
 #include "verify_sums_impl.hip.h"
@@ -340,6 +343,12 @@ const FrPolyOps& frpoly_ops(CurveId id) {     // frpoly_impl.hip.h, per scalar f
                            NS::fp_poly_mul_dev, NS::fp_divmod_zh_dev, NS::fp_divide_zh_coset_dev}
     static const FrPolyOps OPS[2] = {ZK_FRPOLY_OPS(bn254fr), ZK_FRPOLY_OPS(bls12381fr)};
 #undef ZK_FRPOLY_OPS
+    return OPS[id];
+}
+
+const PlonkOps& plonk_ops(CurveId id) {       // plonk_impl.hip.h, per scalar field
+    static const PlonkOps OPS[2] = {{bn254fr::pk_quotient_dev, bn254fr::pk_gate_check_dev, bn254fr::pk_gather_dev},
+                                    {bls12381fr::pk_quotient_dev, bls12381fr::pk_gate_check_dev, bls12381fr::pk_gather_dev}};
     return OPS[id];
 }
 

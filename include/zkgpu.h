@@ -1001,6 +1001,37 @@ int zk_fr_bls12_381_divmod_zh_dev(const uint64_t* d_p, uint64_t n_p, uint32_t lo
 int zk_fr_bn254_divide_zh_coset_dev(uint64_t* d_evals, uint32_t log_m, uint32_t log_n, void* stream);
 int zk_fr_bls12_381_divide_zh_coset_dev(uint64_t* d_evals, uint32_t log_m, uint32_t log_n, void* stream);
 
+/* ---- The device side of the PLONK prover (csrc/plonk_impl.hip.h) ---------------------------------------------------------
+ * The three kernels the prover of eigen_zkvm_amd/plonk.py adds to the layer above; the protocol itself (rounds, transcript, keys, files) is
+ * Python over these calls, as Kzg.open_multi is over zk_kzg_multi_*.  Vectors, scalars and <curve> as for the polynomial layer: n x 4 u64
+ * Montgomery words on the device, 16-byte aligned, input words anything below 2^256; scalars 4 canonical u64 words on the HOST, refused before
+ * any device work when not below r; every output vector canonical.
+ * zk_plonk_<curve>_quotient_dev: the numerator of the quotient on the coset 7 H_m, m = 4n = 4 2^log_n, in the order
+ *   zk_fr_<curve>_ntt_dev(.., coset = 1) leaves it.  d_cols: a HOST array of ZK_PLONK_QUOTIENT_COLS (15) device pointers to m elements each,
+ *   in this order: a, b, c, Z, q_L, q_R, q_O, q_M, q_C, S_sigma1, S_sigma2, S_sigma3, PI, L_1, X.  out[i] =
+ *     a b q_M + a q_L + b q_R + c q_O + q_C + PI
+ *     + alpha ((a + beta X + gamma)(b + beta k1 X + gamma)(c + beta k2 X + gamma) Z
+ *              - (a + beta S_sigma1 + gamma)(b + beta S_sigma2 + gamma)(c + beta S_sigma3 + gamma) Z[(i + 4) mod m])
+ *     + alpha^2 L_1 (Z - 1)
+ *   at element i of every column.  d_out (m elements) overlaps no column.  log_n + 2 beyond the field's 2-adicity is refused.  One lane per
+ *   element, one launch; the division by Z_H is zk_fr_<curve>_divide_zh_coset_dev(d_out, log_n + 2, log_n).
+ * zk_plonk_<curve>_gate_check_dev: the gate equation row by row over n rows.  d_cols: a HOST array of ZK_PLONK_GATE_COLS (9) device pointers
+ *   in the order a, b, c, q_L, q_R, q_O, q_M, q_C, PI (the wire VALUES, the selectors' values on H).  n_bad (HOST): the number of rows with
+ *   q_L a + q_R b + q_O c + q_M a b + q_C + PI != 0, exact; first_bad (HOST): the first of them, UINT64_MAX when none.  Waits for the stream.
+ * zk_fr_<curve>_gather_dev: out[i] = src[idx[i]] for i < n; d_idx: n uint32 on the device; d_out overlaps no source element.  An index that is
+ *   not below n_src reads nothing and leaves zero; the call then fails with their number and the first position.  Waits for the stream.
+ * Not built: a linearisation polynomial, custom gates, lookups, the split of the quotient, a one-call C prover.                            */
+#define ZK_PLONK_QUOTIENT_COLS 15
+#define ZK_PLONK_GATE_COLS 9
+int zk_plonk_bn254_quotient_dev(const uint64_t* const* d_cols, uint32_t log_n, const uint64_t* alpha, const uint64_t* beta, const uint64_t* gamma,
+                                const uint64_t* k1, const uint64_t* k2, uint64_t* d_out, void* stream);
+int zk_plonk_bls12_381_quotient_dev(const uint64_t* const* d_cols, uint32_t log_n, const uint64_t* alpha, const uint64_t* beta, const uint64_t* gamma,
+                                    const uint64_t* k1, const uint64_t* k2, uint64_t* d_out, void* stream);
+int zk_plonk_bn254_gate_check_dev(const uint64_t* const* d_cols, uint64_t n, uint64_t* n_bad, uint64_t* first_bad, void* stream);
+int zk_plonk_bls12_381_gate_check_dev(const uint64_t* const* d_cols, uint64_t n, uint64_t* n_bad, uint64_t* first_bad, void* stream);
+int zk_fr_bn254_gather_dev(const uint64_t* d_src, uint64_t n_src, const uint32_t* d_idx, uint64_t n, uint64_t* d_out, void* stream);
+int zk_fr_bls12_381_gather_dev(const uint64_t* d_src, uint64_t n_src, const uint32_t* d_idx, uint64_t n, uint64_t* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
