@@ -159,13 +159,18 @@ def _powers(base, n, first=1):
     return out
 
 
-def stark_gen(cm_path, su, stark_struct, orc, use_c=True, lean=False, log=None):
+def stark_gen(cm_path, su, stark_struct, orc, use_c=True, lean=False, log=None, cheat=None):
     """cm_path: a .cm file or the trace itself (flat uint64 array).  use_c: constraint programs run through
     oracle/interp.c (same semantics as oracle/interp.py, which use_c=False selects; compared in tests/test_oracle_interp.py).
     lean: sections over the N-row domain are dropped once stage 3 is committed (nothing after it reads them) and the
     trace is not copied -- the 2^24-row golden (tools/gen_golden_full.py) has to fit the build container; same proof.
-    log: callable for progress lines (roots as they appear)."""
+    log: callable for progress lines (roots as they appear).
+    cheat: a DISHONEST prover for the verifiers' rejection tests (tests/stark_forge.py), a dict of optional hooks:
+      "evals":  f(evals, challenge, publics) -> evals, called once the evaluations at xi are computed, before the transcript absorbs them
+      "folded": f(si, pol) -> pol, see fri_prove
+    Whatever a hook changes, the rest of the proof is built on it, so roots, challenges and query indices stay those a verifier derives."""
     log = log or (lambda *a: None)
+    cheat = cheat or {}
     info, prog = su["starkinfo"], su["program"]
     nbits, nbits_ext = stark_struct["nBits"], stark_struct["nBitsExt"]
     ext = nbits_ext - nbits
@@ -285,6 +290,8 @@ def stark_gen(cm_path, su, stark_struct, orc, use_c=True, lean=False, log=None):
             p = info["var_pol_map"][info["cm_2ns"][ev["id"]]]
             buf, width, off, dim = bufs[p["section"]], sN[p["section"]], p["section_pos"], p["dim"]
         evals.append([int(v) for v in orc.eval_dot(buf, width, off, dim, nbits, ext, LpEv if ev["prime"] else LEv)])
+    if cheat.get("evals"):
+        evals[:] = [[int(v) % P for v in e] for e in cheat["evals"]([list(e) for e in evals], [list(c) for c in challenge], list(publics))]
     for e in evals:
         tr.put(e)
     challenge[5] = [int(v) for v in tr.get_field()]
@@ -298,7 +305,7 @@ def stark_gen(cm_path, su, stark_struct, orc, use_c=True, lean=False, log=None):
 
     def query_pol(idx):
         return [group_proof(orc, t["nodes"], t["elements"], t["width"], Next, idx) for t in trees]
-    fri_proof = fri_prove(orc, tr, fri_pol, stark_struct, query_pol)
+    fri_proof = fri_prove(orc, tr, fri_pol, stark_struct, query_pol, cheat=cheat)
     return {"rootC": [int(v) for v in su["const_tree"][-4:]], "root1": [int(v) for v in tree1["nodes"][-4:]],
             "root2": [int(v) for v in tree2["nodes"][-4:]], "root3": [int(v) for v in tree3["nodes"][-4:]],
             "root4": [int(v) for v in tree4["nodes"][-4:]], "fri_proof": fri_proof, "evals": evals, "publics": publics}
@@ -332,7 +339,10 @@ def set_pol(bufs, info, pol_id, pol3, n):                                     # 
     b.reshape(n, size)[:, off:off + p["dim"]] = np.array(pol3, np.uint64).reshape(n, 3)[:, :p["dim"]]
 
 
-def fri_prove(orc, tr, pol, stark_struct, query_pol):                         # fri.rs:84-184
+def fri_prove(orc, tr, pol, stark_struct, query_pol, cheat=None):             # fri.rs:84-184
+    """cheat["folded"]: f(si, pol) -> pol (flat, 3 words a value), called on the result of fold si before it is transposed and
+    merkelized or, for the last step, absorbed -- what a dishonest prover commits to in place of the fold (see stark_gen)"""
+    folded = (cheat or {}).get("folded")
     steps = [s["nBits"] for s in stark_struct["steps"]]
     pol_bits = stark_struct["nBitsExt"]
     shift_inv = pow(49, P - 2, P)
@@ -340,6 +350,9 @@ def fri_prove(orc, tr, pol, stark_struct, query_pol):                         # 
     for si, step_bits in enumerate(steps):
         special_x = tr.get_field()
         pol = orc.fri_fold(pol, pol_bits, step_bits, special_x, shift_inv)
+        if folded:
+            pol = np.ascontiguousarray(folded(si, pol.copy()), dtype=np.uint64).reshape(-1)
+            assert pol.size == 3 << step_bits
         if si < len(steps) - 1:
             nxt = steps[si + 1]
             n_groups, group_size = 1 << nxt, (1 << step_bits) >> nxt
@@ -507,7 +520,15 @@ def v_eq(a, b):                                                                #
     return a == b
 
 
-def stark_verify(proof, const_root, info, prog, stark_struct, orc):
+def checks(stark_struct):
+    """the names of every check stark_verify / fri_verify make for this struct, in the order they make them"""
+    return ("eq30", "merkle") + tuple("fold%d" % k for k in range(1, len(stark_struct["steps"]))) + ("last_fold", "degree")
+
+
+def stark_verify(proof, const_root, info, prog, stark_struct, orc, skip=()):
+    """skip: names of checks (checks()) that are NOT made -- a knob of this restatement only, for tests/test_stark_forge.py, which
+    shows that a forged proof is stopped by one check and no other.  The product has nothing like it."""
+    assert set(skip) <= set(checks(stark_struct)), skip
     nbits, nbits_ext = stark_struct["nBits"], stark_struct["nBitsExt"]
     N = 1 << nbits
     tr = orc.transcript()
@@ -530,13 +551,13 @@ def stark_verify(proof, const_root, info, prog, stark_struct, orc):
     for i in range(info["q_deg"]):
         q = interp.v_add(q, interp.v_mul(x_acc, f3(proof["evals"][info["ev_idx"]["cm"][(0, info["qs"][i])]])))
         x_acc = interp.v_mul(x_acc, x_n)
-    if not v_eq(res, interp.v_mul(q, ctx["Z"])):
+    if "eq30" not in skip and not v_eq(res, interp.v_mul(q, ctx["Z"])):
         return False
     w_ext = orc.root(nbits_ext)
     roots = [proof["root1"], proof["root2"], proof["root3"], proof["root4"], const_root]
 
     def check_query(query, idx):                                               # stark_verify.rs:80-136
-        for (row, path), root in zip(query, roots):
+        for (row, path), root in zip(query, () if "merkle" in skip else roots):
             got = orc.root_from_proof(np.array(row, np.uint64), np.array(path, np.uint64).reshape(-1), idx)
             if [int(v) for v in got] != [int(v) for v in root]:
                 raise ValueError("FRIVerifierFailed")
@@ -546,12 +567,15 @@ def stark_verify(proof, const_root, info, prog, stark_struct, orc):
         q["xDivXSubXi"] = interp.v_mul((x,), f3_inv(orc, interp.v_sub((x,), ch[7])))
         q["xDivXSubWXi"] = interp.v_mul((x,), f3_inv(orc, interp.v_sub((x,), interp.v_mul(ch[7], (w,)))))
         return [execute_code(prog["verifier_query_code"]["first"], q)]
-    return fri_verify(orc, tr, proof["fri_proof"], stark_struct, check_query)
+    return fri_verify(orc, tr, proof["fri_proof"], stark_struct, check_query, skip=skip)
 
 
-def fri_verify(orc, tr, fp, stark_struct, check_query):                        # fri.rs:186-297
+def fri_verify(orc, tr, fp, stark_struct, check_query, skip=()):               # fri.rs:186-297
+    """skip: see stark_verify; "merkle" (the step trees here), "fold<k>" (the fold of step k - 1 against step k's opening), "last_fold" and "degree" """
     steps = [s["nBits"] for s in stark_struct["steps"]]
     nq = stark_struct["nQueries"]
+    if len(fp["queries"]) != len(steps):                                       # fri.rs:195 assert_eq!: a step too few or too many
+        return False
     special_x = []
     for si in range(len(steps)):
         special_x.append(f3(tr.get_field()))
@@ -570,7 +594,7 @@ def fri_verify(orc, tr, fp, stark_struct, check_query):                        #
             else:
                 row, path = item["pol_queries"][i][0]
                 got = orc.root_from_proof(np.array(row, np.uint64), np.array(path, np.uint64).reshape(-1), ys[i])
-                if [int(v) for v in got] != item["root"]:
+                if "merkle" not in skip and [int(v) for v in got] != item["root"]:
                     return False
                 pgroup = [tuple(row[k:k + 3]) for k in range(0, len(row), 3)]                 # split3
             flat = np.array([v for e in pgroup for v in (tuple(e) + (0,) * (3 - len(e)))], np.uint64)
@@ -585,9 +609,9 @@ def fri_verify(orc, tr, fp, stark_struct, check_query):                        #
                 nxt_groups = 1 << steps[si + 1]
                 gi = ys[i] // nxt_groups
                 row = fp["queries"][si + 1]["pol_queries"][i][0][0]
-                if not v_eq(ev, tuple(row[3 * gi:3 * gi + 3])):
+                if "fold%d" % (si + 1) not in skip and not v_eq(ev, tuple(row[3 * gi:3 * gi + 3])):
                     return False
-            elif not v_eq(ev, tuple(fp["last"][ys[i]])):
+            elif "last_fold" not in skip and not v_eq(ev, tuple(fp["last"][ys[i]])):
                 return False
         for _ in range(pol_bits - step_bits):
             shift = shift * shift % P
@@ -596,6 +620,8 @@ def fri_verify(orc, tr, fp, stark_struct, check_query):                        #
             ys = [y % (1 << steps[si + 1]) for y in ys]
     in_bits, max_deg_bits = stark_struct["nBitsExt"], stark_struct["nBits"]
     max_deg = 0 if pol_bits < (in_bits - max_deg_bits) else 1 << (pol_bits - (in_bits - max_deg_bits))
+    if "degree" in skip:
+        return True
     last = np.array([v for e in fp["last"] for v in e], np.uint64)
     coef = orc.f3_ntt(last, pol_bits, inverse=True).reshape(-1, 3)
     return all(not any(int(v) for v in coef[i]) for i in range(max_deg + 1, len(coef)))

@@ -106,20 +106,22 @@ def test_scalar_field_fixture_proofs_accepted(zk, orc, name, hash_type):
     ns.free()
 
 
+# what is bumped, and the FIRST check in the verifier's order that sees it (a root, a public or an evaluation moves the challenges, so Eq. 30
+# at the new xi; s1_root and the last polynomial are absorbed before the query indices are drawn, so the first step-0 path at the new indices)
 TAMPER = {
-    "eval": lambda z: z["evals"][1].__setitem__(0, _bump(z["evals"][1][0])),
-    "public": lambda z: z["publics"].__setitem__(0, _bump(z["publics"][0])),
-    "root1": lambda z: z.__setitem__("root1", [_bump(z["root1"][0])] + z["root1"][1:]),
-    "root4": lambda z: z.__setitem__("root4", z["root4"][:3] + [_bump(z["root4"][3])]),
-    "opened value tree1": lambda z: z["s0_vals1"][0].__setitem__(0, _bump(z["s0_vals1"][0][0])),
-    "opened value consts": lambda z: z["s0_valsC"][7].__setitem__(0, _bump(z["s0_valsC"][7][0])),
-    "sibling level 0": lambda z: z["s0_siblings4"][1][0].__setitem__(2, _bump(z["s0_siblings4"][1][0][2])),
-    "sibling top level": lambda z: z["s0_siblings3"][5][-1].__setitem__(0, _bump(z["s0_siblings3"][5][-1][0])),
-    "fri step root": lambda z: z.__setitem__("s1_root", [_bump(z["s1_root"][0])] + z["s1_root"][1:]),
-    "fri step value": lambda z: z["s1_vals"][2].__setitem__(4, _bump(z["s1_vals"][2][4])),
-    "fri step sibling": lambda z: z["s2_siblings"][6][1].__setitem__(3, _bump(z["s2_siblings"][6][1][3])),
-    "last polynomial": lambda z: z["finalPol"][3].__setitem__(1, _bump(z["finalPol"][3][1])),
-    "queries swapped": lambda z: (z["s0_vals1"].reverse(), z["s0_siblings1"].reverse()),
+    "eval": (lambda z: z["evals"][1].__setitem__(0, _bump(z["evals"][1][0])), "Q != C * P at xi"),
+    "public": (lambda z: z["publics"].__setitem__(0, _bump(z["publics"][0])), "Q != C * P at xi"),
+    "root1": (lambda z: z.__setitem__("root1", [_bump(z["root1"][0])] + z["root1"][1:]), "Q != C * P at xi"),
+    "root4": (lambda z: z.__setitem__("root4", z["root4"][:3] + [_bump(z["root4"][3])]), "Q != C * P at xi"),
+    "opened value tree1": (lambda z: z["s0_vals1"][0].__setitem__(0, _bump(z["s0_vals1"][0][0])), "tree1 does not open to its root"),
+    "opened value consts": (lambda z: z["s0_valsC"][7].__setitem__(0, _bump(z["s0_valsC"][7][0])), "the constants' tree does not open to its root"),
+    "sibling level 0": (lambda z: z["s0_siblings4"][1][0].__setitem__(2, _bump(z["s0_siblings4"][1][0][2])), "tree4 does not open to its root"),
+    "sibling top level": (lambda z: z["s0_siblings3"][5][-1].__setitem__(0, _bump(z["s0_siblings3"][5][-1][0])), "tree3 does not open to its root"),
+    "fri step root": (lambda z: z.__setitem__("s1_root", [_bump(z["s1_root"][0])] + z["s1_root"][1:]), "tree1 does not open to its root"),
+    "fri step value": (lambda z: z["s1_vals"][2].__setitem__(4, _bump(z["s1_vals"][2][4])), "a FRI step does not open to its root"),
+    "fri step sibling": (lambda z: z["s2_siblings"][6][1].__setitem__(3, _bump(z["s2_siblings"][6][1][3])), "a FRI step does not open to its root"),
+    "last polynomial": (lambda z: z["finalPol"][3].__setitem__(1, _bump(z["finalPol"][3][1])), "tree1 does not open to its root"),
+    "queries swapped": (lambda z: (z["s0_vals1"].reverse(), z["s0_siblings1"].reverse()), "tree1 does not open to its root"),
 }
 
 
@@ -129,9 +131,10 @@ def test_tampered_gl_proofs_rejected_like_the_oracle(zk, orc, what):
     ns, program, cm = _setup(stark, GL_CASES["fibonacci_imP" if what == "public" else "plookup_gl"], STRUCT)   # (the plookup fixture has no publics)
     z = ns.gen(cm)
     bad = copy.deepcopy(z)
-    TAMPER[what](bad)
+    tamper, phrase = TAMPER[what]
+    tamper(bad)
     assert bad != z
-    assert ns.verify(bad) is False, what
+    assert ns.verify(bad) is False and phrase in ns.last_reject(), what
     assert ns.last_reject().startswith("stark_verify: ")
     assert _oracle_verdict(bad, ns, program, STRUCT, orc) is False
     assert ns.verify(z) is True                                               # (the setup is not left in a bad state)
@@ -151,12 +154,18 @@ def test_malformed_proofs_are_errors_or_rejections_never_crashes(zk):
     bad = copy.deepcopy(z); bad["evals"][0][0] = "12x"
     with pytest.raises(zk.ZkError):
         ns.verify(bad)
-    for mutate in (lambda b: b["finalPol"].pop(), lambda b: b["s0_vals1"].pop(), lambda b: b["s0_vals1"][0].pop(), lambda b: b["s1_vals"][0].pop(),
-                   lambda b: b["s0_siblings1"][0].pop(), lambda b: b["evals"].pop(), lambda b: b["publics"].pop(),
-                   lambda b: (b.pop("s2_root"), b.pop("s2_vals"), b.pop("s2_siblings")),
-                   lambda b: b.update({"s3_root": b["s2_root"], "s3_vals": b["s2_vals"], "s3_siblings": b["s2_siblings"]})):
+    for mutate, phrase in ((lambda b: b["finalPol"].pop(), "the last polynomial does not hold 2^steps.last values"),
+                           (lambda b: b["s0_vals1"].pop(), "s0_vals1: one opening per query expected"),
+                           (lambda b: b["s0_vals1"][0].pop(), "tree1: rows of one tree differ in width"),
+                           (lambda b: b["s1_vals"][0].pop(), "a FRI step: rows of one tree differ in width"),
+                           (lambda b: b["s0_siblings1"][0].pop(), "tree1: the Merkle path has 10 levels, the tree has 11"),
+                           (lambda b: b["evals"].pop(), "the proof holds fewer evaluations than the starkinfo names"),
+                           (lambda b: b["publics"].pop(), "the proof holds fewer publics than the verifier program reads"),
+                           (lambda b: (b.pop("s2_root"), b.pop("s2_vals"), b.pop("s2_siblings")), "the proof has fewer FRI steps than the starkStruct"),
+                           (lambda b: b.update({"s3_root": b["s2_root"], "s3_vals": b["s2_vals"], "s3_siblings": b["s2_siblings"]}),
+                            "the proof has more FRI steps than the starkStruct")):
         bad = copy.deepcopy(z); mutate(bad)
-        assert ns.verify(bad) is False
+        assert ns.verify(bad) is False and phrase in ns.last_reject(), phrase
     ns.free()
 
 
@@ -187,7 +196,7 @@ def test_poseidong_2p16_and_blowup_4_accepted_then_tampered(zk):
         z = ns.gen(PG.trace(nbits, None, PG.FIRST_COUNT, seed=nbits))
         assert ns.verify(z) is True
         bad = copy.deepcopy(z); bad["s0_vals3"][4][17] = _bump(bad["s0_vals3"][4][17])
-        assert ns.verify(bad) is False
-        bad = copy.deepcopy(z); bad["finalPol"][0][0] = _bump(bad["finalPol"][0][0])
-        assert ns.verify(bad) is False
+        assert ns.verify(bad) is False and "tree3 does not open to its root" in ns.last_reject()
+        bad = copy.deepcopy(z); bad["finalPol"][0][0] = _bump(bad["finalPol"][0][0])       # absorbed before the query indices are drawn: they move
+        assert ns.verify(bad) is False and "tree1 does not open to its root" in ns.last_reject()
         ns.free()
