@@ -77,7 +77,8 @@ EXPORTS = [
     "zk_frpoly_tile_elems", "zk_frpoly_span",
 ] + ["zk_fr_%s_%s_dev" % (c, f) for c in ("bn254", "bls12_381")
      for f in ("prefix_product", "batch_inverse", "pointwise", "powers", "terms", "grand_product", "poly_mul", "divmod_zh", "divide_zh_coset")
-     ] + [n % c for c in ("bn254", "bls12_381") for n in ("zk_plonk_%s_quotient_dev", "zk_plonk_%s_gate_check_dev", "zk_fr_%s_gather_dev")]
+     ] + [n % c for c in ("bn254", "bls12_381") for n in ("zk_plonk_%s_quotient_dev", "zk_plonk_%s_gate_check_dev", "zk_fr_%s_gather_dev")
+     ] + ["zk_plonk_r1cs_wave_min_terms"] + ["zk_plonk_%s_r1cs_%s" % (c, f) for c in ("bn254", "bls12_381") for f in ("new", "info", "tables", "extend_dev", "free")]
 
 # include/zkgpu.h enums
 OP_ADD, OP_SUB, OP_MUL, OP_COPY = 0, 1, 2, 3
@@ -411,6 +412,7 @@ def _load():
         "zk_kzg_multi_verify": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, vp, C.POINTER(C.c_int), vp]),
         "zk_kzg_multi_verify_dev": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, vp, C.POINTER(C.c_int), vp, vp]),
         "zk_frpoly_tile_elems": (C.c_uint64, []), "zk_frpoly_span": (C.c_uint64, []),
+        "zk_plonk_r1cs_wave_min_terms": (C.c_uint64, []),
     }
     for c in ("bn254", "bls12_381"):                    # polynomial arithmetic over the scalar field (frpoly.py)
         sig.update({
@@ -427,6 +429,12 @@ def _load():
             "zk_plonk_%s_quotient_dev" % c: (C.c_int, [vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp]),
             "zk_plonk_%s_gate_check_dev" % c: (C.c_int, [vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp]),
             "zk_fr_%s_gather_dev" % c: (C.c_int, [vp, C.c_uint64, vp, C.c_uint64, vp, vp]),
+            # its R1CS import (plonk.R1csCircuit, plonk.extend_witness)
+            "zk_plonk_%s_r1cs_new" % c: (vp, [vp, C.c_size_t]),
+            "zk_plonk_%s_r1cs_info" % c: (C.c_int, [vp, vp]),
+            "zk_plonk_%s_r1cs_tables" % c: (C.c_int, [vp] * 10),
+            "zk_plonk_%s_r1cs_extend_dev" % c: (C.c_int, [vp, vp, vp]),
+            "zk_plonk_%s_r1cs_free" % c: (C.c_int, [vp]),
         })
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -452,7 +460,7 @@ def __getattr__(name):
     if name in ("Kzg", "divide", "divide_acc", "interleave"):   # kzg.py (KZG commitments over a powers-of-tau file), fetched the same way
         import importlib
         return getattr(importlib.import_module(__name__ + ".kzg"), name)
-    if name in ("Circuit", "PlonkKey"):                         # plonk.py (the PLONK prover and verifier over kzg.py and frpoly.py)
+    if name in ("Circuit", "PlonkKey", "R1csCircuit", "extend_witness"):   # plonk.py (the PLONK prover and verifier over kzg.py and frpoly.py)
         import importlib
         return getattr(importlib.import_module(__name__ + ".plonk"), name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -1010,6 +1010,51 @@ ZK_FRPOLY_API(bls12_381, CURVE_BLS12_381)
 ZK_PLONK_API(bn254, CURVE_BN254)
 ZK_PLONK_API(bls12_381, CURVE_BLS12_381)
 #undef ZK_PLONK_API
+// ---- the R1CS import of the PLONK prover (plonk_r1cs_impl.hip.h through groth16.hip); new, info, tables and free touch no device ----
+uint64_t zk_plonk_r1cs_wave_min_terms(void) { return PLONK_R1CS_WAVE_MIN_TERMS; }
+static const zk_plonk_r1cs_t& plonk_r1cs_of(const zk_plonk_r1cs_t* h, CurveId id) {
+    ZK_REQUIRE(h, "plonk r1cs: null handle");
+    ZK_REQUIRE(h->curve == &curve(id), "plonk r1cs: the handle is over another field");
+    return *h;
+}
+static void plonk_r1cs_info(const zk_plonk_r1cs_t& h, uint64_t* out) {
+    ZK_REQUIRE(out, "plonk r1cs: null argument");
+    const uint64_t v[ZK_PLONK_R1CS_INFO_WORDS] = {h.n_wires, h.n_public, h.n_constraints, h.origin.size(), h.n_vars - h.n_wires, h.seg_first.size(), h.max_terms, h.seg_wire.size()};
+    std::memcpy(out, v, sizeof v);
+}
+static void plonk_r1cs_tables(const zk_plonk_r1cs_t& h, uint64_t* sel, uint32_t* a, uint32_t* b, uint32_t* c, uint32_t* origin, uint32_t* seg_first, uint64_t* seg_ptr, uint32_t* seg_wire,
+                              uint64_t* seg_coef) {
+    const size_t m = h.origin.size(), ns = h.seg_first.size(), nt = h.seg_wire.size();
+    ZK_REQUIRE((sel && a && b && c && origin) || !m, "plonk r1cs: null gate table");
+    ZK_REQUIRE(seg_ptr && ((seg_first || !ns) && ((seg_wire && seg_coef) || !nt)), "plonk r1cs: null segment table");
+    uint32_t* wires[3] = {a, b, c};
+    if (m) {
+        for (int s = 0; s < 5; ++s) std::memcpy(sel + (size_t)s * m * 4, h.sel[s].data(), m * 32);
+        for (int w = 0; w < 3; ++w) std::memcpy(wires[w], h.wire[w].data(), m * 4);
+        std::memcpy(origin, h.origin.data(), m * 4);
+    }
+    std::memcpy(seg_ptr, h.seg_ptr.data(), (ns + 1) * 8);
+    if (ns) std::memcpy(seg_first, h.seg_first.data(), ns * 4);
+    if (nt) { std::memcpy(seg_wire, h.seg_wire.data(), nt * 4); std::memcpy(seg_coef, h.seg_coef.data(), nt * 32); }
+}
+#define ZK_PLONK_R1CS_API(NAME, ID)                                                                                                           \
+    zk_plonk_r1cs_t* zk_plonk_##NAME##_r1cs_new(const void* r1cs, size_t len) {                                                               \
+        zk_plonk_r1cs_t* out = nullptr;                                                                                                       \
+        guard([&] { out = curve(ID).plonk().r1cs_new(r1cs, len); });                                                                          \
+        return out;                                                                                                                           \
+    }                                                                                                                                         \
+    int zk_plonk_##NAME##_r1cs_info(const zk_plonk_r1cs_t* h, uint64_t* out) { return guard([&] { plonk_r1cs_info(plonk_r1cs_of(h, ID), out); }); } \
+    int zk_plonk_##NAME##_r1cs_tables(const zk_plonk_r1cs_t* h, uint64_t* sel, uint32_t* a, uint32_t* b, uint32_t* c, uint32_t* origin, uint32_t* seg_first, uint64_t* seg_ptr,  \
+                                      uint32_t* seg_wire, uint64_t* seg_coef) {                                                               \
+        return guard([&] { plonk_r1cs_tables(plonk_r1cs_of(h, ID), sel, a, b, c, origin, seg_first, seg_ptr, seg_wire, seg_coef); });         \
+    }                                                                                                                                         \
+    int zk_plonk_##NAME##_r1cs_extend_dev(zk_plonk_r1cs_t* h, uint64_t* d_w, void* stream) {                                                  \
+        return guard([&] { plonk_r1cs_of(h, ID); curve(ID).plonk().r1cs_extend_dev(*h, (u64*)d_w, on_stream((hipStream_t)stream)); });        \
+    }                                                                                                                                         \
+    int zk_plonk_##NAME##_r1cs_free(zk_plonk_r1cs_t* h) { return guard([&] { delete h; }); }
+ZK_PLONK_R1CS_API(bn254, CURVE_BN254)
+ZK_PLONK_R1CS_API(bls12_381, CURVE_BLS12_381)
+#undef ZK_PLONK_R1CS_API
 int zk_groth16_verify_aggregate_timing(double* ms) {
     return guard([&] { ZK_REQUIRE(ms, "groth16 verify: null argument"); groth16_verify_aggregate_timing(ms); });
 }

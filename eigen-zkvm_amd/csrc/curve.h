@@ -11,6 +11,7 @@ struct zk_groth16_vk;
 struct zk_srs;
 struct zk_kzg;
 struct zk_kzg_multi;
+struct zk_plonk_r1cs;
 
 namespace zk {
 
@@ -20,6 +21,7 @@ using Groth16Vk = ::zk_groth16_vk;
 using Srs = ::zk_srs;
 using Kzg = ::zk_kzg;
 using KzgMulti = ::zk_kzg_multi;
+using PlonkR1cs = ::zk_plonk_r1cs;
 namespace g16 { struct Circuit; struct Params; }
 // what miller_kernel takes (pairing_impl.hip.h): up to three pairs per item -- G1 points, line tables and infinity words with their strides
 struct MillerArgs {
@@ -117,8 +119,13 @@ struct PlonkOps {
     void (*quotient_dev)(const u64* const* d_cols, u32 log_n, const u64* alpha, const u64* beta, const u64* gamma, const u64* k1, const u64* k2, u64* d_out, hipStream_t st);
     void (*gate_check_dev)(const u64* const* d_cols, u64 n, u64* n_bad, u64* first_bad, hipStream_t st);
     void (*gather_dev)(const u64* d_src, u64 n_src, const u32* d_idx, u64 n, u64* d_out, hipStream_t st);
+    // plonk_r1cs_impl.hip.h: an .r1cs compiled to a gate table on the host (no device is touched); the auxiliary variables
+    // of a witness on the device
+    PlonkR1cs* (*r1cs_new)(const void* r1cs, size_t len);
+    void (*r1cs_extend_dev)(PlonkR1cs& h, u64* d_w, hipStream_t st);
 };
 const PlonkOps& plonk_ops(CurveId id);
+constexpr uint64_t PLONK_R1CS_WAVE_MIN_TERMS = 64;   // a segment of this many terms or more is walked by a whole wave (plonk_r1cs_impl.hip.h)
 // ---- pairing.hip: the steps of the optimal ate pairing and of Groth16 verification (pairing_impl.hip.h)
 struct PairingOps {
     const char* q_hex;                                                      // the base field's modulus
@@ -339,6 +346,22 @@ struct zk_kzg_multi {        // an opening at several points between its stages 
     int stage = 0;                                   // 1 after begin, 2 after quotient, 3 after finish
     zk_kzg_multi() = default; zk_kzg_multi(const zk_kzg_multi&) = delete; zk_kzg_multi& operator=(const zk_kzg_multi&) = delete;
     ~zk_kzg_multi() { for (void* p : {d_tables, d_q}) if (p) zk::pool_free(p); }
+};
+struct zk_plonk_r1cs {       // an .r1cs as the PLONK prover takes it (plonk_r1cs_impl.hip.h): host tables, the segments on the device from the first extension on
+    const zk::Curve* curve = nullptr;
+    uint32_t n_wires = 0, n_public = 0;
+    uint64_t n_constraints = 0, n_vars = 0, max_terms = 0;
+    std::vector<uint64_t> sel[5];                    // qL, qR, qO, qM, qC: 4 canonical words per gate
+    std::vector<uint32_t> wire[3], origin;           // a, b, c: variable ids; the constraint of every gate
+    std::vector<uint32_t> seg_first;                 // per segment: its first auxiliary
+    std::vector<uint64_t> seg_ptr;                   // n_segments + 1 offsets into the terms
+    std::vector<uint32_t> seg_wire;                  // per term: the original wire
+    std::vector<uint64_t> seg_coef;                  // per term: 4 canonical words
+    // the device's copy: offsets, first auxiliaries, wires, the coefficients in internal form (9 words a term), and the segments by kernel
+    zk::DevBuf d_ptr, d_first, d_wire, d_coef, d_short, d_long;
+    uint64_t n_short = 0, n_long = 0;
+    bool on_device = false;
+    zk_plonk_r1cs() = default; zk_plonk_r1cs(const zk_plonk_r1cs&) = delete; zk_plonk_r1cs& operator=(const zk_plonk_r1cs&) = delete;
 };
 struct zk_groth16_vk {       // a verification key, checked and prepared
     const zk::Curve* curve = nullptr;

@@ -3,7 +3,8 @@
 device through zk_fr_<curve>_*_dev, zk_plonk_<curve>_quotient_dev / _gate_check_dev, zk_fr_<curve>_gather_dev and Kzg.open_multi.  There is no
 CPU fallback.  Cut down to what those layers do: NO linearisation polynomial (every polynomial of the identity is opened at zeta, Z at
 zeta w as well, in one Shplonk proof of two points), the quotient t committed WHOLE (degree 3n + 5: the file must hold 3n + 6 G1 powers), a
-circuit is a gate table (no R1CS import, no custom gates, no lookups, not fflonk's interleaved form).
+circuit is a gate table, written by hand or compiled from a circom .r1cs (R1csCircuit); no custom gates, no lookups, not fflonk's
+interleaved form.
 
 Field Fr of BN128 or BLS12381.  n = 2^k >= 8 rows (smaller circuits are padded to 8, others to the next power of two; a padding row has all
 selectors 0 and its wires on variable 0).  H = <w> with the w of zk_fr_<curve>_ntt_dev, w = 7^((r - 1) / n).
@@ -275,6 +276,54 @@ class Circuit:
             return cls(int(z["n_vars"]), [int(v) for v in np.asarray(z["public"]).reshape(-1)], gates, curve)
 
 
+R1CS_INFO = ("n_wires", "n_public", "n_constraints", "n_gates", "n_aux", "n_segments", "max_segment_terms", "n_segment_terms")
+
+
+class R1csCircuit(Circuit):
+    """The gate table of a circom .r1cs (include/zkgpu.h states the compile rule): zk_plonk_<curve>_r1cs_new compiles the file
+    on the host -- no device is touched -- and this is the Circuit of the tables it copies out.  Variable w < n_wires is wire w of the file,
+    the n_aux auxiliaries follow; the publics are wires 1 .. l.  .origin[g] is the constraint gate g came from (g counts the file's gates:
+    row l + g of the table), .segments the table that defines the auxiliaries (seg_first, seg_ptr, seg_wire, seg_coef), .info the counts of
+    R1CS_INFO.  A witness for prove() is the n_wires values of the .wtns, or its bytes; the handle lives until free()."""
+
+    def __init__(self, r1cs_bytes, curve="BN128"):
+        _curve(curve)
+        self.curve, self._h = curve, None
+        data = np.frombuffer(bytes(r1cs_bytes), dtype=np.uint8)
+        self._h = getattr(lib(), "zk_plonk_%s_r1cs_new" % _NAME[curve])(data.ctypes.data, data.size)
+        if not self._h:
+            raise ZkError(lib().zk_last_error().decode())
+        try:
+            info = np.zeros(len(R1CS_INFO), np.uint64)
+            _check(getattr(lib(), "zk_plonk_%s_r1cs_info" % _NAME[curve])(self._h, _ptr(info)))
+            self.info = {k: int(v) for k, v in zip(R1CS_INFO, info)}
+            m, ns, nt = self.info["n_gates"], self.info["n_segments"], self.info["n_segment_terms"]
+            sel = np.zeros((5, m, 4), np.uint64)
+            wires = [np.zeros(max(m, 1), np.uint32) for _ in range(4)]
+            seg = {"seg_first": np.zeros(max(ns, 1), np.uint32), "seg_ptr": np.zeros(ns + 1, np.uint64), "seg_wire": np.zeros(max(nt, 1), np.uint32),
+                   "seg_coef": np.zeros((max(nt, 1), 4), np.uint64)}
+            _check(getattr(lib(), "zk_plonk_%s_r1cs_tables" % _NAME[curve])(self._h, _ptr(sel), *[_ptr(w) for w in wires], *[_ptr(seg[k]) for k in ("seg_first", "seg_ptr", "seg_wire", "seg_coef")]))
+            gates = {s: sel[i] for i, s in enumerate(SELECTORS)}
+            gates.update({w: wires[i][:m] for i, w in enumerate(WIRES)})
+            self.n_wires, self.n_aux, self.origin = self.info["n_wires"], self.info["n_aux"], wires[3][:m]
+            self.segments = {"seg_first": seg["seg_first"][:ns], "seg_ptr": seg["seg_ptr"], "seg_wire": seg["seg_wire"][:nt], "seg_coef": seg["seg_coef"][:nt]}
+            super().__init__(self.n_wires + self.n_aux, range(1, self.info["n_public"] + 1), gates, curve)
+        except Exception:
+            self.free()
+            raise
+
+    def free(self):
+        if getattr(self, "_h", None):
+            getattr(lib(), "zk_plonk_%s_r1cs_free" % _NAME[self.curve])(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 # ---- device helpers: compositions of the layers below, by raw pointer so that a polynomial can sit inside a longer buffer -------------------
 class _View(DevArray):
     """n elements of another DevArray from element `off` on; it owns nothing"""
@@ -342,16 +391,59 @@ def gather_dev(src, d_idx, n, curve="BN128", out=None):
 def _mont_dev(curve, words):
     """(n, 4) u64 canonical words (checked by the caller) -> a DevArray of Montgomery words: the words times R^2 / R on the device (powers
     makes the vector of R^2, pointwise the product), so a witness of 2^20 values is never converted integer by integer"""
-    r, n = _FR[curve], len(words)
+    n = len(words)
     d = DevArray.from_host(words.reshape(-1)) if n else DevArray(4)
+    _mont_in_place(curve, d.ptr, n)
+    return d
+
+
+def _mont_in_place(curve, ptr, n):
+    """the n canonical elements at a device address -> their Montgomery words"""
     if n:
         d_r2 = DevArray(4 * n)
         try:
-            _powers_into(curve, 1, (1 << 256) % r, n, d_r2.ptr)
-            _check(_fn(curve, "pointwise")(fp.MUL, d.ptr, d_r2.ptr, d.ptr, n, 0))
+            _powers_into(curve, 1, (1 << 256) % _FR[curve], n, d_r2.ptr)
+            _check(_fn(curve, "pointwise")(fp.MUL, ptr, d_r2.ptr, ptr, n, 0))
         finally:
             d_r2.free()
-    return d
+
+
+def _r1cs_witness_words(circuit, witness):
+    """what prove() and extend_witness() take for an R1csCircuit -> (n_wires, 4) u64 canonical words; every refusal on the host: the bytes of
+    a .wtns over another field, a wrong count, a value that is not below r, wire 0 that is not the constant 1"""
+    cv = circuit.curve
+    if isinstance(witness, (bytes, bytearray, memoryview)) and bytes(witness[:4]) == b"wtns":
+        from .r1cs import wtns_payload
+        witness, _ = wtns_payload(bytes(witness), cv)
+    ww = _canon_words(witness, _FR[cv], "witness value")
+    if len(ww) != circuit.n_wires:
+        raise ZkError("plonk: the witness has %d values, the .r1cs has %d wires" % (len(ww), circuit.n_wires))
+    if _int_of(ww[0]) != 1:
+        raise ZkError("plonk: witness value 0 is %d: wire 0 of a circom witness is the constant 1" % _int_of(ww[0]))
+    return ww
+
+
+def _extend_words(circuit, ww):
+    cv, n = circuit.curve, circuit.n_wires
+    d = DevArray(4 * circuit.n_vars)
+    try:
+        flat = np.ascontiguousarray(ww.reshape(-1))
+        _check(lib().zk_dev_upload(d.ptr, _ptr(flat), flat.size * 8))
+        _mont_in_place(cv, d.ptr, n)
+        _check(getattr(lib(), "zk_plonk_%s_r1cs_extend_dev" % _NAME[cv])(circuit._h, d.ptr, 0))
+        return d
+    except Exception:
+        d.free()
+        raise
+
+
+def extend_witness(circuit, witness):
+    """the n_vars values of an R1csCircuit's variables on the device, as Montgomery words (what gather reads): the witness in front, then
+    the auxiliaries, every one a prefix of its segment's sum (zk_plonk_<curve>_r1cs_extend_dev) -> a DevArray of n_vars x 4 words.
+    witness: the n_wires canonical values of the .wtns in any form prove() takes, or the bytes of the .wtns itself."""
+    if not isinstance(circuit, R1csCircuit):
+        raise ZkError("plonk: extend_witness takes an R1csCircuit")
+    return _extend_words(circuit, _r1cs_witness_words(circuit, witness))
 
 
 def _upload_mont(curve, values, ptr):
@@ -558,7 +650,9 @@ def setup(kzg, circuit):
 
 # ---- the prover -----------------------------------------------------------------------------------------------------------------------------
 def prove(key, witness, blinding=None, self_check=True, _wires=None, _opening_transcript=None, _mark=None):
-    """-> (proof, publics).  witness: n_vars values below r (integers, 32-byte little-endian values, or (n_vars, 4) u64 words).  proof is a
+    """-> (proof, publics).  witness: n_vars values below r (integers, 32-byte little-endian values, or (n_vars, 4) u64 words); on a key whose
+    circuit is an R1csCircuit the n_wires values of the .wtns in one of those forms, or the bytes of the .wtns: the auxiliaries are then made
+    on the device (extend_witness) and a failing gate is named as the file's gate g (row l + g) with the constraint it came from.  proof is a
     mapping with A, B, C, Z, T, W1, W2 (points, point_bytes each) and values (14 integers: q_L, q_R, q_O, q_M, q_C, S_sigma1, S_sigma2, S_sigma3,
     a, b, c, t at zeta, Z at zeta and at zeta w); publics the l public inputs.  The gate equation is checked first, row by row, and a witness
     that fails names the first row; the permutation product must close.  Before returning, the proof is verified (self_check=False skips it).
@@ -566,9 +660,13 @@ def prove(key, witness, blinding=None, self_check=True, _wires=None, _opening_tr
     cv, n, k, c, kzg = key.curve, key.n, key.log_n, key.circuit, key.kzg
     r = _FR[cv]
     mark = _mark or (lambda name: None)
-    ww = _canon_words(witness, r, "witness value")
-    if len(ww) != c.n_vars:
-        raise ZkError("plonk: the witness has %d values, the circuit has %d variables" % (len(ww), c.n_vars))
+    from_r1cs = isinstance(c, R1csCircuit) and _wires is None
+    if from_r1cs:
+        ww = _r1cs_witness_words(c, witness)
+    else:
+        ww = _canon_words(witness, r, "witness value")
+        if len(ww) != c.n_vars:
+            raise ZkError("plonk: the witness has %d values, the circuit has %d variables" % (len(ww), c.n_vars))
     if blinding is None:
         bs = [secrets.randbelow(r) for _ in range(9)]
     else:
@@ -590,12 +688,15 @@ def prove(key, witness, blinding=None, self_check=True, _wires=None, _opening_tr
             if len(vals) != 3 or any(v.n != 4 * n for v in vals):
                 raise ZkError("plonk: _wires takes three columns of n values")
         else:
-            d_w = keep(_mont_dev(cv, ww))
+            d_w = keep(_extend_words(c, ww) if from_r1cs else _mont_dev(cv, ww))
             vals = [keep(gather(d_w, c.wire[x], cv)) for x in WIRES]
         pi_vals = keep(DevArray(4 * n, zero=True))
         if publics:
             _upload_mont(cv, [(-x) % r for x in publics], pi_vals.ptr)
         bad, first = gate_check(vals + key.sel_vals + [pi_vals], n, cv)
+        if bad and from_r1cs and first >= c.n_public:
+            g = first - c.n_public
+            raise ZkError("plonk: witness does not satisfy gate %d (constraint %d of the .r1cs) (%d rows)" % (g, int(c.origin[g]), bad))
         if bad:
             raise ZkError("plonk: witness does not satisfy gate %d (%d rows)" % (first, bad))
         mark("gate check")

@@ -1032,6 +1032,50 @@ int zk_plonk_bls12_381_gate_check_dev(const uint64_t* const* d_cols, uint64_t n,
 int zk_fr_bn254_gather_dev(const uint64_t* d_src, uint64_t n_src, const uint32_t* d_idx, uint64_t n, uint64_t* d_out, void* stream);
 int zk_fr_bls12_381_gather_dev(const uint64_t* d_src, uint64_t n_src, const uint32_t* d_idx, uint64_t n, uint64_t* d_out, void* stream);
 
+/* ---- The R1CS import of the PLONK prover (csrc/plonk_r1cs_impl.hip.h) -----------------------------------------------------
+ * A circom .r1cs over the curve's scalar field compiled to the gate table the prover takes, and the values of the auxiliary variables that
+ * table adds, computed on the device from the witness at every proof.
+ * The rule.  Wire w is variable w; auxiliaries follow from n_wires in emission order; wire 0 (the constant 1) is never a gate operand with a
+ * non-zero selector; the publics are wires 1 .. n_pub_out + n_pub_in.  A side is normalised: equal wires added, zeros dropped, wire 0 taken
+ * out as the constant k, the signals by ascending wire.  reduce(sig, keep): at most `keep` signals stay as they are; otherwise the first
+ * m = len - keep + 1 signals (s_i, c_i) fold into auxiliaries x_1 .. x_(m-1), x_j = sum_{i <= j+1} c_i w[s_i] -- a PREFIX of the side's sum
+ * over original wires -- by gate 1 (qL, qR, qO, qM, qC) = (c_1, c_2, -1, 0, 0) on (s_1, s_2, x_1) and gates j >= 2 (1, c_(j+1), -1, 0, 0)
+ * on (x_(j-1), s_(j+1), x_j), leaving [(x_(m-1), 1)] and the untouched signals; one SEGMENT (first auxiliary, the m terms) per fold.
+ * Constraint A B = C in file order, constants kA, kB, kC.  Linear (A or B without a signal): L = kA B_sig - C_sig (kB A_sig - C_sig when it
+ * is B), normalised again, k0 = kA kB - kC; nothing left: no gate when k0 = 0, a refusal otherwise; else reduce(L, 3) and one gate
+ * (c_1, c_2, c_3, 0, k0) on (s_1, s_2, s_3), missing operands variable 0 with coefficient 0.  Product: reduce(A, 1), reduce(B, 1),
+ * reduce(C, 1) leaving (sA, fA), (sB, fB), (sC, fC) ((0, 0) when C has no signal), then qM = fA fB, qL = fA kB, qR = kA fB, qO = -fC,
+ * qC = kA kB - kC on (sA, sB, sC).  origin[g] is the constraint of gate g.
+ * zk_plonk_<curve>_r1cs_new: reads the file and applies the rule ON THE HOST; no device is touched.  NULL + zk_last_error() for a malformed
+ *   file, a file over another field, a wire index that is not below n_wires, a table that needs a variable id of more than 32 bits, and a
+ *   constraint 0 = k with k not zero (named by its index).
+ * zk_plonk_<curve>_r1cs_info: out[ZK_PLONK_R1CS_INFO_WORDS] = n_wires, n_public, n_constraints, n_gates, n_aux, n_segments,
+ *   max_segment_terms, n_segment_terms.  n_vars = n_wires + n_aux.
+ * zk_plonk_<curve>_r1cs_tables: copies out, to HOST arrays of the sizes info gives: sel = q_L, q_R, q_O, q_M, q_C one after another, each
+ *   n_gates x 4 canonical u64 words; a, b, c, origin: n_gates uint32 each; seg_first: n_segments uint32 (the first auxiliary of each);
+ *   seg_ptr: n_segments + 1 offsets into the terms; seg_wire: n_segment_terms uint32; seg_coef: n_segment_terms x 4 canonical words.
+ *   Term t >= 1 of segment s defines variable seg_first[s] + t - 1.
+ * zk_plonk_<curve>_r1cs_extend_dev: d_w holds n_vars x 4 u64 words on the device, 16-byte aligned; elements 0 .. n_wires - 1 are the witness
+ *   as Montgomery words (what zk_fr_<curve>_gather_dev reads); the call fills elements n_wires .. n_vars - 1 in the same form, canonical, and
+ *   writes nothing below n_wires.  The segment table goes to the device on the first call and stays with the handle (one call at a time).
+ *   One lane per segment of fewer than zk_plonk_r1cs_wave_min_terms() terms, one wave per longer segment.  Asynchronous on the stream.
+ * Not built: custom gates, folding a chain's last step into the product gate, Goldilocks circuits, a proving-key file.                   */
+#define ZK_PLONK_R1CS_INFO_WORDS 8
+typedef struct zk_plonk_r1cs zk_plonk_r1cs_t;
+uint64_t zk_plonk_r1cs_wave_min_terms(void);
+zk_plonk_r1cs_t* zk_plonk_bn254_r1cs_new(const void* r1cs, size_t len);
+zk_plonk_r1cs_t* zk_plonk_bls12_381_r1cs_new(const void* r1cs, size_t len);
+int zk_plonk_bn254_r1cs_info(const zk_plonk_r1cs_t* h, uint64_t* out);
+int zk_plonk_bls12_381_r1cs_info(const zk_plonk_r1cs_t* h, uint64_t* out);
+int zk_plonk_bn254_r1cs_tables(const zk_plonk_r1cs_t* h, uint64_t* sel, uint32_t* a, uint32_t* b, uint32_t* c, uint32_t* origin, uint32_t* seg_first, uint64_t* seg_ptr,
+                               uint32_t* seg_wire, uint64_t* seg_coef);
+int zk_plonk_bls12_381_r1cs_tables(const zk_plonk_r1cs_t* h, uint64_t* sel, uint32_t* a, uint32_t* b, uint32_t* c, uint32_t* origin, uint32_t* seg_first, uint64_t* seg_ptr,
+                                   uint32_t* seg_wire, uint64_t* seg_coef);
+int zk_plonk_bn254_r1cs_extend_dev(zk_plonk_r1cs_t* h, uint64_t* d_w, void* stream);
+int zk_plonk_bls12_381_r1cs_extend_dev(zk_plonk_r1cs_t* h, uint64_t* d_w, void* stream);
+int zk_plonk_bn254_r1cs_free(zk_plonk_r1cs_t* h);
+int zk_plonk_bls12_381_r1cs_free(zk_plonk_r1cs_t* h);
+
 #ifdef __cplusplus
 }
 #endif
