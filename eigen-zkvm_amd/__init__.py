@@ -78,6 +78,7 @@ EXPORTS = [
 ] + ["zk_fr_%s_%s_dev" % (c, f) for c in ("bn254", "bls12_381")
      for f in ("prefix_product", "batch_inverse", "pointwise", "powers", "terms", "grand_product", "poly_mul", "divmod_zh", "divide_zh_coset")
      ] + [n % c for c in ("bn254", "bls12_381") for n in ("zk_plonk_%s_quotient_dev", "zk_plonk_%s_gate_check_dev", "zk_fr_%s_gather_dev")
+     ] + ["zk_fflonk_%s_quotients_dev" % c for c in ("bn254", "bls12_381")
      ] + ["zk_plonk_r1cs_wave_min_terms"] + ["zk_plonk_%s_r1cs_%s" % (c, f) for c in ("bn254", "bls12_381") for f in ("new", "info", "tables", "extend_dev", "free")]
 
 # include/zkgpu.h enums
@@ -429,6 +430,8 @@ def _load():
             "zk_plonk_%s_quotient_dev" % c: (C.c_int, [vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp]),
             "zk_plonk_%s_gate_check_dev" % c: (C.c_int, [vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp]),
             "zk_fr_%s_gather_dev" % c: (C.c_int, [vp, C.c_uint64, vp, C.c_uint64, vp, vp]),
+            # the device side of the fflonk prover (fflonk.py)
+            "zk_fflonk_%s_quotients_dev" % c: (C.c_int, [vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp]),
             # its R1CS import (plonk.R1csCircuit, plonk.extend_witness)
             "zk_plonk_%s_r1cs_new" % c: (vp, [vp, C.c_size_t]),
             "zk_plonk_%s_r1cs_info" % c: (C.c_int, [vp, vp]),
@@ -463,6 +466,9 @@ def __getattr__(name):
     if name in ("Circuit", "PlonkKey", "R1csCircuit", "extend_witness"):   # plonk.py (the PLONK prover and verifier over kzg.py and frpoly.py)
         import importlib
         return getattr(importlib.import_module(__name__ + ".plonk"), name)
+    if name == "FflonkKey":   # fflonk.py (the fflonk prover and verifier over the interleaved commitments)
+        import importlib
+        return importlib.import_module(__name__ + ".fflonk").FflonkKey
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 

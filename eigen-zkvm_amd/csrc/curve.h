@@ -125,6 +125,12 @@ struct PlonkOps {
     void (*r1cs_extend_dev)(PlonkR1cs& h, u64* d_w, hipStream_t st);
 };
 const PlonkOps& plonk_ops(CurveId id);
+// ---- groth16.hip: the device side of the fflonk prover (fflonk_impl.hip.h): the three numerators of the identity apart, in
+// one launch.  What include/zkgpu.h states for zk_fflonk_<curve>_quotients_dev holds for it
+struct FflonkOps {
+    void (*quotients_dev)(const u64* const* d_cols, u32 log_n, const u64* beta, const u64* gamma, const u64* k1, const u64* k2, u64* d_out0, u64* d_out1, u64* d_out2, hipStream_t st);
+};
+const FflonkOps& fflonk_ops(CurveId id);
 constexpr uint64_t PLONK_R1CS_WAVE_MIN_TERMS = 64;   // a segment of this many terms or more is walked by a whole wave (plonk_r1cs_impl.hip.h)
 // ---- pairing.hip: the steps of the optimal ate pairing and of Groth16 verification (pairing_impl.hip.h)
 struct PairingOps {
@@ -189,6 +195,7 @@ struct Curve {
     const KzgOps& kzg() const { return kzg_ops(id); }
     const FrPolyOps& frpoly() const { return frpoly_ops(id); }
     const PlonkOps& plonk() const { return plonk_ops(id); }
+    const FflonkOps& fflonk() const { return fflonk_ops(id); }
 };
 inline const Curve CURVES[2] = {
     {CURVE_BN254, "BN128", "bn254", 8, {0xf0000001u, 0x43e1f593u, 0x79b97091u, 0x2833e848u, 0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u}},

@@ -11,7 +11,8 @@
 // This unit owns the scalar field's transforms, so the polynomial layer that runs them batched in their own layout lives here too
 // (frpoly_impl.hip.h, DESIGN.md 3.20: zk_fr_<curve>_poly_mul_dev and its siblings; no protocol), and after it the three kernels of the
 // PLONK prover (plonk_impl.hip.h, DESIGN.md 3.21: the fused numerator of the quotient, the gate check, the gather) and its R1CS import
-// (plonk_r1cs_impl.hip.h, DESIGN.md 3.22: the compile rule on the host, the auxiliary variables of a witness on the device).
+// (plonk_r1cs_impl.hip.h, DESIGN.md 3.22: the compile rule on the host, the auxiliary variables of a witness on the device), and the
+// fflonk prover's three numerators in one launch (fflonk_impl.hip.h).
 //   proof.json       groth16/src/json_utils.rs:305-315
 // Key generation (`zkit groth16_setup`, groth16/src/api.rs:42-66) over the same circuit: groth16_keygen_impl.hip.h with a trapdoor,
 // groth16_srs.hip.h from a powers-of-tau file (and the contributions to such a key).
@@ -305,6 +306,7 @@ namespace bn254fr {
 #include "frntt_impl.hip.h"
 #include "frpoly_impl.hip.h"
 #include "plonk_impl.hip.h"
+#include "fflonk_impl.hip.h"
 #include "plonk_r1cs_impl.hip.h"
 #include "groth16_impl.hip.h"
 #include "groth16_keygen_impl.hip.h"
@@ -326,6 +328,7 @@ namespace bls12381fr {
 #include "frntt_impl.hip.h"
 #include "frpoly_impl.hip.h"
 #include "plonk_impl.hip.h"
+#include "fflonk_impl.hip.h"
 #include "plonk_r1cs_impl.hip.h"
 #include "groth16_impl.hip.h"
 #include "groth16_keygen_impl.hip.h"
@@ -352,6 +355,11 @@ const FrPolyOps& frpoly_ops(CurveId id) {     // frpoly_impl.hip.h, per scalar f
 const PlonkOps& plonk_ops(CurveId id) {       // plonk_impl.hip.h and plonk_r1cs_impl.hip.h, per scalar field
     static const PlonkOps OPS[2] = {{bn254fr::pk_quotient_dev, bn254fr::pk_gate_check_dev, bn254fr::pk_gather_dev, bn254fr::pk_r1cs_new, bn254fr::pk_r1cs_extend_dev},
                                     {bls12381fr::pk_quotient_dev, bls12381fr::pk_gate_check_dev, bls12381fr::pk_gather_dev, bls12381fr::pk_r1cs_new, bls12381fr::pk_r1cs_extend_dev}};
+    return OPS[id];
+}
+
+const FflonkOps& fflonk_ops(CurveId id) {     // fflonk_impl.hip.h, per scalar field
+    static const FflonkOps OPS[2] = {{bn254fr::ff_quotients_dev}, {bls12381fr::ff_quotients_dev}};
     return OPS[id];
 }
 

@@ -1032,6 +1032,24 @@ int zk_plonk_bls12_381_gate_check_dev(const uint64_t* const* d_cols, uint64_t n,
 int zk_fr_bn254_gather_dev(const uint64_t* d_src, uint64_t n_src, const uint32_t* d_idx, uint64_t n, uint64_t* d_out, void* stream);
 int zk_fr_bls12_381_gather_dev(const uint64_t* d_src, uint64_t n_src, const uint32_t* d_idx, uint64_t n, uint64_t* d_out, void* stream);
 
+/* ---- The device side of the fflonk prover (csrc/fflonk_impl.hip.h) --------------------------------------------------------
+ * The one kernel the prover of eigen_zkvm_amd/fflonk.py adds: fflonk commits to the three quotients of the identity apart, so their numerators
+ * leave one launch apart where zk_plonk_<curve>_quotient_dev folds them with alpha.  Vectors, scalars, <curve> and d_cols (the same
+ * ZK_PLONK_QUOTIENT_COLS columns in the same order, on the coset 7 H_m, m = 4n = 4 2^log_n) as above.  At element i of every column
+ *   d_out0[i] = a b q_M + a q_L + b q_R + c q_O + q_C + PI
+ *   d_out1[i] = L_1 (Z - 1)
+ *   d_out2[i] = (a + beta X + gamma)(b + beta k1 X + gamma)(c + beta k2 X + gamma) Z
+ *               - (a + beta S_sigma1 + gamma)(b + beta S_sigma2 + gamma)(c + beta S_sigma3 + gamma) Z[(i + 4) mod m]
+ * every one canonical.  An output may be NULL (not all three): that part is not computed and the columns it alone reads are not read, though
+ * every column pointer must still be valid -- T0 is committed before beta and gamma exist, so the prover takes d_out0 in round 1 and the other
+ * two in round 2.  An output (m elements each) overlaps no column and no other output; a scalar that is not below r and log_n + 2 beyond
+ * the field's 2-adicity are refused before any device work.  One lane per element, one launch; each output is then divided by Z_H with
+ * zk_fr_<curve>_divide_zh_coset_dev(d_out, log_n + 2, log_n).                                                                              */
+int zk_fflonk_bn254_quotients_dev(const uint64_t* const* d_cols, uint32_t log_n, const uint64_t* beta, const uint64_t* gamma, const uint64_t* k1,
+                                  const uint64_t* k2, uint64_t* d_out0, uint64_t* d_out1, uint64_t* d_out2, void* stream);
+int zk_fflonk_bls12_381_quotients_dev(const uint64_t* const* d_cols, uint32_t log_n, const uint64_t* beta, const uint64_t* gamma, const uint64_t* k1,
+                                      const uint64_t* k2, uint64_t* d_out0, uint64_t* d_out1, uint64_t* d_out2, void* stream);
+
 /* ---- The R1CS import of the PLONK prover (csrc/plonk_r1cs_impl.hip.h) -----------------------------------------------------
  * A circom .r1cs over the curve's scalar field compiled to the gate table the prover takes, and the values of the auxiliary variables that
  * table adds, computed on the device from the witness at every proof.
