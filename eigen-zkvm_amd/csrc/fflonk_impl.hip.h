@@ -2,28 +2,21 @@
 // identity on the coset as one kernel.  PLONK's pk_quotient_kernel folds them together with alpha; fflonk commits to the three quotients
 // separately (T0 inside C1, T1 and T2 inside C2), so they leave the kernel apart.  The protocol itself (rounds, transcript, files) is
 // eigen_zkvm_amd/fflonk.py.  Included by groth16.hip after plonk_impl.hip.h, in the same namespace: it uses that file's columns and constants
-// (PkCols, PkConsts, pk_setup_kernel with alpha = 0), its loads (pk_plain, pk_internal), pk_times_k and pk_gate_macs.  No include guard on purpose.
+// (PkCols, PkConsts, pk_setup_kernel with alpha = 0), its loads (pk_plain, pk_internal), pk_times_k and pk_gate_macs, and its host checks
+// (pk_scalar, pk_columns, pk_apart).  No include guard on purpose.
 //
 // Vectors, forms (plain P(v) = v R < 6r, internal I(v) = v R', fe_mul(I(u), P(v)) = P(u v)) and the order of d_cols are plonk_impl.hip.h's.
 //
 // zk_fflonk_<curve>_quotients_dev, per lane (ff_quotients_kernel); "=" is the value, "<" the bound against fe29_impl.hip.h's A B <= 68:
-//   A, B, C    = I(a), I(b), I(c) by fe_from_std, ONCE for all three outputs         P < 6r times CIN < r: 6.                 < 2r each
-//   AB         = fe_mul(A, B) = I(a b)                                               2 x 2 = 4                                < 2r
+// Only the rows that differ from plonk_impl.hip.h's table stand here; A, B, C, AB, zm1 and the rows Bx .. D of the permutation difference are
+// that table's (the same twelve lines of code in both kernels: shared through one inlined function they compile to other code, and
+// pk_quotient_kernel came out 4 % slower, profiles/r26/plonk_arith.md), with A, B, C made ONCE for all three outputs.
 //   W0         = A P(q_L) + B P(q_R) + C P(q_O) + AB P(q_M) with ONE reduction (fe_wide_mac, 4 pairs <= FE_WIDE_MAX)
 //                4 x (2 x 6) = 48                                                                                             < 2r, plain
 //   out0       = W0 + P(q_C) + P(PI): < 14r, reduced once in fp_put_plain                                                     canonical
 //   L          = I(L_1) by fe_from_std: 6                                                                                     < 2r
-//   zm1        = P(Z) - P(1) + 2r  (fe_sub<2>, P(1) = R mod r < r)                                                            < 8r
 //   out1       = fe_mul(L, zm1) = P(L_1 (Z - 1)): 2 x 8 = 16; reduced once in fp_put_plain                                    < 2r -> canonical
-//   Bx         = fe_mul(P(X), BI) = I(beta X), BI = beta R'^2 / R (< 2r)             6 x 2 = 12                               < 2r
-//                beta X is made ONCE; k_1 beta X and k_2 beta X are k_j additions of it when k_j <= PK_SMALL_K (= 3: < 6r), else one more
-//                product each by I(k_j) (2 x 2 = 4, < 2r)
-//   f_1 .. f_3 = A + Bx + G, B + k_1 Bx + G, C + k_2 Bx + G, G = I(gamma) canonical  (< r)                                    < 5r, < 9r, < 9r
-//   P1         = ((f_1 f_2) f_3) P(Z): 5 x 9 = 45 -> < 2r; 2 x 9 = 18 -> < 2r; 2 x 6 = 12 -> plain                            < 2r
-//   s_j        = fe_mul(P(S_sigma_j), BI) = I(beta S_sigma_j): 12                                                             < 2r
-//   g_j        = A + s_1 + G, B + s_2 + G, C + s_3 + G                                                                        < 5r each
-//   P2         = ((g_1 g_2) g_3) P(Z(wX)): 25, 10, 12 -> plain                                                                < 2r
-//   out2       = P1 - P2 + 2r  (fe_sub<2>, P2 < 2r): < 4r, reduced once in fp_put_plain                                       canonical
+//   out2       = D = P1 - P2 + 2r: < 4r, reduced once in fp_put_plain                                                         canonical
 // (6r is 2^256 against BN254's r; the true factor is 5.3 there and 2.3 for BLS12-381, so the 48 of W0 is 43 and 19 in fact.)
 // Products: 3 + 1 + 2 + 1 + 3 + 3 + 3 = 16, four multiply-accumulates with one reduction, three reductions on the way out; 2 more when a
 // k_j is large.  Each output is stored as soon as it is made, so that only A, B, C, G and P(Z) live across the three parts.
@@ -68,41 +61,22 @@ __global__ __launch_bounds__(FP_BLOCK) void ff_quotients_kernel(const PkCols cs,
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------------
-static FpWords ff_scalar(const u64* v, const char* what) {
-    ZK_REQUIRE(v, std::string("fflonk: null ") + what);
-    ZK_REQUIRE(fp_curve().fr_canonical((const u32*)v), std::string("fflonk: ") + what + " is not below the scalar field's modulus");
-    FpWords w;
-    std::memcpy(w.w, v, 32);
-    return w;
-}
 void FRN_FN(ff_quotients_dev)(const u64* const* d_cols, u32 log_n, const u64* beta, const u64* gamma, const u64* k1, const u64* k2, u64* d_out0, u64* d_out1, u64* d_out2, hipStream_t st) {
-    const FpWords b = ff_scalar(beta, "beta"), g = ff_scalar(gamma, "gamma"), w1 = ff_scalar(k1, "k1"), w2 = ff_scalar(k2, "k2");
+    const FpWords b = pk_scalar("fflonk", beta, "beta"), g = pk_scalar("fflonk", gamma, "gamma"), w1 = pk_scalar("fflonk", k1, "k1"), w2 = pk_scalar("fflonk", k2, "k2");
     if (log_n + 2 > (u32)FRN_S) throw std::runtime_error("fflonk: the coset of 2^" + std::to_string(log_n + 2) + " points for n = 2^" + std::to_string(log_n) + " exceeds the field's 2-adicity");
     ZK_REQUIRE(d_cols, "fflonk: null argument");
     ZK_REQUIRE(d_out0 || d_out1 || d_out2, "fflonk: quotients: every output is null");
     const u64 m = 4ull << log_n;
     u64* const outs[3] = {d_out0, d_out1, d_out2};
-    PkCols cs{};
+    const PkCols cs = pk_columns("fflonk: quotients", d_cols);
     FfOuts os{};
-    for (int c = 0; c < PK_NCOL; ++c) {
-        cs.c[c] = (const u32*)d_cols[c];
-        ZK_REQUIRE(cs.c[c], "fflonk: quotients: column " + std::to_string(c) + " is null");
-        fp_aligned({cs.c[c]});
-    }
     for (int j = 0; j < 3; ++j) {
         os.o[j] = (u32*)outs[j];
         if (!outs[j]) continue;
         fp_aligned({outs[j]});
-        const uintptr_t o = (uintptr_t)outs[j];
-        for (int c = 0; c < PK_NCOL; ++c) {
-            const uintptr_t lo = (uintptr_t)cs.c[c];
-            ZK_REQUIRE(o + m * 32 <= lo || lo + m * 32 <= o, "fflonk: quotients: output " + std::to_string(j) + " overlaps column " + std::to_string(c));
-        }
-        for (int j2 = 0; j2 < j; ++j2) {
-            if (!outs[j2]) continue;
-            const uintptr_t lo = (uintptr_t)outs[j2];
-            ZK_REQUIRE(o + m * 32 <= lo || lo + m * 32 <= o, "fflonk: quotients: output " + std::to_string(j) + " overlaps output " + std::to_string(j2));
-        }
+        for (int c = 0; c < PK_NCOL; ++c) ZK_REQUIRE(pk_apart(outs[j], cs.c[c], m), "fflonk: quotients: output " + std::to_string(j) + " overlaps column " + std::to_string(c));
+        for (int j2 = 0; j2 < j; ++j2)
+            ZK_REQUIRE(!outs[j2] || pk_apart(outs[j], outs[j2], m), "fflonk: quotients: output " + std::to_string(j) + " overlaps output " + std::to_string(j2));
     }
     FpWords zero{};
     DevBuf pc;

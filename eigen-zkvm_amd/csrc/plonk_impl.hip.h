@@ -164,26 +164,36 @@ __global__ __launch_bounds__(FP_BLOCK) void pk_gather_kernel(const u32* __restri
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------------
-static FpWords pk_scalar(const u64* v, const char* what) {
-    ZK_REQUIRE(v, std::string("plonk: null ") + what);
-    ZK_REQUIRE(fp_curve().fr_canonical((const u32*)v), std::string("plonk: ") + what + " is not below the scalar field's modulus");
+// who: the caller's prefix, "plonk" or "fflonk", and further down its call as well ("plonk: quotient")
+static FpWords pk_scalar(const std::string& who, const u64* v, const char* what) {
+    ZK_REQUIRE(v, who + ": null " + what);
+    ZK_REQUIRE(fp_curve().fr_canonical((const u32*)v), who + ": " + what + " is not below the scalar field's modulus");
     FpWords w;
     std::memcpy(w.w, v, 32);
     return w;
 }
-void FRN_FN(pk_quotient_dev)(const u64* const* d_cols, u32 log_n, const u64* alpha, const u64* beta, const u64* gamma, const u64* k1, const u64* k2, u64* d_out, hipStream_t st) {
-    const FpWords a = pk_scalar(alpha, "alpha"), b = pk_scalar(beta, "beta"), g = pk_scalar(gamma, "gamma"), w1 = pk_scalar(k1, "k1"), w2 = pk_scalar(k2, "k2");
-    if (log_n + 2 > (u32)FRN_S) throw std::runtime_error("plonk: the coset of 2^" + std::to_string(log_n + 2) + " points for n = 2^" + std::to_string(log_n) + " exceeds the field's 2-adicity");
-    ZK_REQUIRE(d_cols && d_out, "plonk: null argument");
-    const u64 m = 4ull << log_n;
+// the PK_NCOL columns of d_cols, every one there and aligned
+static PkCols pk_columns(const std::string& who, const u64* const* d_cols) {
     PkCols cs{};
     for (int c = 0; c < PK_NCOL; ++c) {
         cs.c[c] = (const u32*)d_cols[c];
-        ZK_REQUIRE(cs.c[c], "plonk: quotient: column " + std::to_string(c) + " is null");
+        ZK_REQUIRE(cs.c[c], who + ": column " + std::to_string(c) + " is null");
         fp_aligned({cs.c[c]});
-        const uintptr_t lo = (uintptr_t)cs.c[c], o = (uintptr_t)d_out;
-        ZK_REQUIRE(o + m * 32 <= lo || lo + m * 32 <= o, "plonk: quotient: the output overlaps column " + std::to_string(c));
     }
+    return cs;
+}
+// two vectors of m elements do not overlap
+static bool pk_apart(const void* a, const void* b, u64 m) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x + m * 32 <= y || y + m * 32 <= x;
+}
+void FRN_FN(pk_quotient_dev)(const u64* const* d_cols, u32 log_n, const u64* alpha, const u64* beta, const u64* gamma, const u64* k1, const u64* k2, u64* d_out, hipStream_t st) {
+    const FpWords a = pk_scalar("plonk", alpha, "alpha"), b = pk_scalar("plonk", beta, "beta"), g = pk_scalar("plonk", gamma, "gamma"), w1 = pk_scalar("plonk", k1, "k1"), w2 = pk_scalar("plonk", k2, "k2");
+    if (log_n + 2 > (u32)FRN_S) throw std::runtime_error("plonk: the coset of 2^" + std::to_string(log_n + 2) + " points for n = 2^" + std::to_string(log_n) + " exceeds the field's 2-adicity");
+    ZK_REQUIRE(d_cols && d_out, "plonk: null argument");
+    const u64 m = 4ull << log_n;
+    const PkCols cs = pk_columns("plonk: quotient", d_cols);
+    for (int c = 0; c < PK_NCOL; ++c) ZK_REQUIRE(pk_apart(d_out, cs.c[c], m), "plonk: quotient: the output overlaps column " + std::to_string(c));
     fp_aligned({d_out});
     DevBuf pc;
     pc.reserve(sizeof(PkConsts));

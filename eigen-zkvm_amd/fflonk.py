@@ -1,11 +1,11 @@
 """An fflonk prover and verifier on the interleaved commitments of the KZG layer (kzg.py) over PLONK's arithmetisation
-(plonk.py): setup, prove, verify.  A verification key of ONE G1 point, a proof of four G1 points and
+(plonk_arith.py): setup, prove, verify.  A verification key of ONE G1 point, a proof of four G1 points and
 15 scalars, two pairings for m proofs.  The protocol, the transcript and the files are this module; everything over Fr of size n or more runs
-on the device through the calls plonk.py uses, zk_fflonk_<curve>_quotients_dev, zk_kzg_<curve>_interleave_dev (device to device) and
+on the device through the layer's calls, zk_fflonk_<curve>_quotients_dev, zk_kzg_<curve>_interleave_dev (device to device) and
 Kzg.open_multi.  There is no CPU fallback.  This is the project's own transcript (SHA-256), not snarkjs's keccak or its file formats.
 
-Field, circuit, wiring, k_1, k_2, sigma, H, w = 7^((r - 1) / n), n = 2^k >= 8, the public rows and PI are plonk.py's: Circuit and R1csCircuit
-are taken as they are.
+Field, circuit, wiring, k_1, k_2, sigma, H, w = 7^((r - 1) / n), n = 2^k >= 8, the public rows and PI are the layer's: Circuit and R1csCircuit
+are plonk_arith's, the same objects plonk.py offers.
 
 Interleaving.  interleave_t(f_0 .. f_(t-1)) = sum_m f_m(X^t) X^m: coefficient j t + m is coefficient j of f_m, shorter polynomials zero-padded.
 
@@ -51,17 +51,16 @@ at 0 and only moves for a re-draw.
 Blinding.  The nine blinders come from `secrets`; blinding=[9 integers] is FOR TESTS ONLY (all zero gives the unblinded proof)."""
 import hashlib
 import json
-import secrets
 
 import numpy as np
 
 from . import DevArray, ZkError, _check, _ptr, lib
-from . import frpoly as fp
-from .groth16 import _FR, _NAME
-from .kzg import _scalar, point_from_json, point_to_json, to_mont
-from .plonk import (ACCEPTED, FIXED_NAMES, INPUT_NOT_CANONICAL, REJECTED, SELECTORS, TWO_ADICITY, WIRES, Circuit, R1csCircuit, _blind, _canon_words, _coset_evals, _curve, _draw,
-                    _extend_words, _fn, _int_of, _interpolate, _le, _mont_dev, _ntt, _plain_z, _powers_into, _r1cs_witness_words, _upload_mont, _View, check_size, coset_ks,
-                    gate_check, gather, omega, public_input_at)
+from . import plonk_arith as pa
+from .groth16 import _NAME
+from .kzg import _scalar, point_from_json, point_to_json
+# the layer's names, for this module and for its callers
+from .plonk_arith import (ACCEPTED, FIXED_NAMES, FR, INPUT_NOT_CANONICAL, REJECTED, SELECTORS, TWO_ADICITY, WIRES, ArithKey, Circuit, R1csCircuit, View, check_size, coset_ks, draw,
+                          draw_until, gate_check, gather, le, modulus, omega, public_input_at, smallest_power)
 
 N_VALUES, N_OPENED = 15, 18
 POINT_NAMES = ("C1", "C2", "W1", "W2")
@@ -76,11 +75,8 @@ def required_powers(n):
 
 
 def file_power(log_n):
-    """the smallest power of a .ptau file that holds them: a file of power p has 2^(p + 1) - 1 G1 powers, 8n - 1 < 9n + 18 <= 16n - 1 for n >= 8"""
-    p = log_n
-    while (2 << p) - 1 < required_powers(1 << log_n):
-        p += 1
-    return p
+    """the smallest power of a .ptau file that holds them for n = 2^log_n rows"""
+    return smallest_power(required_powers(1 << log_n))
 
 
 def quotient_coeffs(n):
@@ -91,13 +87,13 @@ def quotient_coeffs(n):
 # ---- the field on the host: the roots of a proof and the two directions between opened values and parts --------------------------------------
 def omega3(curve):
     """the element of order 3 the h2 and h3 halves of S2 are spread by: 7^((r - 1) / 3)"""
-    r = _curve(curve)
+    r = modulus(curve)
     return pow(7, (r - 1) // 3, r)
 
 
 def roots(curve, log_n, s):
     """the seed s -> a mapping with h0, h1, h2, h3, xi, xiw and the three opening sets S0, S1, S2 in the order of round 3"""
-    r, n = _curve(curve), 1 << log_n
+    r, n = modulus(curve), 1 << log_n
     check_size(curve, log_n)
     w = omega(curve, log_n)
     w8, w3 = pow(w, n // 8, r), omega3(curve)
@@ -113,7 +109,7 @@ def roots(curve, log_n, s):
 def host_values(curve, parts, points):
     """y(x) = sum_m parts[m] x^m for every x of `points`: the values of interleave_t(f_0 .. f_(t-1)) at x from the parts f_m(x^t), which are
     the same for every x of a set {h w_t^j} -> as many integers as points"""
-    r = _curve(curve)
+    r = modulus(curve)
     out = []
     for x in points:
         acc = 0
@@ -126,7 +122,7 @@ def host_values(curve, parts, points):
 def parts_of(curve, ys, points):
     """the inverse, a transform of size t = len(points) on the host: points = {h w_t^j}, ys the opened values there ->
     f_m(h^t) = (1 / t) sum_j y_j (h w_t^j)^(-m), m < t"""
-    r = _curve(curve)
+    r = modulus(curve)
     t = len(points)
     inv = [pow(x, -1, r) for x in points]
     tinv = pow(t, -1, r)
@@ -135,14 +131,9 @@ def parts_of(curve, ys, points):
 
 def quotients_at(curve, log_n, k1, k2, publics, beta, gamma, xi, v):
     """(T0, T1, T2)(xi) in the field from the values v[name] of VALUE_NAMES (Zw = Z(xi w); T1w, T2w are not read): what the identities give"""
-    r, n = _FR[curve], 1 << log_n
-    zh_inv = pow((pow(xi, n, r) - 1) % r, -1, r)
-    l1 = (pow(xi, n, r) - 1) * pow(n * (xi - 1) % r, -1, r) % r
-    a, b, c, z = v["a"], v["b"], v["c"], v["Z"]
-    gate = (a * b % r * v["qM"] + a * v["qL"] + b * v["qR"] + c * v["qO"] + v["qC"] + public_input_at(curve, log_n, publics, xi)) % r
-    p1 = (a + beta * xi + gamma) * (b + beta * k1 % r * xi + gamma) % r * (c + beta * k2 % r * xi + gamma) % r * z % r
-    p2 = (a + beta * v["S1"] + gamma) * (b + beta * v["S2"] + gamma) % r * (c + beta * v["S3"] + gamma) % r * v["Zw"] % r
-    return gate * zh_inv % r, l1 * (z - 1) % r * zh_inv % r, (p1 - p2) * zh_inv % r
+    gate, perm, l1z, zh = pa.identity_terms(curve, log_n, k1, k2, publics, xi, v, beta, gamma)
+    zh_inv = pow(zh, -1, FR[curve])
+    return tuple(t * zh_inv % FR[curve] for t in (gate, l1z, perm))
 
 
 def opened_values(curve, log_n, k1, k2, publics, values, beta, gamma, rt):
@@ -164,45 +155,37 @@ def values_of(curve, opened, rt):
 # ---- the transcript -----------------------------------------------------------------------------------------------------------------------
 def vk_digest(curve, log_n, n_public, k1, k2, c0_point):
     """vkd = H(curve || "fflonk-vk" || k u32le || l u32le || k_1 || k_2 || C0)"""
-    return hashlib.sha256(curve.encode("ascii") + b"fflonk-vk" + int(log_n).to_bytes(4, "little") + int(n_public).to_bytes(4, "little") + _le(k1) + _le(k2) + bytes(c0_point)).digest()
+    return hashlib.sha256(curve.encode("ascii") + b"fflonk-vk" + int(log_n).to_bytes(4, "little") + int(n_public).to_bytes(4, "little") + le(k1) + le(k2) + bytes(c0_point)).digest()
 
 
 def transcript_start(curve, vkd, publics):
     """c0 = H(curve || "fflonk-v1" || vkd || l u32le || x_0 .. x_(l-1))"""
-    return hashlib.sha256(curve.encode("ascii") + b"fflonk-v1" + vkd + len(publics).to_bytes(4, "little") + b"".join(_le(x) for x in publics)).digest()
+    return hashlib.sha256(curve.encode("ascii") + b"fflonk-v1" + vkd + len(publics).to_bytes(4, "little") + b"".join(le(x) for x in publics)).digest()
 
 
 def transcript_round1(curve, c0, C1):
     """c1 = H(c0 || C1); beta = H(c1 || 00), gamma = H(c1 || 01) -> (c1, beta, gamma)"""
     c1 = hashlib.sha256(c0 + bytes(C1)).digest()
-    return c1, _draw(curve, c1, b"\x00"), _draw(curve, c1, b"\x01")
+    return c1, draw(curve, c1, b"\x00"), draw(curve, c1, b"\x01")
 
 
 def transcript_round2(curve, c1, C2, log_n):
     """c2 = H(c1 || C2); s = H(c2 || ctr), ctr one byte from 0, drawn again while s = 0 or xi^n = 1 with xi = s^24 -> (c2, s)"""
-    r = _FR[curve]
+    r = FR[curve]
     c2 = hashlib.sha256(c1 + bytes(C2)).digest()
-    for ctr in range(256):
-        s = _draw(curve, c2, bytes([ctr]))
-        if s != 0 and pow(s, 24 << log_n, r) != 1:
-            return c2, s
-    raise ZkError("fflonk: no seed after 256 draws")
+    return c2, draw_until(curve, c2, lambda s: s != 0 and pow(s, 24 << log_n, r) != 1, "fflonk: no seed")
 
 
 def transcript_values(curve, c2, values):
     """c3 = H(c2 || the 15 values, 32 little-endian bytes each); gamma' = H(c3 || 00) -> (c3, gamma')"""
-    c3 = hashlib.sha256(c2 + b"".join(_le(v) for v in values)).digest()
-    return c3, _draw(curve, c3, b"\x00")
+    c3 = hashlib.sha256(c2 + b"".join(le(v) for v in values)).digest()
+    return c3, draw(curve, c3, b"\x00")
 
 
 def transcript_z(curve, c3, W1, avoid):
     """z' = H(c3 || 01 || W1 || ctr), ctr one byte from 0, drawn again while z' is one of the 18 opening points"""
     avoid = {int(p) for p in avoid}
-    for ctr in range(256):
-        z = _draw(curve, c3, b"\x01", bytes(W1), bytes([ctr]))
-        if z not in avoid:
-            return z
-    raise ZkError("fflonk: no opening challenge after 256 draws")
+    return draw_until(curve, c3 + b"\x01" + bytes(W1), lambda z: z not in avoid, "fflonk: no opening challenge")
 
 
 # ---- device helpers ---------------------------------------------------------------------------------------------------------------------------
@@ -225,7 +208,7 @@ def quotients(cols, log_n, beta, gamma, k1, k2, curve="BN128", outs=None, want=(
     """zk_fflonk_<curve>_quotients_dev: cols, 15 DevArrays of 4n elements in the order of zk_plonk_<curve>_quotient_dev -> [out0, out1, out2]
     on the coset: the gate numerator with PI, L_1 (Z - 1), the permutation difference.  want[j] false: output j is not computed (None in its
     place) and the columns it alone reads are not read.  outs: three DevArrays (or None) to write into."""
-    _curve(curve)
+    modulus(curve)
     m = 4 << int(log_n)
     if len(cols) != 15:
         raise ZkError("fflonk: the quotients take 15 columns, not %d" % len(cols))
@@ -259,7 +242,7 @@ class VerifyingKey:
     """(curve, log n, l, k_1, k_2, [C0]); `kzg` is the handle verify() pairs with, when the key came from an FflonkKey"""
 
     def __init__(self, curve, log_n, n_public, k1, k2, c0, kzg=None):
-        _curve(curve)
+        modulus(curve)
         self.curve, self.log_n, self.n_public, self.k1, self.k2 = curve, int(log_n), int(n_public), int(k1), int(k2)
         self.c0, self.kzg = bytes(c0), kzg
         check_size(curve, self.log_n)
@@ -283,7 +266,7 @@ def vk_from_json(text, kzg=None):
 
 def vk_to_bytes(vk):
     """curve's name, a zero byte, k u32le, l u32le, k_1, k_2 as 32 little-endian bytes each, C0"""
-    return vk.curve.encode("ascii") + b"\x00" + vk.log_n.to_bytes(4, "little") + vk.n_public.to_bytes(4, "little") + _le(vk.k1) + _le(vk.k2) + vk.c0
+    return vk.curve.encode("ascii") + b"\x00" + vk.log_n.to_bytes(4, "little") + vk.n_public.to_bytes(4, "little") + le(vk.k1) + le(vk.k2) + vk.c0
 
 
 def vk_from_bytes(data, kzg=None):
@@ -301,100 +284,38 @@ def vk_from_bytes(data, kzg=None):
 
 
 def proof_to_json(proof, curve):
-    out = {"protocol": PROTOCOL, "curve": curve}
-    out.update({name: point_to_json(proof[name], curve) for name in POINT_NAMES})
-    out["values"] = [str(v) for v in proof["values"]]
-    return json.dumps(out, indent=1) + "\n"
+    return pa.proof_to_json(proof, curve, PROTOCOL, POINT_NAMES)
 
 
 def proof_from_json(text, curve):
-    js = json.loads(text)
-    if js.get("protocol") != PROTOCOL or js.get("curve") != curve:
-        raise ZkError('fflonk: not a proof of this prover on %s (protocol "%s", curve "%s")' % (curve, js.get("protocol"), js.get("curve")))
-    proof = {name: point_from_json(js[name], curve) for name in POINT_NAMES}
-    proof["values"] = [int(v, 0) for v in js["values"]]
-    return proof
+    return pa.proof_from_json(text, curve, PROTOCOL, POINT_NAMES, "fflonk")
 
 
 def proof_to_bytes(proof):
     """C1 || C2 || W1 || W2 || the 15 values, 32 little-endian bytes each"""
-    return b"".join(bytes(proof[k]) for k in POINT_NAMES) + b"".join(_le(v) for v in proof["values"])
+    return pa.proof_to_bytes(proof, POINT_NAMES)
 
 
 def proof_from_bytes(data, point_bytes):
-    if len(data) != 4 * point_bytes + 32 * N_VALUES:
-        raise ZkError("fflonk: a proof is %d bytes, not %d" % (4 * point_bytes + 32 * N_VALUES, len(data)))
-    proof = {name: data[i * point_bytes:(i + 1) * point_bytes] for i, name in enumerate(POINT_NAMES)}
-    at = 4 * point_bytes
-    proof["values"] = [int.from_bytes(data[at + 32 * i:at + 32 * (i + 1)], "little") for i in range(N_VALUES)]
-    return proof
+    return pa.proof_from_bytes(data, point_bytes, POINT_NAMES, N_VALUES, (), "fflonk")
 
 
-class FflonkKey:
-    """The proving key on the device, rebuilt from the circuit and the file (there is no proving-key file): what rounds 1 and 2 read on H (the
-    selectors' values, the labels of the positions and of sigma), the values of the 8 fixed polynomials, of L_1 and of X on the coset 7 H_4n,
-    the 8n coefficients of C0 and the point [C0].  The eight fixed polynomials are NOT committed one by one.  Setup is deterministic and has no
-    secret.  self.vk is the verification key."""
+class FflonkKey(ArithKey):
+    """The proving key on the device: ArithKey's columns, and beside them the 8n coefficients of C0 = interleave_8 of the eight fixed
+    polynomials and the point [C0].  The eight are NOT committed one by one, and their own coefficient vectors do not outlive the interleaving.
+    Setup is deterministic and has no secret.  self.vk is the verification key."""
+    KEEPS_COEF = False
 
     def __init__(self, kzg, circuit):
-        cv, n, k = circuit.curve, circuit.n, circuit.log_n
-        if kzg.curve != cv:
-            raise ZkError("fflonk: the circuit is over %s, the file over %s" % (cv, kzg.curve))
-        if kzg.max_coeffs < required_powers(n):
-            raise ZkError("fflonk: the file holds %d G1 powers, n = %d rows need 9n + 18 = %d (a file of power %d has them)" % (kzg.max_coeffs, n, required_powers(n), file_power(k)))
-        self.kzg, self.circuit, self.curve, self.n, self.log_n = kzg, circuit, cv, n, k
-        self.k1, self.k2 = coset_ks(cv, k)
-        self._bufs = []
-        try:
-            self._build()
-        except Exception:
-            self.free()
-            raise
+        super().__init__(kzg, circuit, "fflonk", ("9n + 18", required_powers(circuit.n)))
 
-    def _keep(self, d):
-        self._bufs.append(d)
-        return d
+    def _fixed(self, coef):
+        self.c0_coef = self._keep(interleave_dev(coef, [self.n] * 8, self.curve))
 
     def _build(self):
-        cv, n, k, c = self.curve, self.n, self.log_n, self.circuit
-        w = omega(cv, k)
-        self.sel_vals = [self._keep(_mont_dev(cv, c.sel[s])) for s in SELECTORS]
-        self.labels = self._keep(DevArray(12 * n))
-        for j, kj in enumerate((1, self.k1, self.k2)):
-            _powers_into(cv, w, kj, n, self.labels.ptr + 32 * j * n)
-        self.sigma_vals = self._keep(gather(self.labels, c.sigma(), cv))
-        vals = self.sel_vals + [_View(self.sigma_vals, j * n, n) for j in range(3)]
-        coef = []
-        try:
-            for v in vals:
-                coef.append(_interpolate(cv, v, n, 0, k))
-            self.coset = [self._keep(_coset_evals(cv, d, n, k + 2)) for d in coef]
-            self.c0_coef = self._keep(interleave_dev(coef, [n] * 8, cv))
-        finally:
-            for d in coef:
-                d.free()
-        l1 = DevArray(4 * n, zero=True)
-        try:
-            _upload_mont(cv, [1], l1.ptr)
-            _ntt(cv, l1.ptr, k, inverse=True)
-            self.l1_coset = self._keep(_coset_evals(cv, l1, n, k + 2))
-        finally:
-            l1.free()
-        self.x_coset = self._keep(DevArray(16 * n))
-        _powers_into(cv, omega(cv, k + 2), 7, 4 * n, self.x_coset.ptr)
+        super()._build()
         self.c0 = self.kzg.commit(self.c0_coef)
-        self.vk = VerifyingKey(cv, k, c.n_public, self.k1, self.k2, self.c0, self.kzg)
-
-    def free(self):
-        for d in self._bufs:
-            d.free()
-        self._bufs = []
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+        self.vk = VerifyingKey(self.curve, self.log_n, self.circuit.n_public, self.k1, self.k2, self.c0, self.kzg)
 
 
 def setup(kzg, circuit):
@@ -403,18 +324,7 @@ def setup(kzg, circuit):
 
 
 # ---- the prover -----------------------------------------------------------------------------------------------------------------------------
-def _quotient_coeffs(cv, k, d, n_coef, name, keep):
-    """the numerator's values on the coset, in place -> the quotient's 4n coefficients; those from n_coef on must be zero (batch_inverse's
-    zero count: a composition, no kernel of its own)"""
-    n = 1 << k
-    _check(_fn(cv, "divide_zh_coset")(d.ptr, k + 2, k, 0))
-    _ntt(cv, d.ptr, k + 2, inverse=True, coset=True)
-    high = 4 * n - n_coef
-    scratch = keep(DevArray(4 * high))
-    _, zeros, _ = fp.batch_inverse(_View(d, n_coef, high), cv, out=scratch)
-    if zeros != high:
-        raise ZkError("fflonk: %s has %d non-zero coefficients from %d on: the identity does not hold on H" % (name, high - zeros, n_coef))
-    return _View(d, 0, n_coef)
+NOT_ZERO = "fflonk: %s has %%d non-zero coefficients from %%d on: the identity does not hold on H"
 
 
 def prove(key, witness, blinding=None, self_check=True, _wires=None, _opening_transcript=None, _mark=None):
@@ -423,23 +333,8 @@ def prove(key, witness, blinding=None, self_check=True, _wires=None, _opening_tr
     a mapping with C1, C2, W1, W2 (points, point_bytes each) and values (15 integers in VALUE_NAMES order).  The gate equation is checked
     first, row by row; the permutation product must close.  Before returning, the proof is verified (self_check=False skips it).
     blinding: nine integers, FOR TESTS ONLY.  _wires, _opening_transcript, _mark: hooks of the tests and of tools/fflonk_time.py."""
-    cv, n, k, c, kzg = key.curve, key.n, key.log_n, key.circuit, key.kzg
-    r = _FR[cv]
+    cv, n, k, kzg = key.curve, key.n, key.log_n, key.kzg
     mark = _mark or (lambda name: None)
-    from_r1cs = isinstance(c, R1csCircuit) and _wires is None
-    if from_r1cs:
-        ww = _r1cs_witness_words(c, witness)
-    else:
-        ww = _canon_words(witness, r, "witness value")
-        if len(ww) != c.n_vars:
-            raise ZkError("fflonk: the witness has %d values, the circuit has %d variables" % (len(ww), c.n_vars))
-    if blinding is None:
-        bs = [secrets.randbelow(r) for _ in range(9)]
-    else:
-        bs = [int(b) for b in blinding]
-        if len(bs) != 9 or not all(0 <= b < r for b in bs):
-            raise ZkError("fflonk: blinding takes nine integers below the scalar field's modulus")
-    publics = [_int_of(ww[v]) for v in c.public]
     n0, n1, n2 = quotient_coeffs(n)
     own = []
 
@@ -447,56 +342,28 @@ def prove(key, witness, blinding=None, self_check=True, _wires=None, _opening_tr
         own.append(d)
         return d
     try:
-        mark("start")
-        if _wires is not None:
-            vals = [keep(DevArray.from_host(to_mont(col, cv).reshape(-1))) for col in _wires]
-            if len(vals) != 3 or any(v.n != 4 * n for v in vals):
-                raise ZkError("fflonk: _wires takes three columns of n values")
-        else:
-            d_w = keep(_extend_words(c, ww) if from_r1cs else _mont_dev(cv, ww))
-            vals = [keep(gather(d_w, c.wire[x], cv)) for x in WIRES]
-        pi_vals = keep(DevArray(4 * n, zero=True))
-        if publics:
-            _upload_mont(cv, [(-x) % r for x in publics], pi_vals.ptr)
-        bad, first = gate_check(vals + key.sel_vals + [pi_vals], n, cv)
-        if bad and from_r1cs and first >= c.n_public:
-            g = first - c.n_public
-            raise ZkError("fflonk: witness does not satisfy gate %d (constraint %d of the .r1cs) (%d rows)" % (g, int(c.origin[g]), bad))
-        if bad:
-            raise ZkError("fflonk: witness does not satisfy gate %d (%d rows)" % (first, bad))
-        mark("gate check")
+        vals, pi_vals, publics, bs = pa.witness_columns(key, witness, blinding, _wires, "fflonk", keep, mark)
         # round 1: T0 needs neither Z nor beta, gamma, which do not exist yet; a's column stands where Z's pointer must be valid
-        coef = [keep(_interpolate(cv, v, n, 2, k)) for v in vals]
-        for j, d in enumerate(coef):
-            _blind(cv, d, n, [bs[2 * j + 1], bs[2 * j]])
-        pi_coef = keep(_interpolate(cv, pi_vals, n, 0, k))
-        wire_cos = [keep(_coset_evals(cv, d, n + 2, k + 2)) for d in coef]
-        pi_cos = keep(_coset_evals(cv, pi_coef, n, k + 2))
+        coef = pa.blinded_wires(key, vals, bs, keep)
+        pi_coef = keep(pa.interpolate(cv, pi_vals, n, 0, k))
+        wire_cos = [keep(pa.coset_evals(cv, d, n + 2, k + 2)) for d in coef]
+        pi_cos = keep(pa.coset_evals(cv, pi_coef, n, k + 2))
         cols = wire_cos + [wire_cos[0]] + key.coset + [pi_cos, key.l1_coset, key.x_coset]
         t0 = keep(quotients(cols, k, 0, 0, key.k1, key.k2, cv, want=(True, False, False))[0])
-        t0_view = _quotient_coeffs(cv, k, t0, n0, "T0", keep)
+        t0_view = pa.quotient_coeffs(cv, k, t0, n0, NOT_ZERO % "T0", keep)
         c1_coef = keep(interleave_dev(coef + [t0_view], [n + 2] * 3 + [n0], cv))
         C1 = kzg.commit(c1_coef)
         c0h = transcript_start(cv, key.vk.digest, publics)
         c1h, beta, gamma = transcript_round1(cv, c0h, C1)
         mark("round 1")
         # round 2
-        labels = [_View(key.labels, j * n, n) for j in range(3)]
-        sigmas = [_View(key.sigma_vals, j * n, n) for j in range(3)]
-        num = keep(fp.terms(vals, labels, beta, gamma, cv, dev=True))
-        den = keep(fp.terms(vals, sigmas, beta, gamma, cv, dev=True))
-        z_vals, last = fp.grand_product(num, den, cv)
-        keep(z_vals)
-        if last != 1:
-            raise ZkError("fflonk: the permutation product does not close (z_n = %d): the wire values break a copy constraint" % last)
-        z_coef = keep(_interpolate(cv, z_vals, n, 3, k))
-        _blind(cv, z_coef, n, [bs[8], bs[7], bs[6]])
-        cols[3] = keep(_coset_evals(cv, z_coef, n + 3, k + 2))
+        z_coef = pa.permutation_product(key, vals, beta, gamma, bs, "fflonk", keep)
+        cols[3] = keep(pa.coset_evals(cv, z_coef, n + 3, k + 2))
         _, t1, t2 = quotients(cols, k, beta, gamma, key.k1, key.k2, cv, want=(False, True, True))
         keep(t1); keep(t2)
-        t1_view = _quotient_coeffs(cv, k, t1, n1, "T1", keep)
-        t2_view = _quotient_coeffs(cv, k, t2, n2, "T2", keep)
-        c2_coef = keep(interleave_dev([_View(z_coef, 0, n + 3), t1_view, t2_view], [n + 3, n1, n2], cv))
+        t1_view = pa.quotient_coeffs(cv, k, t1, n1, NOT_ZERO % "T1", keep)
+        t2_view = pa.quotient_coeffs(cv, k, t2, n2, NOT_ZERO % "T2", keep)
+        c2_coef = keep(interleave_dev([View(z_coef, 0, n + 3), t1_view, t2_view], [n + 3, n1, n2], cv))
         C2 = kzg.commit(c2_coef)
         c2h, s = transcript_round2(cv, c1h, C2, k)
         mark("round 2")
@@ -517,7 +384,7 @@ def prove(key, witness, blinding=None, self_check=True, _wires=None, _opening_tr
             state["values"], state["t"] = values_of(curve, opened, rt)
             return _opening_transcript(curve, commitments, sets_, opened)
         _, W1, W2, _, _ = kzg.open_multi([key.c0_coef, c1_coef, c2_coef], sets, transcript=opening_gamma if _opening_transcript is None else loose_gamma,
-                                         transcript_z=opening_z if _opening_transcript is None else _plain_z, commitments=[key.c0, C1, C2])
+                                         transcript_z=opening_z if _opening_transcript is None else pa.plain_z, commitments=[key.c0, C1, C2])
         mark("round 4")
         values = state["values"]
         want_t = quotients_at(cv, k, key.k1, key.k2, publics, beta, gamma, rt["xi"], dict(zip(VALUE_NAMES, values)))
@@ -552,21 +419,11 @@ def host_check(vk, publics, proof, point_bytes=None):
     """what the verifier decides on the host, before any device work: lengths (an error), every scalar below r (else INPUT_NOT_CANONICAL), the
     challenges, the 18 values the opening must have -> (verdict, the tuple Kzg.verify_multi takes, built with the verifier's OWN gamma' and
     z').  The identities are not checked here: they are what the rebuilt values of T0, T1, T2 make the opening enforce."""
-    cv, r = vk.curve, _FR[vk.curve]
-    missing = [k for k in POINT_NAMES + ("values",) if k not in proof]
-    if missing:
-        raise ZkError("fflonk: the proof holds no %s" % ", ".join(missing))
-    if len(proof["values"]) != N_VALUES:
-        raise ZkError("fflonk: a proof holds %d values, not %d" % (N_VALUES, len(proof["values"])))
-    pb = point_bytes if point_bytes is not None else len(vk.c0)
-    for name in POINT_NAMES:
-        if len(proof[name]) != pb:
-            raise ZkError("fflonk: point %s of the proof is %d bytes, not %d" % (name, len(proof[name]), pb))
-    if len(publics) != vk.n_public:
-        raise ZkError("fflonk: %d public inputs, the verification key has %d" % (len(publics), vk.n_public))
-    values, publics = [int(v) for v in proof["values"]], [int(x) for x in publics]
-    if not all(0 <= v < r for v in values + publics):
+    cv = vk.curve
+    shape = pa.check_proof_shape(proof, POINT_NAMES, N_VALUES, point_bytes if point_bytes is not None else len(vk.c0), vk.n_public, publics, FR[cv], "fflonk")
+    if shape is None:
         return INPUT_NOT_CANONICAL, None
+    values, publics = shape
     ch = challenges(vk, publics, proof)
     rt = roots(cv, vk.log_n, ch["s"])
     ys = opened_values(cv, vk.log_n, vk.k1, vk.k2, publics, values, ch["beta"], ch["gamma"], rt)
@@ -577,26 +434,4 @@ def verify(vk, publics, proofs, kzg=None, seed=None, locate=True):
     """m proofs under one verification key: publics[i] are proof i's public inputs -> (verdict, first_bad) as Kzg.verify_multi gives them.
     The host part of every proof first (host_check), then ONE randomised pairing check of all of them: two pairings.  kzg: the handle to pair
     with, when the key does not carry one.  seed: 32 bytes for the weights, FOR TESTS ONLY."""
-    kzg = kzg if kzg is not None else vk.kzg
-    if kzg is None:
-        raise ZkError("fflonk: verify needs the Kzg handle of the file (kzg=), this verification key carries none")
-    if kzg.curve != vk.curve:
-        raise ZkError("fflonk: the verification key is over %s, the file over %s" % (vk.curve, kzg.curve))
-    if len(publics) != len(proofs):
-        raise ZkError("fflonk: %d lists of public inputs for %d proofs" % (len(publics), len(proofs)))
-    tuples, bad = [], None
-    for i, (x, p) in enumerate(zip(publics, proofs)):
-        verdict, tup = host_check(vk, x, p, kzg.point_bytes)
-        if verdict != ACCEPTED:
-            bad = (verdict, i)
-            break
-        tuples.append(tup)
-    if bad is None:
-        return kzg.verify_multi(tuples, seed=seed, locate=locate)
-    if not locate:
-        return REJECTED, None
-    if tuples:                                                      # a proof before the one the host refused may fail the pairing check
-        verdict, first = kzg.verify_multi(tuples, seed=seed, locate=True)
-        if verdict != ACCEPTED:
-            return verdict, first
-    return bad
+    return pa.verify_batch(vk, publics, proofs, host_check, kzg, seed, locate, "fflonk")

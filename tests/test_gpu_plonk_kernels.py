@@ -184,7 +184,7 @@ def test_gather(zk, plonk, cv):
             plonk.gather(src, [0, 1, 2, m], cv)                                            # the host has the indices: refused there
         bad = list(idx)
         bad[2], bad[300], bad[519] = m, 0xFFFFFFFF, m + 7
-        d_idx = plonk._upload_indices(np.asarray(bad, dtype=np.int64))
+        d_idx = plonk.upload_indices(np.asarray(bad, dtype=np.int64))
         d_out = zk.DevArray(4 * len(bad))
         try:
             with pytest.raises(plonk.ZkError, match="gather: 3 indices are not below the source's %d elements, the first at position 2" % m):

@@ -34,7 +34,7 @@ def test_header_declares_and_package_binds_the_entry_points(zk, plonk):
 
 @pytest.mark.parametrize("field", FIELDS)
 def test_the_librarys_tables_are_the_models_array_for_array(plonk, field):
-    ints = lambda words: [plonk._int_of(w) for w in words]
+    ints = lambda words: [plonk.int_of(w) for w in words]
     for name, data, w, _ in circuits(field):
         m = model.Compiled(data, field)
         t = m.tables()

@@ -43,6 +43,16 @@ def test_package_exports_and_binds_them(zk, plonk):
         assert "H(" in fn.__doc__, fn.__name__           # the hashed bytes are stated where the function is
 
 
+def test_the_layers_names_are_one_object_through_the_three_modules(zk, plonk):
+    arith, fflonk = importlib.import_module("eigen_zkvm_amd.plonk_arith"), importlib.import_module("eigen_zkvm_amd.fflonk")
+    for name in ("Circuit", "R1csCircuit", "ACCEPTED", "ZkError", "gather", "omega"):     # isinstance(c, R1csCircuit) decides the witness path
+        assert getattr(plonk, name) is getattr(fflonk, name) is getattr(arith, name), name
+    assert issubclass(plonk.PlonkKey, arith.ArithKey) and issubclass(fflonk.FflonkKey, arith.ArithKey)
+    text = (ROOT / "eigen-zkvm_amd" / "fflonk.py").read_text()
+    assert not re.search(r"^\s*(from\s+\.plonk\s+import|from\s+\.\s+import\s+plonk\b|import\s+\S*\.plonk\b)", text, flags=re.M)   # fflonk stands on the layer alone
+    assert not any(plonk.__name__ in (getattr(v, "__module__", None), isinstance(v, types.ModuleType) and v.__name__) for v in vars(fflonk).values())
+
+
 def test_cli_parses_its_three_commands():
     sys.path.insert(0, str(ROOT / "tools"))
     cli = importlib.import_module("zkgpu_plonk")
@@ -88,7 +98,7 @@ def test_refusals_before_any_device_work(zk, plonk):
     c = plonk.Circuit(n_vars, public, gates)
     assert (c.n, c.log_n, c.n_public, c.n_gates) == (8, 3, 1, 6)
     t = ref.Table("BN128", n_vars, public, gates)
-    assert all([plonk._int_of(w) for w in c.sel[k]] == t.sel[k] for k in ref.SELECTORS) and all(c.wire[k].tolist() == t.wire[k] for k in "abc")
+    assert all([plonk.int_of(w) for w in c.sel[k]] == t.sel[k] for k in ref.SELECTORS) and all(c.wire[k].tolist() == t.wire[k] for k in "abc")
     with pytest.raises(plonk.ZkError, match="selector qM of gate 2 is not below the scalar field's modulus"):
         plonk.Circuit(*_gates(r, qM=(2, r))[:3])
     with pytest.raises(plonk.ZkError, match="wire b of gate 3 is variable %d, the circuit has %d variables" % (n_vars, n_vars)):

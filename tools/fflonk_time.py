@@ -39,7 +39,7 @@ def _wall(fn, reps, warmup):
 def time_provers(zk, plonk, fflonk, fp, curve, log_n, reps, warmup, tmp):
     """-> {prover: ({round: ms, "total": ms}, {1: ms, 16: ms} of verify, key seconds)}"""
     g16, kzg_mod = importlib.import_module("eigen_zkvm_amd.groth16"), importlib.import_module("eigen_zkvm_amd.kzg")
-    r, n = plonk._FR[curve], 1 << log_n
+    r, n = plonk.FR[curve], 1 << log_n
     n_vars, public, gates, ww = plonk_time.chain_arrays(log_n, r)
     circuit = plonk.Circuit(n_vars, public, gates, curve)
     path = os.path.join(tmp, "t%d.ptau" % log_n)
@@ -76,7 +76,7 @@ def time_provers(zk, plonk, fflonk, fp, curve, log_n, reps, warmup, tmp):
 
 
 def time_kernel(zk, plonk, fflonk, fp, curve, log_n, reps, warmup):
-    r, m = plonk._FR[curve], 4 << log_n
+    r, m = plonk.FR[curve], 4 << log_n
     beta, gamma, k1, k2 = 0x2222, 0x3333, 2, 3
     cols = [fp.powers(5 + 2 * j, 7 + j, m, curve, dev=True) for j in range(15)]
     outs = [zk.DevArray(4 * m) for _ in range(3)]

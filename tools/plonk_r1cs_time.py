@@ -127,11 +127,11 @@ def circuit(a, zk, plonk, fp):
     g16, kzg_mod = importlib.import_module("eigen_zkvm_amd.groth16"), importlib.import_module("eigen_zkvm_amd.kzg")
     t0 = time.time()
     data, w = circom_shaped(a.curve, a.constraints_log, a.long_rows_log, a.terms)
-    ww = plonk._canon_words(w, PRIME[a.curve], "witness value")
+    ww = plonk.canon_words(w, PRIME[a.curve], "witness value")
     lines = []
     c = plonk.R1csCircuit(data, a.curve)
     info = dict(c.info)
-    d_w = plonk._extend_words(c, ww)                                                 # the witness in front, as the prover leaves it
+    d_w = plonk.extend_words(c, ww)                                                 # the witness in front, as the prover leaves it
     c.free()
     print("circuit made in %.1f s: %s" % (time.time() - t0, info), flush=True)
     res = {}

@@ -90,7 +90,7 @@ def device_ptau(zk, fp, curve, power, tau, path):
     ones.free()
     g1 = zk.mul_generator_fr(d, abi).to_host()[:(2 * n - 1) * n8 // 4].astype("<u8").tobytes()
     plonk = importlib.import_module("eigen_zkvm_amd.plonk")
-    g2 = zk.mul_generator_fr(plonk._View(d, 0, n), abi, group="g2").to_host()[:n * n8 // 2].astype("<u8").tobytes()
+    g2 = zk.mul_generator_fr(plonk.View(d, 0, n), abi, group="g2").to_host()[:n * n8 // 2].astype("<u8").tobytes()
     d.free()
     payloads = {2: g1, 3: g2, 4: g1[:2 * n8 * n], 5: g1[:2 * n8 * n], 6: g2[:4 * n8]}
     pathlib.Path(path).write_bytes(make_test_ptau.container(curve, power, payloads))
@@ -98,7 +98,7 @@ def device_ptau(zk, fp, curve, power, tau, path):
 
 def time_prover(zk, plonk, fp, curve, log_n, reps, warmup, tmp):
     g16, kzg_mod = importlib.import_module("eigen_zkvm_amd.groth16"), importlib.import_module("eigen_zkvm_amd.kzg")
-    r, n = plonk._FR[curve], 1 << log_n
+    r, n = plonk.FR[curve], 1 << log_n
     t0 = time.time()
     n_vars, public, gates, ww = chain_arrays(log_n, r)
     circuit = plonk.Circuit(n_vars, public, gates, curve)
@@ -124,7 +124,7 @@ def time_prover(zk, plonk, fp, curve, log_n, reps, warmup, tmp):
     med["total"] = statistics.median(sum(t[k] for k in names) for t in runs)
     # round 5 with and without the 8 fixed polynomials: stand-in coefficients of the right lengths, fixed challenges
     src = fp.powers(3, 1, 4 * n, curve, dev=True)
-    live = [plonk._View(src, 0, n + 2), plonk._View(src, 8, n + 2), plonk._View(src, 16, n + 2), plonk._View(src, 24, 3 * n + 6), plonk._View(src, 32, n + 3)]
+    live = [plonk.View(src, 0, n + 2), plonk.View(src, 8, n + 2), plonk.View(src, 16, n + 2), plonk.View(src, 24, 3 * n + 6), plonk.View(src, 32, n + 3)]
     zeta = 0x1234567
     sets5 = [[zeta]] * 4 + [[zeta, zeta * plonk.omega(curve, log_n) % r]]
     opens = {}
@@ -141,7 +141,7 @@ def time_prover(zk, plonk, fp, curve, log_n, reps, warmup, tmp):
 
 
 def time_kernel(zk, plonk, fp, curve, log_n, reps, warmup):
-    r, m = plonk._FR[curve], 4 << log_n
+    r, m = plonk.FR[curve], 4 << log_n
     alpha, beta, gamma, k1, k2 = 0x1111, 0x2222, 0x3333, 2, 3
     cols = [fp.powers(5 + 2 * j, 7 + j, m, curve, dev=True) for j in range(15)]
     a, b, c, Z, qL, qR, qO, qM, qC, S1, S2, S3, PI, L1, X = cols
@@ -158,8 +158,8 @@ def time_kernel(zk, plonk, fp, curve, log_n, reps, warmup):
     # the same bracket from the layer's public calls
     k1x, k2x = (fp.pointwise("mul", X, fp.powers(1, k, m, curve, dev=True), curve) for k in (k1, k2))
     Zw = zk.DevArray(4 * m)
-    plonk._add_into(curve, Z.ptr + 32 * 4, _zero(zk, Zw, m).ptr, m - 4)
-    plonk._add_into(curve, Z.ptr, Zw.ptr + 32 * (m - 4), 4)
+    plonk.add_into(curve, Z.ptr + 32 * 4, _zero(zk, Zw, m).ptr, m - 4)
+    plonk.add_into(curve, Z.ptr, Zw.ptr + 32 * (m - 4), 4)
     va, va2, ones = fp.powers(1, alpha, m, curve, dev=True), fp.powers(1, alpha * alpha % r, m, curve, dev=True), fp.powers(1, 1, m, curve, dev=True)
     t1, acc = zk.DevArray(4 * m), zk.DevArray(4 * m)
     pw = lambda op, x, y, o: fp.pointwise(op, x, y, curve, out=o)
