@@ -76,7 +76,8 @@ EXPORTS = [
     "zk_kzg_multi_begin", "zk_kzg_multi_quotient", "zk_kzg_multi_finish", "zk_kzg_multi_free", "zk_kzg_multi_verify", "zk_kzg_multi_verify_dev",
     "zk_frpoly_tile_elems", "zk_frpoly_span",
 ] + ["zk_fr_%s_%s_dev" % (c, f) for c in ("bn254", "bls12_381")
-     for f in ("prefix_product", "batch_inverse", "pointwise", "powers", "terms", "grand_product", "poly_mul", "divmod_zh", "divide_zh_coset")
+     for f in ("prefix_product", "prefix_sum", "batch_inverse", "pointwise", "powers", "terms", "grand_product", "poly_mul", "divmod_zh", "divide_zh_coset")
+     ] + ["zk_plonk_%s_lookup_%s" % (c, f) for c in ("bn254", "bls12_381") for f in ("table_new", "table_free", "count_dev", "terms_dev", "summands_dev", "quotient_dev")
      ] + [n % c for c in ("bn254", "bls12_381") for n in ("zk_plonk_%s_quotient_dev", "zk_plonk_%s_gate_check_dev", "zk_fr_%s_gather_dev")
      ] + ["zk_fflonk_%s_quotients_dev" % c for c in ("bn254", "bls12_381")
      ] + ["zk_plonk_r1cs_wave_min_terms"] + ["zk_plonk_%s_r1cs_%s" % (c, f) for c in ("bn254", "bls12_381") for f in ("new", "info", "tables", "extend_dev", "free")]
@@ -438,6 +439,14 @@ def _load():
             "zk_plonk_%s_r1cs_tables" % c: (C.c_int, [vp] * 10),
             "zk_plonk_%s_r1cs_extend_dev" % c: (C.c_int, [vp, vp, vp]),
             "zk_plonk_%s_r1cs_free" % c: (C.c_int, [vp]),
+            # the device side of the lookup argument (plonk_lookup.py), and the running sum it adds to the polynomial layer
+            "zk_fr_%s_prefix_sum_dev" % c: (C.c_int, [vp, C.c_uint64, C.c_int, vp, vp, vp]),
+            "zk_plonk_%s_lookup_table_new" % c: (vp, [vp, vp, vp, C.c_uint64, vp]),
+            "zk_plonk_%s_lookup_table_free" % c: (C.c_int, [vp]),
+            "zk_plonk_%s_lookup_count_dev" % c: (C.c_int, [vp, vp, vp, vp, vp, C.c_uint64, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp]),
+            "zk_plonk_%s_lookup_terms_dev" % c: (C.c_int, [vp, C.c_uint64, vp, vp, vp, vp]),
+            "zk_plonk_%s_lookup_summands_dev" % c: (C.c_int, [vp, vp, vp, C.c_uint64, vp, vp]),
+            "zk_plonk_%s_lookup_quotient_dev" % c: (C.c_int, [vp, C.c_uint32, vp, vp, vp, vp, vp]),
         })
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -469,6 +478,9 @@ def __getattr__(name):
     if name == "FflonkKey":   # fflonk.py (the fflonk prover and verifier over the interleaved commitments)
         import importlib
         return importlib.import_module(__name__ + ".fflonk").FflonkKey
+    if name in ("LookupCircuit", "LookupKey"):   # plonk_lookup.py (the PLONK prover and verifier with the log-derivative lookup argument)
+        import importlib
+        return getattr(importlib.import_module(__name__ + ".plonk_lookup"), name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 

@@ -988,6 +988,9 @@ uint64_t zk_frpoly_span(void) { return FRPOLY_SPAN; }
     }                                                                                                                                         \
     int zk_fr_##NAME##_divide_zh_coset_dev(uint64_t* d_evals, uint32_t log_m, uint32_t log_n, void* stream) {                                 \
         return guard([&] { curve(ID).frpoly().divide_zh_coset_dev((u64*)d_evals, log_m, log_n, on_stream((hipStream_t)stream)); });           \
+    }                                                                                                                                         \
+    int zk_fr_##NAME##_prefix_sum_dev(const uint64_t* d_in, uint64_t n, int inclusive, uint64_t* d_out, uint64_t* total_out, void* stream) {  \
+        return guard([&] { curve(ID).frpoly().prefix_sum_dev((const u64*)d_in, n, inclusive != 0, (u64*)d_out, (u64*)total_out, on_stream((hipStream_t)stream)); }); \
     }
 ZK_FRPOLY_API(bn254, CURVE_BN254)
 ZK_FRPOLY_API(bls12_381, CURVE_BLS12_381)
@@ -1022,6 +1025,41 @@ ZK_PLONK_API(bls12_381, CURVE_BLS12_381)
 ZK_FFLONK_API(bn254, CURVE_BN254)
 ZK_FFLONK_API(bls12_381, CURVE_BLS12_381)
 #undef ZK_FFLONK_API
+// ---- the device side of PLONK's lookup argument (plonk_lookup_impl.hip.h through groth16.hip) ----
+static const zk_plonk_lookup_table_t& plonk_lookup_table_of(const zk_plonk_lookup_table_t* h, CurveId id) {
+    ZK_REQUIRE(h, "plonk lookup: null table");
+    ZK_REQUIRE(h->curve == &curve(id), "plonk lookup: the table is over another field");
+    return *h;
+}
+#define ZK_PLONK_LOOKUP_API(NAME, ID)                                                                                                         \
+    zk_plonk_lookup_table_t* zk_plonk_##NAME##_lookup_table_new(const uint64_t* d_t1, const uint64_t* d_t2, const uint64_t* d_t3, uint64_t T, void* stream) { \
+        zk_plonk_lookup_table_t* out = nullptr;                                                                                               \
+        guard([&] { out = curve(ID).plonk_lookup().table_new((const u64*)d_t1, (const u64*)d_t2, (const u64*)d_t3, T, on_stream((hipStream_t)stream)); }); \
+        return out;                                                                                                                           \
+    }                                                                                                                                         \
+    int zk_plonk_##NAME##_lookup_table_free(zk_plonk_lookup_table_t* table) { return guard([&] { delete table; }); }                          \
+    int zk_plonk_##NAME##_lookup_count_dev(const zk_plonk_lookup_table_t* table, const uint64_t* d_a, const uint64_t* d_b, const uint64_t* d_c, const uint64_t* d_qK, uint64_t n, \
+                                           uint64_t* d_m_out, uint64_t* n_bad, uint64_t* first_bad, void* stream) {                           \
+        return guard([&] {                                                                                                                    \
+            curve(ID).plonk_lookup().count_dev(plonk_lookup_table_of(table, ID), (const u64*)d_a, (const u64*)d_b, (const u64*)d_c, (const u64*)d_qK, n, (u64*)d_m_out, (u64*)n_bad, \
+                                               (u64*)first_bad, on_stream((hipStream_t)stream));                                              \
+        });                                                                                                                                   \
+    }                                                                                                                                         \
+    int zk_plonk_##NAME##_lookup_terms_dev(const uint64_t* const* d_cols, uint64_t n, const uint64_t* eta, const uint64_t* delta, uint64_t* d_out, void* stream) { \
+        return guard([&] { curve(ID).plonk_lookup().terms_dev((const u64* const*)d_cols, n, (const u64*)eta, (const u64*)delta, (u64*)d_out, on_stream((hipStream_t)stream)); }); \
+    }                                                                                                                                         \
+    int zk_plonk_##NAME##_lookup_summands_dev(const uint64_t* d_inv, const uint64_t* d_qK, const uint64_t* d_m, uint64_t n, uint64_t* d_out, void* stream) { \
+        return guard([&] { curve(ID).plonk_lookup().summands_dev((const u64*)d_inv, (const u64*)d_qK, (const u64*)d_m, n, (u64*)d_out, on_stream((hipStream_t)stream)); }); \
+    }                                                                                                                                         \
+    int zk_plonk_##NAME##_lookup_quotient_dev(const uint64_t* const* d_cols, uint32_t log_n, const uint64_t* alpha, const uint64_t* eta, const uint64_t* delta, uint64_t* d_acc, \
+                                              void* stream) {                                                                                 \
+        return guard([&] {                                                                                                                    \
+            curve(ID).plonk_lookup().quotient_dev((const u64* const*)d_cols, log_n, (const u64*)alpha, (const u64*)eta, (const u64*)delta, (u64*)d_acc, on_stream((hipStream_t)stream)); \
+        });                                                                                                                                   \
+    }
+ZK_PLONK_LOOKUP_API(bn254, CURVE_BN254)
+ZK_PLONK_LOOKUP_API(bls12_381, CURVE_BLS12_381)
+#undef ZK_PLONK_LOOKUP_API
 // ---- the R1CS import of the PLONK prover (plonk_r1cs_impl.hip.h through groth16.hip); new, info, tables and free touch no device ----
 uint64_t zk_plonk_r1cs_wave_min_terms(void) { return PLONK_R1CS_WAVE_MIN_TERMS; }
 static const zk_plonk_r1cs_t& plonk_r1cs_of(const zk_plonk_r1cs_t* h, CurveId id) {

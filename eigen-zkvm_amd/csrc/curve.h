@@ -12,6 +12,7 @@ struct zk_srs;
 struct zk_kzg;
 struct zk_kzg_multi;
 struct zk_plonk_r1cs;
+struct zk_plonk_lookup_table;
 
 namespace zk {
 
@@ -22,6 +23,7 @@ using Srs = ::zk_srs;
 using Kzg = ::zk_kzg;
 using KzgMulti = ::zk_kzg_multi;
 using PlonkR1cs = ::zk_plonk_r1cs;
+using PlonkLookupTable = ::zk_plonk_lookup_table;
 namespace g16 { struct Circuit; struct Params; }
 // what miller_kernel takes (pairing_impl.hip.h): up to three pairs per item -- G1 points, line tables and infinity words with their strides
 struct MillerArgs {
@@ -110,6 +112,7 @@ struct FrPolyOps {
     void (*poly_mul_dev)(const u64* d_a, u64 na, const u64* d_b, u64 nb, u64* d_out, hipStream_t st);
     void (*divmod_zh_dev)(const u64* d_p, u64 n_p, u32 log_n, u64* d_q, u64* d_rem, u64* rem_nonzero, hipStream_t st);
     void (*divide_zh_coset_dev)(u64* d_evals, u32 log_m, u32 log_n, hipStream_t st);
+    void (*prefix_sum_dev)(const u64* d_in, u64 n, bool inclusive, u64* d_out, u64* total_out, hipStream_t st);   // plonk_lookup_impl.hip.h: the same tiles under addition
 };
 const FrPolyOps& frpoly_ops(CurveId id);
 constexpr uint64_t FRPOLY_TILE = 2048, FRPOLY_SPAN = 512;   // elements per workgroup of the running product; tile aggregates per step of the combining workgroup
@@ -131,6 +134,16 @@ struct FflonkOps {
     void (*quotients_dev)(const u64* const* d_cols, u32 log_n, const u64* beta, const u64* gamma, const u64* k1, const u64* k2, u64* d_out0, u64* d_out1, u64* d_out2, hipStream_t st);
 };
 const FflonkOps& fflonk_ops(CurveId id);
+// ---- groth16.hip: the device side of PLONK's lookup argument (plonk_lookup_impl.hip.h).  Vectors and scalars as for FrPolyOps;
+// what include/zkgpu.h states for zk_plonk_<curve>_lookup_* holds for these
+struct PlonkLookupOps {
+    PlonkLookupTable* (*table_new)(const u64* d_t1, const u64* d_t2, const u64* d_t3, u64 T, hipStream_t st);
+    void (*count_dev)(const PlonkLookupTable& h, const u64* d_a, const u64* d_b, const u64* d_c, const u64* d_qk, u64 n, u64* d_m_out, u64* n_bad, u64* first_bad, hipStream_t st);
+    void (*terms_dev)(const u64* const* d_cols, u64 n, const u64* eta, const u64* delta, u64* d_out, hipStream_t st);
+    void (*summands_dev)(const u64* d_inv, const u64* d_qk, const u64* d_m, u64 n, u64* d_out, hipStream_t st);
+    void (*quotient_dev)(const u64* const* d_cols, u32 log_n, const u64* alpha, const u64* eta, const u64* delta, u64* d_acc, hipStream_t st);
+};
+const PlonkLookupOps& plonk_lookup_ops(CurveId id);
 constexpr uint64_t PLONK_R1CS_WAVE_MIN_TERMS = 64;   // a segment of this many terms or more is walked by a whole wave (plonk_r1cs_impl.hip.h)
 // ---- pairing.hip: the steps of the optimal ate pairing and of Groth16 verification (pairing_impl.hip.h)
 struct PairingOps {
@@ -196,6 +209,7 @@ struct Curve {
     const FrPolyOps& frpoly() const { return frpoly_ops(id); }
     const PlonkOps& plonk() const { return plonk_ops(id); }
     const FflonkOps& fflonk() const { return fflonk_ops(id); }
+    const PlonkLookupOps& plonk_lookup() const { return plonk_lookup_ops(id); }
 };
 inline const Curve CURVES[2] = {
     {CURVE_BN254, "BN128", "bn254", 8, {0xf0000001u, 0x43e1f593u, 0x79b97091u, 0x2833e848u, 0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u}},
@@ -369,6 +383,12 @@ struct zk_plonk_r1cs {       // an .r1cs as the PLONK prover takes it (plonk_r1c
     uint64_t n_short = 0, n_long = 0;
     bool on_device = false;
     zk_plonk_r1cs() = default; zk_plonk_r1cs(const zk_plonk_r1cs&) = delete; zk_plonk_r1cs& operator=(const zk_plonk_r1cs&) = delete;
+};
+struct zk_plonk_lookup_table {   // the rows of a lookup table as a hash table on the device (plonk_lookup_impl.hip.h); read-only once built
+    const zk::Curve* curve = nullptr;
+    uint64_t n_rows = 0, n_slots = 0;                // n_slots: the smallest power of two >= 2 n_rows
+    zk::DevBuf d_keys, d_slots;                      // per row: the 24 canonical Montgomery words of its key; per slot: a row or 0xffffffff
+    zk_plonk_lookup_table() = default; zk_plonk_lookup_table(const zk_plonk_lookup_table&) = delete; zk_plonk_lookup_table& operator=(const zk_plonk_lookup_table&) = delete;
 };
 struct zk_groth16_vk {       // a verification key, checked and prepared
     const zk::Curve* curve = nullptr;

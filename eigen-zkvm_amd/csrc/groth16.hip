@@ -12,7 +12,8 @@
 // (frpoly_impl.hip.h, DESIGN.md 3.20: zk_fr_<curve>_poly_mul_dev and its siblings; no protocol), and after it the three kernels of the
 // PLONK prover (plonk_impl.hip.h, DESIGN.md 3.21: the fused numerator of the quotient, the gate check, the gather) and its R1CS import
 // (plonk_r1cs_impl.hip.h, DESIGN.md 3.22: the compile rule on the host, the auxiliary variables of a witness on the device), and the
-// fflonk prover's three numerators in one launch (fflonk_impl.hip.h).
+// fflonk prover's three numerators in one launch (fflonk_impl.hip.h), and the lookup argument of the PLONK prover
+// (plonk_lookup_impl.hip.h, DESIGN.md 3.24: the running sum, the hash table and the count, the denominators, the summand, the quotient's term).
 //   proof.json       groth16/src/json_utils.rs:305-315
 // Key generation (`zkit groth16_setup`, groth16/src/api.rs:42-66) over the same circuit: groth16_keygen_impl.hip.h with a trapdoor,
 // groth16_srs.hip.h from a powers-of-tau file (and the contributions to such a key).
@@ -306,6 +307,7 @@ namespace bn254fr {
 #include "frntt_impl.hip.h"
 #include "frpoly_impl.hip.h"
 #include "plonk_impl.hip.h"
+#include "plonk_lookup_impl.hip.h"
 #include "fflonk_impl.hip.h"
 #include "plonk_r1cs_impl.hip.h"
 #include "groth16_impl.hip.h"
@@ -328,6 +330,7 @@ namespace bls12381fr {
 #include "frntt_impl.hip.h"
 #include "frpoly_impl.hip.h"
 #include "plonk_impl.hip.h"
+#include "plonk_lookup_impl.hip.h"
 #include "fflonk_impl.hip.h"
 #include "plonk_r1cs_impl.hip.h"
 #include "groth16_impl.hip.h"
@@ -346,7 +349,7 @@ const Groth16Ops& groth16_ops(CurveId id) {   // the table's slice of this unit 
 
 const FrPolyOps& frpoly_ops(CurveId id) {     // frpoly_impl.hip.h, per scalar field
 #define ZK_FRPOLY_OPS(NS) {NS::fp_prefix_product_dev, NS::fp_batch_inverse_dev, NS::fp_pointwise_dev, NS::fp_powers_dev, NS::fp_terms_dev, NS::fp_grand_product_dev, \
-                           NS::fp_poly_mul_dev, NS::fp_divmod_zh_dev, NS::fp_divide_zh_coset_dev}
+                           NS::fp_poly_mul_dev, NS::fp_divmod_zh_dev, NS::fp_divide_zh_coset_dev, NS::fp_prefix_sum_dev}
     static const FrPolyOps OPS[2] = {ZK_FRPOLY_OPS(bn254fr), ZK_FRPOLY_OPS(bls12381fr)};
 #undef ZK_FRPOLY_OPS
     return OPS[id];
@@ -360,6 +363,13 @@ const PlonkOps& plonk_ops(CurveId id) {       // plonk_impl.hip.h and plonk_r1cs
 
 const FflonkOps& fflonk_ops(CurveId id) {     // fflonk_impl.hip.h, per scalar field
     static const FflonkOps OPS[2] = {{bn254fr::ff_quotients_dev}, {bls12381fr::ff_quotients_dev}};
+    return OPS[id];
+}
+
+const PlonkLookupOps& plonk_lookup_ops(CurveId id) {   // plonk_lookup_impl.hip.h, per scalar field
+#define ZK_PLONK_LOOKUP_OPS(NS) {NS::pl_table_new, NS::pl_count_dev, NS::pl_terms_dev, NS::pl_summands_dev, NS::pl_quotient_dev}
+    static const PlonkLookupOps OPS[2] = {ZK_PLONK_LOOKUP_OPS(bn254fr), ZK_PLONK_LOOKUP_OPS(bls12381fr)};
+#undef ZK_PLONK_LOOKUP_OPS
     return OPS[id];
 }
 

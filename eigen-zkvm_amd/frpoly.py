@@ -1,5 +1,5 @@
 """Polynomial arithmetic over the scalar fields of BN254 and BLS12-381 on the device (include/zkgpu.h, "Polynomial arithmetic over the
-scalar field"): running products, batch inversion, pointwise work, powers, the terms of a grand product, the grand product
+scalar field"): running products and sums, batch inversion, pointwise work, powers, the terms of a grand product, the grand product
 itself, products of polynomials and quotients by X^N - 1.  One function per entry point zk_fr_<curve>_<name>_dev.  No protocol: what a
 PLONK-family prover is made of, not the prover.  Everything runs on the device; there is no CPU fallback.
 
@@ -76,7 +76,17 @@ def _int4(words):
 def prefix_product(v, curve="BN128", inclusive=False, out=None, total_only=False):
     """-> (products, total): products[i] = prod_{j < i} v[j] (inclusive: j <= i), total = prod v.  total_only: (None, total), nothing is
     written.  n = 0 gives ([], 1)."""
-    fn = _fn(curve, "prefix_product")
+    return _prefix("prefix_product", v, curve, inclusive, out, total_only)
+
+
+def prefix_sum(v, curve="BN128", inclusive=False, out=None, total_only=False):
+    """-> (sums, total): sums[i] = sum_{j < i} v[j] (inclusive: j <= i), total = sum v: prefix_product's tiles and rules under addition.
+    n = 0 gives ([], 0)."""
+    return _prefix("prefix_sum", v, curve, inclusive, out, total_only)
+
+
+def _prefix(name, v, curve, inclusive, out, total_only):
+    fn = _fn(curve, name)
     x = _Vec(v, curve)
     tot = np.zeros(4, np.uint64)
     d_out = None

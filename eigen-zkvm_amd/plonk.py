@@ -5,7 +5,8 @@ here as well.  Everything over Fr runs on the device through zk_fr_<curve>_*_dev
 zk_fr_<curve>_gather_dev and Kzg.open_multi.  There is no CPU fallback.  Cut down to what those layers do: NO linearisation polynomial (every
 polynomial of the identity is opened at zeta, Z at zeta w as well, in one Shplonk proof of two points), the quotient t committed WHOLE
 (degree 3n + 5: the file must hold 3n + 6 G1 powers), a circuit is a gate table, written by hand or compiled from a circom .r1cs (R1csCircuit,
-DESIGN.md 3.22); no custom gates, no lookups, not fflonk's interleaved form.
+DESIGN.md 3.22); no custom gates, not fflonk's interleaved form.  Lookups are a protocol of their own on the same layer: plonk_lookup.py
+(DESIGN.md 3.24).
 
 Field Fr of BN128 or BLS12381.  n = 2^k >= 8 rows (smaller circuits are padded to 8, others to the next power of two; a padding row has all
 selectors 0 and its wires on variable 0).  H = <w> with the w of zk_fr_<curve>_ntt_dev, w = 7^((r - 1) / n).

@@ -137,9 +137,10 @@ def plain_z(curve, gamma, W1, avoid=()):
 class Circuit:
     """A gate table.  gates: a mapping with qL, qR, qO, qM, qC (integers below r, or (m, 4) u64 canonical words) and a, b, c (variable ids) of
     one length m; public: l variable ids.  The class puts the l public rows in front and pads to n = 2^k >= 8 rows: self.sel[name] is (n, 4)
-    u64, self.wire[name] n u32.  Everything here is host integers: no device work."""
+    u64, self.wire[name] n u32.  min_rows: n holds at least this many rows as well (a protocol whose circuit carries a table of that many).
+    Everything here is host integers: no device work."""
 
-    def __init__(self, n_vars, public, gates, curve="BN128"):
+    def __init__(self, n_vars, public, gates, curve="BN128", min_rows=0):
         r = modulus(curve)
         self.curve, self.n_vars = curve, int(n_vars)
         self.public = [int(v) for v in public]
@@ -160,7 +161,7 @@ class Circuit:
         self.gates = {**raw_sel, **{w: raw_wire[w].astype(np.uint32) for w in WIRES}}
         self.n_public, self.n_gates = len(self.public), m
         rows = self.n_public + m
-        self.log_n = max(3, (rows - 1).bit_length())
+        self.log_n = max(3, (max(rows, int(min_rows)) - 1).bit_length())
         self.n = 1 << self.log_n
         check_size(curve, self.log_n)
         self.sel, self.wire = {}, {}
@@ -501,10 +502,14 @@ class ArithKey:
 
 
 # ---- the prover's steps that are no protocol's ----------------------------------------------------------------------------------------------
-def witness_columns(key, witness, blinding, _wires, who, keep, mark=lambda name: None):
-    """what prove() takes -> (the three value columns on H, PI's values, the public inputs, the nine blinders).  Every refusal of the witness
-    and of the blinders on the host first; then, between the marks "start" and "gate check", the columns gathered from the witness (on an
-    R1csCircuit from the extended one) and the gate equation row by row: a witness that fails names the first row."""
+COUNT_WORDS = {9: "nine", 14: "fourteen"}
+
+
+def witness_columns(key, witness, blinding, _wires, who, keep, mark=lambda name: None, n_blinders=9):
+    """what prove() takes -> (the three value columns on H, PI's values, the public inputs, the nine blinders; n_blinders of them for a
+    protocol that blinds more polynomials).  Every refusal of the witness and of the blinders on the host first; then, between the marks
+    "start" and "gate check", the columns gathered from the witness (on an R1csCircuit from the extended one) and the gate equation row by
+    row: a witness that fails names the first row."""
     cv, n, c = key.curve, key.n, key.circuit
     r = FR[cv]
     from_r1cs = isinstance(c, R1csCircuit) and _wires is None
@@ -515,11 +520,11 @@ def witness_columns(key, witness, blinding, _wires, who, keep, mark=lambda name:
         if len(ww) != c.n_vars:
             raise ZkError("%s: the witness has %d values, the circuit has %d variables" % (who, len(ww), c.n_vars))
     if blinding is None:
-        bs = [secrets.randbelow(r) for _ in range(9)]
+        bs = [secrets.randbelow(r) for _ in range(n_blinders)]
     else:
         bs = [int(b) for b in blinding]
-        if len(bs) != 9 or not all(0 <= b < r for b in bs):
-            raise ZkError("%s: blinding takes nine integers below the scalar field's modulus" % who)
+        if len(bs) != n_blinders or not all(0 <= b < r for b in bs):
+            raise ZkError("%s: blinding takes %s integers below the scalar field's modulus" % (who, COUNT_WORDS.get(n_blinders, str(n_blinders))))
     publics = [int_of(ww[v]) for v in c.public]
     mark("start")
     if _wires is not None:

@@ -957,6 +957,8 @@ int zk_kzg_multi_verify_dev(zk_kzg_t* k, const void* d_proofs, uint64_t bytes, u
  * zk_fr_<curve>_prefix_product_dev: out[i] = prod_{j < i} in[j] (inclusive = 0, so out[0] = 1) or prod_{j <= i} in[j]; total_out = prod in.
  *   d_out == NULL: the total alone.  n = 0: total 1.  d_out may be d_in.  A zero element is an ordinary value.  A tiled scan:
  *   zk_frpoly_tile_elems() elements per workgroup, the tile aggregates combined by one workgroup that walks them zk_frpoly_span() at a time.
+ * zk_fr_<curve>_prefix_sum_dev: out[i] = sum_{j < i} in[j] (inclusive = 0, so out[0] = 0) or sum_{j <= i} in[j]; total_out = sum in.  The
+ *   same tiles and the same argument rules under addition: d_out == NULL the total alone, n = 0 total 0, d_out may be d_in.
  * zk_fr_<curve>_batch_inverse_dev: out[i] = 1 / in[i]; a zero stays zero and does not disturb its neighbours.  n_zero, first_zero (HOST,
  *   either may be NULL): how many zeros, the index of the first (UINT64_MAX when none).  d_out may be d_in.  One inversion per tile.
  * zk_fr_<curve>_pointwise_dev: out[i] = a[i] op b[i], op one of ZK_FR_MUL, ZK_FR_ADD, ZK_FR_SUB; d_out may be either operand.
@@ -982,6 +984,8 @@ uint64_t zk_frpoly_tile_elems(void);
 uint64_t zk_frpoly_span(void);
 int zk_fr_bn254_prefix_product_dev(const uint64_t* d_in, uint64_t n, int inclusive, uint64_t* d_out, uint64_t* total_out, void* stream);
 int zk_fr_bls12_381_prefix_product_dev(const uint64_t* d_in, uint64_t n, int inclusive, uint64_t* d_out, uint64_t* total_out, void* stream);
+int zk_fr_bn254_prefix_sum_dev(const uint64_t* d_in, uint64_t n, int inclusive, uint64_t* d_out, uint64_t* total_out, void* stream);
+int zk_fr_bls12_381_prefix_sum_dev(const uint64_t* d_in, uint64_t n, int inclusive, uint64_t* d_out, uint64_t* total_out, void* stream);
 int zk_fr_bn254_batch_inverse_dev(const uint64_t* d_in, uint64_t n, uint64_t* d_out, uint64_t* n_zero, uint64_t* first_zero, void* stream);
 int zk_fr_bls12_381_batch_inverse_dev(const uint64_t* d_in, uint64_t n, uint64_t* d_out, uint64_t* n_zero, uint64_t* first_zero, void* stream);
 int zk_fr_bn254_pointwise_dev(int op, const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_out, uint64_t n, void* stream);
@@ -1020,7 +1024,7 @@ int zk_fr_bls12_381_divide_zh_coset_dev(uint64_t* d_evals, uint32_t log_m, uint3
  *   q_L a + q_R b + q_O c + q_M a b + q_C + PI != 0, exact; first_bad (HOST): the first of them, UINT64_MAX when none.  Waits for the stream.
  * zk_fr_<curve>_gather_dev: out[i] = src[idx[i]] for i < n; d_idx: n uint32 on the device; d_out overlaps no source element.  An index that is
  *   not below n_src reads nothing and leaves zero; the call then fails with their number and the first position.  Waits for the stream.
- * Not built: a linearisation polynomial, custom gates, lookups, the split of the quotient, a one-call C prover.                            */
+ * Not built: a linearisation polynomial, custom gates, the split of the quotient, a one-call C prover.  Lookups: the section after fflonk's. */
 #define ZK_PLONK_QUOTIENT_COLS 15
 #define ZK_PLONK_GATE_COLS 9
 int zk_plonk_bn254_quotient_dev(const uint64_t* const* d_cols, uint32_t log_n, const uint64_t* alpha, const uint64_t* beta, const uint64_t* gamma,
@@ -1049,6 +1053,54 @@ int zk_fflonk_bn254_quotients_dev(const uint64_t* const* d_cols, uint32_t log_n,
                                   const uint64_t* k2, uint64_t* d_out0, uint64_t* d_out1, uint64_t* d_out2, void* stream);
 int zk_fflonk_bls12_381_quotients_dev(const uint64_t* const* d_cols, uint32_t log_n, const uint64_t* beta, const uint64_t* gamma, const uint64_t* k1,
                                       const uint64_t* k2, uint64_t* d_out0, uint64_t* d_out1, uint64_t* d_out2, void* stream);
+
+/* ---- The device side of PLONK's lookup argument (csrc/plonk_lookup_impl.hip.h) -------------------------------------------
+ * What the prover of eigen_zkvm_amd/plonk_lookup.py adds: the log-derivative argument.  A row of the gate table with q_K = 1 claims that
+ * (a, b, c) is a row (t1, t2, t3) of a table; with f = a + eta b + eta^2 c, t = t1 + eta t2 + eta^2 t3 and m_j the number of selected rows
+ * that equal table row j, the claim holds exactly when sum_i q_K,i / (delta + f_i) = sum_j m_j / (delta + t_j) for random eta, delta.
+ * Vectors, scalars and <curve> as for the polynomial layer; every output vector canonical; results are integers of the field, the same on
+ * every run.  The running sum is zk_fr_<curve>_prefix_sum_dev, the inverses are zk_fr_<curve>_batch_inverse_dev.
+ * zk_plonk_<curve>_lookup_table_new: the T >= 1 rows (d_t1[j], d_t2[j], d_t3[j]) as an open-addressing hash table on the device; NULL +
+ *   zk_last_error() on failure; T > ZK_PLONK_LOOKUP_MAX_ROWS is refused.  The key of a row is the CANONICAL value of its three elements: the
+ *   encodings v and v + r are one key.  The hash is FNV-1a over the 24 u32 words of the canonical Montgomery representatives of t1, t2, t3
+ *   (h = 0x811c9dc5; h = (h ^ word) * 0x01000193), then h ^= h >> 16; the slot is h & (slots - 1), slots the smallest power of two >= 2T;
+ *   a collision walks to the next slot and wraps.  A slot is claimed by atomicCAS and keeps the SMALLEST row index of its key (atomicMin).
+ *   The columns are read during the call's launches only; the handle is read-only afterwards and is freed by ..._lookup_table_free.
+ * zk_plonk_<curve>_lookup_count_dev: one lane per row i < n.  A row whose q_K is not zero looks (a_i, b_i, c_i) up and adds 1 to the counter
+ *   of the table row it finds (the smallest index of that key); d_m_out[j] (n elements, T <= n) receives the count of table row j as a field
+ *   element, 0 from T on.  n_bad (HOST): the selected rows that are no row of the table, exact; first_bad (HOST): the first of them,
+ *   UINT64_MAX when none.  The lanes of a wave that hit one counter are combined before the global atomic.  Waits for the stream.
+ * zk_plonk_<curve>_lookup_terms_dev: d_cols: a HOST array of ZK_PLONK_LOOKUP_TERMS_COLS (6) device pointers to n elements each: a, b, c, t1,
+ *   t2, t3.  d_out[i] = delta + a + eta b + eta^2 c and d_out[n + i] = delta + t1 + eta t2 + eta^2 t3 at row i: 2n elements, overlapping no
+ *   column.
+ * zk_plonk_<curve>_lookup_summands_dev: d_out[i] = q_K[i] inv[i] - m[i] inv[n + i]; d_inv holds 2n elements (the inverses of the terms);
+ *   d_out (n elements) overlaps no input.
+ * zk_plonk_<curve>_lookup_quotient_dev: on the coset 7 H_m, m = 4n = 4 2^log_n.  d_cols: a HOST array of ZK_PLONK_LOOKUP_QUOTIENT_COLS (9)
+ *   device pointers to m elements each: a, b, c, q_K, t1, t2, t3, M, Phi.  With f and t as above at element i,
+ *     d_acc[i] = d_acc[i] + alpha^3 ((Phi[(i + 4) mod m] - Phi[i]) (delta + f)(delta + t) - q_K (delta + t) + M (delta + f))
+ *   in place, canonical on the way out; d_acc overlaps no column.  It runs after zk_plonk_<curve>_quotient_dev on that call's output and
+ *   before the division by Z_H.  One lane per element, one launch.
+ * Not built: tables of more or fewer than three columns, several tables in one circuit, lookups under fflonk, a one-call C prover.       */
+#define ZK_PLONK_LOOKUP_TERMS_COLS 6
+#define ZK_PLONK_LOOKUP_QUOTIENT_COLS 9
+#define ZK_PLONK_LOOKUP_MAX_ROWS 1073741824
+typedef struct zk_plonk_lookup_table zk_plonk_lookup_table_t;
+zk_plonk_lookup_table_t* zk_plonk_bn254_lookup_table_new(const uint64_t* d_t1, const uint64_t* d_t2, const uint64_t* d_t3, uint64_t T, void* stream);
+zk_plonk_lookup_table_t* zk_plonk_bls12_381_lookup_table_new(const uint64_t* d_t1, const uint64_t* d_t2, const uint64_t* d_t3, uint64_t T, void* stream);
+int zk_plonk_bn254_lookup_table_free(zk_plonk_lookup_table_t* table);
+int zk_plonk_bls12_381_lookup_table_free(zk_plonk_lookup_table_t* table);
+int zk_plonk_bn254_lookup_count_dev(const zk_plonk_lookup_table_t* table, const uint64_t* d_a, const uint64_t* d_b, const uint64_t* d_c, const uint64_t* d_qK, uint64_t n,
+                                    uint64_t* d_m_out, uint64_t* n_bad, uint64_t* first_bad, void* stream);
+int zk_plonk_bls12_381_lookup_count_dev(const zk_plonk_lookup_table_t* table, const uint64_t* d_a, const uint64_t* d_b, const uint64_t* d_c, const uint64_t* d_qK, uint64_t n,
+                                        uint64_t* d_m_out, uint64_t* n_bad, uint64_t* first_bad, void* stream);
+int zk_plonk_bn254_lookup_terms_dev(const uint64_t* const* d_cols, uint64_t n, const uint64_t* eta, const uint64_t* delta, uint64_t* d_out, void* stream);
+int zk_plonk_bls12_381_lookup_terms_dev(const uint64_t* const* d_cols, uint64_t n, const uint64_t* eta, const uint64_t* delta, uint64_t* d_out, void* stream);
+int zk_plonk_bn254_lookup_summands_dev(const uint64_t* d_inv, const uint64_t* d_qK, const uint64_t* d_m, uint64_t n, uint64_t* d_out, void* stream);
+int zk_plonk_bls12_381_lookup_summands_dev(const uint64_t* d_inv, const uint64_t* d_qK, const uint64_t* d_m, uint64_t n, uint64_t* d_out, void* stream);
+int zk_plonk_bn254_lookup_quotient_dev(const uint64_t* const* d_cols, uint32_t log_n, const uint64_t* alpha, const uint64_t* eta, const uint64_t* delta, uint64_t* d_acc,
+                                       void* stream);
+int zk_plonk_bls12_381_lookup_quotient_dev(const uint64_t* const* d_cols, uint32_t log_n, const uint64_t* alpha, const uint64_t* eta, const uint64_t* delta, uint64_t* d_acc,
+                                           void* stream);
 
 /* ---- The R1CS import of the PLONK prover (csrc/plonk_r1cs_impl.hip.h) -----------------------------------------------------
  * A circom .r1cs over the curve's scalar field compiled to the gate table the prover takes, and the values of the auxiliary variables that

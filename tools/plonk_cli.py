@@ -1,4 +1,4 @@
-"""The command-line body that tools/zkgpu_plonk.py and tools/zkgpu_fflonk.py share: <prefix>_setup, <prefix>_prove, <prefix>_verify on files, for
+"""The command-line body that tools/zkgpu_plonk.py, tools/zkgpu_fflonk.py and tools/zkgpu_plonk_lookup.py share: <prefix>_setup, <prefix>_prove, <prefix>_verify on files, for
 a prover over eigen_zkvm_amd.plonk_arith.  A tool is a Tool record and delegates; its own docstring says what its files hold."""
 import argparse, collections, importlib, json, pathlib
 
@@ -24,9 +24,16 @@ def split_pair(tool, text):
     return parts[0], parts[1]
 
 
+def refuse_r1cs(tool, mod, a):
+    """a prover whose module names its own circuit class (CIRCUIT) proves gate tables only: --r1cs is refused with one line"""
+    if a.r1cs is not None and hasattr(mod, "CIRCUIT"):
+        print("%s: %s takes no --r1cs: a circuit compiled from an .r1cs has no lookups (tools/zkgpu_plonk.py proves it)" % (tool.name, a.cmd))
+        raise SystemExit(1)
+
+
 def _key(tool, mod, h, curve, a):
     try:
-        circuit = mod.R1csCircuit(pathlib.Path(a.r1cs).read_bytes(), curve) if a.r1cs is not None else mod.Circuit.load(a.circuit, curve)
+        circuit = mod.R1csCircuit(pathlib.Path(a.r1cs).read_bytes(), curve) if a.r1cs is not None else getattr(mod, getattr(mod, "CIRCUIT", "Circuit")).load(a.circuit, curve)
         return getattr(mod, tool.key)(h, circuit)
     except mod.ZkError as e:
         print("%s: %s" % (tool.name, e))
@@ -117,4 +124,6 @@ def main(tool, argv=None):
     a = ap.parse_args(argv)
     if a.cmd == tool.prefix + "_prove" and (a.r1cs is None) != (a.wtns is None):
         ap.error("--circuit goes with --witness, --r1cs with --wtns")
+    if getattr(a, "r1cs", None) is not None:
+        refuse_r1cs(tool, importlib.import_module(tool.module), a)
     return a.fn(a)
