@@ -80,6 +80,7 @@ EXPORTS = [
      ] + ["zk_plonk_%s_lookup_%s" % (c, f) for c in ("bn254", "bls12_381") for f in ("table_new", "table_free", "count_dev", "terms_dev", "summands_dev", "quotient_dev")
      ] + [n % c for c in ("bn254", "bls12_381") for n in ("zk_plonk_%s_quotient_dev", "zk_plonk_%s_gate_check_dev", "zk_fr_%s_gather_dev")
      ] + ["zk_fflonk_%s_quotients_dev" % c for c in ("bn254", "bls12_381")
+     ] + ["zk_fflonk_%s_lookup_quotients_dev" % c for c in ("bn254", "bls12_381")
      ] + ["zk_plonk_r1cs_wave_min_terms"] + ["zk_plonk_%s_r1cs_%s" % (c, f) for c in ("bn254", "bls12_381") for f in ("new", "info", "tables", "extend_dev", "free")]
 
 # include/zkgpu.h enums
@@ -447,6 +448,8 @@ def _load():
             "zk_plonk_%s_lookup_terms_dev" % c: (C.c_int, [vp, C.c_uint64, vp, vp, vp, vp]),
             "zk_plonk_%s_lookup_summands_dev" % c: (C.c_int, [vp, vp, vp, C.c_uint64, vp, vp]),
             "zk_plonk_%s_lookup_quotient_dev" % c: (C.c_int, [vp, C.c_uint32, vp, vp, vp, vp, vp]),
+            # the device side of the fflonk prover with lookups (fflonk_lookup.py)
+            "zk_fflonk_%s_lookup_quotients_dev" % c: (C.c_int, [vp, C.c_uint32] + [vp] * 11),
         })
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -481,6 +484,9 @@ def __getattr__(name):
     if name in ("LookupCircuit", "LookupKey"):   # plonk_lookup.py (the PLONK prover and verifier with the log-derivative lookup argument)
         import importlib
         return getattr(importlib.import_module(__name__ + ".plonk_lookup"), name)
+    if name == "FflonkLookupKey":   # fflonk_lookup.py (the fflonk prover and verifier with the lookup argument on interleaved commitments)
+        import importlib
+        return importlib.import_module(__name__ + ".fflonk_lookup").FflonkLookupKey
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 

@@ -144,6 +144,13 @@ struct PlonkLookupOps {
     void (*quotient_dev)(const u64* const* d_cols, u32 log_n, const u64* alpha, const u64* eta, const u64* delta, u64* d_acc, hipStream_t st);
 };
 const PlonkLookupOps& plonk_lookup_ops(CurveId id);
+// ---- groth16.hip: the device side of the fflonk prover with lookups (fflonk_lookup_impl.hip.h): the four numerators of the
+// identity apart, in one launch.  What include/zkgpu.h states for zk_fflonk_<curve>_lookup_quotients_dev holds for it
+struct FflonkLookupOps {
+    void (*quotients_dev)(const u64* const* d_cols, u32 log_n, const u64* beta, const u64* gamma, const u64* k1, const u64* k2, const u64* eta, const u64* delta, u64* d_out0, u64* d_out1,
+                          u64* d_out2, u64* d_out3, hipStream_t st);
+};
+const FflonkLookupOps& fflonk_lookup_ops(CurveId id);
 constexpr uint64_t PLONK_R1CS_WAVE_MIN_TERMS = 64;   // a segment of this many terms or more is walked by a whole wave (plonk_r1cs_impl.hip.h)
 // ---- pairing.hip: the steps of the optimal ate pairing and of Groth16 verification (pairing_impl.hip.h)
 struct PairingOps {
@@ -210,6 +217,7 @@ struct Curve {
     const PlonkOps& plonk() const { return plonk_ops(id); }
     const FflonkOps& fflonk() const { return fflonk_ops(id); }
     const PlonkLookupOps& plonk_lookup() const { return plonk_lookup_ops(id); }
+    const FflonkLookupOps& fflonk_lookup() const { return fflonk_lookup_ops(id); }
 };
 inline const Curve CURVES[2] = {
     {CURVE_BN254, "BN128", "bn254", 8, {0xf0000001u, 0x43e1f593u, 0x79b97091u, 0x2833e848u, 0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u}},

@@ -13,7 +13,8 @@
 // PLONK prover (plonk_impl.hip.h, DESIGN.md 3.21: the fused numerator of the quotient, the gate check, the gather) and its R1CS import
 // (plonk_r1cs_impl.hip.h, DESIGN.md 3.22: the compile rule on the host, the auxiliary variables of a witness on the device), and the
 // fflonk prover's three numerators in one launch (fflonk_impl.hip.h), and the lookup argument of the PLONK prover
-// (plonk_lookup_impl.hip.h, DESIGN.md 3.24: the running sum, the hash table and the count, the denominators, the summand, the quotient's term).
+// (plonk_lookup_impl.hip.h, DESIGN.md 3.24: the running sum, the hash table and the count, the denominators, the summand, the quotient's term),
+// and the four numerators of the fflonk prover with lookups in one launch (fflonk_lookup_impl.hip.h).
 //   proof.json       groth16/src/json_utils.rs:305-315
 // Key generation (`zkit groth16_setup`, groth16/src/api.rs:42-66) over the same circuit: groth16_keygen_impl.hip.h with a trapdoor,
 // groth16_srs.hip.h from a powers-of-tau file (and the contributions to such a key).
@@ -309,6 +310,7 @@ namespace bn254fr {
 #include "plonk_impl.hip.h"
 #include "plonk_lookup_impl.hip.h"
 #include "fflonk_impl.hip.h"
+#include "fflonk_lookup_impl.hip.h"
 #include "plonk_r1cs_impl.hip.h"
 #include "groth16_impl.hip.h"
 #include "groth16_keygen_impl.hip.h"
@@ -332,6 +334,7 @@ namespace bls12381fr {
 #include "plonk_impl.hip.h"
 #include "plonk_lookup_impl.hip.h"
 #include "fflonk_impl.hip.h"
+#include "fflonk_lookup_impl.hip.h"
 #include "plonk_r1cs_impl.hip.h"
 #include "groth16_impl.hip.h"
 #include "groth16_keygen_impl.hip.h"
@@ -363,6 +366,11 @@ const PlonkOps& plonk_ops(CurveId id) {       // plonk_impl.hip.h and plonk_r1cs
 
 const FflonkOps& fflonk_ops(CurveId id) {     // fflonk_impl.hip.h, per scalar field
     static const FflonkOps OPS[2] = {{bn254fr::ff_quotients_dev}, {bls12381fr::ff_quotients_dev}};
+    return OPS[id];
+}
+
+const FflonkLookupOps& fflonk_lookup_ops(CurveId id) {   // fflonk_lookup_impl.hip.h, per scalar field
+    static const FflonkLookupOps OPS[2] = {{bn254fr::fl_quotients_dev}, {bls12381fr::fl_quotients_dev}};
     return OPS[id];
 }
 

@@ -1102,6 +1102,27 @@ int zk_plonk_bn254_lookup_quotient_dev(const uint64_t* const* d_cols, uint32_t l
 int zk_plonk_bls12_381_lookup_quotient_dev(const uint64_t* const* d_cols, uint32_t log_n, const uint64_t* alpha, const uint64_t* eta, const uint64_t* delta, uint64_t* d_acc,
                                            void* stream);
 
+/* ---- The device side of the fflonk prover with lookups (csrc/fflonk_lookup_impl.hip.h) -----------------------------------
+ * The one kernel the prover of eigen_zkvm_amd/fflonk_lookup.py adds -- that module is where the log-derivative argument lives under fflonk:
+ * the lookup term is a fourth quotient there, so its numerator leaves the launch beside the three of zk_fflonk_<curve>_quotients_dev, with
+ * a, b, c read once for all four.  Vectors, scalars and <curve> as above.  d_cols: a HOST array of ZK_FFLONK_LOOKUP_QUOTIENT_COLS (21) device
+ * pointers to m = 4n = 4 2^log_n elements each, on the coset 7 H_m: the ZK_PLONK_QUOTIENT_COLS columns in their order, then q_K, t1, t2, t3,
+ * M, Phi.  At element i of every column, with f = a + eta b + eta^2 c and t = t1 + eta t2 + eta^2 t3,
+ *   d_out0[i], d_out1[i], d_out2[i] = exactly zk_fflonk_<curve>_quotients_dev's
+ *   d_out3[i] = (Phi[(i + 4) mod m] - Phi[i]) (delta + f)(delta + t) - q_K (delta + t) + M (delta + f)
+ * every one canonical.  An output may be NULL (not all four): that part is not computed and the columns it alone reads are not read, though
+ * every column pointer must still be valid.  An output (m elements each) overlaps no column and no other output; a scalar that is not below r
+ * and log_n + 2 beyond the field's 2-adicity are refused before any device work.  One lane per element, one launch; each output is then
+ * divided by Z_H with zk_fr_<curve>_divide_zh_coset_dev(d_out, log_n + 2, log_n).
+ * Not built: a one-call C prover, tables of another width, several tables in one circuit.                                              */
+#define ZK_FFLONK_LOOKUP_QUOTIENT_COLS 21
+int zk_fflonk_bn254_lookup_quotients_dev(const uint64_t* const* d_cols, uint32_t log_n, const uint64_t* beta, const uint64_t* gamma, const uint64_t* k1,
+                                         const uint64_t* k2, const uint64_t* eta, const uint64_t* delta, uint64_t* d_out0, uint64_t* d_out1, uint64_t* d_out2,
+                                         uint64_t* d_out3, void* stream);
+int zk_fflonk_bls12_381_lookup_quotients_dev(const uint64_t* const* d_cols, uint32_t log_n, const uint64_t* beta, const uint64_t* gamma, const uint64_t* k1,
+                                             const uint64_t* k2, const uint64_t* eta, const uint64_t* delta, uint64_t* d_out0, uint64_t* d_out1, uint64_t* d_out2,
+                                             uint64_t* d_out3, void* stream);
+
 /* ---- The R1CS import of the PLONK prover (csrc/plonk_r1cs_impl.hip.h) -----------------------------------------------------
  * A circom .r1cs over the curve's scalar field compiled to the gate table the prover takes, and the values of the auxiliary variables that
  * table adds, computed on the device from the witness at every proof.
