@@ -78,6 +78,7 @@ EXPORTS = [
 ] + ["zk_fr_%s_%s_dev" % (c, f) for c in ("bn254", "bls12_381")
      for f in ("prefix_product", "prefix_sum", "batch_inverse", "pointwise", "powers", "terms", "grand_product", "poly_mul", "divmod_zh", "divide_zh_coset")
      ] + ["zk_plonk_%s_lookup_%s" % (c, f) for c in ("bn254", "bls12_381") for f in ("table_new", "table_free", "count_dev", "terms_dev", "summands_dev", "quotient_dev")
+     ] + ["zk_plonk_%s_lookup_tagged_%s" % (c, f) for c in ("bn254", "bls12_381") for f in ("table_new", "count_dev", "terms_dev", "quotient_dev")
      ] + [n % c for c in ("bn254", "bls12_381") for n in ("zk_plonk_%s_quotient_dev", "zk_plonk_%s_gate_check_dev", "zk_fr_%s_gather_dev")
      ] + ["zk_fflonk_%s_quotients_dev" % c for c in ("bn254", "bls12_381")
      ] + ["zk_fflonk_%s_lookup_quotients_dev" % c for c in ("bn254", "bls12_381")
@@ -448,6 +449,11 @@ def _load():
             "zk_plonk_%s_lookup_terms_dev" % c: (C.c_int, [vp, C.c_uint64, vp, vp, vp, vp]),
             "zk_plonk_%s_lookup_summands_dev" % c: (C.c_int, [vp, vp, vp, C.c_uint64, vp, vp]),
             "zk_plonk_%s_lookup_quotient_dev" % c: (C.c_int, [vp, C.c_uint32, vp, vp, vp, vp, vp]),
+            # its tagged form: several tables in one circuit, the tag a fourth column
+            "zk_plonk_%s_lookup_tagged_table_new" % c: (vp, [vp, vp, vp, vp, C.c_uint64, vp]),
+            "zk_plonk_%s_lookup_tagged_count_dev" % c: (C.c_int, [vp, vp, vp, vp, vp, C.c_uint64, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp]),
+            "zk_plonk_%s_lookup_tagged_terms_dev" % c: (C.c_int, [vp, C.c_uint64, vp, vp, vp, vp]),
+            "zk_plonk_%s_lookup_tagged_quotient_dev" % c: (C.c_int, [vp, C.c_uint32, vp, vp, vp, vp, vp]),
             # the device side of the fflonk prover with lookups (fflonk_lookup.py)
             "zk_fflonk_%s_lookup_quotients_dev" % c: (C.c_int, [vp, C.c_uint32] + [vp] * 11),
         })

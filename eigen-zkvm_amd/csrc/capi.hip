@@ -1025,7 +1025,7 @@ ZK_PLONK_API(bls12_381, CURVE_BLS12_381)
 ZK_FFLONK_API(bn254, CURVE_BN254)
 ZK_FFLONK_API(bls12_381, CURVE_BLS12_381)
 #undef ZK_FFLONK_API
-// ---- the device side of PLONK's lookup argument (plonk_lookup_impl.hip.h through groth16.hip) ----
+// ---- the device side of PLONK's lookup argument (plonk_lookup_impl.hip.h and plonk_lookup_tagged_impl.hip.h through groth16.hip) ----
 static const zk_plonk_lookup_table_t& plonk_lookup_table_of(const zk_plonk_lookup_table_t* h, CurveId id) {
     ZK_REQUIRE(h, "plonk lookup: null table");
     ZK_REQUIRE(h->curve == &curve(id), "plonk lookup: the table is over another field");
@@ -1057,9 +1057,36 @@ static const zk_plonk_lookup_table_t& plonk_lookup_table_of(const zk_plonk_looku
             curve(ID).plonk_lookup().quotient_dev((const u64* const*)d_cols, log_n, (const u64*)alpha, (const u64*)eta, (const u64*)delta, (u64*)d_acc, on_stream((hipStream_t)stream)); \
         });                                                                                                                                   \
     }
+#define ZK_PLONK_LOOKUP_TAGGED_API(NAME, ID)                                                                                                  \
+    zk_plonk_lookup_table_t* zk_plonk_##NAME##_lookup_tagged_table_new(const uint64_t* d_t0, const uint64_t* d_t1, const uint64_t* d_t2, const uint64_t* d_t3, uint64_t T, \
+                                                                       void* stream) {                                                        \
+        zk_plonk_lookup_table_t* out = nullptr;                                                                                               \
+        guard([&] { out = curve(ID).plonk_lookup().tagged_table_new((const u64*)d_t0, (const u64*)d_t1, (const u64*)d_t2, (const u64*)d_t3, T, on_stream((hipStream_t)stream)); }); \
+        return out;                                                                                                                           \
+    }                                                                                                                                         \
+    int zk_plonk_##NAME##_lookup_tagged_count_dev(const zk_plonk_lookup_table_t* table, const uint64_t* d_a, const uint64_t* d_b, const uint64_t* d_c, const uint64_t* d_qK, \
+                                                  uint64_t n, uint64_t* d_m_out, uint64_t* n_bad, uint64_t* first_bad, void* stream) {        \
+        return guard([&] {                                                                                                                    \
+            curve(ID).plonk_lookup().tagged_count_dev(plonk_lookup_table_of(table, ID), (const u64*)d_a, (const u64*)d_b, (const u64*)d_c, (const u64*)d_qK, n, (u64*)d_m_out, \
+                                                      (u64*)n_bad, (u64*)first_bad, on_stream((hipStream_t)stream));                          \
+        });                                                                                                                                   \
+    }                                                                                                                                         \
+    int zk_plonk_##NAME##_lookup_tagged_terms_dev(const uint64_t* const* d_cols, uint64_t n, const uint64_t* eta, const uint64_t* delta, uint64_t* d_out, void* stream) { \
+        return guard([&] { curve(ID).plonk_lookup().tagged_terms_dev((const u64* const*)d_cols, n, (const u64*)eta, (const u64*)delta, (u64*)d_out, on_stream((hipStream_t)stream)); }); \
+    }                                                                                                                                         \
+    int zk_plonk_##NAME##_lookup_tagged_quotient_dev(const uint64_t* const* d_cols, uint32_t log_n, const uint64_t* alpha, const uint64_t* eta, const uint64_t* delta, \
+                                                     uint64_t* d_acc, void* stream) {                                                         \
+        return guard([&] {                                                                                                                    \
+            curve(ID).plonk_lookup().tagged_quotient_dev((const u64* const*)d_cols, log_n, (const u64*)alpha, (const u64*)eta, (const u64*)delta, (u64*)d_acc, \
+                                                         on_stream((hipStream_t)stream));                                                     \
+        });                                                                                                                                   \
+    }
 ZK_PLONK_LOOKUP_API(bn254, CURVE_BN254)
 ZK_PLONK_LOOKUP_API(bls12_381, CURVE_BLS12_381)
 #undef ZK_PLONK_LOOKUP_API
+ZK_PLONK_LOOKUP_TAGGED_API(bn254, CURVE_BN254)
+ZK_PLONK_LOOKUP_TAGGED_API(bls12_381, CURVE_BLS12_381)
+#undef ZK_PLONK_LOOKUP_TAGGED_API
 // ---- the device side of the fflonk prover with lookups (fflonk_lookup_impl.hip.h through groth16.hip) ----
 #define ZK_FFLONK_LOOKUP_API(NAME, ID)                                                                                                        \
     int zk_fflonk_##NAME##_lookup_quotients_dev(const uint64_t* const* d_cols, uint32_t log_n, const uint64_t* beta, const uint64_t* gamma, const uint64_t* k1, \

@@ -142,6 +142,11 @@ struct PlonkLookupOps {
     void (*terms_dev)(const u64* const* d_cols, u64 n, const u64* eta, const u64* delta, u64* d_out, hipStream_t st);
     void (*summands_dev)(const u64* d_inv, const u64* d_qk, const u64* d_m, u64 n, u64* d_out, hipStream_t st);
     void (*quotient_dev)(const u64* const* d_cols, u32 log_n, const u64* alpha, const u64* eta, const u64* delta, u64* d_acc, hipStream_t st);
+    // the tagged argument (plonk_lookup_tagged_impl.hip.h): several tables, a fourth column T0 / q_K; zk_plonk_<curve>_lookup_tagged_*
+    PlonkLookupTable* (*tagged_table_new)(const u64* d_t0, const u64* d_t1, const u64* d_t2, const u64* d_t3, u64 T, hipStream_t st);
+    void (*tagged_count_dev)(const PlonkLookupTable& h, const u64* d_a, const u64* d_b, const u64* d_c, const u64* d_qk, u64 n, u64* d_m_out, u64* n_bad, u64* first_bad, hipStream_t st);
+    void (*tagged_terms_dev)(const u64* const* d_cols, u64 n, const u64* eta, const u64* delta, u64* d_out, hipStream_t st);
+    void (*tagged_quotient_dev)(const u64* const* d_cols, u32 log_n, const u64* alpha, const u64* eta, const u64* delta, u64* d_acc, hipStream_t st);
 };
 const PlonkLookupOps& plonk_lookup_ops(CurveId id);
 // ---- groth16.hip: the device side of the fflonk prover with lookups (fflonk_lookup_impl.hip.h): the four numerators of the
@@ -396,6 +401,8 @@ struct zk_plonk_lookup_table {   // the rows of a lookup table as a hash table o
     const zk::Curve* curve = nullptr;
     uint64_t n_rows = 0, n_slots = 0;                // n_slots: the smallest power of two >= 2 n_rows
     zk::DevBuf d_keys, d_slots;                      // per row: the 24 canonical Montgomery words of its key; per slot: a row or 0xffffffff
+    bool tagged = false;                             // a tagged table (plonk_lookup_tagged_impl.hip.h): keys of 32 words, the tag first
+    zk::DevBuf d_tags;                               // tagged: per row, its tag 1 .. 65535 as a u32
     zk_plonk_lookup_table() = default; zk_plonk_lookup_table(const zk_plonk_lookup_table&) = delete; zk_plonk_lookup_table& operator=(const zk_plonk_lookup_table&) = delete;
 };
 struct zk_groth16_vk {       // a verification key, checked and prepared

@@ -14,6 +14,7 @@
 // (plonk_r1cs_impl.hip.h, DESIGN.md 3.22: the compile rule on the host, the auxiliary variables of a witness on the device), and the
 // fflonk prover's three numerators in one launch (fflonk_impl.hip.h), and the lookup argument of the PLONK prover
 // (plonk_lookup_impl.hip.h, DESIGN.md 3.24: the running sum, the hash table and the count, the denominators, the summand, the quotient's term),
+// the tagged form of that argument for several tables (plonk_lookup_tagged_impl.hip.h),
 // and the four numerators of the fflonk prover with lookups in one launch (fflonk_lookup_impl.hip.h).
 //   proof.json       groth16/src/json_utils.rs:305-315
 // Key generation (`zkit groth16_setup`, groth16/src/api.rs:42-66) over the same circuit: groth16_keygen_impl.hip.h with a trapdoor,
@@ -309,6 +310,7 @@ namespace bn254fr {
 #include "frpoly_impl.hip.h"
 #include "plonk_impl.hip.h"
 #include "plonk_lookup_impl.hip.h"
+#include "plonk_lookup_tagged_impl.hip.h"
 #include "fflonk_impl.hip.h"
 #include "fflonk_lookup_impl.hip.h"
 #include "plonk_r1cs_impl.hip.h"
@@ -333,6 +335,7 @@ namespace bls12381fr {
 #include "frpoly_impl.hip.h"
 #include "plonk_impl.hip.h"
 #include "plonk_lookup_impl.hip.h"
+#include "plonk_lookup_tagged_impl.hip.h"
 #include "fflonk_impl.hip.h"
 #include "fflonk_lookup_impl.hip.h"
 #include "plonk_r1cs_impl.hip.h"
@@ -374,8 +377,9 @@ const FflonkLookupOps& fflonk_lookup_ops(CurveId id) {   // fflonk_lookup_impl.h
     return OPS[id];
 }
 
-const PlonkLookupOps& plonk_lookup_ops(CurveId id) {   // plonk_lookup_impl.hip.h, per scalar field
-#define ZK_PLONK_LOOKUP_OPS(NS) {NS::pl_table_new, NS::pl_count_dev, NS::pl_terms_dev, NS::pl_summands_dev, NS::pl_quotient_dev}
+const PlonkLookupOps& plonk_lookup_ops(CurveId id) {   // plonk_lookup_impl.hip.h and plonk_lookup_tagged_impl.hip.h, per scalar field
+#define ZK_PLONK_LOOKUP_OPS(NS) {NS::pl_table_new, NS::pl_count_dev, NS::pl_terms_dev, NS::pl_summands_dev, NS::pl_quotient_dev, \
+                                 NS::plt_table_new, NS::plt_count_dev, NS::plt_terms_dev, NS::plt_quotient_dev}
     static const PlonkLookupOps OPS[2] = {ZK_PLONK_LOOKUP_OPS(bn254fr), ZK_PLONK_LOOKUP_OPS(bls12381fr)};
 #undef ZK_PLONK_LOOKUP_OPS
     return OPS[id];

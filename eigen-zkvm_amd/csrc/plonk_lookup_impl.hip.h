@@ -2,7 +2,9 @@
 // argument of eigen_zkvm_amd/plonk_lookup.py.  A running SUM beside frpoly_impl.hip.h's running product, a hash table over the table's rows
 // and the count of how often each is used, the two denominators of a row, the summand of the sum, and the term alpha^3 L the quotient gains.
 // Included by groth16.hip after plonk_impl.hip.h, in the same namespace: it uses frpoly_impl.hip.h's word helpers and host checks and
-// plonk_impl.hip.h's pk_plain / pk_internal / pk_scalar / pk_apart.  No include guard on purpose.
+// plonk_impl.hip.h's pk_plain / pk_internal / pk_scalar / pk_apart.  No include guard on purpose.  Several tables in one circuit, bound by a
+// tag column, are plonk_lookup_tagged_impl.hip.h: kernels of its own over four-column keys; the summand and the running sum
+// of this file serve both.
 //
 // A vector is n x 8 u32 Montgomery words (R = 2^256), element-major; the words of an input may be any integer below 2^256 (< 6r), every
 // output word vector is the canonical representative.  Forms as in plonk_impl.hip.h: plain P(v) = fp_split(words) = v R mod r as the integer
@@ -332,6 +334,7 @@ PlonkLookupTable* FRN_FN(pl_table_new)(const u64* d_t1, const u64* d_t2, const u
 
 void FRN_FN(pl_count_dev)(const PlonkLookupTable& h, const u64* d_a, const u64* d_b, const u64* d_c, const u64* d_qk, u64 n, u64* d_m_out, u64* n_bad, u64* first_bad, hipStream_t st) {
     ZK_REQUIRE(n_bad && first_bad && ((d_a && d_b && d_c && d_qk && d_m_out) || n == 0), "plonk lookup: null argument");
+    ZK_REQUIRE(!h.tagged, "plonk lookup: count: the table is a tagged one (zk_plonk_<curve>_lookup_tagged_count_dev counts over it)");
     fp_limit(n);
     ZK_REQUIRE(n == 0 || h.n_rows <= n, "plonk lookup: count: the table has " + std::to_string(h.n_rows) + " rows, the multiplicities only " + std::to_string(n));
     u64 stat[2] = {0, ~0ull};

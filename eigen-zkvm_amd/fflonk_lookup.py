@@ -63,8 +63,9 @@ starts at 0 and only moves for a re-draw.
 Blinding.  The fourteen blinders come from `secrets`, in plonk_lookup.py's numbering; blinding=[14 integers] is FOR TESTS ONLY (all zero
 gives the unblinded proof).
 
-Not built: tables of another width than three, several tables in one circuit, lookups in a circuit compiled from an .r1cs, snarkjs's files
-or its keccak transcript, a Solidity verifier."""
+Not built: tables of another width than three, several tables in one circuit (the tagged lookups of plonk_lookup.py, DESIGN.md 3.26: the
+interleaved C0L has four slots, and a fifth polynomial T0 changes its opening sets; setup refuses a tagged circuit and says so), lookups in
+a circuit compiled from an .r1cs, snarkjs's files or its keccak transcript, a Solidity verifier."""
 import hashlib
 import json
 
@@ -285,6 +286,9 @@ class FflonkLookupKey(ArithKey):
             raise ZkError("%s: an R1csCircuit has no lookups: prove it with fflonk.py" % WHO)
         if not isinstance(circuit, LookupCircuit):
             raise ZkError("%s: the key takes a LookupCircuit" % WHO)
+        if getattr(circuit, "tagged", False):
+            raise ZkError("%s: the circuit has %d tagged tables: fflonk with lookups proves one table (C0L interleaves four polynomials and has no slot for T0); "
+                          "plonk_lookup.py proves a tagged circuit" % (WHO, len(circuit.table_sizes)))
         self.table = None
         super().__init__(kzg, circuit, WHO, ("8n + 8", required_powers(circuit.n)))
 

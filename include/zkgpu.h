@@ -1080,10 +1080,30 @@ int zk_fflonk_bls12_381_quotients_dev(const uint64_t* const* d_cols, uint32_t lo
  *     d_acc[i] = d_acc[i] + alpha^3 ((Phi[(i + 4) mod m] - Phi[i]) (delta + f)(delta + t) - q_K (delta + t) + M (delta + f))
  *   in place, canonical on the way out; d_acc overlaps no column.  It runs after zk_plonk_<curve>_quotient_dev on that call's output and
  *   before the division by Z_H.  One lane per element, one launch.
- * Not built: tables of more or fewer than three columns, several tables in one circuit, lookups under fflonk, a one-call C prover.       */
+ * Not built: tables of more or fewer than three columns, several tables in one circuit, lookups under fflonk, a one-call C prover.  (That is
+ * these five calls; several tables in one circuit are the tagged calls that follow.)
+ *
+ * TAGGED lookups (csrc/plonk_lookup_tagged_impl.hip.h): several tables in one circuit.  Table row j is (T0_j, t1_j, t2_j,
+ * t3_j), T0_j = k in 1 .. ZK_PLONK_LOOKUP_MAX_TABLES the number of its table; a gate row with q_K = k != 0 claims that (a, b, c) is a row of
+ * table k.  f = a + eta b + eta^2 c + eta^3 q_K, t = t1 + eta t2 + eta^2 t3 + eta^3 T0, m_j = T0_j x (the selected rows whose (q_K, a, b, c)
+ * equals (T0_j, t1_j, t2_j, t3_j)); the sum and the identity keep their form.  The summand and the running sum are the calls above.
+ * zk_plonk_<curve>_lookup_tagged_table_new: as ..._lookup_table_new over four columns, d_t0 the tags as field elements.  A key is the 32 words
+ *   of the canonical Montgomery representatives of T0, t1, t2, t3 in that order, hashed and stored as there: the same (t1, t2, t3) under two
+ *   tags are two keys.  A tag outside 1 .. ZK_PLONK_LOOKUP_MAX_TABLES is refused, with the first such row and their count.  Waits for the
+ *   stream.  The handle is freed by ..._lookup_table_free; ..._lookup_count_dev refuses it, as ..._lookup_tagged_count_dev refuses a plain one.
+ * zk_plonk_<curve>_lookup_tagged_count_dev: as ..._lookup_count_dev, the key of a selected row being (q_K, a, b, c): a tuple that sits only in
+ *   another table than the one q_K names is a miss.  d_m_out[j] = T0_j x the count of table row j, an integer below 2^46, as a field element.
+ * zk_plonk_<curve>_lookup_tagged_terms_dev: d_cols: ZK_PLONK_LOOKUP_TAGGED_TERMS_COLS (8) pointers: a, b, c, q_K, t1, t2, t3, T0.
+ *   d_out[i] = delta + a + eta b + eta^2 c + eta^3 q_K and d_out[n + i] = delta + t1 + eta t2 + eta^2 t3 + eta^3 T0 at row i.
+ * zk_plonk_<curve>_lookup_tagged_quotient_dev: d_cols: ZK_PLONK_LOOKUP_TAGGED_QUOTIENT_COLS (10) pointers: a, b, c, q_K, t1, t2, t3, T0, M,
+ *   Phi; d_acc as for ..._lookup_quotient_dev with the f and t of the tagged argument.
+ * Not built for the tagged calls: tables of more than three columns, tagged tables under fflonk.                                          */
 #define ZK_PLONK_LOOKUP_TERMS_COLS 6
 #define ZK_PLONK_LOOKUP_QUOTIENT_COLS 9
 #define ZK_PLONK_LOOKUP_MAX_ROWS 1073741824
+#define ZK_PLONK_LOOKUP_TAGGED_TERMS_COLS 8
+#define ZK_PLONK_LOOKUP_TAGGED_QUOTIENT_COLS 10
+#define ZK_PLONK_LOOKUP_MAX_TABLES 65535
 typedef struct zk_plonk_lookup_table zk_plonk_lookup_table_t;
 zk_plonk_lookup_table_t* zk_plonk_bn254_lookup_table_new(const uint64_t* d_t1, const uint64_t* d_t2, const uint64_t* d_t3, uint64_t T, void* stream);
 zk_plonk_lookup_table_t* zk_plonk_bls12_381_lookup_table_new(const uint64_t* d_t1, const uint64_t* d_t2, const uint64_t* d_t3, uint64_t T, void* stream);
@@ -1101,6 +1121,18 @@ int zk_plonk_bn254_lookup_quotient_dev(const uint64_t* const* d_cols, uint32_t l
                                        void* stream);
 int zk_plonk_bls12_381_lookup_quotient_dev(const uint64_t* const* d_cols, uint32_t log_n, const uint64_t* alpha, const uint64_t* eta, const uint64_t* delta, uint64_t* d_acc,
                                            void* stream);
+zk_plonk_lookup_table_t* zk_plonk_bn254_lookup_tagged_table_new(const uint64_t* d_t0, const uint64_t* d_t1, const uint64_t* d_t2, const uint64_t* d_t3, uint64_t T, void* stream);
+zk_plonk_lookup_table_t* zk_plonk_bls12_381_lookup_tagged_table_new(const uint64_t* d_t0, const uint64_t* d_t1, const uint64_t* d_t2, const uint64_t* d_t3, uint64_t T, void* stream);
+int zk_plonk_bn254_lookup_tagged_count_dev(const zk_plonk_lookup_table_t* table, const uint64_t* d_a, const uint64_t* d_b, const uint64_t* d_c, const uint64_t* d_qK, uint64_t n,
+                                           uint64_t* d_m_out, uint64_t* n_bad, uint64_t* first_bad, void* stream);
+int zk_plonk_bls12_381_lookup_tagged_count_dev(const zk_plonk_lookup_table_t* table, const uint64_t* d_a, const uint64_t* d_b, const uint64_t* d_c, const uint64_t* d_qK, uint64_t n,
+                                               uint64_t* d_m_out, uint64_t* n_bad, uint64_t* first_bad, void* stream);
+int zk_plonk_bn254_lookup_tagged_terms_dev(const uint64_t* const* d_cols, uint64_t n, const uint64_t* eta, const uint64_t* delta, uint64_t* d_out, void* stream);
+int zk_plonk_bls12_381_lookup_tagged_terms_dev(const uint64_t* const* d_cols, uint64_t n, const uint64_t* eta, const uint64_t* delta, uint64_t* d_out, void* stream);
+int zk_plonk_bn254_lookup_tagged_quotient_dev(const uint64_t* const* d_cols, uint32_t log_n, const uint64_t* alpha, const uint64_t* eta, const uint64_t* delta, uint64_t* d_acc,
+                                              void* stream);
+int zk_plonk_bls12_381_lookup_tagged_quotient_dev(const uint64_t* const* d_cols, uint32_t log_n, const uint64_t* alpha, const uint64_t* eta, const uint64_t* delta,
+                                                  uint64_t* d_acc, void* stream);
 
 /* ---- The device side of the fflonk prover with lookups (csrc/fflonk_lookup_impl.hip.h) -----------------------------------
  * The one kernel the prover of eigen_zkvm_amd/fflonk_lookup.py adds -- that module is where the log-derivative argument lives under fflonk:

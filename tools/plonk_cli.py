@@ -80,7 +80,8 @@ def verify(tool, a):
     if vk.curve != curve:
         raise SystemExit("%s: %s is a key on %s, the file is %s" % (tool.name, a.vk, vk.curve, curve))
     pairs = [split_pair(tool, p) for p in a.pairs]
-    proofs = [mod.proof_from_json(pathlib.Path(p).read_text(), curve) for p, _ in pairs]
+    which = {"tagged": vk.tagged} if hasattr(vk, "tagged") else {}     # a prover with two protocols reads a proof as one of its key's
+    proofs = [mod.proof_from_json(pathlib.Path(p).read_text(), curve, **which) for p, _ in pairs]
     publics = [[int(x, 0) for x in json.loads(pathlib.Path(x).read_text())] for _, x in pairs]
     verdict, _ = mod.verify(vk, publics, proofs, locate=False)
     if verdict == 1:
