@@ -82,6 +82,7 @@ EXPORTS = [
      ] + [n % c for c in ("bn254", "bls12_381") for n in ("zk_plonk_%s_quotient_dev", "zk_plonk_%s_gate_check_dev", "zk_fr_%s_gather_dev")
      ] + ["zk_fflonk_%s_quotients_dev" % c for c in ("bn254", "bls12_381")
      ] + ["zk_fflonk_%s_lookup_quotients_dev" % c for c in ("bn254", "bls12_381")
+     ] + ["zk_fflonk_%s_lookup_tagged_quotients_dev" % c for c in ("bn254", "bls12_381")
      ] + ["zk_plonk_r1cs_wave_min_terms"] + ["zk_plonk_%s_r1cs_%s" % (c, f) for c in ("bn254", "bls12_381") for f in ("new", "info", "tables", "extend_dev", "free")]
 
 # include/zkgpu.h enums
@@ -456,6 +457,8 @@ def _load():
             "zk_plonk_%s_lookup_tagged_quotient_dev" % c: (C.c_int, [vp, C.c_uint32, vp, vp, vp, vp, vp]),
             # the device side of the fflonk prover with lookups (fflonk_lookup.py)
             "zk_fflonk_%s_lookup_quotients_dev" % c: (C.c_int, [vp, C.c_uint32] + [vp] * 11),
+            # and with tagged lookups (fflonk_lookup_tagged.py)
+            "zk_fflonk_%s_lookup_tagged_quotients_dev" % c: (C.c_int, [vp, C.c_uint32] + [vp] * 11),
         })
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -493,6 +496,9 @@ def __getattr__(name):
     if name == "FflonkLookupKey":   # fflonk_lookup.py (the fflonk prover and verifier with the lookup argument on interleaved commitments)
         import importlib
         return importlib.import_module(__name__ + ".fflonk_lookup").FflonkLookupKey
+    if name == "FflonkLookupTaggedKey":   # fflonk_lookup_tagged.py (fflonk with the lookup argument over several tagged tables)
+        import importlib
+        return importlib.import_module(__name__ + ".fflonk_lookup_tagged").FflonkLookupTaggedKey
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 

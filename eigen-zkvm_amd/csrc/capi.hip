@@ -1087,7 +1087,7 @@ ZK_PLONK_LOOKUP_API(bls12_381, CURVE_BLS12_381)
 ZK_PLONK_LOOKUP_TAGGED_API(bn254, CURVE_BN254)
 ZK_PLONK_LOOKUP_TAGGED_API(bls12_381, CURVE_BLS12_381)
 #undef ZK_PLONK_LOOKUP_TAGGED_API
-// ---- the device side of the fflonk prover with lookups (fflonk_lookup_impl.hip.h through groth16.hip) ----
+// ---- the device side of the fflonk prover with lookups (fflonk_lookup_impl.hip.h and fflonk_lookup_tagged_impl.hip.h through groth16.hip) ----
 #define ZK_FFLONK_LOOKUP_API(NAME, ID)                                                                                                        \
     int zk_fflonk_##NAME##_lookup_quotients_dev(const uint64_t* const* d_cols, uint32_t log_n, const uint64_t* beta, const uint64_t* gamma, const uint64_t* k1, \
                                                 const uint64_t* k2, const uint64_t* eta, const uint64_t* delta, uint64_t* d_out0, uint64_t* d_out1, uint64_t* d_out2, \
@@ -1095,6 +1095,15 @@ ZK_PLONK_LOOKUP_TAGGED_API(bls12_381, CURVE_BLS12_381)
         return guard([&] {                                                                                                                    \
             curve(ID).fflonk_lookup().quotients_dev((const u64* const*)d_cols, log_n, (const u64*)beta, (const u64*)gamma, (const u64*)k1, (const u64*)k2, (const u64*)eta, \
                                                     (const u64*)delta, (u64*)d_out0, (u64*)d_out1, (u64*)d_out2, (u64*)d_out3, on_stream((hipStream_t)stream)); \
+        });                                                                                                                                   \
+    }                                                                                                                                         \
+    int zk_fflonk_##NAME##_lookup_tagged_quotients_dev(const uint64_t* const* d_cols, uint32_t log_n, const uint64_t* beta, const uint64_t* gamma, const uint64_t* k1, \
+                                                       const uint64_t* k2, const uint64_t* eta, const uint64_t* delta, uint64_t* d_out0, uint64_t* d_out1,          \
+                                                       uint64_t* d_out2, uint64_t* d_out3, void* stream) {                                    \
+        return guard([&] {                                                                                                                    \
+            curve(ID).fflonk_lookup().tagged_quotients_dev((const u64* const*)d_cols, log_n, (const u64*)beta, (const u64*)gamma, (const u64*)k1, (const u64*)k2,    \
+                                                           (const u64*)eta, (const u64*)delta, (u64*)d_out0, (u64*)d_out1, (u64*)d_out2, (u64*)d_out3,             \
+                                                           on_stream((hipStream_t)stream));                                                   \
         });                                                                                                                                   \
     }
 ZK_FFLONK_LOOKUP_API(bn254, CURVE_BN254)

@@ -154,6 +154,9 @@ const PlonkLookupOps& plonk_lookup_ops(CurveId id);
 struct FflonkLookupOps {
     void (*quotients_dev)(const u64* const* d_cols, u32 log_n, const u64* beta, const u64* gamma, const u64* k1, const u64* k2, const u64* eta, const u64* delta, u64* d_out0, u64* d_out1,
                           u64* d_out2, u64* d_out3, hipStream_t st);
+    // the tagged form (fflonk_lookup_tagged_impl.hip.h): one more column, Tg; zk_fflonk_<curve>_lookup_tagged_quotients_dev
+    void (*tagged_quotients_dev)(const u64* const* d_cols, u32 log_n, const u64* beta, const u64* gamma, const u64* k1, const u64* k2, const u64* eta, const u64* delta, u64* d_out0,
+                                 u64* d_out1, u64* d_out2, u64* d_out3, hipStream_t st);
 };
 const FflonkLookupOps& fflonk_lookup_ops(CurveId id);
 constexpr uint64_t PLONK_R1CS_WAVE_MIN_TERMS = 64;   // a segment of this many terms or more is walked by a whole wave (plonk_r1cs_impl.hip.h)

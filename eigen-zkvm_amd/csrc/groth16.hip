@@ -15,7 +15,8 @@
 // fflonk prover's three numerators in one launch (fflonk_impl.hip.h), and the lookup argument of the PLONK prover
 // (plonk_lookup_impl.hip.h, DESIGN.md 3.24: the running sum, the hash table and the count, the denominators, the summand, the quotient's term),
 // the tagged form of that argument for several tables (plonk_lookup_tagged_impl.hip.h),
-// and the four numerators of the fflonk prover with lookups in one launch (fflonk_lookup_impl.hip.h).
+// the four numerators of the fflonk prover with lookups in one launch (fflonk_lookup_impl.hip.h),
+// and the same four with the tag column of several tables in the lookup term (fflonk_lookup_tagged_impl.hip.h).
 //   proof.json       groth16/src/json_utils.rs:305-315
 // Key generation (`zkit groth16_setup`, groth16/src/api.rs:42-66) over the same circuit: groth16_keygen_impl.hip.h with a trapdoor,
 // groth16_srs.hip.h from a powers-of-tau file (and the contributions to such a key).
@@ -313,6 +314,7 @@ namespace bn254fr {
 #include "plonk_lookup_tagged_impl.hip.h"
 #include "fflonk_impl.hip.h"
 #include "fflonk_lookup_impl.hip.h"
+#include "fflonk_lookup_tagged_impl.hip.h"
 #include "plonk_r1cs_impl.hip.h"
 #include "groth16_impl.hip.h"
 #include "groth16_keygen_impl.hip.h"
@@ -338,6 +340,7 @@ namespace bls12381fr {
 #include "plonk_lookup_tagged_impl.hip.h"
 #include "fflonk_impl.hip.h"
 #include "fflonk_lookup_impl.hip.h"
+#include "fflonk_lookup_tagged_impl.hip.h"
 #include "plonk_r1cs_impl.hip.h"
 #include "groth16_impl.hip.h"
 #include "groth16_keygen_impl.hip.h"
@@ -372,8 +375,8 @@ const FflonkOps& fflonk_ops(CurveId id) {     // fflonk_impl.hip.h, per scalar f
     return OPS[id];
 }
 
-const FflonkLookupOps& fflonk_lookup_ops(CurveId id) {   // fflonk_lookup_impl.hip.h, per scalar field
-    static const FflonkLookupOps OPS[2] = {{bn254fr::fl_quotients_dev}, {bls12381fr::fl_quotients_dev}};
+const FflonkLookupOps& fflonk_lookup_ops(CurveId id) {   // fflonk_lookup_impl.hip.h and fflonk_lookup_tagged_impl.hip.h, per scalar field
+    static const FflonkLookupOps OPS[2] = {{bn254fr::fl_quotients_dev, bn254fr::flt_quotients_dev}, {bls12381fr::fl_quotients_dev, bls12381fr::flt_quotients_dev}};
     return OPS[id];
 }
 

@@ -4,8 +4,9 @@ with plonk.py or fflonk.py and its keys and proofs are refused by them, as their
 of plonk.py, and for the argument zk_plonk_<curve>_lookup_table_new / _lookup_count_dev (a hash table over the table's rows and the count
 of how often each is used), _lookup_terms_dev, zk_fr_<curve>_batch_inverse_dev, _lookup_summands_dev, zk_fr_<curve>_prefix_sum_dev and
 _lookup_quotient_dev.  There is no CPU fallback.  Several tables in one circuit are the TAGGED variant below.  Not built:
-tables wider than three, lookups under fflonk (fflonk.py knows no q_K; fflonk_lookup.py has one table and refuses a tagged circuit),
-lookups in a circuit compiled from an .r1cs, a linearisation polynomial.
+tables wider than three, lookups under fflonk (fflonk.py knows no q_K; fflonk_lookup.py has one table and refuses a tagged circuit;
+fflonk_lookup_tagged.py, DESIGN.md 3.27, is the tagged argument under fflonk, a protocol of its own), lookups in a circuit compiled from an
+.r1cs, a linearisation polynomial.
 
 A LOOKUP CIRCUIT is a gate table (plonk_arith.Circuit) plus a selector qK per gate, which must be 0 or 1, and a table of T >= 1 rows of
 three field values (t1, t2, t3).  n = 2^k >= 8 must hold the l public rows plus the gates, and must also hold T.  The table is padded to n

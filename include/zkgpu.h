@@ -1097,7 +1097,7 @@ int zk_fflonk_bls12_381_quotients_dev(const uint64_t* const* d_cols, uint32_t lo
  *   d_out[i] = delta + a + eta b + eta^2 c + eta^3 q_K and d_out[n + i] = delta + t1 + eta t2 + eta^2 t3 + eta^3 T0 at row i.
  * zk_plonk_<curve>_lookup_tagged_quotient_dev: d_cols: ZK_PLONK_LOOKUP_TAGGED_QUOTIENT_COLS (10) pointers: a, b, c, q_K, t1, t2, t3, T0, M,
  *   Phi; d_acc as for ..._lookup_quotient_dev with the f and t of the tagged argument.
- * Not built for the tagged calls: tables of more than three columns, tagged tables under fflonk.                                          */
+ * Not built for the tagged calls: tables of more than three columns.  Under fflonk: zk_fflonk_<curve>_lookup_tagged_quotients_dev below.    */
 #define ZK_PLONK_LOOKUP_TERMS_COLS 6
 #define ZK_PLONK_LOOKUP_QUOTIENT_COLS 9
 #define ZK_PLONK_LOOKUP_MAX_ROWS 1073741824
@@ -1146,7 +1146,7 @@ int zk_plonk_bls12_381_lookup_tagged_quotient_dev(const uint64_t* const* d_cols,
  * every column pointer must still be valid.  An output (m elements each) overlaps no column and no other output; a scalar that is not below r
  * and log_n + 2 beyond the field's 2-adicity are refused before any device work.  One lane per element, one launch; each output is then
  * divided by Z_H with zk_fr_<curve>_divide_zh_coset_dev(d_out, log_n + 2, log_n).
- * Not built: a one-call C prover, tables of another width, several tables in one circuit.                                              */
+ * Not built: a one-call C prover, tables of another width.  Several tables in one circuit: the tagged call below.                       */
 #define ZK_FFLONK_LOOKUP_QUOTIENT_COLS 21
 int zk_fflonk_bn254_lookup_quotients_dev(const uint64_t* const* d_cols, uint32_t log_n, const uint64_t* beta, const uint64_t* gamma, const uint64_t* k1,
                                          const uint64_t* k2, const uint64_t* eta, const uint64_t* delta, uint64_t* d_out0, uint64_t* d_out1, uint64_t* d_out2,
@@ -1154,6 +1154,25 @@ int zk_fflonk_bn254_lookup_quotients_dev(const uint64_t* const* d_cols, uint32_t
 int zk_fflonk_bls12_381_lookup_quotients_dev(const uint64_t* const* d_cols, uint32_t log_n, const uint64_t* beta, const uint64_t* gamma, const uint64_t* k1,
                                              const uint64_t* k2, const uint64_t* eta, const uint64_t* delta, uint64_t* d_out0, uint64_t* d_out1, uint64_t* d_out2,
                                              uint64_t* d_out3, void* stream);
+
+/* ---- The device side of the fflonk prover with tagged lookups (csrc/fflonk_lookup_tagged_impl.hip.h) ---------------------
+ * The one kernel the prover of eigen_zkvm_amd/fflonk_lookup_tagged.py adds: zk_fflonk_<curve>_lookup_quotients_dev with the tag column of
+ * several tables in the lookup term.  d_cols: a HOST array of ZK_FFLONK_LOOKUP_TAGGED_QUOTIENT_COLS (22) device pointers to
+ * m = 4n = 4 2^log_n elements each, on the coset 7 H_m: the ZK_FFLONK_LOOKUP_QUOTIENT_COLS columns in their order, then Tg, the table's tag
+ * column (the T0 of the zk_plonk_<curve>_lookup_tagged_* calls).  At element i of every column, with f = a + eta b + eta^2 c + eta^3 q_K and
+ * t = t1 + eta t2 + eta^2 t3 + eta^3 Tg,
+ *   d_out0[i], d_out1[i], d_out2[i] = exactly zk_fflonk_<curve>_quotients_dev's
+ *   d_out3[i] = (Phi[(i + 4) mod m] - Phi[i]) (delta + f)(delta + t) - q_K (delta + t) + M (delta + f)
+ * every one canonical; d_out3 is what zk_plonk_<curve>_lookup_tagged_quotient_dev adds to a zero accumulator under alpha = 1.  Null outputs,
+ * overlaps, scalars and log_n as for zk_fflonk_<curve>_lookup_quotients_dev.  One lane per element, one launch.
+ * Not built: a one-call C prover, tables wider than three.                                                                                */
+#define ZK_FFLONK_LOOKUP_TAGGED_QUOTIENT_COLS 22
+int zk_fflonk_bn254_lookup_tagged_quotients_dev(const uint64_t* const* d_cols, uint32_t log_n, const uint64_t* beta, const uint64_t* gamma, const uint64_t* k1,
+                                                const uint64_t* k2, const uint64_t* eta, const uint64_t* delta, uint64_t* d_out0, uint64_t* d_out1,
+                                                uint64_t* d_out2, uint64_t* d_out3, void* stream);
+int zk_fflonk_bls12_381_lookup_tagged_quotients_dev(const uint64_t* const* d_cols, uint32_t log_n, const uint64_t* beta, const uint64_t* gamma, const uint64_t* k1,
+                                                    const uint64_t* k2, const uint64_t* eta, const uint64_t* delta, uint64_t* d_out0, uint64_t* d_out1,
+                                                    uint64_t* d_out2, uint64_t* d_out3, void* stream);
 
 /* ---- The R1CS import of the PLONK prover (csrc/plonk_r1cs_impl.hip.h) -----------------------------------------------------
  * A circom .r1cs over the curve's scalar field compiled to the gate table the prover takes, and the values of the auxiliary variables that
