@@ -35,6 +35,7 @@ namespace bn128fr {
 #define FH_NAME "bn128"
 #define FH_FN(name) bn128_##name
 #include "frhash_impl.hip.h"
+#include "frhash_probe_impl.hip.h"   // test hooks: zk_bn128_mf_probe, zk_bn128_mf_emulate_probe
 #undef FH_NRP
 #undef FH_OUT_IDX
 #undef FH_NAME

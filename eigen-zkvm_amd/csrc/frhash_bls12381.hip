@@ -22,6 +22,7 @@ namespace bls12381fr {
 #define FH_NAME "bls12381"
 #define FH_FN(name) bls12381_##name
 #include "frhash_impl.hip.h"
+#include "frhash_probe_impl.hip.h"   // test hooks: zk_bls12381_mf_probe, zk_bls12381_mf_emulate_probe
 }  // namespace bls12381fr
 
 void bls12381_load_constants(const char* path) { bls12381fr::bls12381_load_constants(path); }
