@@ -83,7 +83,8 @@ EXPORTS = [
      ] + ["zk_fflonk_%s_quotients_dev" % c for c in ("bn254", "bls12_381")
      ] + ["zk_fflonk_%s_lookup_quotients_dev" % c for c in ("bn254", "bls12_381")
      ] + ["zk_fflonk_%s_lookup_tagged_quotients_dev" % c for c in ("bn254", "bls12_381")
-     ] + ["zk_plonk_r1cs_wave_min_terms"] + ["zk_plonk_%s_r1cs_%s" % (c, f) for c in ("bn254", "bls12_381") for f in ("new", "info", "tables", "extend_dev", "free")]
+     ] + ["zk_plonk_r1cs_wave_min_terms"] + ["zk_plonk_%s_r1cs_%s" % (c, f) for c in ("bn254", "bls12_381") for f in ("new", "info", "tables", "extend_dev", "free")
+     ] + ["zk_plonk_%s_next_%s" % (c, f) for c in ("bn254", "bls12_381") for f in ("quotient_dev", "gate_check_dev", "r1cs_new", "r1cs_qn")]
 
 # include/zkgpu.h enums
 OP_ADD, OP_SUB, OP_MUL, OP_COPY = 0, 1, 2, 3
@@ -442,6 +443,11 @@ def _load():
             "zk_plonk_%s_r1cs_tables" % c: (C.c_int, [vp] * 10),
             "zk_plonk_%s_r1cs_extend_dev" % c: (C.c_int, [vp, vp, vp]),
             "zk_plonk_%s_r1cs_free" % c: (C.c_int, [vp]),
+            # the device side of the PLONK prover with a next-row term (plonk_next.py), and the import's chain rule
+            "zk_plonk_%s_next_quotient_dev" % c: (C.c_int, [vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp]),
+            "zk_plonk_%s_next_gate_check_dev" % c: (C.c_int, [vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp]),
+            "zk_plonk_%s_next_r1cs_new" % c: (vp, [vp, C.c_size_t]),
+            "zk_plonk_%s_next_r1cs_qn" % c: (C.c_int, [vp, vp]),
             # the device side of the lookup argument (plonk_lookup.py), and the running sum it adds to the polynomial layer
             "zk_fr_%s_prefix_sum_dev" % c: (C.c_int, [vp, C.c_uint64, C.c_int, vp, vp, vp]),
             "zk_plonk_%s_lookup_table_new" % c: (vp, [vp, vp, vp, C.c_uint64, vp]),
@@ -496,6 +502,9 @@ def __getattr__(name):
     if name == "FflonkLookupKey":   # fflonk_lookup.py (the fflonk prover and verifier with the lookup argument on interleaved commitments)
         import importlib
         return importlib.import_module(__name__ + ".fflonk_lookup").FflonkLookupKey
+    if name in ("NextCircuit", "NextR1csCircuit", "NextKey"):   # plonk_next.py (the PLONK prover and verifier whose gate reads the next row's c)
+        import importlib
+        return getattr(importlib.import_module(__name__ + ".plonk_next"), name)
     if name == "FflonkLookupTaggedKey":   # fflonk_lookup_tagged.py (fflonk with the lookup argument over several tagged tables)
         import importlib
         return importlib.import_module(__name__ + ".fflonk_lookup_tagged").FflonkLookupTaggedKey

@@ -1007,6 +1007,16 @@ ZK_FRPOLY_API(bls12_381, CURVE_BLS12_381)
     int zk_plonk_##NAME##_gate_check_dev(const uint64_t* const* d_cols, uint64_t n, uint64_t* n_bad, uint64_t* first_bad, void* stream) {      \
         return guard([&] { curve(ID).plonk().gate_check_dev((const u64* const*)d_cols, n, (u64*)n_bad, (u64*)first_bad, on_stream((hipStream_t)stream)); }); \
     }                                                                                                                                         \
+    int zk_plonk_##NAME##_next_quotient_dev(const uint64_t* const* d_cols, uint32_t log_n, const uint64_t* alpha, const uint64_t* beta, const uint64_t* gamma, \
+                                            const uint64_t* k1, const uint64_t* k2, uint64_t* d_out, void* stream) {                          \
+        return guard([&] {                                                                                                                    \
+            curve(ID).plonk().next_quotient_dev((const u64* const*)d_cols, log_n, (const u64*)alpha, (const u64*)beta, (const u64*)gamma, (const u64*)k1, (const u64*)k2, (u64*)d_out, \
+                                                on_stream((hipStream_t)stream));                                                              \
+        });                                                                                                                                   \
+    }                                                                                                                                         \
+    int zk_plonk_##NAME##_next_gate_check_dev(const uint64_t* const* d_cols, uint64_t n, uint64_t* n_bad, uint64_t* first_bad, void* stream) { \
+        return guard([&] { curve(ID).plonk().next_gate_check_dev((const u64* const*)d_cols, n, (u64*)n_bad, (u64*)first_bad, on_stream((hipStream_t)stream)); }); \
+    }                                                                                                                                         \
     int zk_fr_##NAME##_gather_dev(const uint64_t* d_src, uint64_t n_src, const uint32_t* d_idx, uint64_t n, uint64_t* d_out, void* stream) {   \
         return guard([&] { curve(ID).plonk().gather_dev((const u64*)d_src, n_src, d_idx, n, (u64*)d_out, on_stream((hipStream_t)stream)); }); \
     }
@@ -1136,19 +1146,34 @@ static void plonk_r1cs_tables(const zk_plonk_r1cs_t& h, uint64_t* sel, uint32_t*
     if (ns) std::memcpy(seg_first, h.seg_first.data(), ns * 4);
     if (nt) { std::memcpy(seg_wire, h.seg_wire.data(), nt * 4); std::memcpy(seg_coef, h.seg_coef.data(), nt * 32); }
 }
+// q_N of a handle compiled under the chain rule (plonk_next_impl.hip.h): n_gates x 4 canonical words
+static void plonk_r1cs_qn(const zk_plonk_r1cs_t& h, uint64_t* qn) {
+    ZK_REQUIRE(h.store_step == 2, "plonk r1cs: the handle was not compiled under the chain rule");
+    ZK_REQUIRE(qn || h.sel_n.empty(), "plonk r1cs: null gate table");
+    if (!h.sel_n.empty()) std::memcpy(qn, h.sel_n.data(), h.sel_n.size() * 8);
+}
 #define ZK_PLONK_R1CS_API(NAME, ID)                                                                                                           \
     zk_plonk_r1cs_t* zk_plonk_##NAME##_r1cs_new(const void* r1cs, size_t len) {                                                               \
         zk_plonk_r1cs_t* out = nullptr;                                                                                                       \
         guard([&] { out = curve(ID).plonk().r1cs_new(r1cs, len); });                                                                          \
         return out;                                                                                                                           \
     }                                                                                                                                         \
+    zk_plonk_r1cs_t* zk_plonk_##NAME##_next_r1cs_new(const void* r1cs, size_t len) {                                                          \
+        zk_plonk_r1cs_t* out = nullptr;                                                                                                       \
+        guard([&] { out = curve(ID).plonk().next_r1cs_new(r1cs, len); });                                                                     \
+        return out;                                                                                                                           \
+    }                                                                                                                                         \
+    int zk_plonk_##NAME##_next_r1cs_qn(const zk_plonk_r1cs_t* h, uint64_t* qn) { return guard([&] { plonk_r1cs_qn(plonk_r1cs_of(h, ID), qn); }); } \
     int zk_plonk_##NAME##_r1cs_info(const zk_plonk_r1cs_t* h, uint64_t* out) { return guard([&] { plonk_r1cs_info(plonk_r1cs_of(h, ID), out); }); } \
     int zk_plonk_##NAME##_r1cs_tables(const zk_plonk_r1cs_t* h, uint64_t* sel, uint32_t* a, uint32_t* b, uint32_t* c, uint32_t* origin, uint32_t* seg_first, uint64_t* seg_ptr,  \
                                       uint32_t* seg_wire, uint64_t* seg_coef) {                                                               \
         return guard([&] { plonk_r1cs_tables(plonk_r1cs_of(h, ID), sel, a, b, c, origin, seg_first, seg_ptr, seg_wire, seg_coef); });         \
     }                                                                                                                                         \
     int zk_plonk_##NAME##_r1cs_extend_dev(zk_plonk_r1cs_t* h, uint64_t* d_w, void* stream) {                                                  \
-        return guard([&] { plonk_r1cs_of(h, ID); curve(ID).plonk().r1cs_extend_dev(*h, (u64*)d_w, on_stream((hipStream_t)stream)); });        \
+        return guard([&] {                                                                                                                    \
+            const PlonkOps& ops = curve(ID).plonk();                                                                                          \
+            (plonk_r1cs_of(h, ID).store_step == 2 ? ops.next_r1cs_extend_dev : ops.r1cs_extend_dev)(*h, (u64*)d_w, on_stream((hipStream_t)stream)); \
+        });                                                                                                                                   \
     }                                                                                                                                         \
     int zk_plonk_##NAME##_r1cs_free(zk_plonk_r1cs_t* h) { return guard([&] { delete h; }); }
 ZK_PLONK_R1CS_API(bn254, CURVE_BN254)

@@ -126,6 +126,12 @@ struct PlonkOps {
     // of a witness on the device
     PlonkR1cs* (*r1cs_new)(const void* r1cs, size_t len);
     void (*r1cs_extend_dev)(PlonkR1cs& h, u64* d_w, hipStream_t st);
+    // plonk_next_impl.hip.h: the gate with the term q_N c(wX): one more column behind the others', and the import's chain rule
+    // (a handle of next_r1cs_new is extended by next_r1cs_extend_dev: two terms a stored prefix)
+    void (*next_quotient_dev)(const u64* const* d_cols, u32 log_n, const u64* alpha, const u64* beta, const u64* gamma, const u64* k1, const u64* k2, u64* d_out, hipStream_t st);
+    void (*next_gate_check_dev)(const u64* const* d_cols, u64 n, u64* n_bad, u64* first_bad, hipStream_t st);
+    PlonkR1cs* (*next_r1cs_new)(const void* r1cs, size_t len);
+    void (*next_r1cs_extend_dev)(PlonkR1cs& h, u64* d_w, hipStream_t st);
 };
 const PlonkOps& plonk_ops(CurveId id);
 // ---- groth16.hip: the device side of the fflonk prover (fflonk_impl.hip.h): the three numerators of the identity apart, in
@@ -390,6 +396,8 @@ struct zk_plonk_r1cs {       // an .r1cs as the PLONK prover takes it (plonk_r1c
     uint64_t n_constraints = 0, n_vars = 0, max_terms = 0;
     std::vector<uint64_t> sel[5];                    // qL, qR, qO, qM, qC: 4 canonical words per gate
     std::vector<uint32_t> wire[3], origin;           // a, b, c: variable ids; the constraint of every gate
+    std::vector<uint64_t> sel_n;                     // the chain rule (plonk_next_impl.hip.h): q_N, 4 canonical words per gate; empty otherwise
+    uint32_t store_step = 1;                         // 1: every term after the first defines an auxiliary; 2 (the chain rule): every second one and the last
     std::vector<uint32_t> seg_first;                 // per segment: its first auxiliary
     std::vector<uint64_t> seg_ptr;                   // n_segments + 1 offsets into the terms
     std::vector<uint32_t> seg_wire;                  // per term: the original wire

@@ -316,6 +316,7 @@ namespace bn254fr {
 #include "fflonk_lookup_impl.hip.h"
 #include "fflonk_lookup_tagged_impl.hip.h"
 #include "plonk_r1cs_impl.hip.h"
+#include "plonk_next_impl.hip.h"
 #include "groth16_impl.hip.h"
 #include "groth16_keygen_impl.hip.h"
 #include "verify_sums_impl.hip.h"
@@ -342,6 +343,7 @@ namespace bls12381fr {
 #include "fflonk_lookup_impl.hip.h"
 #include "fflonk_lookup_tagged_impl.hip.h"
 #include "plonk_r1cs_impl.hip.h"
+#include "plonk_next_impl.hip.h"
 #include "groth16_impl.hip.h"
 #include "groth16_keygen_impl.hip.h"
 #include "verify_sums_impl.hip.h"
@@ -364,9 +366,11 @@ const FrPolyOps& frpoly_ops(CurveId id) {     // frpoly_impl.hip.h, per scalar f
     return OPS[id];
 }
 
-const PlonkOps& plonk_ops(CurveId id) {       // plonk_impl.hip.h and plonk_r1cs_impl.hip.h, per scalar field
-    static const PlonkOps OPS[2] = {{bn254fr::pk_quotient_dev, bn254fr::pk_gate_check_dev, bn254fr::pk_gather_dev, bn254fr::pk_r1cs_new, bn254fr::pk_r1cs_extend_dev},
-                                    {bls12381fr::pk_quotient_dev, bls12381fr::pk_gate_check_dev, bls12381fr::pk_gather_dev, bls12381fr::pk_r1cs_new, bls12381fr::pk_r1cs_extend_dev}};
+const PlonkOps& plonk_ops(CurveId id) {       // plonk_impl.hip.h, plonk_r1cs_impl.hip.h and plonk_next_impl.hip.h, per scalar field
+#define ZK_PLONK_OPS(NS) {NS::pk_quotient_dev, NS::pk_gate_check_dev, NS::pk_gather_dev, NS::pk_r1cs_new, NS::pk_r1cs_extend_dev, \
+                          NS::pn_quotient_dev, NS::pn_gate_check_dev, NS::pn_r1cs_new, NS::pn_r1cs_extend_dev}
+    static const PlonkOps OPS[2] = {ZK_PLONK_OPS(bn254fr), ZK_PLONK_OPS(bls12381fr)};
+#undef ZK_PLONK_OPS
     return OPS[id];
 }
 

@@ -202,13 +202,13 @@ PlonkR1cs* FRN_FN(pk_r1cs_new)(const void* r1cs, size_t len) {
     return h.release();
 }
 
-// d_w: n_vars elements, the first n_wires in the stored form; fills the rest.  The segment table goes up on the first call.
-void FRN_FN(pk_r1cs_extend_dev)(PlonkR1cs& h, u64* d_w, hipStream_t st) {
+// the segment table to the device, on the first extension of a handle -> false when there is no segment
+static bool pr_upload(PlonkR1cs& h, u64* d_w, hipStream_t st) {
     ZK_REQUIRE(h.curve == &fp_curve(), "plonk r1cs: the handle is over another field");
     ZK_REQUIRE(d_w, "plonk r1cs: null argument");
     fp_aligned({d_w});
     const u64 n_seg = h.seg_first.size(), n_terms = h.seg_wire.size();
-    if (!n_seg) return;
+    if (!n_seg) return false;
     if (!h.on_device) {
         u64 wave_min = PLONK_R1CS_WAVE_MIN_TERMS;
         if (const char* e = getenv("ZK_PLONK_R1CS_WAVE_MIN")) wave_min = std::max<u64>(2, strtoull(e, nullptr, 10));   // the knob of tools/plonk_time.py: either kernel alone
@@ -227,6 +227,12 @@ void FRN_FN(pk_r1cs_extend_dev)(PlonkR1cs& h, u64* d_w, hipStream_t st) {
         h.n_short = ids_short.size(); h.n_long = ids_long.size();
         h.on_device = true;
     }
+    return true;
+}
+// d_w: n_vars elements, the first n_wires in the stored form; fills the rest.  The segment table goes up on the first call.
+void FRN_FN(pk_r1cs_extend_dev)(PlonkR1cs& h, u64* d_w, hipStream_t st) {
+    ZK_REQUIRE(h.store_step == 1, "plonk r1cs: the handle was compiled under the chain rule");
+    if (!pr_upload(h, d_w, st)) return;
     if (h.n_short)
         hipLaunchKernelGGL(pk_r1cs_extend_kernel, dim3(fp_blocks(h.n_short)), dim3(FP_BLOCK), 0, st, (const u32*)h.d_short.p, h.n_short, (const u64*)h.d_ptr.p, (const u32*)h.d_first.p,
                            (const u32*)h.d_wire.p, (const u32*)h.d_coef.p, (u32*)d_w);

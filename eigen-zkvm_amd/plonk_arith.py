@@ -204,6 +204,8 @@ class Circuit:
             missing = [k for k in SELECTORS + WIRES + ("n_vars", "public") if k not in z]
             if missing:
                 raise ZkError("plonk: %s holds no %s" % (path, ", ".join(missing)))
+            if "qN" in z and not getattr(cls, "has_next", False):
+                raise ZkError("plonk: %s holds a next-row selector qN: it is a circuit of plonk_next.py" % path)
             gates = {k: np.asarray(z[k], dtype=np.uint64).reshape(-1, 4) for k in SELECTORS}
             gates.update({k: np.asarray(z[k]).reshape(-1) for k in WIRES})
             return cls(int(z["n_vars"]), [int(v) for v in np.asarray(z["public"]).reshape(-1)], gates, curve)
@@ -219,11 +221,16 @@ class R1csCircuit(Circuit):
     row l + g of the table), .segments the table that defines the auxiliaries (seg_first, seg_ptr, seg_wire, seg_coef), .info the counts of
     R1CS_INFO.  A witness for prove() is the n_wires values of the .wtns, or its bytes; the handle lives until free()."""
 
+    _NEW = "r1cs_new"                                                 # the call that compiles: a subclass under another rule names its own
+
+    def _more_gates(self, gates, m):
+        """further columns of the m gates, for a subclass whose rule emits them"""
+
     def __init__(self, r1cs_bytes, curve="BN128"):
         modulus(curve)
         self.curve, self._h = curve, None
         data = np.frombuffer(bytes(r1cs_bytes), dtype=np.uint8)
-        self._h = getattr(lib(), "zk_plonk_%s_r1cs_new" % _NAME[curve])(data.ctypes.data, data.size)
+        self._h = getattr(lib(), "zk_plonk_%s_%s" % (_NAME[curve], self._NEW))(data.ctypes.data, data.size)
         if not self._h:
             raise ZkError(lib().zk_last_error().decode())
         try:
@@ -240,6 +247,7 @@ class R1csCircuit(Circuit):
             gates.update({w: wires[i][:m] for i, w in enumerate(WIRES)})
             self.n_wires, self.n_aux, self.origin = self.info["n_wires"], self.info["n_aux"], wires[3][:m]
             self.segments = {"seg_first": seg["seg_first"][:ns], "seg_ptr": seg["seg_ptr"], "seg_wire": seg["seg_wire"][:nt], "seg_coef": seg["seg_coef"][:nt]}
+            self._more_gates(gates, m)
             super().__init__(self.n_wires + self.n_aux, range(1, self.info["n_public"] + 1), gates, curve)
         except Exception:
             self.free()
@@ -440,9 +448,12 @@ class ArithKey:
     7 H_4n.  The coefficients of the 8 fixed polynomials go to _fixed(), which a protocol writes: with KEEPS_COEF they stay the key's, without
     it they are freed as soon as _fixed() returns.  required: (the formula in words, the G1 powers the file must hold)."""
     KEEPS_COEF = True
+    TAKES_NEXT = False                                                # plonk_next.py's key: the one that reads a circuit's next-row selector
 
     def __init__(self, kzg, circuit, who, required):
         cv, n, k = circuit.curve, circuit.n, circuit.log_n
+        if getattr(circuit, "has_next", False) and not self.TAKES_NEXT:
+            raise ZkError("%s: the circuit has a next-row selector qN, which this prover does not read: prove it with plonk_next.py" % who)
         if kzg.curve != cv:
             raise ZkError("%s: the circuit is over %s, the file over %s" % (who, cv, kzg.curve))
         if kzg.max_coeffs < required[1]:
@@ -502,14 +513,15 @@ class ArithKey:
 
 
 # ---- the prover's steps that are no protocol's ----------------------------------------------------------------------------------------------
-COUNT_WORDS = {9: "nine", 14: "fourteen"}
+COUNT_WORDS = {9: "nine", 10: "ten", 14: "fourteen"}
 
 
-def witness_columns(key, witness, blinding, _wires, who, keep, mark=lambda name: None, n_blinders=9):
+def witness_columns(key, witness, blinding, _wires, who, keep, mark=lambda name: None, n_blinders=9, check=None):
     """what prove() takes -> (the three value columns on H, PI's values, the public inputs, the nine blinders; n_blinders of them for a
     protocol that blinds more polynomials).  Every refusal of the witness and of the blinders on the host first; then, between the marks
     "start" and "gate check", the columns gathered from the witness (on an R1csCircuit from the extended one) and the gate equation row by
-    row: a witness that fails names the first row."""
+    row: a witness that fails names the first row.  check(vals, pi_vals) -> (rows that fail, the first): a protocol's own gate equation in
+    place of gate_check."""
     cv, n, c = key.curve, key.n, key.circuit
     r = FR[cv]
     from_r1cs = isinstance(c, R1csCircuit) and _wires is None
@@ -537,7 +549,7 @@ def witness_columns(key, witness, blinding, _wires, who, keep, mark=lambda name:
     pi_vals = keep(DevArray(4 * n, zero=True))
     if publics:
         upload_mont(cv, [(-x) % r for x in publics], pi_vals.ptr)
-    bad, first = gate_check(vals + key.sel_vals + [pi_vals], n, cv)
+    bad, first = check(vals, pi_vals) if check is not None else gate_check(vals + key.sel_vals + [pi_vals], n, cv)
     if bad and from_r1cs and first >= c.n_public:
         g = first - c.n_public
         raise ZkError("%s: witness does not satisfy gate %d (constraint %d of the .r1cs) (%d rows)" % (who, g, int(c.origin[g]), bad))

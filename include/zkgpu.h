@@ -1024,7 +1024,8 @@ int zk_fr_bls12_381_divide_zh_coset_dev(uint64_t* d_evals, uint32_t log_m, uint3
  *   q_L a + q_R b + q_O c + q_M a b + q_C + PI != 0, exact; first_bad (HOST): the first of them, UINT64_MAX when none.  Waits for the stream.
  * zk_fr_<curve>_gather_dev: out[i] = src[idx[i]] for i < n; d_idx: n uint32 on the device; d_out overlaps no source element.  An index that is
  *   not below n_src reads nothing and leaves zero; the call then fails with their number and the first position.  Waits for the stream.
- * Not built: a linearisation polynomial, custom gates, the split of the quotient, a one-call C prover.  Lookups: the section after fflonk's. */
+ * Not built: a linearisation polynomial, the split of the quotient, a one-call C prover.  Lookups: the section after fflonk's.  A custom gate:
+ * the next-row term, the last section of this header.                                                                                       */
 #define ZK_PLONK_QUOTIENT_COLS 15
 #define ZK_PLONK_GATE_COLS 9
 int zk_plonk_bn254_quotient_dev(const uint64_t* const* d_cols, uint32_t log_n, const uint64_t* alpha, const uint64_t* beta, const uint64_t* gamma,
@@ -1201,7 +1202,8 @@ int zk_fflonk_bls12_381_lookup_tagged_quotients_dev(const uint64_t* const* d_col
  *   as Montgomery words (what zk_fr_<curve>_gather_dev reads); the call fills elements n_wires .. n_vars - 1 in the same form, canonical, and
  *   writes nothing below n_wires.  The segment table goes to the device on the first call and stays with the handle (one call at a time).
  *   One lane per segment of fewer than zk_plonk_r1cs_wave_min_terms() terms, one wave per longer segment.  Asynchronous on the stream.
- * Not built: custom gates, folding a chain's last step into the product gate, Goldilocks circuits, a proving-key file.                   */
+ * Not built: folding a chain's last step into the product gate, Goldilocks circuits, a proving-key file.  A gate that reads the next row and
+ * the import rule that uses it: the next section.                                                                                          */
 #define ZK_PLONK_R1CS_INFO_WORDS 8
 typedef struct zk_plonk_r1cs zk_plonk_r1cs_t;
 uint64_t zk_plonk_r1cs_wave_min_terms(void);
@@ -1217,6 +1219,49 @@ int zk_plonk_bn254_r1cs_extend_dev(zk_plonk_r1cs_t* h, uint64_t* d_w, void* stre
 int zk_plonk_bls12_381_r1cs_extend_dev(zk_plonk_r1cs_t* h, uint64_t* d_w, void* stream);
 int zk_plonk_bn254_r1cs_free(zk_plonk_r1cs_t* h);
 int zk_plonk_bls12_381_r1cs_free(zk_plonk_r1cs_t* h);
+
+/* ---- PLONK with a next-row term (csrc/plonk_next_impl.hip.h) -------------------------------------------------------------
+ * The device side of eigen_zkvm_amd/plonk_next.py: row i of the gate table satisfies
+ *   q_L a + q_R b + q_O c + q_M a b + q_C + q_N c[(i + 1) mod n] + PI = 0,
+ * the next row cyclic on H.  Vectors, scalars and <curve> as for zk_plonk_<curve>_quotient_dev.
+ * zk_plonk_<curve>_next_quotient_dev: d_cols: a HOST array of ZK_PLONK_NEXT_QUOTIENT_COLS (16) device pointers to m = 4n elements each: the
+ *   ZK_PLONK_QUOTIENT_COLS columns in their order, then q_N.  out[i] = what zk_plonk_<curve>_quotient_dev gives + q_N[i] c[(i + 4) mod m]: on
+ *   the coset of 4n points c(wX) is c four elements on.  With q_N = 0 everywhere the output is that call's, word for word.  The same refusals;
+ *   one lane per element, one launch.
+ * zk_plonk_<curve>_next_gate_check_dev: d_cols: ZK_PLONK_NEXT_GATE_COLS (10) pointers to n elements: the ZK_PLONK_GATE_COLS columns in their
+ *   order, then q_N.  n_bad: the rows i < n that fail the equation above, exact; first_bad: the first, UINT64_MAX when none.  Row n - 1 reads
+ *   c[0].  Waits for the stream.
+ * The chain rule: the R1CS import of the section above with a second way to fold.  Normalisation, the numbering of wires and auxiliaries,
+ * origin, the linear and the product case, the refusals and folds of two signals (one gate (c_1, c_2, -1, 0, 0) on (s_1, s_2, x_1)) are that
+ * section's.  A fold of m >= 3 signals (s_i, c_i) is chain(sig): k = ceil(m / 2) rows; row j = 1 .. k has (a, b) = (s_(2j-1), s_(2j)),
+ * (q_L, q_R) = (c_(2j-1), c_(2j)) -- for odd m the last row has b = variable 0 and q_R = 0 --, q_O = 0 in row 1 and 1 after it, c = x_(j-1)
+ * for j >= 2, q_N = -1 (that is r - 1), q_M = q_C = 0; k auxiliaries x_j = sum_{i <= min(2j, m)} c_i w[s_i], x_k the fold's value.  Row j
+ * constrains the c of the row after it, so x_k must stand in c of the row emitted NEXT: row 1 of the next chain takes it (its c is free,
+ * q_O = 0); the closing product gate has it when x_k is its C side; otherwise a row of its own follows, every selector zero and a = b =
+ * variable 0, c = x_k.  Product constraint: the folds of two signals first, in the order A, B, C; then the chains in the order A, B, C;
+ * then the landing row when the last chain is not C's; then the gate of the section above on (sA, sB, sC).  Linear constraint with L of at
+ * most three signals: that section's one gate.  With m >= 4 signals: one chain CLOSED on itself: rows as above, but the last row has q_N = 0
+ * and q_C = k0, there are k - 1 auxiliaries and nothing lands.  Every row outside a chain has q_N = 0; the last gate of a table never has
+ * q_N != 0.  Segments: one per fold; a chain's holds its m terms, a closed chain's the first 2 (k - 1).  Term t >= 1 (from 0) of a segment
+ * of m terms defines an auxiliary when t is odd or t = m - 1: variable seg_first[s] + t / 2 (rounded down).
+ * zk_plonk_<curve>_next_r1cs_new: as zk_plonk_<curve>_r1cs_new under the chain rule.  The handle is read by zk_plonk_<curve>_r1cs_info (the
+ *   same eight words), _r1cs_tables and _r1cs_free, and zk_plonk_<curve>_r1cs_extend_dev extends a witness by it: the same lane and wave
+ *   kernels with a store step of 2, chosen by the handle.
+ * zk_plonk_<curve>_next_r1cs_qn: qn: n_gates x 4 canonical u64 words on the HOST, q_N of every gate; refused for a handle of _r1cs_new.
+ * Not built: the term in the fflonk and lookup provers, other custom gates, a linearisation polynomial, a one-call C prover, Rust
+ * declarations.                                                                                                                              */
+#define ZK_PLONK_NEXT_QUOTIENT_COLS 16
+#define ZK_PLONK_NEXT_GATE_COLS 10
+int zk_plonk_bn254_next_quotient_dev(const uint64_t* const* d_cols, uint32_t log_n, const uint64_t* alpha, const uint64_t* beta, const uint64_t* gamma,
+                                     const uint64_t* k1, const uint64_t* k2, uint64_t* d_out, void* stream);
+int zk_plonk_bls12_381_next_quotient_dev(const uint64_t* const* d_cols, uint32_t log_n, const uint64_t* alpha, const uint64_t* beta, const uint64_t* gamma,
+                                         const uint64_t* k1, const uint64_t* k2, uint64_t* d_out, void* stream);
+int zk_plonk_bn254_next_gate_check_dev(const uint64_t* const* d_cols, uint64_t n, uint64_t* n_bad, uint64_t* first_bad, void* stream);
+int zk_plonk_bls12_381_next_gate_check_dev(const uint64_t* const* d_cols, uint64_t n, uint64_t* n_bad, uint64_t* first_bad, void* stream);
+zk_plonk_r1cs_t* zk_plonk_bn254_next_r1cs_new(const void* r1cs, size_t len);
+zk_plonk_r1cs_t* zk_plonk_bls12_381_next_r1cs_new(const void* r1cs, size_t len);
+int zk_plonk_bn254_next_r1cs_qn(const zk_plonk_r1cs_t* h, uint64_t* qn);
+int zk_plonk_bls12_381_next_r1cs_qn(const zk_plonk_r1cs_t* h, uint64_t* qn);
 
 #ifdef __cplusplus
 }

@@ -1,4 +1,4 @@
-"""The command-line body that tools/zkgpu_plonk.py, tools/zkgpu_fflonk.py and tools/zkgpu_plonk_lookup.py share: <prefix>_setup, <prefix>_prove, <prefix>_verify on files, for
+"""The command-line body that tools/zkgpu_plonk.py, tools/zkgpu_fflonk.py, tools/zkgpu_plonk_lookup.py and tools/zkgpu_plonk_next.py share: <prefix>_setup, <prefix>_prove, <prefix>_verify on files, for
 a prover over eigen_zkvm_amd.plonk_arith.  A tool is a Tool record and delegates; its own docstring says what its files hold."""
 import argparse, collections, importlib, json, pathlib
 
@@ -25,15 +25,16 @@ def split_pair(tool, text):
 
 
 def refuse_r1cs(tool, mod, a):
-    """a prover whose module names its own circuit class (CIRCUIT) proves gate tables only: --r1cs is refused with one line"""
-    if a.r1cs is not None and hasattr(mod, "CIRCUIT"):
+    """a prover whose module names its own circuit class (CIRCUIT) and no class for an .r1cs (R1CS_CIRCUIT) proves gate tables only: --r1cs
+    is refused with one line"""
+    if a.r1cs is not None and hasattr(mod, "CIRCUIT") and not hasattr(mod, "R1CS_CIRCUIT"):
         print("%s: %s takes no --r1cs: a circuit compiled from an .r1cs has no lookups (tools/zkgpu_plonk.py proves it)" % (tool.name, a.cmd))
         raise SystemExit(1)
 
 
 def _key(tool, mod, h, curve, a):
     try:
-        circuit = mod.R1csCircuit(pathlib.Path(a.r1cs).read_bytes(), curve) if a.r1cs is not None else getattr(mod, getattr(mod, "CIRCUIT", "Circuit")).load(a.circuit, curve)
+        circuit = getattr(mod, getattr(mod, "R1CS_CIRCUIT", "R1csCircuit"))(pathlib.Path(a.r1cs).read_bytes(), curve) if a.r1cs is not None else getattr(mod, getattr(mod, "CIRCUIT", "Circuit")).load(a.circuit, curve)
         return getattr(mod, tool.key)(h, circuit)
     except mod.ZkError as e:
         print("%s: %s" % (tool.name, e))
