@@ -19,6 +19,10 @@
 //     A 2^24 transform is three such passes (8+8+8 bits), 2 LDS accesses / element / pass.
 //   * twiddles w_N^e come from a two-level table (4096 + N/4096 entries, L2 resident); the
 //     per-thread chain over the 16 outputs needs 2 lookups + 1 multiply per element.
+//   * every table load of a tile goes out in one group right behind its data loads: no table address depends on the data.  A 16-lane
+//     row shares its 16 entries of w256 (sub-step A) and, where 16 | s*n_pols, of the direct inter-pass table: one load per lane and a
+//     DPP row broadcast at the use (2 + 2 table loads per lane where there were 15 + 16); the two-level look-ups of a chain ride along.
+//     2^24 points 83.4 -> 85.7 GElem/s; the same loads in FRONT of the data loads gain nothing (profiles/r32/ntt_table_loads.md).
 //   * HBM-bound: 16 B / element / pass; bytes per transform = 16 * passes * N * n_pols.  A pass reads every data word once, so the
 //     sixteen data loads of a lane are non-temporal (the tables, which are re-read, and the stores are plain): 2^24 points 75.9 -> 82.3
 //     GElem/s.  Measured on the same kernel and not kept: non-temporal stores (slower), LDS sized per launch, an XCD-contiguous
@@ -59,12 +63,20 @@ struct PassParams {
     u32 np;
     u32 log_s;
     u32 has_tw;        // L > R (not the last pass)
+    u32 row_p;         // tw_mid set, not the one-column thread order, 16 | s_np: the 16 lanes of a row share p (row-shared table loads)
 };
 
-// Two-level table look-up w^e.  The result is NOT canonical (some u64 congruent to it): every use below is a factor of a further product
-// (gl::mul_tw / gl::mul_tw_nc take any u64), so the canonicalisation would be spent for nothing.
-__device__ __forceinline__ u64 tab2(const u64* __restrict__ lo, const u64* __restrict__ hi, u64 e) {
-    return gl::mul_tw_nc(hi[e >> TW_LO_BITS], lo[e & (TW_LO - 1)]);
+// Lane SRC of every 16-lane row to the whole row: one DPP move per half (row_newbcast), no LDS and no memory.  Every lane of the row
+// must be active.  Values entering and leaving a DPP move go through an empty asm (DESIGN_HISTORY.md section 3.9).  (The same by two
+// ds_bpermute_b32 measured no faster and costs a wave of occupancy: profiles/r32/ntt_table_loads.md.)
+__device__ __forceinline__ u32 dpp_opaque(u32 v) { asm volatile("" : "+v"(v)); return v; }
+template <int SRC>
+__device__ __forceinline__ u64 row_bcast(u64 v) {
+    static_assert(SRC >= 0 && SRC < 16, "a lane of the row");
+    const u32 v0 = dpp_opaque((u32)v), v1 = dpp_opaque((u32)(v >> 32));
+    const u32 z0 = dpp_opaque((u32)__builtin_amdgcn_update_dpp(0, (int)v0, 0x150 + SRC, 0xF, 0xF, false));
+    const u32 z1 = dpp_opaque((u32)__builtin_amdgcn_update_dpp(0, (int)v1, 0x150 + SRC, 0xF, 0xF, false));
+    return gl::mk64(z0, z1);
 }
 
 template <int LOGA, int LOGB, bool KMODE, bool INV>
@@ -80,6 +92,66 @@ __global__ __launch_bounds__(NTT_TILE / 16) void ntt_pass_kernel(const PassParam
 
     const int t = threadIdx.x;
     const u64 u0 = (u64)blockIdx.x * C;
+
+    // lane c of the tile -> (p, rem) = divmod(lane's word index within a transform-axis index, s n_pols); a dead lane is lane 0's.
+    // p: a shift for one column; a 32-bit division when the matrix has fewer than 2^32 words per transform-axis index (every size
+    // in use); the 64-bit division otherwise -- uniform branches, the general case cost ~100 instructions per lane
+    auto lane_pos = [&](int c, u64& p, u64& rem) {
+        const u64 u = u0 + c, uc = u < P.inner ? u : 0;
+        if (P.np == 1) { p = uc >> P.log_s; rem = uc & (((u64)1 << P.log_s) - 1); }
+        else if ((P.inner >> 32) == 0) { const u32 p32 = (u32)uc / (u32)P.s_np; p = p32; rem = (u32)uc - p32 * (u32)P.s_np; }
+        else
+        { p = uc / P.s_np; rem = uc - p * P.s_np; }
+    };
+    // sub-step B's thread order
+    const int cb = KMODE ? t / TG : t % C, tb = KMODE ? t % TG : t / C;
+
+    // ---- The table values of a tile.  No table address depends on the data, so every table load of a tile is requested in one group
+    // right behind the data loads (request_tables, called below): one trip through the vector-memory pipe per tile.  Behind, not in
+    // front: a wave's loads return in order, and a table load that misses L2 in front of the data holds the data back (measured).
+    // The 16 lanes of a row (t / 16) share ta, and tb outside the one-column order, so a row's 16 entries of a table are fetched one per
+    // lane and handed round by row_bcast at the point of use: two registers held per table, where sixteen per-lane values held from
+    // the top would cost a wave of occupancy.
+    static_assert(C % 16 == 0 && GA * RA == 16 && GB * RB == 16, "a 16-lane row shares ta and owns 16 table entries");
+    const int r16 = t & 15;
+    // sub-step A: entry (g, ka) = w256[(jb ka) << (8 - LOGR)], jb = ta GA + g, in lane g RA + ka of the row
+    const bool shift_a = LOGR <= 6 && C >= 64 && LOGB > 0 && P.pre_scale == 1;   // the twiddles of sub-step A are shifts (below)
+    u64 wa = 0;
+    // sub-step B, direct table, p shared by the row (taken from the row's first lane): entry (g, kb) = tw_mid[(p kappa) << sh],
+    // kappa = tb + g TG + RA kb, in lane g RB + kb.  (inner is a multiple of 16 here: a row is wholly live or wholly dead.)
+    u64 wm = 0;
+    const bool row_p = !KMODE && P.row_p;
+    // sub-step B, two-level table w^e = hi[e >> 12] lo[e & 4095] (L > 2^16), or the scaled last pass of an extension: the first factor
+    // of each chain and the chain's step.  The two halves of each look-up are requested with the rest and multiplied once sub-step A
+    // is through.  The products are NOT canonical (some u64 congruent to them): every use is a factor of a further product
+    // (gl::mul_tw / gl::mul_tw_nc take any u64), so the canonicalisation would be spent for nothing.
+    const bool chain_tab = !P.tw_mid && (P.has_tw || P.sc_lo);
+    u64 f0[GB], tw_step = 1, t2h[GB + 1], t2l[GB + 1];
+    auto request_tables = [&]() {
+        if (LOGB > 0 && !shift_a) wa = P.w256[(((t / C) * GA + r16 / RA) * (r16 % RA)) << (8 - LOGR)];
+        if (row_p) {
+            u64 p, rem;
+            lane_pos(cb & ~15, p, rem);
+            const u32 kappa = tb + (r16 / RB) * TG + RA * (r16 % RB);
+            wm = *(const u64*)((const char*)P.tw_mid + (u32)((((u32)p * kappa) << (P.log_s - P.dshift)) * 8));
+        }
+        if (chain_tab) {
+            u64 p, rem;
+            lane_pos(cb, p, rem);
+            const u64 row_q = !P.sc_lo ? 0 : P.np == 1 ? rem : (P.inner >> 32) == 0 ? (u64)((u32)rem / P.np) : rem / P.np;  // output row = kappa*s + row_q (last pass: p == 0)
+            const u64 es = (p * RA) << P.log_s;
+            t2h[GB] = P.has_tw ? P.tw_hi[es >> TW_LO_BITS] : 1; t2l[GB] = P.has_tw ? P.tw_lo[es & (TW_LO - 1)] : 1;
+            const u64* __restrict__ hi = P.sc_lo ? P.sc_hi : P.tw_hi;
+            const u64* __restrict__ lo = P.sc_lo ? P.sc_lo : P.tw_lo;
+#pragma unroll
+            for (int g = 0; g < GB; ++g) {
+                const int ka = tb + g * TG;
+                const u64 e = P.sc_lo ? ((u64)ka << P.log_s) + row_q : (p * ka) << P.log_s;
+                t2h[g] = hi[e >> TW_LO_BITS]; t2l[g] = lo[e & (TW_LO - 1)];
+            }
+        }
+    };
+    u64 tw[GB][RB];   // per-lane entries of the direct table where p differs inside a row
 
     {   // ---- sub-step A: RA-point transforms over ja (j = ja*RB + jb), twiddle w_R^(jb*ka)
         const int c = t % C, ta = t / C;
@@ -109,13 +181,14 @@ __global__ __launch_bounds__(NTT_TILE / 16) void ntt_pass_kernel(const PassParam
                     x[g][ja] = ok ? v : 0;
                 }
         }
+        request_tables();
 #pragma unroll
         for (int g = 0; g < GA; ++g) ntt_reg<LOGA, INV>(x[g]);
         // Passes of <= 6 bits: w_R is a power of two (w_64 = 2^39, ntt_reg.hip.h), so the twiddle w_R^(jb ka) between the two halves is a
         // shift like the butterflies' own -- once jb is a compile-time number.  jb = ta GA + g and ta = t / C with C = 4096 / R >= 64
         // lanes: the same in every lane of a wave, so a switch over ta (R / 16 <= 4 cases) costs no divergence and turns the 15 general
         // products of a lane into 15 shifts.  (Not for the pre-scaled last pass of a plain inverse transform: its 1/N rides on the table.)
-        if (LOGR <= 6 && C >= 64 && LOGB > 0 && P.pre_scale == 1) {
+        if (shift_a) {
             static_for<0, TG>([&](auto TA) {
                 constexpr int ta_c = decltype(TA)::value;
                 if (ta == ta_c) {
@@ -133,24 +206,48 @@ __global__ __launch_bounds__(NTT_TILE / 16) void ntt_pass_kernel(const PassParam
                 }
             });
         } else
-        {
-#pragma unroll
-            for (int g = 0; g < GA; ++g) {
-                const int jb = ta * GA + g;
-#pragma unroll
-                for (int ka = 0; ka < RA; ++ka) {
+        {   // the general products, by the row's entries of the table (dead lanes take part: a broadcast needs the whole row)
+            static_for<0, GA>([&](auto GI) {
+                constexpr int g = decltype(GI)::value;
+                const int jb = ta * GA + g;   // entry (g, ka) of the row is w256[(jb ka) << (8 - LOGR)]
+                static_for<0, RA>([&](auto KA) {
+                    constexpr int ka = decltype(KA)::value;
                     u64 v = x[g][bitrev_c(ka, LOGA)];
-                    if (LOGB > 0 && ka > 0) v = gl::mul_tw(v, P.w256[(jb * ka) << (8 - LOGR)]);
+                    if (LOGB > 0 && ka > 0) v = gl::mul_tw(v, row_bcast<g * RA + ka>(wa));
                     else if (P.pre_scale != 1) v = gl::mul_tw(v, P.pre_scale);
                     lds[ka * ROW + jb * C + c] = v;
-                }
-            }
+                });
+            });
         }
+    }
+    // per-lane entries of the direct table (p differs inside a row: the one-column thread order, s n_pols no multiple of 16): every
+    // twiddle w_L^(p*kappa) is one load from the 512 KB table (L2), no chain; requested here, where sub-step A's registers are free
+    // again, so that the barrier, the LDS reads and the radix-2^LOGB butterflies hide the latency.  Entry (p kappa) << (log_s - dshift)
+    // of the table (it is only set where log_s >= dshift), below 2^16: linear in kb, so one 32-bit byte offset per ka and one add per entry
+    auto load_mid = [&]() {
+        u64 p, rem;
+        lane_pos(cb, p, rem);
+        const u32 sh = P.log_s - P.dshift, istep = (((u32)p * RA) << sh) * 8;
+#pragma unroll
+        for (int g = 0; g < GB; ++g) {
+            const u32 ka = tb + g * TG, i0 = (((u32)p * ka) << sh) * 8;
+#pragma unroll
+            for (int kb = 0; kb < RB; ++kb) tw[g][kb] = *(const u64*)((const char*)P.tw_mid + (u32)(i0 + kb * istep));
+        }
+    };
+    // (a uniform run-time branch on purpose: as `if constexpr` the compiler sinks these loads below the
+    // butterflies to save registers and the L2 latency lands on the critical path again)
+    if (P.tw_mid && !row_p) load_mid();
+#pragma unroll
+    for (int g = 0; g < GB; ++g) f0[g] = P.out_scale;
+    if (chain_tab) {   // the two halves of each look-up arrived with the data
+#pragma unroll
+        for (int g = 0; g < GB; ++g) f0[g] = gl::mul_tw_nc(t2h[g], t2l[g]);
+        if (P.has_tw) tw_step = gl::mul_tw_nc(t2h[GB], t2l[GB]);
     }
     __syncthreads();
     {   // ---- sub-step B: RB-point transforms over jb -> kappa = RA*kb + ka
-        int c, tb;
-        if (KMODE) { tb = t % TG; c = t / TG; } else { c = t % C; tb = t / C; }
+        const int c = cb;
         const u64 u = u0 + c;
         u64 y[GB][RB];
 #pragma unroll
@@ -159,32 +256,21 @@ __global__ __launch_bounds__(NTT_TILE / 16) void ntt_pass_kernel(const PassParam
 #pragma unroll
             for (int jb = 0; jb < RB; ++jb) y[g][jb] = lds[ka * ROW + jb * C + c];
         }
-        const u64 uc = u < P.inner ? u : 0;
-        // p = uc / (s n_pols): a shift for one column; a 32-bit division when the matrix has fewer than 2^32 words per transform-axis
-        // index (every size in use); the 64-bit division otherwise -- uniform branches, the general case cost ~100 instructions per lane
-        u64 p, rem;
-        if (P.np == 1) { p = uc >> P.log_s; rem = uc & (((u64)1 << P.log_s) - 1); }
-        else if ((P.inner >> 32) == 0) { const u32 p32 = (u32)uc / (u32)P.s_np; p = p32; rem = (u32)uc - p32 * (u32)P.s_np; }
-        else
-        { p = uc / P.s_np; rem = uc - p * P.s_np; }
-        u64 tw[GB][RB];
-        if (P.tw_mid) {  // L <= 2^16: every twiddle w_L^(p*kappa) is one load from the 512 KB table (L2), no chain;
-                         // issued here so that the radix-2^LOGB butterflies below hide the latency
-            // entry (p kappa) << (log_s - dshift) of the table (it is only set where log_s >= dshift), below 2^16: linear in kb, so one
-            // 32-bit byte offset per ka and one add per entry
-            const u32 sh = P.log_s - P.dshift, istep = (((u32)p * RA) << sh) * 8;
-#pragma unroll
-            for (int g = 0; g < GB; ++g) {
-                const u32 ka = tb + g * TG, i0 = (((u32)p * ka) << sh) * 8;
-#pragma unroll
-                for (int kb = 0; kb < RB; ++kb) tw[g][kb] = *(const u64*)((const char*)P.tw_mid + (u32)(i0 + kb * istep));
-            }
-        }
-        // (a uniform run-time branch on purpose: as `if constexpr` the compiler sinks these loads below the
-        // butterflies to save registers and the L2 latency lands on the critical path again)
 #pragma unroll
         for (int g = 0; g < GB; ++g) ntt_reg<LOGB, INV>(y[g]);
+        if (row_p) {   // the inter-pass twiddles by the row's entries of the table, in front of the exit of the dead lanes
+            static_for<0, GB>([&](auto GI) {
+                constexpr int g = decltype(GI)::value;
+                static_for<0, RB>([&](auto KB) {
+                    constexpr int kb = decltype(KB)::value;
+                    u64& v = y[g][bitrev_c(kb, LOGB)];
+                    v = gl::mul_tw(v, row_bcast<g * RB + kb>(wm));
+                });
+            });
+        }
         if (u >= P.inner) return;
+        u64 p, rem;
+        lane_pos(c, p, rem);
 
         // output kappa = RA kb + ka of the lane lies (RA kb + ka) s_np words past the lane's base: linear in kb.  Whole matrix under 4 GiB
         // (uniform): a lane's stores are then a uniform base plus a 32-bit byte offset, one add per store where the general form
@@ -198,7 +284,13 @@ __global__ __launch_bounds__(NTT_TILE / 16) void ntt_pass_kernel(const PassParam
                 if constexpr (SMALL) *(u64*)((char*)P.out + (u32)(b0 + ka * (u32)P.s_np * 8 + kb * bstep)) = v;
                 else outp[(u64)(RA * kb + ka) * kstride] = v;
             };
-            const u64 row_q = !P.sc_lo ? 0 : P.np == 1 ? rem : (P.inner >> 32) == 0 ? (u64)((u32)rem / P.np) : rem / P.np;  // output row = kappa*s + row_q (last pass: p == 0)
+            if (row_p) {   // twiddled above
+#pragma unroll
+                for (int g = 0; g < GB; ++g)
+#pragma unroll
+                    for (int kb = 0; kb < RB; ++kb) put(tb + g * TG, kb, y[g][bitrev_c(kb, LOGB)]);
+                return;
+            }
             if (P.tw_mid) {
 #pragma unroll
                 for (int g = 0; g < GB; ++g) {
@@ -212,14 +304,10 @@ __global__ __launch_bounds__(NTT_TILE / 16) void ntt_pass_kernel(const PassParam
                 }
                 return;
             }
-            u64 tw_step = 1;
-            if (P.has_tw) tw_step = tab2(P.tw_lo, P.tw_hi, (p * RA) << P.log_s);
 #pragma unroll
             for (int g = 0; g < GB; ++g) {
                 const int ka = tb + g * TG;
-                u64 f = P.out_scale;
-                if (P.has_tw) f = tab2(P.tw_lo, P.tw_hi, (p * ka) << P.log_s);
-                if (P.sc_lo) f = tab2(P.sc_lo, P.sc_hi, ((u64)ka << P.log_s) + row_q);
+                u64 f = f0[g];                                              // the chain's first factor, looked up with the data
                 const bool scaled = P.has_tw || P.sc_lo || P.out_scale != 1;
                 const u64 fstep = P.sc_lo ? P.sc_step : tw_step;
 #pragma unroll
@@ -401,6 +489,7 @@ void run_transform(const u64* in, u64* a, u64* b, /* ping-pong, result must land
         P.dshift = T.dshift;
         P.tw_mid = (!last && log_s >= T.dshift) ? T.mid.u() : nullptr;  // L = N >> log_s <= 2^16
         const bool kmode = P.s_np < 16;
+        P.row_p = (P.tw_mid && !kmode && P.s_np % 16 == 0) ? 1 : 0;
         launch_pass_logr(logr, P, kmode, inverse, st);
         cur = dstbuf;
         log_s += logr;
