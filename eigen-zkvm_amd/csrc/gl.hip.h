@@ -346,6 +346,227 @@ __device__ __forceinline__ u64 mul_pow2(u64 x) {
     }
 }
 
+// ---- paired forms of the NTT passes' primitives: two (bfly2_m: four) independent carry chains whose instructions alternate, so that the
+// instruction behind a flag's producer belongs to another chain and not to the flag's consumer.  The single forms above keep every
+// dependent instruction right behind its producer and write the two wait states between a vector instruction that writes an SGPR pair
+// and the vector instruction that reads it as `s_nop 1`; here the other chain's instructions are those wait states, every chain has
+// carry and mask SGPR pairs of its own (the VOP3 forms), and vcc only ever takes a carry-out nobody reads.  Where two chains leave a
+// single instruction between producer and consumer, the second wait state is a written `s_nop 0`, named at its place.
+// A primitive is a short run of asm statements, not one: inline asm cannot name the halves of a 64-bit operand, so a value that 32-bit
+// carry instructions write and a multiply-add reads as a pair (or the other way round) changes its shape between two statements; every
+// statement holds all chains, and no wait state is counted across a statement's end (the compiler pads one state there, no more).
+// Results are bit for bit those of the single forms (tests/test_gpu_ntt_pairs.py).
+// sum = add_m(a, b), diff = sub_m(a, b); canonical in -> canonical out
+__device__ __forceinline__ void bfly_m(u64 a, u64 b, u64& sum, u64& diff) {
+    u32 s0, s1, e0, e1, m, r0, r1; u64 cA, cS, dA, t, rs;
+    asm("v_sub_co_u32 %[e0], %[cS], %[a0], %[b0]\n\t"
+        "v_add_co_u32 %[s0], %[cA], %[a0], %[b0]\n\t"
+        "s_nop 0\n\t"                                             // two chains: the second wait state of both carries
+        "v_subb_co_u32 %[e1], %[cS], %[a1], %[b1], %[cS]\n\t"
+        "v_addc_co_u32 %[s1], %[cA], %[a1], %[b1], %[cA]"
+        : [e0] "=&v"(e0), [s0] "=&v"(s0), [e1] "=&v"(e1), [s1] "=v"(s1), [cS] "=&s"(cS), [cA] "=&s"(cA)
+        : [a0] "v"((u32)a), [a1] "v"((u32)(a >> 32)), [b0] "v"((u32)b), [b1] "v"((u32)(b >> 32)));
+    asm("v_mad_u64_u32 %[t], %[dA], 1, -1, %[S]\n\t"              // (the borrow cS: the sum's last carry and this stand behind its producer)
+        "v_cndmask_b32_e64 %[m], 0, %[k], %[cS]\n\t"
+        "v_mad_i64_i32 %[rs], vcc, %[m], %[c], %[D]\n\t"
+        "s_or_b64 %[dA], %[dA], %[cA]"
+        : [t] "=&v"(t), [dA] "=&s"(dA), [m] "=&v"(m), [rs] "=v"(rs)
+        : [S] "v"(mk64(s0, s1)), [D] "v"(mk64(e0, e1)), [cS] "s"(cS), [cA] "s"(cA), [k] "v"(-65537), [c] "s"(65535) : "vcc", "scc");
+    asm("v_cndmask_b32_e64 %[r0], %[s0], %[t0], %[dA]\n\tv_cndmask_b32_e64 %[r1], %[s1], %[t1], %[dA]"
+        : [r0] "=&v"(r0), [r1] "=v"(r1) : [s0] "v"(s0), [s1] "v"(s1), [t0] "v"((u32)t), [t1] "v"((u32)(t >> 32)), [dA] "s"(dA));
+    sum = mk64(r0, r1); diff = rs;
+}
+// two butterflies on independent operands, four chains (A: a + b, S: a - b, C: c + d, T: c - d): no written wait state
+__device__ __forceinline__ void bfly2_m(u64 a, u64 b, u64 c, u64 d, u64& sum_ab, u64& diff_ab, u64& sum_cd, u64& diff_cd) {
+    u32 s0, s1, e0, e1, u0, u1, f0, f1, mS, mT, r0, r1, q0, q1; u64 cA, cS, cC, cT, dA, dC, tA, tC, rs, rt;
+    asm("v_add_co_u32 %[s0], %[cA], %[a0], %[b0]\n\t"
+        "v_sub_co_u32 %[e0], %[cS], %[a0], %[b0]\n\t"
+        "v_add_co_u32 %[u0], %[cC], %[c0], %[d0]\n\t"
+        "v_sub_co_u32 %[f0], %[cT], %[c0], %[d0]\n\t"
+        "v_addc_co_u32 %[s1], %[cA], %[a1], %[b1], %[cA]\n\t"
+        "v_subb_co_u32 %[e1], %[cS], %[a1], %[b1], %[cS]\n\t"
+        "v_addc_co_u32 %[u1], %[cC], %[c1], %[d1], %[cC]\n\t"
+        "v_subb_co_u32 %[f1], %[cT], %[c1], %[d1], %[cT]"
+        : [s0] "=&v"(s0), [e0] "=&v"(e0), [u0] "=&v"(u0), [f0] "=&v"(f0), [s1] "=&v"(s1), [e1] "=&v"(e1), [u1] "=&v"(u1), [f1] "=v"(f1),
+          [cA] "=&s"(cA), [cS] "=&s"(cS), [cC] "=&s"(cC), [cT] "=&s"(cT)
+        : [a0] "v"((u32)a), [a1] "v"((u32)(a >> 32)), [b0] "v"((u32)b), [b1] "v"((u32)(b >> 32)),
+          [c0] "v"((u32)c), [c1] "v"((u32)(c >> 32)), [d0] "v"((u32)d), [d1] "v"((u32)(d >> 32)));
+    asm("v_mad_u64_u32 %[tA], %[dA], 1, -1, %[SA]\n\t"
+        "v_mad_u64_u32 %[tC], %[dC], 1, -1, %[SC]\n\t"
+        "v_cndmask_b32_e64 %[mS], 0, %[k], %[cS]\n\t"
+        "v_cndmask_b32_e64 %[mT], 0, %[k], %[cT]\n\t"             // cT: the last instruction of the statement above, three behind
+        "v_mad_i64_i32 %[rs], vcc, %[mS], %[c], %[DS]\n\t"
+        "v_mad_i64_i32 %[rt], vcc, %[mT], %[c], %[DT]\n\t"
+        "s_or_b64 %[dA], %[dA], %[cA]\n\t"
+        "s_or_b64 %[dC], %[dC], %[cC]"
+        : [tA] "=&v"(tA), [tC] "=&v"(tC), [dA] "=&s"(dA), [dC] "=&s"(dC), [mS] "=&v"(mS), [mT] "=&v"(mT), [rs] "=&v"(rs), [rt] "=v"(rt)
+        : [SA] "v"(mk64(s0, s1)), [SC] "v"(mk64(u0, u1)), [DS] "v"(mk64(e0, e1)), [DT] "v"(mk64(f0, f1)),
+          [cS] "s"(cS), [cT] "s"(cT), [cA] "s"(cA), [cC] "s"(cC), [k] "v"(-65537), [c] "s"(65535) : "vcc", "scc");
+    asm("v_cndmask_b32_e64 %[r0], %[s0], %[t0], %[dA]\n\tv_cndmask_b32_e64 %[r1], %[s1], %[t1], %[dA]\n\t"
+        "v_cndmask_b32_e64 %[q0], %[u0], %[v0], %[dC]\n\tv_cndmask_b32_e64 %[q1], %[u1], %[v1], %[dC]"
+        : [r0] "=&v"(r0), [r1] "=&v"(r1), [q0] "=&v"(q0), [q1] "=v"(q1)
+        : [s0] "v"(s0), [s1] "v"(s1), [t0] "v"((u32)tA), [t1] "v"((u32)(tA >> 32)), [dA] "s"(dA),
+          [u0] "v"(u0), [u1] "v"(u1), [v0] "v"((u32)tC), [v1] "v"((u32)(tC >> 32)), [dC] "s"(dC));
+    sum_ab = mk64(r0, r1); diff_ab = rs; sum_cd = mk64(q0, q1); diff_cd = rt;
+}
+// two differences, sub_m(a, b) and sub_m(c, d)
+__device__ __forceinline__ void sub2_m(u64 a, u64 b, u64 c, u64 d, u64& diff_ab, u64& diff_cd) {
+    u32 e0, e1, f0, f1, mS, mT; u64 cS, cT, rs, rt;
+    asm("v_sub_co_u32 %[e0], %[cS], %[a0], %[b0]\n\t"
+        "v_sub_co_u32 %[f0], %[cT], %[c0], %[d0]\n\t"
+        "s_nop 0\n\t"                                             // two chains: the second wait state of both borrows
+        "v_subb_co_u32 %[e1], %[cS], %[a1], %[b1], %[cS]\n\t"
+        "v_subb_co_u32 %[f1], %[cT], %[c1], %[d1], %[cT]\n\t"
+        "s_nop 0\n\t"                                             // the same
+        "v_cndmask_b32_e64 %[mS], 0, %[k], %[cS]\n\t"
+        "v_cndmask_b32_e64 %[mT], 0, %[k], %[cT]"
+        : [e0] "=&v"(e0), [f0] "=&v"(f0), [e1] "=&v"(e1), [f1] "=&v"(f1), [mS] "=&v"(mS), [mT] "=v"(mT), [cS] "=&s"(cS), [cT] "=&s"(cT)
+        : [a0] "v"((u32)a), [a1] "v"((u32)(a >> 32)), [b0] "v"((u32)b), [b1] "v"((u32)(b >> 32)),
+          [c0] "v"((u32)c), [c1] "v"((u32)(c >> 32)), [d0] "v"((u32)d), [d1] "v"((u32)(d >> 32)), [k] "v"(-65537));
+    asm("v_mad_i64_i32 %[rs], vcc, %[mS], %[c], %[DS]\n\tv_mad_i64_i32 %[rt], vcc, %[mT], %[c], %[DT]"
+        : [rs] "=&v"(rs), [rt] "=v"(rt) : [mS] "v"(mS), [mT] "v"(mT), [DS] "v"(mk64(e0, e1)), [DT] "v"(mk64(f0, f1)), [c] "s"(65535) : "vcc");
+    diff_ab = rs; diff_cd = rt;
+}
+
+// The tail of two products or shifts, t + r2 (2^32 - 1) mod p twice (mad_eps_nc / mad_eps_m).  The carried fix-up u += 2^32 - 1 is ONE
+// multiply-add, m * 1 + u with m = 0 or 2^32 - 1, where mad_eps_nc leaves a 64-bit addition (two carry instructions) to the compiler.
+// HEAD: both multiply-adds, then both masks; TAIL_NC / TAIL_M: the fix-up (and the canonicalising multiply-add, whose mask gA has the
+// other chain's two instructions behind it, gB the first two selects of the last statement)
+#define GL_TAIL2_HEAD \
+        "v_mad_u64_u32 %[tA], %[kA], %[r2A], -1, %[tA]\n\t" \
+        "v_mad_u64_u32 %[tB], %[kB], %[r2B], -1, %[tB]\n\t" \
+        "s_nop 0\n\t"                                             /* two chains: the second wait state of both carries */ \
+        "v_cndmask_b32_e64 %[r2A], 0, -1, %[kA]\n\t" \
+        "v_cndmask_b32_e64 %[r2B], 0, -1, %[kB]\n\t"
+#define GL_TAIL2_NC \
+        "v_mad_u64_u32 %[tA], vcc, %[r2A], 1, %[tA]\n\t" \
+        "v_mad_u64_u32 %[tB], vcc, %[r2B], 1, %[tB]"
+#define GL_TAIL2_M \
+        "v_mad_u64_u32 %[tA], vcc, %[r2A], 1, %[tA]\n\t" \
+        "v_mad_u64_u32 %[vA], %[gA], 1, -1, %[tA]\n\t" \
+        "v_mad_u64_u32 %[tB], vcc, %[r2B], 1, %[tB]\n\t" \
+        "v_mad_u64_u32 %[vB], %[gB], 1, -1, %[tB]"
+// the 2^96 fold's last step in front of the tail (sub_eps_if on both chains)
+#define GL_FOLD2 \
+        "v_mad_i64_i32 %[tA], vcc, %[bA], %[c], %[tA]\n\t" \
+        "v_mad_i64_i32 %[tB], vcc, %[bB], %[c], %[tB]\n\t"
+// Every value of a chain stays in the registers of the one it replaces (t -> u, r2 -> the mask): a pair of products holds no more
+// registers than its operands and the two canonicalised candidates
+__device__ __forceinline__ void canon_select2(u64 uA, u64 vA, u64 gA, u64 uB, u64 vB, u64 gB, u64& ra, u64& rb) {
+    u32 r0 = (u32)uA, r1 = (u32)(uA >> 32), q0 = (u32)uB, q1 = (u32)(uB >> 32);
+    asm("v_cndmask_b32_e64 %[r0], %[r0], %[v0], %[gA]\n\tv_cndmask_b32_e64 %[r1], %[r1], %[v1], %[gA]\n\t"
+        "v_cndmask_b32_e64 %[q0], %[q0], %[y0], %[gB]\n\tv_cndmask_b32_e64 %[q1], %[q1], %[y1], %[gB]"
+        : [r0] "+v"(r0), [r1] "+v"(r1), [q0] "+v"(q0), [q1] "+v"(q1)
+        : [v0] "v"((u32)vA), [v1] "v"((u32)(vA >> 32)), [gA] "s"(gA), [y0] "v"((u32)vB), [y1] "v"((u32)(vB >> 32)), [gB] "s"(gB));
+    ra = mk64(r0, r1); rb = mk64(q0, q1);
+}
+// mad_eps_m(r2a, ta) and mad_eps_m(r2b, tb)
+__device__ __forceinline__ void mad_eps2_m(u32 r2a, u64 ta, u32 r2b, u64 tb, u64& ra, u64& rb) {
+    u64 vA, vB, kA, kB, gA, gB;
+    asm(GL_TAIL2_HEAD GL_TAIL2_M
+        : [tA] "+v"(ta), [tB] "+v"(tb), [r2A] "+v"(r2a), [r2B] "+v"(r2b), [vA] "=&v"(vA), [vB] "=&v"(vB),
+          [kA] "=&s"(kA), [kB] "=&s"(kB), [gA] "=&s"(gA), [gB] "=&s"(gB)
+        : : "vcc");
+    canon_select2(ta, vA, gA, tb, vB, gB, ra, rb);
+}
+
+// Two twiddle products, mul_fold96 twice: (t0 : t1), the fold's mask b and r2 of each, for the tail above
+struct fold96_pair { u32 t0A, t1A, bA, r2A, t0B, t1B, bB, r2B; };
+__device__ __forceinline__ fold96_pair mul_fold96_2(u64 x0, u64 w0, u64 x1, u64 w1) {
+    u64 lA, mA, hA, lB, mB, hB, cA, cB;
+    asm("v_mad_u64_u32 %[mA], vcc, %[xa0], %[wa1], 0\n\t"
+        "v_mad_u64_u32 %[mB], vcc, %[xb0], %[wb1], 0\n\t"
+        "v_mad_u64_u32 %[mA], %[cA], %[xa1], %[wa0], %[mA]\n\t"
+        "v_mad_u64_u32 %[mB], %[cB], %[xb1], %[wb0], %[mB]\n\t"
+        "v_mad_u64_u32 %[lA], vcc, %[xa0], %[wa0], 0\n\t"
+        "v_mad_u64_u32 %[lB], vcc, %[xb0], %[wb0], 0\n\t"
+        "v_mad_u64_u32 %[hA], vcc, %[xa1], %[wa1], 0\n\t"
+        "v_mad_u64_u32 %[hB], vcc, %[xb1], %[wb1], 0"
+        : [lA] "=&v"(lA), [mA] "=&v"(mA), [hA] "=&v"(hA), [lB] "=&v"(lB), [mB] "=&v"(mB), [hB] "=v"(hB), [cA] "=&s"(cA), [cB] "=&s"(cB)
+        : [xa0] "v"((u32)x0), [xa1] "v"((u32)(x0 >> 32)), [wa0] "v"((u32)w0), [wa1] "v"((u32)(w0 >> 32)),
+          [xb0] "v"((u32)x1), [xb1] "v"((u32)(x1 >> 32)), [wb0] "v"((u32)w1), [wb1] "v"((u32)(w1 >> 32)) : "vcc");
+    // The column sums and the fold, as mul_fold96 orders them per chain, every result in the register of the word it replaces:
+    // l0 -> t0, l1 -> w1 -> t1, m0 -> the fold's mask, m1 -> r2, h1 -> h1 + c.  h1 (no flag of its chain) fills a wait state of each side.
+    u32 lA0 = (u32)lA, lA1 = (u32)(lA >> 32), mA0 = (u32)mA, mA1 = (u32)(mA >> 32), hA1 = (u32)(hA >> 32);
+    u32 lB0 = (u32)lB, lB1 = (u32)(lB >> 32), mB0 = (u32)mB, mB1 = (u32)(mB >> 32), hB1 = (u32)(hB >> 32);
+    u64 kA, kB;
+    asm("v_add_co_u32 %[lA1], %[kA], %[lA1], %[mA0]\n\t"
+        "v_add_co_u32 %[lB1], %[kB], %[lB1], %[mB0]\n\t"
+        "v_addc_co_u32 %[hA1], vcc, 0, %[hA1], %[cA]\n\t"
+        "v_addc_co_u32 %[mA1], %[kA], %[mA1], %[hA0], %[kA]\n\t"
+        "v_addc_co_u32 %[mB1], %[kB], %[mB1], %[hB0], %[kB]\n\t"
+        "v_addc_co_u32 %[hB1], vcc, 0, %[hB1], %[cB]\n\t"
+        "v_subb_co_u32 %[lA0], %[kA], %[lA0], %[hA1], %[kA]\n\t"
+        "v_subb_co_u32 %[lB0], %[kB], %[lB0], %[hB1], %[kB]\n\t"
+        "s_nop 0\n\t"                                             // two chains, nothing else left to do: the second wait state of both borrows
+        "v_subbrev_co_u32 %[lA1], %[kA], 0, %[lA1], %[kA]\n\t"
+        "v_subbrev_co_u32 %[lB1], %[kB], 0, %[lB1], %[kB]\n\t"
+        "s_nop 0\n\t"                                             // the same
+        "v_cndmask_b32_e64 %[mA0], 0, %[k], %[kA]\n\t"
+        "v_cndmask_b32_e64 %[mB0], 0, %[k], %[kB]"
+        : [lA0] "+v"(lA0), [lA1] "+v"(lA1), [mA0] "+v"(mA0), [mA1] "+v"(mA1), [hA1] "+v"(hA1),
+          [lB0] "+v"(lB0), [lB1] "+v"(lB1), [mB0] "+v"(mB0), [mB1] "+v"(mB1), [hB1] "+v"(hB1), [kA] "=&s"(kA), [kB] "=&s"(kB)
+        : [hA0] "v"((u32)hA), [hB0] "v"((u32)hB), [cA] "s"(cA), [cB] "s"(cB), [k] "v"(-65537) : "vcc");
+    return fold96_pair{lA0, lA1, mA0, mA1, lB0, lB1, mB0, mB1};
+}
+// r0 = mul_tw(x0, w0), r1 = mul_tw(x1, w1): any u64 in, canonical out
+__device__ __forceinline__ void mul_tw2(u64 x0, u64 w0, u64 x1, u64 w1, u64& r0, u64& r1) {
+    fold96_pair F = mul_fold96_2(x0, w0, x1, w1);
+    u64 tA = mk64(F.t0A, F.t1A), tB = mk64(F.t0B, F.t1B), vA, vB, kA, kB, gA, gB;
+    asm(GL_FOLD2 GL_TAIL2_HEAD GL_TAIL2_M
+        : [tA] "+v"(tA), [tB] "+v"(tB), [r2A] "+v"(F.r2A), [r2B] "+v"(F.r2B), [vA] "=&v"(vA), [vB] "=&v"(vB),
+          [kA] "=&s"(kA), [kB] "=&s"(kB), [gA] "=&s"(gA), [gB] "=&s"(gB)
+        : [bA] "v"(F.bA), [bB] "v"(F.bB), [c] "s"(65535) : "vcc");
+    canon_select2(tA, vA, gA, tB, vB, gB, r0, r1);
+}
+// r0 = mul_tw_nc(x0, w0), r1 = mul_tw_nc(x1, w1): some u64 congruent to the products
+__device__ __forceinline__ void mul_tw2_nc(u64 x0, u64 w0, u64 x1, u64 w1, u64& r0, u64& r1) {
+    fold96_pair F = mul_fold96_2(x0, w0, x1, w1);
+    u64 tA = mk64(F.t0A, F.t1A), tB = mk64(F.t0B, F.t1B), kA, kB;
+    asm(GL_FOLD2 GL_TAIL2_HEAD GL_TAIL2_NC
+        : [tA] "+v"(tA), [tB] "+v"(tB), [r2A] "+v"(F.r2A), [r2B] "+v"(F.r2B), [kA] "=&s"(kA), [kB] "=&s"(kB)
+        : [bA] "v"(F.bA), [bB] "v"(F.bB), [c] "s"(65535) : "vcc");
+    r0 = tA; r1 = tB;
+}
+// one of each: r0 = mul_tw(x0, w0) is stored, r1 = mul_tw_nc(x1, w1) only feeds products (a chain step beside the use of the factor before)
+__device__ __forceinline__ void mul_tw2_m_nc(u64 x0, u64 w0, u64 x1, u64 w1, u64& r0, u64& r1) {
+    fold96_pair F = mul_fold96_2(x0, w0, x1, w1);
+    u64 tA = mk64(F.t0A, F.t1A), tB = mk64(F.t0B, F.t1B), vA, kA, kB, gA;
+    asm(GL_FOLD2
+        "v_mad_u64_u32 %[tA], %[kA], %[r2A], -1, %[tA]\n\t"
+        "v_mad_u64_u32 %[tB], %[kB], %[r2B], -1, %[tB]\n\t"
+        "s_nop 0\n\t"                                             // two chains: the second wait state of both carries
+        "v_cndmask_b32_e64 %[r2A], 0, -1, %[kA]\n\t"
+        "v_mad_u64_u32 %[tA], vcc, %[r2A], 1, %[tA]\n\t"
+        "v_mad_u64_u32 %[vA], %[gA], 1, -1, %[tA]\n\t"            // gA: the two instructions below stand behind it
+        "v_cndmask_b32_e64 %[r2B], 0, -1, %[kB]\n\t"
+        "v_mad_u64_u32 %[tB], vcc, %[r2B], 1, %[tB]"
+        : [tA] "+v"(tA), [tB] "+v"(tB), [r2A] "+v"(F.r2A), [r2B] "+v"(F.r2B), [vA] "=&v"(vA), [kA] "=&s"(kA), [kB] "=&s"(kB), [gA] "=&s"(gA)
+        : [bA] "v"(F.bA), [bB] "v"(F.bB), [c] "s"(65535) : "vcc");
+    u32 q0 = (u32)tA, q1 = (u32)(tA >> 32);
+    asm("v_cndmask_b32_e64 %[q0], %[q0], %[v0], %[gA]\n\tv_cndmask_b32_e64 %[q1], %[q1], %[v1], %[gA]"
+        : [q0] "+v"(q0), [q1] "+v"(q1) : [v0] "v"((u32)vA), [v1] "v"((u32)(vA >> 32)), [gA] "s"(gA));
+    r0 = mk64(q0, q1); r1 = tB;
+}
+
+// x0 2^E0 and x1 2^E1 (mul_pow2) with the two shifts' chains alternating where both exponents fall into the same of mul_pow2's cases
+// (a layer's two blocks of the same j always do); exponents of different cases, and the case 32 < E < 64, run one behind the other
+template <int E0, int E1>
+__device__ __forceinline__ void mul_pow2_2(u64 x0, u64 x1, u64& r0, u64& r1) {
+    static_assert(E0 >= 0 && E0 < 96 && E1 >= 0 && E1 < 96, "fold 2^96 = -1 first");
+    if constexpr (E0 >= 1 && E0 <= 32 && E1 >= 1 && E1 <= 32) {
+        GL_OPAQUE(x0); GL_OPAQUE(x1);
+        mad_eps2_m((u32)(x0 >> (64 - E0)), x0 << E0, (u32)(x1 >> (64 - E1)), x1 << E1, r0, r1);
+    } else if constexpr (E0 >= 64 && E1 >= 64) {
+        GL_OPAQUE(x0); GL_OPAQUE(x1);
+        constexpr int ra = E0 - 64, rb = E1 - 64;
+        const u32 ta = (u32)x0 << ra, tb = (u32)x1 << rb;
+        sub2_m(((u64)ta << 32) - ta, ra == 0 ? (x0 >> 32) : (x0 >> (32 - ra)), ((u64)tb << 32) - tb, rb == 0 ? (x1 >> 32) : (x1 >> (32 - rb)), r0, r1);
+    } else {
+        r0 = mul_pow2<E0>(x0); r1 = mul_pow2<E1>(x1);
+    }
+}
+
 // host-side twins (used only to build twiddle tables at context creation)
 inline u64 hmul(u64 a, u64 b) {
     unsigned __int128 x = (unsigned __int128)a * b;

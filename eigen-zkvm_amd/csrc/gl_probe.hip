@@ -1,6 +1,7 @@
 // Test hooks for the field operations that have no entry point of their own: the NTT passes' twiddle product (gl::mul_tw, gl::mul_tw_nc)
 // applied to operand pairs from the host, and the shift twiddle gl::mul_pow2<E> for every exponent (tests/test_gpu_ntt_lean.py); the
 // passes' multiply-add forms gl::add_m, gl::sub_m, gl::mad_eps_m beside gl::sub and gl::add_nc (tests/test_gpu_ntt_issue_slots.py); every
+// paired forms of the passes' sums, differences, products and shifts on two slots of operands (tests/test_gpu_ntt_pairs.py); every
 // other primitive of gl.hip.h, the carry-free accumulators of acc6.hip.h and the matrix-pipe product of gl_mfma.hip.h on operands from
 // the host (tests/test_gpu_field_ops.py).  Not part of include/zkgpu.h; the tests bind them by name.  Every probe writes what the
 // primitive returned, unreduced.
@@ -81,6 +82,32 @@ __global__ void ntt_arith_probe_kernel(const u64* __restrict__ pa, const u64* __
     o[4 * n] = gl::mul_tw(s, w);
     o[5 * n] = gl::mad_eps_m((u32)w, a);
     o[6 * n] = gl::mul_tw(a, w);
+}
+
+// The paired forms of the NTT passes (gl::bfly_m, gl::bfly2_m, gl::sub2_m, gl::mul_tw2, gl::mul_tw2_nc, gl::mul_tw2_m_nc, gl::mad_eps2_m,
+// gl::mul_pow2_2) on two slots of operands, (p0, q0) and (p1, q1), as returned.  The sums, differences and shifts get the operands
+// mod p.  Rows of n: 0-1 bfly_m of slot 0 (sum, difference); 2-5 bfly2_m (sum, difference of slot 0, then of slot 1); 6-7 sub2_m;
+// 8-9 mul_tw2; 10-11 mul_tw2_nc; 12-13 mul_tw2_m_nc; 14-15 mad_eps2_m((u32)q, p); then for every E < 96 the rows 16 + 4 E ... + 3:
+// mul_pow2_2<E, E>(p0, p1) and mul_pow2_2<E, 95 - E>(p0, p1)   (tests/test_gpu_ntt_pairs.py)
+constexpr int NTT_PAIR_ROWS = 16 + 4 * 96;
+__global__ void ntt_pair_probe_kernel(const u64* __restrict__ pp0, const u64* __restrict__ pq0, const u64* __restrict__ pp1, const u64* __restrict__ pq1,
+                                      u64* __restrict__ out, u64 n) {
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const u64 p0 = pp0[i], q0 = pq0[i], p1 = pp1[i], q1 = pq1[i], a = canon(p0), b = canon(q0), c = canon(p1), d = canon(q1);
+    u64* __restrict__ o = out + i;
+    gl::bfly_m(a, b, o[0 * n], o[1 * n]);
+    gl::bfly2_m(a, b, c, d, o[2 * n], o[3 * n], o[4 * n], o[5 * n]);
+    gl::sub2_m(a, b, c, d, o[6 * n], o[7 * n]);
+    gl::mul_tw2(p0, q0, p1, q1, o[8 * n], o[9 * n]);
+    gl::mul_tw2_nc(p0, q0, p1, q1, o[10 * n], o[11 * n]);
+    gl::mul_tw2_m_nc(p0, q0, p1, q1, o[12 * n], o[13 * n]);
+    gl::mad_eps2_m((u32)q0, p0, (u32)q1, p1, o[14 * n], o[15 * n]);
+    static_for<0, 96>([&](auto EI) {
+        constexpr int E = decltype(EI)::value;
+        gl::mul_pow2_2<E, E>(a, c, o[(u64)(16 + 4 * E) * n], o[(u64)(17 + 4 * E) * n]);
+        gl::mul_pow2_2<E, 95 - E>(a, c, o[(u64)(18 + 4 * E) * n], o[(u64)(19 + 4 * E) * n]);
+    });
 }
 
 // rows of 3 n words: f3_add(x, y), f3_sub(x, y), f3_mul(x, y), f3_muls(x, s), f3_inv(x); x, y canonical, s any u64
@@ -185,6 +212,23 @@ extern "C" int zk_gl_ntt_arith_probe(const uint64_t* a, const uint64_t* b, const
         hipLaunchKernelGGL(ntt_arith_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, da.u(), db.u(), dw.u(), dout.u(), (u64)n);
         ZK_HIP(hipGetLastError());
         ZK_HIP(hipMemcpy(out, dout.p, NTT_ARITH_ROWS * n * 8, hipMemcpyDeviceToHost));
+    });
+}
+
+// p0, q0, p1, q1: n host words each (any u64); out: (16 + 4 * 96) n host words, one row per result (ntt_pair_probe_kernel)
+extern "C" int zk_gl_ntt_pair_probe(const uint64_t* p0, const uint64_t* q0, const uint64_t* p1, const uint64_t* q1, uint64_t* out, size_t n) {
+    using namespace zk;
+    return guard([&] {
+        ZK_REQUIRE(p0 && q0 && p1 && q1 && out && n > 0 && n <= ((size_t)1 << 16), "zk_gl_ntt_pair_probe: bad arguments");
+        DevBuf d0, d1, d2, d3, dout;
+        d0.reserve(n * 8); d1.reserve(n * 8); d2.reserve(n * 8); d3.reserve(n * 8); dout.reserve(NTT_PAIR_ROWS * n * 8);
+        ZK_HIP(hipMemcpy(d0.p, p0, n * 8, hipMemcpyHostToDevice));
+        ZK_HIP(hipMemcpy(d1.p, q0, n * 8, hipMemcpyHostToDevice));
+        ZK_HIP(hipMemcpy(d2.p, p1, n * 8, hipMemcpyHostToDevice));
+        ZK_HIP(hipMemcpy(d3.p, q1, n * 8, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(ntt_pair_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, d0.u(), d1.u(), d2.u(), d3.u(), dout.u(), (u64)n);
+        ZK_HIP(hipGetLastError());
+        ZK_HIP(hipMemcpy(out, dout.p, NTT_PAIR_ROWS * n * 8, hipMemcpyDeviceToHost));
     });
 }
 

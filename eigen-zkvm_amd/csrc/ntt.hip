@@ -23,6 +23,13 @@
 //     row shares its 16 entries of w256 (sub-step A) and, where 16 | s*n_pols, of the direct inter-pass table: one load per lane and a
 //     DPP row broadcast at the use (2 + 2 table loads per lane where there were 15 + 16); the two-level look-ups of a chain ride along.
 //     2^24 points 83.4 -> 85.7 GElem/s; the same loads in FRONT of the data loads gain nothing (profiles/r32/ntt_table_loads.md).
+//   * the butterflies of a lane go two at a time through ntt_reg's paired form: the sums and differences of two butterflies as four carry
+//     chains alternating inside one asm block, their shifts as two (gl::bfly2_m, gl::mul_pow2_2).  The single forms keep every dependent
+//     instruction right behind its producer and write the wait states of each flag as s_nop; in a <4,4> kernel the vector instructions
+//     that read what the one before them wrote fall from 56 % to 40 %, the written s_nop from 1 291 to 846, the same 2 802 vector
+//     instructions (tools/asm_chain_stats.py).  2^24 points 84.8-86.8 -> 87.7-89.6 GElem/s, five
+//     alternating runs each, slowest above the parent's fastest, 91 -> 93 VGPRs, five waves.  The twiddle products in the same form gained
+//     nothing beside it and are not used here (profiles/r33/ntt_chains.md, tools/experiments/ntt_pair_products_r33.patch).
 //   * HBM-bound: 16 B / element / pass; bytes per transform = 16 * passes * N * n_pols.  A pass reads every data word once, so the
 //     sixteen data loads of a lane are non-temporal (the tables, which are re-read, and the stores are plain): 2^24 points 75.9 -> 82.3
 //     GElem/s.  Measured on the same kernel and not kept: non-temporal stores (slower), LDS sized per launch, an XCD-contiguous
@@ -183,7 +190,7 @@ __global__ __launch_bounds__(NTT_TILE / 16) void ntt_pass_kernel(const PassParam
         }
         request_tables();
 #pragma unroll
-        for (int g = 0; g < GA; ++g) ntt_reg<LOGA, INV>(x[g]);
+        for (int g = 0; g < GA; ++g) ntt_reg<LOGA, INV, true>(x[g]);
         // Passes of <= 6 bits: w_R is a power of two (w_64 = 2^39, ntt_reg.hip.h), so the twiddle w_R^(jb ka) between the two halves is a
         // shift like the butterflies' own -- once jb is a compile-time number.  jb = ta GA + g and ta = t / C with C = 4096 / R >= 64
         // lanes: the same in every lane of a wave, so a switch over ta (R / 16 <= 4 cases) costs no divergence and turns the 15 general
@@ -257,7 +264,7 @@ __global__ __launch_bounds__(NTT_TILE / 16) void ntt_pass_kernel(const PassParam
             for (int jb = 0; jb < RB; ++jb) y[g][jb] = lds[ka * ROW + jb * C + c];
         }
 #pragma unroll
-        for (int g = 0; g < GB; ++g) ntt_reg<LOGB, INV>(y[g]);
+        for (int g = 0; g < GB; ++g) ntt_reg<LOGB, INV, true>(y[g]);
         if (row_p) {   // the inter-pass twiddles by the row's entries of the table, in front of the exit of the dead lanes
             static_for<0, GB>([&](auto GI) {
                 constexpr int g = decltype(GI)::value;

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdint>
+#include <cstdlib>
+#include "../eigen-zkvm_amd/csrc/gl.hip.h"   // the paired forms of round 33 (kpair)
 typedef unsigned long long u64;
 typedef unsigned int u32;
 
@@ -204,6 +206,42 @@ __global__ __launch_bounds__(256) void ksub(u64* out, int iters, u32 seed) {
     out[blockIdx.x * blockDim.x + threadIdx.x] = ((u64)hi << 32) | lo;
 }
 
+// The paired forms of csrc/gl.hip.h against their single forms called back to back (round 33): two butterflies or two twiddle products on
+// independent operands per step, 16 steps per iteration.  MODE 0: add_m, sub_m twice; 1: bfly_m twice; 2: bfly2_m; 3: mul_tw twice; 4: mul_tw2
+template <int MODE>
+__global__ __launch_bounds__(256) void kpair(u64* out, int iters, u32 seed) {
+    const u64 p = 0xFFFFFFFF00000001ull;
+    u64 a = (threadIdx.x + seed) * 0x9E3779B97F4A7C15ull % p, b = (a * 31 + 7) % p, c = (a * 131 + 5) % p, d = (b * 17 + 3) % p;
+    for (int i = 0; i < iters; ++i) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            u64 s0, d0, s1, d1;
+            if constexpr (MODE == 0) { s0 = gl::add_m(a, b); d0 = gl::sub_m(a, b); s1 = gl::add_m(c, d); d1 = gl::sub_m(c, d); }
+            else if constexpr (MODE == 1) { gl::bfly_m(a, b, s0, d0); gl::bfly_m(c, d, s1, d1); }
+            else if constexpr (MODE == 2) gl::bfly2_m(a, b, c, d, s0, d0, s1, d1);
+            else if constexpr (MODE == 3) { s0 = gl::mul_tw(a, b); s1 = gl::mul_tw(c, d); d0 = b; d1 = d; }
+            else { gl::mul_tw2(a, b, c, d, s0, s1); d0 = b; d1 = d; }
+            a = s0; b = d1; c = s1; d = d0;
+        }
+    }
+    out[blockIdx.x * blockDim.x + threadIdx.x] = a ^ b ^ c ^ d;
+}
+// cycles of a SIMD per operation of one wave (a butterfly, a product): 32 of them per iteration
+template <class Kern>
+void run_ops(const char* name, Kern kern, u64* d, int waves_per_simd) {
+    const int iters = 2000;
+    dim3 grid(256 * waves_per_simd), block(256);
+    hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
+    hipLaunchKernelGGL(kern, grid, block, 0, 0, d, iters, 1u);
+    hipDeviceSynchronize();
+    hipEventRecord(e0);
+    hipLaunchKernelGGL(kern, grid, block, 0, 0, d, iters, 1u);
+    hipEventRecord(e1); hipEventSynchronize(e1);
+    float ms; hipEventElapsedTime(&ms, e0, e1);
+    printf("%-36s waves/SIMD=%d  %.3f ms  -> %.2f cycles per operation (at 2.4 GHz)\n", name, waves_per_simd, ms,
+           ms * 1e-3 * 2.4e9 / ((double)iters * 32 * waves_per_simd));
+}
+
 template <int W>
 void run(const char* name, u64* d, int waves_per_simd) {
     const int iters = 3000;
@@ -240,6 +278,16 @@ void run_blk(const char* name, Kern kern, u64* d, int waves_per_simd, int insts,
 
 int main() {
     u64* d; hipMalloc(&d, 256 * 8 * 256 * sizeof(u64));
+    if (getenv("UBENCH_PAIRS")) {   // the paired forms alone (tools/ubench_valu_pairs.txt)
+        for (int w : {1, 2, 4, 5}) {
+            run_ops("butterfly: add_m, sub_m", kpair<0>, d, w);
+            run_ops("butterfly: bfly_m", kpair<1>, d, w);
+            run_ops("butterfly: bfly2_m", kpair<2>, d, w);
+            run_ops("product: mul_tw", kpair<3>, d, w);
+            run_ops("product: mul_tw2", kpair<4>, d, w);
+        }
+        return 0;
+    }
     for (int w : {8}) {
         run<0>("v_add_u32", d, w);
         run<1>("v_mad_u64_u32", d, w);
